@@ -11,8 +11,16 @@ All inputs (s, z, right-hand sides) are resident in HBM when the timed region
 starts; outputs stay in HBM.  No PyTorch: device buffers, streams and the RCCL
 exchange all go through the C ABI (include/clarabel_hip.h).
 
+A plain run sets up, warms up (--warmup steps), times --steps steps and prints the result line: `metric`, `value`
+(timed steps per second), `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload's shape.  Every other
+figure named below (parity against the CPU oracle, CPU baselines, the roofline pass with hipEvent pairs, the other
+solve or exchange policy, per-rank exchange figures, the batched_c4 / c2 / c5 / l1_dropin objects) takes runs of its
+own and is measured only with --full; its field is null in a plain line.
+--dump-outputs DIR writes what the last timed step computed -- every solve's solution [x; z] and, with an exchange, the
+        all-gathered step direction -- as DIR/<name>.npy in float64, at most 64 MB in all (see dump_outputs).
+
 --gpus 1 (default): BASELINE config 3, portfolio SOCP n = 10^6 (1000 x SOC(1001)) --
-        the configuration the metric is quoted on -- on one MI355X; the JSON line also carries
+        the configuration the metric is quoted on -- on one MI355X; with --full the JSON line also carries
         `parity` (solutions against the CPU oracle on the same inputs), `cpu_baseline`
         (the oracle, 1 core), `cpu_baseline_mt` (oracle/ldl_mt.c: the same column algorithm on OpenMP
         threads, labelled non-reference)
@@ -62,6 +70,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 HBM_ACHIEVABLE_GBS = 6300.0  # what a plain copy reaches on this part (same guide): `frac_of_achievable` beside `frac`
 MFMA_F64_PEAK_TFLOPS = 78.6  # dense fp64 matrix-core peak
 TOL = 1e-8             # north_star: "solution within 1e-8 relative of reference"
+DUMP_BYTES = 60 << 20  # --dump-outputs: below 64 MB in all, the .npy headers included
 
 
 def baseline_metric():
@@ -161,7 +170,7 @@ class Workload:
                         comm.allgather_step(ks, self.lhs[k].ptr, gathered[k].ptr, counts)
 
     def run(self, steps, warmup, profile_family=0, comm=None, gathered=None, counts=None, events_in_timed_region=True,
-            sequential_pass=True):
+            sequential_pass=True, keep_outputs=False):
         """W warm-up steps, then K timed steps bracketed by synchronisations.  The dominant kernel's launch durations come from
         hipEvent pairs on the engine's stream around each of its launches (chip_kkt_profile): inside the timed region when the
         events_in_timed_region, in a SECOND pass of the same steps right after it otherwise (the default of every workload
@@ -188,6 +197,13 @@ class Workload:
         d = np.diff(np.asarray(marks)) * 1e3
         self.step_ms = {"min": round(float(d.min()), 4), "median": round(float(np.median(d)), 4),
                         "max": round(float(d.max()), 4)} if len(d) else None
+        self.outputs = None
+        if keep_outputs:
+            # what the last timed step handed its caller, copied to the host outside the timed region and before any
+            # later pass overwrites it: every solve's solution [x; z] and, with an exchange, the gathered step direction
+            self.outputs = {"solution_%d" % k: a for k, a in enumerate(self.solutions())}
+            if gathered is not None:
+                self.outputs["step_direction_gathered"] = gathered[len(self.rhs) - 1].numpy()
         self.events_pass = None
         self.sequential = None
         if not events_in_timed_region and self.pair and sequential_pass:
@@ -239,6 +255,21 @@ def profile_commit(name):
 
 def relerr(a, b):
     return float(np.max(np.abs(a - b)) / max(1.0, np.max(np.abs(b))))
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every array as <outdir>/<name>.npy in float64.  When all of them together exceed `budget` bytes,
+    an array longer than its share (budget / 8 / number of arrays entries) is written as a sample of that many entries:
+    positions drawn without replacement by a generator of seed 0 and sorted, so that they depend on the array's length
+    alone and two runs with the same arguments write the same entries."""
+    os.makedirs(outdir, exist_ok=True)
+    share = budget // 8 // max(1, len(arrays))
+    sample = sum(np.size(a) for a in arrays.values()) * 8 > budget
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if sample and a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def sweep_roofline(ks, wm, prof, steps, nsolves):
@@ -857,11 +888,22 @@ def main():
     ap.add_argument("--gather-every-solve", action="store_true",
                     help="N > 1: all-gather the solution of each of the 3 solves, not only the step direction")
     ap.add_argument("--cpu-steps", type=int, default=-1, help="oracle steps for cpu_baseline (-1 auto, 0 off)")
-    ap.add_argument("--no-extras", action="store_true", help="skip parity / cpu legs / batched_c4 (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip parity / cpu legs / batched_c4 and the other objects (profiling runs)")
     ap.add_argument("--profile-family", type=int, default=5,
-                    help="kernel family timed with hipEvents for the roofline (5 = k_bundle_ir, the fused solve + "
+                    help="with --full: kernel family timed with hipEvents for the roofline (5 = k_bundle_ir, the fused solve + "
                          "refinement launch; 6 = k_bundle_factor; 1 = k_bundle_symv on the one-kernel-per-phase path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every figure that takes runs of its own: roofline, parity against the CPU oracle, CPU "
+                         "baselines, the other solve / exchange policy, per-rank figures and the batched_c4 / c2 / c5 / "
+                         "l1_dropin objects (a plain run: set-up, warm-up, the timed steps and the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed (every solve's solution [x; z], with an exchange the "
+                         "gathered step direction) as DIR/<name>.npy, float64, at most 64 MB in all (a fixed sample of "
+                         "larger outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -895,7 +937,7 @@ def main():
     elif workload in ("c5", "c5m"):
         nc = 200 if workload == "c5" else 50
         # (quarter size: the oracle runs live and needs the numpy restatement's Hs blocks)
-        pr = problems.chordal_sdp(nc, 50, 10, nc, 51, seed=5, with_hs=(nc != 200 and not args.no_extras))
+        pr = problems.chordal_sdp(nc, 50, 10, nc, 51, seed=5, with_hs=(nc != 200 and args.full and not args.no_extras))
         desc = ("chordal SDP (BASELINE config 5%s): %d x PSD(50) cliques with overlap 10 + %d x SOC(51); PSD scalings, "
                 "Hs = skron(R R') and all cone state on the device" % ("" if nc == 200 else ", quarter size", nc, nc))
     else:
@@ -918,14 +960,18 @@ def main():
         comm = FileComm(hip, world, rank) if args.fake_comm else hip.Comm(rendezvous_id(hip, rank, world), world, rank, device)
         comm.attach(w.ks)
         gathered = [hip.DeviceArray(int(sum(counts))) for _ in range(3)]
-    elapsed, prof = w.run(args.steps, args.warmup, args.profile_family, comm, gathered, counts,
-                          events_in_timed_region=False, sequential_pass=workload in ("c2", "c5", "c5m"))
+    elapsed, prof = w.run(args.steps, args.warmup, args.profile_family if args.full else 0, comm, gathered, counts,
+                          events_in_timed_region=False, sequential_pass=args.full and workload in ("c2", "c5", "c5m"),
+                          keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if w.outputs is not None:
+        dump_outputs(args.dump_outputs, w.outputs)
+        w.outputs = None
     own_elapsed_main, own_repeats_main = getattr(w, "own_elapsed", elapsed), w.repeats  # (this rank's clock of the run `value` comes from)
     ir = w.ks.linear_solver_info().last_ir_iterations
     # N > 1: the same steps once more with the OTHER exchange policy, so that the driver's curve can be read either way
     # (SURVEY 8(e) says one all-gather per solve; the default gathers the step direction only)
     other_policy = None
-    if comm is not None and world > 1:
+    if comm is not None and world > 1 and args.full:
         w.gather_every_solve = not w.gather_every_solve
         el2, _ = w.run(args.steps, args.warmup, 0, comm, gathered, counts)
         other_policy = {"policy": "3 x all-gather per step (every solve's solution)" if w.gather_every_solve else
@@ -938,7 +984,7 @@ def main():
     #      real run on several GPUs can be read: a slow rank, a rank whose persistent launches lost co-residency, or the
     #      collective itself
     per_rank = None
-    if comm is not None:
+    if comm is not None and args.full:
         last = len(w.rhs) - 1
         w.ks.synchronize()
         comm.synchronize()
@@ -965,7 +1011,7 @@ def main():
 
     # ---- N > 1: every rank checks ITS shard against the oracle; the ranks reduce the verdict ----------------
     parity_sharded = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         # (a) bit-for-bit: the gathered step direction against every rank's local solution -- checksums (sum and
         # sum of |.|) of each rank's segment of MY gathered copy against the owner's, all-reduced
         comm.wait(w.ks)
@@ -1038,7 +1084,7 @@ def main():
                       7: ["k_snode_update"],
                       11: ["k_snode_gsweep", "k_snode_gfwd", "k_snode_gbwd"] if ks.sweep_model()["g_levels"] else ["k_snode_tri"]}.get(fam)
             full_size = (workload == "c3" and args.nblocks == 1000 and args.blocksize == 1000) or workload in ("c2", "c5", "c4")
-            if pj and knames and full_size:
+            if args.full and pj and knames and full_size:
                 kk = json.load(open(pj[-1]))["kernels"]
                 have = [k for k in knames if k in kk]  # (launch-weighted mean over the family's kernels, per launch)
                 traffic = round(sum(kk[k]["hbm_bytes"] * kk[k].get("launches_sampled", 1) for k in have) /
@@ -1095,12 +1141,12 @@ def main():
         w_fallbacks = int(w.ks.fused_fallbacks())
         if world > 1:
             parity = parity_sharded
-        elif not args.no_extras and workload == "c5":
+        elif args.full and not args.no_extras and workload == "c5":
             parity = fixture_parity_c5(w, hip)
             if args.cpu_steps != 0:
                 cpu = quarter_c5_cpu_baseline(hip, problems, args)
                 cpu_mt = sn_leg(w, hip)
-        elif not args.no_extras:
+        elif args.full and not args.no_extras:
             parity, cpu, ko = oracle_leg(w, args, time_it=args.cpu_steps != 0)
             if args.cpu_steps != 0 and workload in ("c3", "c4"):
                 cpu_mt = mt_leg(w, ko)
@@ -1151,7 +1197,7 @@ def main():
                                          int(sum(counts)))) if comm is not None else "none"},
             "step_ms": step_ms,
             "timing": "value / ms_per_step: K steps between two synchronisations WITHOUT the hipEvent pairs of the roofline "
-                      "measurement on the stream; roofline: the same K steps once more, right after, with a pair around every launch "
+                      "measurement on the stream; roofline (--full): the same K steps once more, right after, with a pair around every launch "
                       "of the dominant kernel (roofline_events_pass.ms_per_step_with_events is that pass)",
             "roofline_events_pass": w_events_pass,
             "roofline": roof, "parity": parity, "cpu_baseline": cpu, "cpu_baseline_mt": cpu_mt, "batched_c4": c4,

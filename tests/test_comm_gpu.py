@@ -146,7 +146,7 @@ def test_bench_sharded_code_path_with_file_comm(hip):
     stand-in for the RCCL exchange (--fake-comm) -- RCCL itself refuses two ranks on one device."""
     import json
     import subprocess
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--fake-comm", "--nbatch", "8",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--fake-comm", "--nbatch", "8",
                           "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

@@ -8,18 +8,18 @@ QUICK=$2
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd $R
-python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 bash tools/prof_bench.sh $TAG > /dev/null 2>&1
 cp $O/prof_$TAG/r_kernel_stats.csv $O/${TAG}_kernel_stats.csv
 bash tools/pmc_traffic.sh > /dev/null 2>&1
 python tools/pmc_summarize.py $O $O/${TAG}_pmc_traffic.json > $O/${TAG}_pmc_traffic.txt 2>&1
 find $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE -name "*.csv" -size +1M -delete 2>/dev/null
 rm -f $O/pmc_*/*.db $O/pmc_*/*/*.db 2>/dev/null
-python bench.py --workload c4 --nbatch 128 --cpu-steps 0 > $O/${TAG}_bench_c4_128.json 2>> $O/${TAG}_bench.err
-python bench.py --workload c4 --nbatch 256 --cpu-steps 0 > $O/${TAG}_bench_c4_256.json 2>> $O/${TAG}_bench.err
+python bench.py --full --workload c4 --nbatch 128 --cpu-steps 0 > $O/${TAG}_bench_c4_128.json 2>> $O/${TAG}_bench.err
+python bench.py --full --workload c4 --nbatch 256 --cpu-steps 0 > $O/${TAG}_bench_c4_256.json 2>> $O/${TAG}_bench.err
 if [ -z "$QUICK" ]; then
-python bench.py --workload c2 > $O/${TAG}_bench_c2.json 2>> $O/${TAG}_bench.err
-python bench.py --workload c5 --steps 10 > $O/${TAG}_bench_c5.json 2>> $O/${TAG}_bench.err
+python bench.py --full --workload c2 > $O/${TAG}_bench_c2.json 2>> $O/${TAG}_bench.err
+python bench.py --full --workload c5 --steps 10 > $O/${TAG}_bench_c5.json 2>> $O/${TAG}_bench.err
 bash tools/prof_bench.sh ${TAG}_c2 --workload c2 --steps 5 --warmup 2 > /dev/null 2>&1
 cp $O/prof_${TAG}_c2/r_kernel_stats.csv $O/${TAG}_c2_kernel_stats.csv
 bash tools/prof_bench.sh ${TAG}_c5 --workload c5 --steps 5 --warmup 2 > /dev/null 2>&1

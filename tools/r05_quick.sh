@@ -18,7 +18,7 @@ for w in $WLS; do
     c4_*) extra="--workload c4 --nbatch ${w#c4_}";;
     *) extra="--workload $w";;
   esac
-  timeout 600 python bench.py $extra --cpu-steps 0 > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err
+  timeout 600 python bench.py --full $extra --cpu-steps 0 > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err
   python - $O/${TAG}_bench_$w.json <<'PY'
 import json, sys
 try:

@@ -8,7 +8,7 @@ for rep in 1 2; do
 for st in $SETS; do
   e=$(echo $st | tr ',' ' ')
   if [ "$st" = "default" ]; then e=""; fi
-  env $e timeout 600 python bench.py --workload $W --cpu-steps 0 $([ -n "$AB_PARITY" ] || echo --no-extras) --steps 20 --warmup 3 2> /dev/null | python -c "
+  env $e timeout 600 python bench.py --full --workload $W --cpu-steps 0 $([ -n "$AB_PARITY" ] || echo --no-extras) --steps 20 --warmup 3 2> /dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d.get('roofline') or {}

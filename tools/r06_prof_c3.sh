@@ -4,7 +4,7 @@
 TAG=${1:-r06_x}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
 cd $R
-python bench.py --workload c3 --cpu-steps 0 --no-extras > $O/${TAG}_bench_c3.json 2> $O/${TAG}_bench_c3.err
+python bench.py --full --workload c3 --cpu-steps 0 --no-extras > $O/${TAG}_bench_c3.json 2> $O/${TAG}_bench_c3.err
 bash tools/prof_bench.sh ${TAG}_c3 --workload c3 --steps 10 --warmup 2 > /dev/null 2>&1
 cp $O/prof_${TAG}_c3/r_kernel_stats.csv $O/${TAG}_c3_kernel_stats.csv
 bash tools/pmc_traffic.sh c3 > /dev/null 2>&1
