@@ -746,6 +746,127 @@ class HipKKTSystem:
 
 
 # ---------------------------------------------------------------------------
+# L4: DefaultSolver::new(P, q, A, b, cones, settings).solve() on the device (csrc/solver.cpp)
+# ---------------------------------------------------------------------------
+# SolverStatus (core/solver.rs:19-45), in the order of chip_solver_status
+SOLVER_STATUS = ("Unsolved", "Solved", "PrimalInfeasible", "DualInfeasible", "AlmostSolved", "AlmostPrimalInfeasible",
+                 "AlmostDualInfeasible", "MaxIterations", "MaxTime", "NumericalError", "InsufficientProgress",
+                 "CallbackTerminated")
+
+
+class SolverSettings(C.Structure):
+    """chip_solver_settings: the DefaultSettings fields (settings.rs) the loop and the equilibration read, with the
+    linear-system settings embedded as `linsys`"""
+    _fields_ = [("linsys", Settings), ("max_iter", C.c_int32), ("equilibrate_enable", C.c_int32),
+                ("time_limit", C.c_double), ("max_step_fraction", C.c_double), ("tol_gap_abs", C.c_double),
+                ("tol_gap_rel", C.c_double), ("tol_feas", C.c_double), ("tol_infeas_abs", C.c_double),
+                ("tol_infeas_rel", C.c_double), ("tol_ktratio", C.c_double), ("reduced_tol_gap_abs", C.c_double),
+                ("reduced_tol_gap_rel", C.c_double), ("reduced_tol_feas", C.c_double),
+                ("reduced_tol_infeas_abs", C.c_double), ("reduced_tol_infeas_rel", C.c_double),
+                ("reduced_tol_ktratio", C.c_double), ("equilibrate_max_iter", C.c_int32), ("reserved0", C.c_int32),
+                ("equilibrate_min_scaling", C.c_double), ("equilibrate_max_scaling", C.c_double),
+                ("linesearch_backtrack_step", C.c_double), ("min_switch_step_length", C.c_double),
+                ("min_terminate_step_length", C.c_double)]
+
+    @staticmethod
+    def default(**kw):
+        """DefaultSettings::default(); keyword arguments override fields (`device=` and the other linear-system
+        fields go to .linsys)"""
+        s = SolverSettings()
+        lib().chip_solver_settings_default(C.byref(s))
+        own = {f[0] for f in SolverSettings._fields_}
+        lin = {f[0] for f in Settings._fields_}
+        for k, v in kw.items():
+            if k not in own and k not in lin:
+                raise TypeError("SolverSettings.default: no setting named %r" % k)
+            setattr(s if k in own else s.linsys, k, v)
+        return s
+
+
+class SolutionInfo(C.Structure):
+    """chip_solution_info"""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("obj_val", C.c_double),
+                ("obj_val_dual", C.c_double), ("r_prim", C.c_double), ("r_dual", C.c_double),
+                ("solve_time", C.c_double), ("setup_time", C.c_double), ("equilibration_time", C.c_double),
+                ("iteration_time", C.c_double)]
+
+
+class Solution:
+    """DefaultSolution (solution.rs): x, s, z, status (the reference's status name), obj_val, obj_val_dual,
+    iterations, r_prim, r_dual, solve_time (+ setup_time, equilibration_time, iteration_time)"""
+
+    def __init__(self, x, s, z, info):
+        self.x, self.s, self.z = x, s, z
+        self.status = SOLVER_STATUS[info.status]
+        for k in ("obj_val", "obj_val_dual", "iterations", "r_prim", "r_dual", "solve_time", "setup_time",
+                  "equilibration_time", "iteration_time"):
+            setattr(self, k, getattr(info, k))
+
+    def __repr__(self):
+        return "Solution(status=%s, iterations=%d, obj_val=%r)" % (self.status, self.iterations, self.obj_val)
+
+
+class HipSolver:
+    """DefaultSolver::new(P, q, A, b, cones, settings) (default/solver.rs) with every layer on the device: Ruiz
+    equilibration, the interior-point loop, termination and the status.  P: n x n triu CscMatrix, A: m x n CscMatrix,
+    cones as in HipKKTSolver ((tag, dim), (tag, dim, dim2), (tag, dim, dim2, alpha); GenPowerConeT =
+    (5, len(alpha), dim2, alpha))."""
+
+    def __init__(self, P, q, A, b, cones, settings=None):
+        n, m = P.n, A.m
+        assert P.m == n and A.n == n
+        q, b = _f(q), _f(b)
+        assert len(q) == n and len(b) == m
+        self.n, self.m = n, m
+        self.settings = settings or SolverSettings.default()
+        cones = [tuple(c) for c in cones]
+        tags = np.array([c[0] for c in cones], dtype=np.int32)
+        dims = np.array([c[1] for c in cones], dtype=np.int64)
+        dims2 = np.array([c[2] if len(c) > 2 else 0 for c in cones], dtype=np.int64)
+        alphas = np.array([c[3] if (len(c) > 3 and c[0] == PowerConeT) else 0.5 for c in cones], dtype=np.float64)
+        gp = [np.asarray(c[3], dtype=np.float64) for c in cones if c[0] == GenPowerConeT]
+        for c, a in zip([c for c in cones if c[0] == GenPowerConeT], gp):
+            assert len(a) == c[1]
+        gpa = _f(np.concatenate(gp)) if gp else None
+        self._h = C.c_void_p()
+        _check(lib().chip_solver_create(C.byref(self._h), C.c_int64(n), C.c_int64(m), _pu(P.colptr), _pu(P.rowval),
+                                        _pf(P.nzval), _pf(q), _pu(A.colptr), _pu(A.rowval), _pf(A.nzval), _pf(b),
+                                        C.c_int64(len(cones)), tags.ctypes.data_as(P_I32), dims.ctypes.data_as(P_I64),
+                                        dims2.ctypes.data_as(P_I64), _pf(alphas),
+                                        None if gpa is None else _pf(gpa), C.byref(self.settings)),
+               "chip_solver_create")
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().chip_solver_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def solve(self):
+        """IPSolver::solve -> Solution (a second call restarts from default_start)"""
+        _check(lib().chip_solver_solve(self._h), "chip_solver_solve")
+        x, s, z = np.zeros(self.n), np.zeros(self.m), np.zeros(self.m)
+        info = SolutionInfo()
+        _check(lib().chip_solver_get_solution(self._h, _pf(x), _pf(s), _pf(z), C.byref(info)),
+               "chip_solver_get_solution")
+        return Solution(x, s, z, info)
+
+    def solution_dev(self):
+        """(x, s, z) of the last solve as non-owning DeviceArray views (valid until the next solve)"""
+        px, ps, pz = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().chip_solver_get_solution_dev(self._h, C.byref(px), C.byref(ps), C.byref(pz)),
+               "chip_solver_get_solution_dev")
+        return (DeviceArray.view(px.value, self.n), DeviceArray.view(ps.value, self.m),
+                DeviceArray.view(pz.value, self.m))
+
+    def equilibration(self):
+        """DefaultEquilibrationData: (d, e, c)"""
+        d, e, c = np.zeros(self.n), np.zeros(self.m), C.c_double()
+        _check(lib().chip_solver_get_equilibration(self._h, _pf(d), _pf(e), C.byref(c)),
+               "chip_solver_get_equilibration")
+        return d, e, c.value
+
+
+# ---------------------------------------------------------------------------
 # sharded path (SURVEY.md 8e): RCCL communicator of the C ABI (csrc/comm.cpp)
 # ---------------------------------------------------------------------------
 COMM_ID_BYTES = 128

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "equilibrate.hpp"
 
 using namespace chip;
 
@@ -107,6 +108,7 @@ struct chip_kktsystem {
            *work_conic = nullptr, *wn = nullptr, *workx2 = nullptr, *wn2 = nullptr, *negq = nullptr;
     dev::DotBatch batch{}; // dot products queued for ONE launch pair (flushed by read_dots)
     double *dots = nullptr, *scratch = nullptr; // 16 result slots + reduction scratch
+    double *scratch_w = nullptr;                // weighted norms of the L4 solver (allocated on first use)
     double hdots[16];
 
     void spmv(const SpMat &M, double *y, const double *aux, double alpha, const double *x) {
@@ -376,8 +378,11 @@ int32_t chip_residuals_update(chip_kktsystem *h, const chip_vars *var, double *r
                               double *rz_inf, double *Px, double out5[5]) {
     return chip_residuals_update_norms(h, var, rx, rz, rx_inf, rz_inf, Px, out5, nullptr);
 }
-int32_t chip_residuals_update_norms(chip_kktsystem *h, const chip_vars *var, double *rx, double *rz, double *rx_inf,
-                                    double *rz_inf, double *Px, double out5[5], double *norms5) {
+// the residual pass behind chip_residuals_update_norms and the L4 solver's residuals_update_wnorms: the weighted
+// norms of `wn` (slots 0-7 of the dot buffer) are reduced after the residual vectors and before the one copy
+static int residuals_pass(chip_kktsystem *h, const chip_vars *var, double *rx, double *rz, double *rx_inf,
+                          double *rz_inf, double *Px, double out5[5], double *norms5, const dev::WNormBatch *wn,
+                          double *wsq) {
     if (!h || !var || !out5) return CHIP_ERR_ARG;
     CHIP_HIP(hipSetDevice(h->device));
     const int n = h->n, m = h->m;
@@ -402,9 +407,12 @@ int32_t chip_residuals_update_norms(chip_kktsystem *h, const chip_vars *var, dou
         h->dot(3, rz, rz, m);
         h->dot(4, rx, rx, n);
     }
+    if (wn) dev::wnorm_batch(s, *wn, h->dots, h->scratch_w);
     if ((rc = h->read_dots())) return rc;
     if (norms5)
         for (int k = 0; k < 5; k++) norms5[k] = std::sqrt(h->hdots[k]);
+    if (wn)
+        for (int k = 0; k < wn->count; k++) wsq[k] = h->hdots[wn->s[k].slot];
     const double qx = h->hdots[8], bz = h->hdots[9], sz = h->hdots[10], xPx = h->nnzP ? h->hdots[11] : 0.0;
     out5[0] = qx + bz + var->kappa + xPx / var->tau;
     out5[1] = qx;
@@ -412,6 +420,21 @@ int32_t chip_residuals_update_norms(chip_kktsystem *h, const chip_vars *var, dou
     out5[3] = sz;
     out5[4] = xPx;
     return CHIP_OK;
+}
+int32_t chip_residuals_update_norms(chip_kktsystem *h, const chip_vars *var, double *rx, double *rz, double *rx_inf,
+                                    double *rz_inf, double *Px, double out5[5], double *norms5) {
+    return residuals_pass(h, var, rx, rz, rx_inf, rz_inf, Px, out5, norms5, nullptr, nullptr);
+}
+int chip::residuals_update_wnorms(chip_kktsystem *h, const chip_vars *var, double *rx, double *rz, double *rx_inf,
+                                  double *rz_inf, double *Px, double out5[5], const dev::WNormBatch *wn, double *wsq) {
+    if (!h || !wn || !wsq || wn->count > dev::WNORM_MAX) return CHIP_ERR_ARG;
+    if (!h->scratch_w) {
+        int rc = h->pool.alloc(&h->scratch_w, (size_t)dev::wnorm_scratch_doubles());
+        if (rc) return rc;
+    }
+    for (int k = 0; k < wn->count; k++)
+        if (wn->s[k].slot < 0 || wn->s[k].slot > 7) return CHIP_ERR_ARG;
+    return residuals_pass(h, var, rx, rz, rx_inf, rz_inf, Px, out5, nullptr, wn, wsq);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,0 +1,608 @@
+// solver.cpp -- L4 of the C ABI: DefaultSolver::new(P, q, A, b, cones, settings).solve() on one GPU.
+//   setup: DefaultProblemData::new + equilibrate (default/problemdata.rs:86-312) with the data on the device
+//          (equilibrate.hip), then the L2 / L3 handles built from the equilibrated values;
+//   solve: the interior-point loop of core/solver.rs:242-464 over the L3 entry points, with DefaultInfo's update /
+//          check_termination / post_process (default/info.rs:80-389) and DefaultSolution::post_process
+//          (default/solution.rs:68-111) on the host: only scalars cross the boundary per iteration.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <memory>
+#include <vector>
+
+#include "engine.hpp"
+#include "equilibrate.hpp"
+
+using namespace chip;
+
+namespace {
+
+int fails(int code, const std::string &msg) {
+    set_error(msg);
+    return code;
+}
+
+double now_s() {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+enum { PRIMAL_DUAL = 0, DUAL = 1 }; // ScalingStrategy (core/solver.rs:77-80)
+
+struct DevBuf {
+    std::vector<void *> ptrs;
+    template <typename T> int alloc(T **dst, size_t n) {
+        void *p = nullptr;
+        CHIP_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+        ptrs.push_back(p);
+        *dst = (T *)p;
+        return CHIP_OK;
+    }
+    template <typename T> int upload(T **dst, const T *src, size_t n) {
+        int rc = alloc(dst, n);
+        if (rc) return rc;
+        if (n) CHIP_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+        return CHIP_OK;
+    }
+    ~DevBuf() {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+};
+
+// the scalars of DefaultInfo (default/info.rs:12-64) the loop reads and writes
+struct InfoState {
+    double cost_primal = 0, cost_dual = 0, res_primal = 0, res_dual = 0, res_primal_inf = 0, res_dual_inf = 0;
+    double gap_abs = 0, gap_rel = 0, ktratio = 0;
+    double prev_cost_primal = 0, prev_cost_dual = 0, prev_res_primal = 0, prev_res_dual = 0, prev_gap_abs = 0,
+           prev_gap_rel = 0;
+    double solve_time = 0;
+    int iterations = 0;
+    int status = CHIP_SOLVER_UNSOLVED;
+};
+
+bool is_infeasible(int s) {
+    return s == CHIP_SOLVER_PRIMAL_INFEASIBLE || s == CHIP_SOLVER_DUAL_INFEASIBLE ||
+           s == CHIP_SOLVER_ALMOST_PRIMAL_INFEASIBLE || s == CHIP_SOLVER_ALMOST_DUAL_INFEASIBLE;
+}
+
+} // namespace
+
+struct chip_solver {
+    int n = 0, m = 0, device = 0;
+    chip_solver_settings st{};
+    DevBuf mem;
+    // the problem data: patterns in coordinate form, equilibrated values, scalings
+    dev::EqMats M{};
+    double *q = nullptr, *b = nullptr, *d = nullptr, *e = nullptr, *dinv = nullptr, *einv = nullptr;
+    double c = 1.0, normq = 0.0, normb = 0.0;
+    chip_kkt *kkt = nullptr;
+    chip_kktsystem *sys = nullptr;
+    hipStream_t stream = nullptr;
+    bool symmetric = true, allows_primal_dual = true;
+    int64_t degree = 0;
+    chip_vars vars{}, lhs{}, rhs{}, prev{};
+    double *rx = nullptr, *rz = nullptr, *rx_inf = nullptr, *rz_inf = nullptr, *Pxv = nullptr;
+    double *xo = nullptr, *so = nullptr, *zo = nullptr; // the unscaled solution
+    InfoState info;
+    double setup_time = 0, equilibration_time = 0, iteration_time = 0;
+    double obj_val = 0, obj_val_dual = 0;
+    bool solved_once = false;
+
+    ~chip_solver() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        chip_kktsystem_destroy(sys);
+        chip_kkt_destroy(kkt);
+    }
+    int alloc_vars(chip_vars &v) {
+        int rc;
+        if ((rc = mem.alloc(&v.x, (size_t)n)) || (rc = mem.alloc(&v.z, (size_t)m)) || (rc = mem.alloc(&v.s, (size_t)m)))
+            return rc;
+        v.tau = v.kappa = 1.0;
+        return CHIP_OK;
+    }
+    int copy_vars(chip_vars &dst, const chip_vars &src) {
+        if (n) CHIP_HIP(hipMemcpyAsync(dst.x, src.x, (size_t)n * 8, hipMemcpyDeviceToDevice, stream));
+        if (m) CHIP_HIP(hipMemcpyAsync(dst.z, src.z, (size_t)m * 8, hipMemcpyDeviceToDevice, stream));
+        if (m) CHIP_HIP(hipMemcpyAsync(dst.s, src.s, (size_t)m * 8, hipMemcpyDeviceToDevice, stream));
+        dst.tau = src.tau;
+        dst.kappa = src.kappa;
+        return CHIP_OK;
+    }
+    int equilibrate(const std::vector<ConeSpec> &cones);
+    int default_start();
+    int residuals_and_info();
+    bool check_termination(int iter);
+    void check_convergence(bool almost);
+    int backtrack_step_to_barrier(double alpha_init, double *alpha_out);
+    int post_process();
+    double out5[5] = {0, 0, 0, 0, 0}; // r_tau, dot_qx, dot_bz, dot_sz, dot_xPx of the last residual update
+    double t_solve0 = 0;
+};
+
+void chip_solver_settings_default(chip_solver_settings *s) {
+    std::memset(s, 0, sizeof(*s));
+    chip_settings_default(&s->linsys);
+    s->max_iter = 200;
+    s->time_limit = std::numeric_limits<double>::infinity();
+    s->max_step_fraction = 0.99;
+    s->tol_gap_abs = 1e-8;
+    s->tol_gap_rel = 1e-8;
+    s->tol_feas = 1e-8;
+    s->tol_infeas_abs = 1e-8;
+    s->tol_infeas_rel = 1e-8;
+    s->tol_ktratio = 1e-6;
+    s->reduced_tol_gap_abs = 5e-5;
+    s->reduced_tol_gap_rel = 5e-5;
+    s->reduced_tol_feas = 1e-4;
+    s->reduced_tol_infeas_abs = 5e-12;
+    s->reduced_tol_infeas_rel = 5e-5;
+    s->reduced_tol_ktratio = 1e-4;
+    s->equilibrate_enable = 1;
+    s->equilibrate_max_iter = 10;
+    s->equilibrate_min_scaling = 1e-4;
+    s->equilibrate_max_scaling = 1e4;
+    s->linesearch_backtrack_step = 0.8;
+    s->min_switch_step_length = 0.1;
+    s->min_terminate_step_length = 1e-4;
+}
+
+// DefaultProblemData::equilibrate (problemdata.rs:231-312): every Ruiz step enqueued without a host synchronisation,
+// c on the device until the end
+int chip_solver::equilibrate(const std::vector<ConeSpec> &cones) {
+    std::vector<double> ones((size_t)std::max(n, m), 1.0);
+    if (n) CHIP_HIP(hipMemcpy(d, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    if (m) CHIP_HIP(hipMemcpy(e, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
+    c = 1.0;
+    if (!st.equilibrate_enable) {
+        if (n) CHIP_HIP(hipMemcpy(dinv, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+        if (m) CHIP_HIP(hipMemcpy(einv, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
+        return CHIP_OK;
+    }
+    DevBuf work;
+    unsigned long long *bits = nullptr;
+    double *partials = nullptr, *cstate = nullptr, *delta = nullptr;
+    const size_t nbits = dev::eq_bits_words(n, m);
+    int rc;
+    if ((rc = work.alloc(&bits, nbits)) || (rc = work.alloc(&partials, (size_t)dev::eq_cost_partials())) ||
+        (rc = work.alloc(&cstate, 2)) || (rc = work.alloc(&delta, (size_t)m)))
+        return rc;
+    hipStream_t s = nullptr;
+    CHIP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    const double c0[2] = {1.0, 1.0};
+    hipError_t err = hipMemcpyAsync(cstate, c0, sizeof(c0), hipMemcpyHostToDevice, s);
+    for (int it = 0; err == hipSuccess && it < st.equilibrate_max_iter; it++) {
+        err = hipMemsetAsync(bits, 0, nbits * sizeof(unsigned long long), s);
+        if (err == hipSuccess)
+            dev::eq_ruiz_step(s, M, q, b, d, e, n, m, bits, partials, cstate, st.equilibrate_min_scaling,
+                              st.equilibrate_max_scaling);
+    }
+    // rectification (compositecone.rs:183-195): SOC, PSDTriangle, Exp, Pow, GenPow take mean(e) / e over their range
+    std::vector<int> sb, se;
+    for (const ConeSpec &cs : cones)
+        if (cs.tag >= CHIP_CONE_SECONDORDER && cs.numel > 0) {
+            sb.push_back((int)cs.start);
+            se.push_back((int)(cs.start + cs.numel));
+        }
+    int *dsb = nullptr, *dse = nullptr;
+    if (err == hipSuccess && !sb.empty()) {
+        if ((rc = work.upload(&dsb, sb.data(), sb.size())) || (rc = work.upload(&dse, se.data(), se.size()))) {
+            (void)hipStreamDestroy(s);
+            return rc;
+        }
+        dev::eq_rectify(s, M, b, e, m, dsb, dse, (int)sb.size(), delta);
+    }
+    if (err == hipSuccess) dev::eq_invert(s, d, dinv, n, e, einv, m);
+    double hc[2] = {1.0, 1.0};
+    if (err == hipSuccess) err = hipMemcpyAsync(hc, cstate, sizeof(hc), hipMemcpyDeviceToHost, s);
+    if (err == hipSuccess) err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+    if (err != hipSuccess) return fails(CHIP_ERR_HIP, hip_err(err, "equilibrate"));
+    c = hc[0];
+    return CHIP_OK;
+}
+
+int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval,
+                           const double *Pnzval, const double *q, const uint64_t *Acolptr, const uint64_t *Arowval,
+                           const double *Anzval, const double *b, int64_t ncones, const int32_t *cone_tags,
+                           const int64_t *cone_dims, const int64_t *cone_dims2, const double *cone_alphas_or_null,
+                           const double *genpow_alphas_or_null, const chip_solver_settings *settings) {
+    if (!out || n < 0 || m < 0 || !Pcolptr || !Acolptr || ncones < 0 || (ncones && (!cone_tags || !cone_dims)))
+        return fails(CHIP_ERR_ARG, "chip_solver_create: bad argument");
+    *out = nullptr;
+    const double t0 = now_s();
+    std::unique_ptr<chip_solver> h(new chip_solver());
+    if (settings) h->st = *settings;
+    else chip_solver_settings_default(&h->st);
+    chip_solver_settings &st = h->st;
+    st.linsys.linesearch_backtrack_step = st.linesearch_backtrack_step;
+    st.linsys.min_terminate_step_length = st.min_terminate_step_length;
+    if (st.linsys.device == CHIP_DEVICE_HOST_ONLY || chip_device_count() < 1)
+        return fails(CHIP_ERR_NO_DEVICE, "chip_solver_create: no HIP device (the product has no CPU fallback)");
+    const uint64_t nnzP = Pcolptr[n], nnzA = Acolptr[n];
+    if ((nnzP && (!Prowval || !Pnzval)) || (nnzA && (!Arowval || !Anzval)) || (n && !q) || (m && !b))
+        return fails(CHIP_ERR_ARG, "chip_solver_create: missing data");
+    // the entry-parallel passes of equilibrate.hip index P and A together, and A with b / e, in int32
+    if (nnzP + nnzA + (uint64_t)n + (uint64_t)m >= (1ull << 31) || n + 2 * m >= (1ll << 31))
+        return fails(CHIP_ERR_DIM, "chip_solver_create: sizes out of int32 range");
+    std::vector<ConeSpec> cones;
+    int64_t mm = 0, p = 0, nHs = 0;
+    if (build_cone_specs(ncones, cone_tags, cone_dims, cone_dims2, cones, mm, p, nHs))
+        return fails(CHIP_ERR_ARG, "chip_solver_create: bad cone");
+    if (mm != m) return fails(CHIP_ERR_DIM, "chip_solver_create: cone dimensions do not add up to m");
+    h->n = (int)n;
+    h->m = (int)m;
+    if (st.linsys.device >= 0) CHIP_HIP(hipSetDevice(st.linsys.device));
+    CHIP_HIP(hipGetDevice(&h->device));
+    // ---- the data (problemdata.rs:86-160): b capped at the reference's infinity, norms of the unequilibrated q, b
+    std::vector<int> Prow(nnzP), Pcol(nnzP), Arow(nnzA), Acol(nnzA);
+    for (int64_t j = 0; j < n; j++) {
+        for (uint64_t k = Pcolptr[j]; k < Pcolptr[j + 1]; k++) {
+            if ((int64_t)Prowval[k] > j) return fails(CHIP_ERR_NOT_TRIU, "P is not upper triangular");
+            Prow[k] = (int)Prowval[k];
+            Pcol[k] = (int)j;
+        }
+        for (uint64_t k = Acolptr[j]; k < Acolptr[j + 1]; k++) {
+            if ((int64_t)Arowval[k] >= m) return fails(CHIP_ERR_DIM, "A row index out of range");
+            Arow[k] = (int)Arowval[k];
+            Acol[k] = (int)j;
+        }
+    }
+    std::vector<double> bcap(b, b + m);
+    for (double &v : bcap) v = std::min(v, 1e20); // problemdata.rs:125-127 (get_infinity)
+    double nq = 0.0, nb = 0.0;
+    for (int64_t j = 0; j < n; j++) nq = std::isnan(q[j]) ? q[j] : std::max(nq, std::fabs(q[j]));
+    for (double v : bcap) nb = std::isnan(v) ? v : std::max(nb, std::fabs(v));
+    h->normq = nq;
+    h->normb = nb;
+    DevBuf &mem = h->mem;
+    int rc;
+    dev::EqMats &M = h->M;
+    int *dPr, *dPc, *dAr, *dAc;
+    if ((rc = mem.upload(&dPr, Prow.data(), nnzP)) || (rc = mem.upload(&dPc, Pcol.data(), nnzP)) ||
+        (rc = mem.upload(&M.Px, Pnzval, nnzP)) || (rc = mem.upload(&dAr, Arow.data(), nnzA)) ||
+        (rc = mem.upload(&dAc, Acol.data(), nnzA)) || (rc = mem.upload(&M.Ax, Anzval, nnzA)) ||
+        (rc = mem.upload(&h->q, q, (size_t)n)) || (rc = mem.upload(&h->b, bcap.data(), (size_t)m)))
+        return rc;
+    M.Prow = dPr;
+    M.Pcol = dPc;
+    M.Arow = dAr;
+    M.Acol = dAc;
+    M.nnzP = (int)nnzP;
+    M.nnzA = (int)nnzA;
+    if ((rc = mem.alloc(&h->d, (size_t)n)) || (rc = mem.alloc(&h->e, (size_t)m)) || (rc = mem.alloc(&h->dinv, (size_t)n)) ||
+        (rc = mem.alloc(&h->einv, (size_t)m)))
+        return rc;
+    const double te = now_s();
+    if ((rc = h->equilibrate(cones))) return rc;
+    h->equilibration_time = now_s() - te;
+    // ---- the KKT system of the equilibrated data: one copy of the scaled values to the host, then L2 / L3 as built
+    // from host arrays (the patterns do not change)
+    std::vector<double> Px(nnzP), Ax(nnzA), qs(n), bs(m);
+    if (nnzP) CHIP_HIP(hipMemcpy(Px.data(), M.Px, nnzP * 8, hipMemcpyDeviceToHost));
+    if (nnzA) CHIP_HIP(hipMemcpy(Ax.data(), M.Ax, nnzA * 8, hipMemcpyDeviceToHost));
+    if (n) CHIP_HIP(hipMemcpy(qs.data(), h->q, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (m) CHIP_HIP(hipMemcpy(bs.data(), h->b, (size_t)m * 8, hipMemcpyDeviceToHost));
+    if ((rc = chip_kkt_create(&h->kkt, n, m, Pcolptr, Prowval, Px.data(), Acolptr, Arowval, Ax.data(), ncones,
+                              cone_tags, cone_dims, cone_dims2, cone_alphas_or_null, &st.linsys, nullptr)))
+        return rc;
+    const double *ga = genpow_alphas_or_null;
+    for (int64_t i = 0; i < ncones; i++) {
+        if (cone_tags[i] == CHIP_CONE_GENPOWER) {
+            if (!ga) return fails(CHIP_ERR_ARG, "chip_solver_create: GenPow cone without its powers");
+            if ((rc = chip_kkt_set_genpow_alpha(h->kkt, i, ga))) return rc;
+            ga += cone_dims[i];
+        }
+        if (cone_tags[i] == CHIP_CONE_EXPONENTIAL || cone_tags[i] == CHIP_CONE_POWER || cone_tags[i] == CHIP_CONE_GENPOWER)
+            h->symmetric = false;
+        if (cone_tags[i] == CHIP_CONE_GENPOWER) h->allows_primal_dual = false; // genpowcone.rs:96-98
+    }
+    if ((rc = chip_kktsystem_create(&h->sys, h->kkt, Pcolptr, Prowval, Px.data(), Acolptr, Arowval, Ax.data(),
+                                    qs.data(), bs.data())))
+        return rc;
+    h->stream = (hipStream_t)chip_kkt_stream(h->kkt);
+    if ((rc = chip_kkt_degree(h->kkt, &h->degree))) return rc;
+    if ((rc = h->alloc_vars(h->vars)) || (rc = h->alloc_vars(h->lhs)) || (rc = h->alloc_vars(h->rhs)) ||
+        (rc = h->alloc_vars(h->prev)))
+        return rc;
+    if ((rc = mem.alloc(&h->rx, (size_t)n)) || (rc = mem.alloc(&h->rz, (size_t)m)) ||
+        (rc = mem.alloc(&h->rx_inf, (size_t)n)) || (rc = mem.alloc(&h->rz_inf, (size_t)m)) ||
+        (rc = mem.alloc(&h->Pxv, (size_t)n)) || (rc = mem.alloc(&h->xo, (size_t)n)) ||
+        (rc = mem.alloc(&h->so, (size_t)m)) || (rc = mem.alloc(&h->zo, (size_t)m)))
+        return rc;
+    h->setup_time = now_s() - t0;
+    *out = h.release();
+    return CHIP_OK;
+}
+
+void chip_solver_destroy(chip_solver *h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    delete h;
+}
+
+// default_start (core/solver.rs:525-541)
+int chip_solver::default_start() {
+    int rc;
+    if (symmetric) {
+        // set_identity_scaling: the scaling at s = z = the cones' unit vector is the identity (W = I)
+        if ((rc = chip_kkt_unit_initialization_dev(kkt, rhs.z, rhs.s))) return rc;
+        if ((rc = chip_kkt_update_scaling_dev(kkt, rhs.z, rhs.z, 1.0, PRIMAL_DUAL)) < 0) return rc;
+        if ((rc = chip_kktsystem_update(sys)) < 0) return rc; // (the reference ignores the bool here)
+        if ((rc = chip_kktsystem_solve_initial_point(sys, &vars)) < 0) return rc;
+        return chip_variables_symmetric_initialization(sys, &vars);
+    }
+    return chip_variables_unit_initialization(sys, &vars);
+}
+
+// Residuals::update + calc_mu's dot + DefaultInfo::update (info.rs:113-178) with ONE device-to-host copy
+int chip_solver::residuals_and_info() {
+    dev::WNormBatch wn{};
+    const dev::WNormSpec specs[8] = {{vars.x, d, n, 0},     {vars.z, e, m, 1},   {vars.s, einv, m, 2},
+                                     {rx_inf, dinv, n, 3}, {Pxv, dinv, n, 4},   {rz_inf, einv, m, 5},
+                                     {rz, einv, m, 6},     {rx, dinv, n, 7}};
+    for (int k = 0; k < 8; k++) wn.s[k] = specs[k];
+    wn.count = 8;
+    double sq[8];
+    int rc = residuals_update_wnorms(sys, &vars, rx, rz, rx_inf, rz_inf, Pxv, out5, &wn, sq);
+    if (rc) return rc;
+    double nrm[8];
+    for (int k = 0; k < 8; k++) nrm[k] = std::sqrt(sq[k]);
+    const double tinv = 1.0 / vars.tau, cinv = 1.0 / c;
+    const double dot_qx = out5[1], dot_bz = out5[2], dot_xPx = out5[4];
+    const double xPx2 = dot_xPx * tinv * tinv / 2.0;
+    info.cost_primal = (dot_qx * tinv + xPx2) * cinv;
+    info.cost_dual = (-dot_bz * tinv - xPx2) * cinv;
+    double normx = nrm[0], normz = nrm[1] * cinv, norms = nrm[2];
+    info.res_primal_inf = (nrm[3] * cinv) / std::max(1.0, normz);
+    info.res_dual_inf = std::max(nrm[4] / std::max(1.0, normx), nrm[5] / std::max(1.0, normx + norms));
+    normx *= tinv;
+    normz *= tinv;
+    norms *= tinv;
+    info.res_primal = nrm[6] * tinv / std::max(1.0, normb + normx + norms);
+    info.res_dual = nrm[7] * tinv * cinv / std::max(1.0, normq + normx + normz);
+    info.gap_abs = std::fabs(info.cost_primal - info.cost_dual);
+    info.gap_rel = info.gap_abs / std::max(1.0, std::min(std::fabs(info.cost_primal), std::fabs(info.cost_dual)));
+    info.ktratio = vars.kappa * tinv;
+    info.solve_time = setup_time + (now_s() - t_solve0);
+    return CHIP_OK;
+}
+
+// check_convergence_full / _almost (info.rs:277-389)
+void chip_solver::check_convergence(bool almost) {
+    const double tga = almost ? st.reduced_tol_gap_abs : st.tol_gap_abs;
+    const double tgr = almost ? st.reduced_tol_gap_rel : st.tol_gap_rel;
+    const double tf = almost ? st.reduced_tol_feas : st.tol_feas;
+    const double tia = almost ? st.reduced_tol_infeas_abs : st.tol_infeas_abs;
+    const double tir = almost ? st.reduced_tol_infeas_rel : st.tol_infeas_rel;
+    const double tkt = almost ? st.reduced_tol_ktratio : st.tol_ktratio;
+    const double dot_qx = out5[1], dot_bz = out5[2];
+    if (info.ktratio <= 1.0 && (info.gap_abs < tga || info.gap_rel < tgr) && info.res_primal < tf && info.res_dual < tf) {
+        info.status = almost ? CHIP_SOLVER_ALMOST_SOLVED : CHIP_SOLVER_SOLVED;
+    } else if (info.ktratio > (1.0 / tkt) * 1000.0) {
+        if (dot_bz < -tia && info.res_primal_inf < -tir * dot_bz)
+            info.status = almost ? CHIP_SOLVER_ALMOST_PRIMAL_INFEASIBLE : CHIP_SOLVER_PRIMAL_INFEASIBLE;
+        else if (dot_qx < -tia && info.res_dual_inf < -tir * dot_qx)
+            info.status = almost ? CHIP_SOLVER_ALMOST_DUAL_INFEASIBLE : CHIP_SOLVER_DUAL_INFEASIBLE;
+    }
+}
+
+// check_termination (info.rs:182-231)
+bool chip_solver::check_termination(int iter) {
+    check_convergence(false);
+    if (info.status == CHIP_SOLVER_UNSOLVED && iter > 1 &&
+        (info.res_dual > info.prev_res_dual || info.res_primal > info.prev_res_primal)) {
+        if (info.ktratio < std::numeric_limits<double>::epsilon() * 100.0 &&
+            (info.prev_gap_abs < st.tol_gap_abs || info.prev_gap_rel < st.tol_gap_rel))
+            info.status = CHIP_SOLVER_INSUFFICIENT_PROGRESS;
+        if (info.ktratio < 1.0) {
+            if ((info.res_dual > st.tol_feas * 100.0 && info.res_dual > info.prev_res_dual * 100.0) ||
+                (info.res_primal > st.tol_feas * 100.0 && info.res_primal > info.prev_res_primal * 100.0))
+                info.status = CHIP_SOLVER_INSUFFICIENT_PROGRESS;
+        }
+    }
+    if (info.status == CHIP_SOLVER_UNSOLVED) {
+        if (st.max_iter == info.iterations) info.status = CHIP_SOLVER_MAX_ITERATIONS;
+        else if (info.solve_time > st.time_limit) info.status = CHIP_SOLVER_MAX_TIME;
+    }
+    return info.status != CHIP_SOLVER_UNSOLVED;
+}
+
+// backtrack_step_to_barrier (core/solver.rs:571-584)
+int chip_solver::backtrack_step_to_barrier(double alpha_init, double *alpha_out) {
+    double alpha = alpha_init;
+    for (int k = 0; k < 50; k++) {
+        double barrier = 0.0;
+        int rc = chip_variables_barrier(sys, &vars, &lhs, alpha, &barrier);
+        if (rc) return rc;
+        if (barrier < 1.0) break;
+        alpha *= st.linesearch_backtrack_step;
+    }
+    *alpha_out = alpha;
+    return CHIP_OK;
+}
+
+// info.post_process (info.rs:95-105) + solution.post_process (solution.rs:68-111) with variables.unscale
+int chip_solver::post_process() {
+    const int s = info.status;
+    if (s == CHIP_SOLVER_NUMERICAL_ERROR || s == CHIP_SOLVER_INSUFFICIENT_PROGRESS || s == CHIP_SOLVER_MAX_ITERATIONS ||
+        s == CHIP_SOLVER_MAX_TIME)
+        check_convergence(true);
+    const bool inf = is_infeasible(info.status);
+    obj_val = inf ? std::numeric_limits<double>::quiet_NaN() : info.cost_primal;
+    obj_val_dual = inf ? std::numeric_limits<double>::quiet_NaN() : info.cost_dual;
+    const double scaleinv = inf ? 1.0 / vars.kappa : 1.0 / vars.tau, cinv = 1.0 / c;
+    dev::unscale(stream, xo, vars.x, d, scaleinv, n, zo, vars.z, e, scaleinv * cinv, so, vars.s, einv, scaleinv, m);
+    CHIP_HIP(hipGetLastError());
+    CHIP_HIP(hipStreamSynchronize(stream));
+    info.solve_time = setup_time + (now_s() - t_solve0);
+    return CHIP_OK;
+}
+
+// IPSolver::solve (core/solver.rs:242-464)
+int32_t chip_solver_solve(chip_solver *h) {
+    if (!h) return CHIP_ERR_ARG;
+    CHIP_HIP(hipSetDevice(h->device));
+    InfoState &info = h->info;
+    info = InfoState(); // info.reset; the previous-iterate scalars start from the same values on every solve
+    h->t_solve0 = now_s();
+    int rc;
+    if ((rc = h->default_start()) < 0) return rc;
+    CHIP_HIP(hipStreamSynchronize(h->stream));
+    const double t_loop0 = now_s();
+    int scaling = h->allows_primal_dual ? PRIMAL_DUAL : DUAL;
+    int iter = 0;
+    double sigma = 1.0, alpha = 0.0, mu = 0.0;
+    const bool sym = h->symmetric;
+    const chip_solver_settings &st = h->st;
+    while (true) {
+        if ((rc = h->residuals_and_info())) return rc;
+        if ((rc = chip_variables_calc_mu(h->sys, &h->vars, h->out5[3], &mu))) return rc;
+        info.iterations = iter; // save_scalars
+        if (h->check_termination(iter)) {
+            // strategy_checkpoint_insufficient_progress (core/solver.rs:586-608)
+            if (info.status != CHIP_SOLVER_INSUFFICIENT_PROGRESS) break;
+            info.cost_primal = info.prev_cost_primal; // reset_to_prev_iterate (info.rs:244-253)
+            info.cost_dual = info.prev_cost_dual;
+            info.res_primal = info.prev_res_primal;
+            info.res_dual = info.prev_res_dual;
+            info.gap_abs = info.prev_gap_abs;
+            info.gap_rel = info.prev_gap_rel;
+            if ((rc = h->copy_vars(h->vars, h->prev))) return rc;
+            if (!sym && scaling == PRIMAL_DUAL) { // Update(s) => {scaling = s; continue}: alpha is kept here
+                info.status = CHIP_SOLVER_UNSOLVED; // (core/solver.rs:322), unlike the two checkpoints below
+                scaling = DUAL;
+                continue;
+            }
+            break;
+        }
+        // scale cones; the device verdict arrives with the KKT update below (strategy_checkpoint_is_scaling_success)
+        if ((rc = chip_kkt_update_scaling_dev(h->kkt, h->vars.s, h->vars.z, mu, scaling)) < 0) return rc;
+        iter++;
+        rc = chip_kktsystem_update(h->sys);
+        if (rc < 0) return rc;
+        bool ok = rc == 1;
+        if (!ok) {
+            const int sc = chip_kkt_scaling_ok(h->kkt);
+            if (sc < 0) return sc;
+            if (sc == 0) { // the reference stops before counting the iteration
+                iter--;
+                info.status = CHIP_SOLVER_NUMERICAL_ERROR;
+                break;
+            }
+        }
+        if ((rc = chip_variables_affine_step_rhs(h->sys, &h->rhs, h->rx, h->rz, h->out5[0], &h->vars))) return rc;
+        if (ok) {
+            rc = chip_kktsystem_solve(h->sys, &h->lhs, &h->rhs, &h->vars, CHIP_STEP_AFFINE);
+            if (rc < 0) return rc;
+            ok = rc == 1;
+        }
+        if (ok) {
+            if ((rc = chip_variables_calc_step_length(h->sys, &h->vars, &h->lhs, CHIP_STEP_AFFINE, st.max_step_fraction,
+                                                      &alpha)))
+                return rc;
+            sigma = std::pow(1.0 - alpha, 3);
+            const double mm = iter > 1 ? 1.0 : alpha;
+            if ((rc = chip_variables_combined_step_rhs(h->sys, &h->rhs, h->rx, h->rz, h->out5[0], &h->vars, &h->lhs,
+                                                       sigma, mu, mm)))
+                return rc;
+            rc = chip_kktsystem_solve(h->sys, &h->lhs, &h->rhs, &h->vars, CHIP_STEP_COMBINED);
+            if (rc < 0) return rc;
+            ok = rc == 1;
+        }
+        // strategy_checkpoint_numerical_error (core/solver.rs:610-628)
+        if (!ok) {
+            alpha = 0.0;
+            if (!sym && scaling == PRIMAL_DUAL) {
+                scaling = DUAL;
+                continue;
+            }
+            info.status = CHIP_SOLVER_NUMERICAL_ERROR;
+            break;
+        }
+        if ((rc = chip_variables_calc_step_length(h->sys, &h->vars, &h->lhs, CHIP_STEP_COMBINED, st.max_step_fraction,
+                                                  &alpha)))
+            return rc;
+        if (!sym && scaling == DUAL && (rc = h->backtrack_step_to_barrier(alpha, &alpha))) return rc;
+        // strategy_checkpoint_small_step (core/solver.rs:630-654)
+        if (!sym && scaling == PRIMAL_DUAL && alpha < st.min_switch_step_length) {
+            alpha = 0.0;
+            scaling = DUAL;
+            continue;
+        } else if (alpha <= std::max(0.0, st.min_terminate_step_length)) {
+            alpha = 0.0;
+            info.status = CHIP_SOLVER_INSUFFICIENT_PROGRESS;
+            break;
+        }
+        // save_prev_iterate (info.rs:233-242) + add_step (variables.rs:162-168): the new iterate is written into the
+        // previous iterate's buffers (the arithmetic of chip_variables_add_step) and the two sets swap, so keeping the
+        // previous iterate costs no copy
+        info.prev_cost_primal = info.cost_primal;
+        info.prev_cost_dual = info.cost_dual;
+        info.prev_res_primal = info.res_primal;
+        info.prev_res_dual = info.res_dual;
+        info.prev_gap_abs = info.gap_abs;
+        info.prev_gap_rel = info.gap_rel;
+        chip_vars &nv = h->prev, &v = h->vars, &st_ = h->lhs;
+        dev::waxpby(h->stream, nv.x, alpha, st_.x, 1.0, v.x, h->n);
+        dev::waxpby(h->stream, nv.s, alpha, st_.s, 1.0, v.s, h->m);
+        dev::waxpby(h->stream, nv.z, alpha, st_.z, 1.0, v.z, h->m);
+        CHIP_HIP(hipGetLastError());
+        nv.tau = v.tau;
+        nv.tau += alpha * st_.tau;
+        nv.kappa = v.kappa;
+        nv.kappa += alpha * st_.kappa;
+        std::swap(h->vars, h->prev);
+    }
+    h->iteration_time = now_s() - t_loop0;
+    if (alpha == 0.0) info.iterations = iter;
+    if ((rc = h->post_process())) return rc;
+    h->solved_once = true;
+    return CHIP_OK;
+}
+
+int32_t chip_solver_get_solution(chip_solver *h, double *x, double *s, double *z, chip_solution_info *out) {
+    if (!h) return CHIP_ERR_ARG;
+    CHIP_HIP(hipSetDevice(h->device));
+    if (h->solved_once) {
+        if (x && h->n) CHIP_HIP(hipMemcpy(x, h->xo, (size_t)h->n * 8, hipMemcpyDeviceToHost));
+        if (s && h->m) CHIP_HIP(hipMemcpy(s, h->so, (size_t)h->m * 8, hipMemcpyDeviceToHost));
+        if (z && h->m) CHIP_HIP(hipMemcpy(z, h->zo, (size_t)h->m * 8, hipMemcpyDeviceToHost));
+    } else {
+        if (x) std::fill(x, x + h->n, 0.0);
+        if (s) std::fill(s, s + h->m, 0.0);
+        if (z) std::fill(z, z + h->m, 0.0);
+    }
+    if (out) {
+        std::memset(out, 0, sizeof(*out));
+        out->status = h->solved_once ? h->info.status : CHIP_SOLVER_UNSOLVED;
+        out->iterations = h->info.iterations;
+        out->obj_val = h->obj_val;
+        out->obj_val_dual = h->obj_val_dual;
+        out->r_prim = h->info.res_primal;
+        out->r_dual = h->info.res_dual;
+        out->solve_time = h->info.solve_time;
+        out->setup_time = h->setup_time;
+        out->equilibration_time = h->equilibration_time;
+        out->iteration_time = h->iteration_time;
+    }
+    return CHIP_OK;
+}
+
+int32_t chip_solver_get_solution_dev(chip_solver *h, double **x_dev, double **s_dev, double **z_dev) {
+    if (!h) return CHIP_ERR_ARG;
+    if (x_dev) *x_dev = h->xo;
+    if (s_dev) *s_dev = h->so;
+    if (z_dev) *z_dev = h->zo;
+    return CHIP_OK;
+}
+
+int32_t chip_solver_get_equilibration(chip_solver *h, double *d, double *e, double *c) {
+    if (!h) return CHIP_ERR_ARG;
+    CHIP_HIP(hipSetDevice(h->device));
+    if (d && h->n) CHIP_HIP(hipMemcpy(d, h->d, (size_t)h->n * 8, hipMemcpyDeviceToHost));
+    if (e && h->m) CHIP_HIP(hipMemcpy(e, h->e, (size_t)h->m * 8, hipMemcpyDeviceToHost));
+    if (c) *c = h->c;
+    return CHIP_OK;
+}

@@ -512,6 +512,93 @@ int32_t chip_vec_norms(chip_kktsystem *h, int32_t count, const double *const *ve
                        double *out);
 
 /* ===========================================================================
+ * L4 -- the whole solve: DefaultSolver::new(P, q, A, b, cones, settings).solve()
+ * (src/solver/implementations/default/solver.rs, core/solver.rs:242-464) on one GPU, built on L3:
+ *   setup   ProblemData::new + equilibrate (default/problemdata.rs:231-312, Ruiz scaling and the cones'
+ *           rectification compositecone.rs:183-195) on the device, then chip_kkt / chip_kktsystem built from the
+ *           equilibrated values.  No presolve: rows with infinite bounds are NOT dropped (b is only capped at
+ *           1e20 like problemdata.rs:125-127); no chordal decomposition.
+ *   solve   default_start, DefaultInfo::update with the scaled norms (info.rs:113-178), check_termination with the
+ *           full and reduced tolerances and the poor-progress rules (info.rs:182-231, 277-389), the four strategy
+ *           checkpoints incl. reset_to_prev_iterate and the switch to the dual scaling for nonsymmetric cones
+ *           (core/solver.rs:586-680), backtrack_step_to_barrier, info.post_process and solution.post_process
+ *           (solution.rs:68-111).  Per iteration the host reads scalars only.
+ * A second chip_solver_solve restarts from default_start and returns the same answer.  No callbacks, no printing.
+ * ===========================================================================*/
+typedef struct chip_solver chip_solver;
+/* SolverStatus (core/solver.rs:19-45), same order */
+typedef enum {
+    CHIP_SOLVER_UNSOLVED = 0,
+    CHIP_SOLVER_SOLVED = 1,
+    CHIP_SOLVER_PRIMAL_INFEASIBLE = 2,
+    CHIP_SOLVER_DUAL_INFEASIBLE = 3,
+    CHIP_SOLVER_ALMOST_SOLVED = 4,
+    CHIP_SOLVER_ALMOST_PRIMAL_INFEASIBLE = 5,
+    CHIP_SOLVER_ALMOST_DUAL_INFEASIBLE = 6,
+    CHIP_SOLVER_MAX_ITERATIONS = 7,
+    CHIP_SOLVER_MAX_TIME = 8,
+    CHIP_SOLVER_NUMERICAL_ERROR = 9,
+    CHIP_SOLVER_INSUFFICIENT_PROGRESS = 10,
+    CHIP_SOLVER_CALLBACK_TERMINATED = 11 /* reserved: this library has no callbacks */
+} chip_solver_status;
+/* the DefaultSettings fields (settings.rs) the loop and the equilibration read; linsys = the CoreSettings of L1/L2
+ * plus the engine knobs (its line-search fields are overwritten by the two below) */
+typedef struct {
+    chip_settings linsys;
+    int32_t max_iter;                     /* 200 */
+    int32_t equilibrate_enable;           /* 1 */
+    double time_limit;                    /* +inf (seconds, setup included as in the reference's timers) */
+    double max_step_fraction;             /* 0.99 */
+    double tol_gap_abs, tol_gap_rel;      /* 1e-8, 1e-8 */
+    double tol_feas;                      /* 1e-8 */
+    double tol_infeas_abs, tol_infeas_rel;/* 1e-8, 1e-8 */
+    double tol_ktratio;                   /* 1e-6 */
+    double reduced_tol_gap_abs, reduced_tol_gap_rel;       /* 5e-5, 5e-5 */
+    double reduced_tol_feas;                               /* 1e-4 */
+    double reduced_tol_infeas_abs, reduced_tol_infeas_rel; /* 5e-12, 5e-5 */
+    double reduced_tol_ktratio;                            /* 1e-4 */
+    int32_t equilibrate_max_iter;         /* 10 */
+    int32_t reserved0;
+    double equilibrate_min_scaling;       /* 1e-4 */
+    double equilibrate_max_scaling;       /* 1e4 */
+    double linesearch_backtrack_step;     /* 0.8 */
+    double min_switch_step_length;        /* 0.1 */
+    double min_terminate_step_length;     /* 1e-4 */
+} chip_solver_settings;
+/* DefaultSolution's scalars (solution.rs) + DefaultInfo's timings */
+typedef struct {
+    int32_t status;            /* chip_solver_status */
+    int32_t iterations;
+    double obj_val, obj_val_dual; /* NaN for the infeasible statuses */
+    double r_prim, r_dual;
+    double solve_time;         /* seconds, setup included (info.rs:174-176) */
+    double setup_time;         /* seconds of chip_solver_create */
+    double equilibration_time; /* seconds of the device equilibration inside setup_time */
+    double iteration_time;     /* seconds of the interior-point iterations (solve_time without setup, default_start
+                                  and post-processing) */
+} chip_solution_info;
+/* DefaultSettings::default() -- no GPU touched */
+void chip_solver_settings_default(chip_solver_settings *s);
+/* P: n x n triu CSC, A: m x n CSC, cones as in chip_kkt_create; genpow_alphas: the powers of every GenPow cone
+ * concatenated in cone order (NULL when there is none).  Copies everything it needs.  No device (or a
+ * CHIP_DEVICE_HOST_ONLY setting): CHIP_ERR_NO_DEVICE -- there is no CPU fallback. */
+int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval,
+                           const double *Pnzval, const double *q, const uint64_t *Acolptr, const uint64_t *Arowval,
+                           const double *Anzval, const double *b, int64_t ncones, const int32_t *cone_tags,
+                           const int64_t *cone_dims, const int64_t *cone_dims2, const double *cone_alphas_or_null,
+                           const double *genpow_alphas_or_null, const chip_solver_settings *settings);
+void chip_solver_destroy(chip_solver *h);
+/* runs the interior-point loop; returns CHIP_OK (the outcome is the status of chip_solver_get_solution) or a
+ * negative chip_status when a HIP call failed */
+int32_t chip_solver_solve(chip_solver *h);
+/* host copies of the unscaled solution (any of x[n], s[m], z[m] may be NULL) and its scalars */
+int32_t chip_solver_get_solution(chip_solver *h, double *x, double *s, double *z, chip_solution_info *info);
+/* the same vectors on the device, owned by the handle (valid until the next solve or the destruction) */
+int32_t chip_solver_get_solution_dev(chip_solver *h, double **x_dev, double **s_dev, double **z_dev);
+/* the equilibration of DefaultEquilibrationData: d[n], e[m] (host copies, either may be NULL) and c */
+int32_t chip_solver_get_equilibration(chip_solver *h, double *d, double *e, double *c);
+
+/* ===========================================================================
  * Sharded path: one process per GPU, whole connected components of the elimination
  * forest per rank (BASELINE config 4: 1024 independent SOCPs, 128 per GPU at 8 GPUs).  Factorisation,
  * substitutions and refinement of a rank's blocks need no exchange; the exchange step is ONE RCCL
