@@ -828,6 +828,10 @@ class HipSolver:
         for c, a in zip([c for c in cones if c[0] == GenPowerConeT], gp):
             assert len(a) == c[1]
         gpa = _f(np.concatenate(gp)) if gp else None
+        # the patterns, for update()'s check_equal_sparsity
+        self._pattern = {"P": (P.m, P.n, P.colptr.copy(), P.rowval.copy()), "A": (A.m, A.n, A.colptr.copy(),
+                                                                                 A.rowval.copy())}
+        self._len = {"P": P.nnz, "A": A.nnz, "q": n, "b": m}
         self._h = C.c_void_p()
         _check(lib().chip_solver_create(C.byref(self._h), C.c_int64(n), C.c_int64(m), _pu(P.colptr), _pu(P.rowval),
                                         _pf(P.nzval), _pf(q), _pu(A.colptr), _pu(A.rowval), _pf(A.nzval), _pf(b),
@@ -864,6 +868,157 @@ class HipSolver:
         _check(lib().chip_solver_get_equilibration(self._h, _pf(d), _pf(e), C.byref(c)),
                "chip_solver_get_equilibration")
         return d, e, c.value
+
+    # ---- data updates (default/data_updating.rs, python/impl_default_py.rs:699) ------------------------------------
+    def update(self, P=None, q=None, A=None, b=None, settings=None):
+        """solver.update(P=..., q=..., A=..., b=..., settings=...): each piece may be a CscMatrix with the setup's
+        pattern (P, A), a full value vector, an (index, values) tuple, an empty vector (no-op) or torch tensors on the
+        GPU (float64 values, int64 index).  Every piece is classified before any is applied; they are then applied in
+        the order P, q, A, b, settings, and the first refusal raises ChipError (the pieces before it stay applied, as
+        in the reference)."""
+        forms = [(k, classify_update(k, v, self._len[k], self._pattern.get(k)))
+                 for k, v in (("P", P), ("q", q), ("A", A), ("b", b)) if v is not None]
+        for k, f in forms:
+            self._apply_update(k, f)
+        if settings is not None:
+            self.update_settings(settings)
+
+    def update_P(self, data):
+        self._apply_update("P", classify_update("P", data, self._len["P"], self._pattern["P"]))
+
+    def update_A(self, data):
+        self._apply_update("A", classify_update("A", data, self._len["A"], self._pattern["A"]))
+
+    def update_q(self, data):
+        self._apply_update("q", classify_update("q", data, self._len["q"]))
+
+    def update_b(self, data):
+        self._apply_update("b", classify_update("b", data, self._len["b"]))
+
+    def _apply_update(self, key, form):
+        kind = form[0]
+        if kind == "none":
+            return
+        if kind in ("full", "partial"):
+            idx, vals = form[1], form[2]
+            fn = getattr(lib(), "chip_problem_update_" + key)
+            _check(fn(self._h, None if idx is None else _pu(idx), _pf(vals), C.c_int64(len(vals))),
+                   "chip_problem_update_" + key)
+            return
+        import torch
+        idx, vals = form[1], form[2]
+        torch.cuda.current_stream(vals.device).synchronize()  # the values are written before the call reads them
+        fn = getattr(lib(), "chip_problem_update_%s_dev" % key)
+        _check(fn(self._h, None if idx is None else C.c_void_p(idx.data_ptr()), C.c_void_p(vals.data_ptr()),
+                  C.c_int64(vals.numel())), "chip_problem_update_%s_dev" % key)
+
+    def update_settings(self, settings=None, **kw):
+        """DefaultSolver::update_settings: a SolverSettings, or keyword overrides of the current settings
+        (linear-system fields go to .linsys).  An immutable field that differs raises ChipError(ERR_ARG) and the
+        settings stay as they were."""
+        new = SolverSettings.from_buffer_copy(settings if settings is not None else self.settings)
+        own = {f[0] for f in SolverSettings._fields_}
+        lin = {f[0] for f in Settings._fields_}
+        for k, v in kw.items():
+            if k not in own and k not in lin:
+                raise TypeError("update_settings: no setting named %r" % k)
+            setattr(new if k in own else new.linsys, k, v)
+        _check(lib().chip_problem_update_settings(self._h, C.byref(new)), "chip_problem_update_settings")
+        self.settings = new
+
+    def is_data_update_allowed(self):
+        allowed = C.c_int32()
+        _check(lib().chip_problem_update_allowed(self._h, C.byref(allowed)), "chip_problem_update_allowed")
+        return bool(allowed.value)
+
+    def scaled_data(self):
+        """solver.data as the solver holds it, after equilibration: (P.nzval, A.nzval, q, b)"""
+        Px, Ax = np.zeros(self._len["P"]), np.zeros(self._len["A"])
+        q, b = np.zeros(self.n), np.zeros(self.m)
+        _check(lib().chip_problem_get_scaled(self._h, _pf(Px), _pf(Ax), _pf(q), _pf(b)), "chip_problem_get_scaled")
+        return Px, Ax, q, b
+
+
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+def _host_array(x, what, integer):
+    """a host vector (list, numpy array, CPU torch tensor) -> 1-D numpy array; TypeError for a dtype the form does not
+    take (indices: integers; values: real numbers)"""
+    if _is_torch(x):
+        x = x.detach().numpy()
+    a = np.asarray(x)
+    if a.ndim != 1:
+        raise ChipError(ERR_DIM, "update %s: a 1-D vector is needed" % what)
+    if a.size == 0:
+        return a
+    if integer and a.dtype.kind not in "iu":
+        raise TypeError("update %s: indices must be integers, not %s" % (what, a.dtype))
+    if not integer and a.dtype.kind not in "iuf":
+        raise TypeError("update %s: values must be real numbers, not %s" % (what, a.dtype))
+    return a
+
+
+def classify_update(key, data, length, pattern=None):
+    """The form of one piece of update data (no GPU touched): ("none",), ("full", None, values),
+    ("partial", index, values) with host numpy arrays (uint64 / float64), or ("dev_full", None, values) /
+    ("dev_partial", index, values) with torch tensors on the GPU (int64 / float64, contiguous).  key: "P", "A", "q"
+    or "b"; length: nnz(P) / nnz(A) / n / m; pattern: (m, n, colptr, rowval) of P / A for a CscMatrix
+    (check_equal_sparsity).  ChipError(ERR_DIM) for a pattern that differs, a full vector of the wrong length or an
+    index / value count mismatch; TypeError for a dtype or kind the piece does not take."""
+    if data is None:
+        return ("none",)
+    if isinstance(data, CscMatrix):
+        if pattern is None:
+            raise TypeError("update %s: a vector, not a matrix" % key)
+        m, n, colptr, rowval = pattern
+        if (data.m, data.n) != (m, n) or not np.array_equal(data.colptr, colptr) or \
+                not np.array_equal(data.rowval, rowval):
+            raise ChipError(ERR_DIM, "update %s: the sparsity pattern differs from the setup's" % key)
+        data = data.nzval
+    if isinstance(data, tuple):
+        if len(data) != 2:
+            raise TypeError("update %s: an (index, values) tuple has two members" % key)
+        idx, vals = data
+        on_gpu = [_is_torch(a) and a.is_cuda for a in (idx, vals)]
+        if on_gpu[0] != on_gpu[1]:
+            raise TypeError("update %s: index and values must both be host arrays or both GPU tensors" % key)
+        if on_gpu[1]:
+            import torch
+            if idx.dtype != torch.int64 or vals.dtype != torch.float64:
+                raise TypeError("update %s: GPU index / values must be int64 / float64, not %s / %s"
+                                % (key, idx.dtype, vals.dtype))
+            if idx.dim() != 1 or vals.dim() != 1 or idx.numel() != vals.numel():
+                raise ChipError(ERR_DIM, "update %s: index and values differ in length" % key)
+            if vals.numel() == 0:
+                return ("none",)
+            return ("dev_partial", idx.contiguous(), vals.contiguous())
+        idx, vals = _host_array(idx, key, True), _host_array(vals, key, False)
+        if idx.size != vals.size:
+            raise ChipError(ERR_DIM, "update %s: index and values differ in length" % key)
+        if vals.size == 0:
+            return ("none",)
+        if idx.dtype.kind == "i" and np.any(idx < 0):
+            idx = np.where(idx < 0, np.iinfo(np.int64).max, idx)  # (refused by the library as out of range)
+        return ("partial", _u(idx), _f(vals))
+    if _is_torch(data) and data.is_cuda:
+        import torch
+        if data.dtype != torch.float64:
+            raise TypeError("update %s: GPU values must be float64, not %s" % (key, data.dtype))
+        if data.dim() != 1:
+            raise ChipError(ERR_DIM, "update %s: a 1-D vector is needed" % key)
+        if data.numel() == 0:
+            return ("none",)
+        if data.numel() != length:
+            raise ChipError(ERR_DIM, "update %s: %d values for %d entries" % (key, data.numel(), length))
+        return ("dev_full", None, data.contiguous())
+    vals = _host_array(data, key, False)
+    if vals.size == 0:
+        return ("none",)
+    if vals.size != length:
+        raise ChipError(ERR_DIM, "update %s: %d values for %d entries" % (key, vals.size, length))
+    return ("full", None, _f(vals))
 
 
 # ---------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 #include <memory>
 
 #include "engine.hpp"
+#include "problem_update.hpp"
 #include "../../include/clarabel_hip_testing.h"
 
 using namespace chip;
@@ -320,6 +321,16 @@ int kkt_note_exchange(::chip_kkt *h, hipStream_t comm_stream) {
     return CHIP_OK;
 }
 bool kkt_host_only(const ::chip_kkt *h) { return h->E.host_only; }
+// the L4 data updates (solver.cpp): K's device store only -- nothing reads the host mirror K.nzval after create but
+// chip_kkt_get_matrix and the host-array updates of this layer, which the L4 solver does not use
+int kkt_update_values_dev(::chip_kkt *h, int block, const double *src_dev, const int64_t *idx_dev, int k) {
+    Engine &E = h->E;
+    if (E.host_only) return fail(CHIP_ERR_NO_DEVICE, "host-only handle: no numeric work without a GPU");
+    dev::pu_scatter(E.stream, E.Kx, block == 0 ? h->mapP : h->mapA, src_dev, idx_dev, k);
+    CHIP_HIP(hipGetLastError());
+    return CHIP_OK;
+}
+void kkt_set_static_diag_max(::chip_kkt *h, double v) { h->static_diag_max = v; }
 } // namespace chip
 }
 

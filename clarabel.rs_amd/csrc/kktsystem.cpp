@@ -12,6 +12,7 @@
 
 #include "engine.hpp"
 #include "equilibrate.hpp"
+#include "problem_update.hpp"
 
 using namespace chip;
 
@@ -271,6 +272,24 @@ int32_t chip_kktsystem_update_data(chip_kktsystem *h, const double *P, const dou
     if (rc) return rc;
     if (P && (rc = chip_kkt_update_P(h->kkt, P))) return rc; // directldlkktsolver.rs:191-197
     if (A && (rc = chip_kkt_update_A(h->kkt, A))) return rc;
+    return CHIP_OK;
+}
+
+// the L4 data updates (solver.cpp): the same refresh from the solver's device arrays, enqueued without a host
+// synchronisation (the values are read in place, no staging)
+int chip::kktsystem_update_data_dev(chip_kktsystem *h, const double *P, const double *A, const double *q,
+                                    const double *b) {
+    if (P && h->nnzP) dev::gather_values(h->stream, h->Psym.val, P, h->Psym.map, (int)h->Psym.nnz);
+    if (A && h->nnzA) {
+        dev::gather_values(h->stream, h->Arow.val, A, h->Arow.map, (int)h->Arow.nnz);
+        dev::gather_values(h->stream, h->Acol.val, A, h->Acol.map, (int)h->Acol.nnz);
+    }
+    if (q && h->n) {
+        CHIP_HIP(hipMemcpyAsync(h->q, q, (size_t)h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        dev::waxpby(h->stream, h->negq, -1.0, h->q, 0.0, nullptr, h->n);
+    }
+    if (b && h->m) CHIP_HIP(hipMemcpyAsync(h->b, b, (size_t)h->m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    CHIP_HIP(hipGetLastError());
     return CHIP_OK;
 }
 

@@ -14,6 +14,7 @@
 
 #include "engine.hpp"
 #include "equilibrate.hpp"
+#include "problem_update.hpp"
 
 using namespace chip;
 
@@ -88,9 +89,19 @@ struct chip_solver {
     double setup_time = 0, equilibration_time = 0, iteration_time = 0;
     double obj_val = 0, obj_val_dual = 0;
     bool solved_once = false;
+    // the data updates (problem_update.hip), allocated by the first one: host-form staging (grown to the longest
+    // update), the last-occurrence scratch (-1 between updates), the index check's flag and the reductions
+    double *stage_v = nullptr;
+    int64_t *stage_i = nullptr;
+    size_t stage_cap = 0;
+    int *pos = nullptr, *flag = nullptr;
+    unsigned long long *npart = nullptr;
+    double *nout = nullptr;
 
     ~chip_solver() {
         if (stream) (void)hipStreamSynchronize(stream);
+        (void)hipFree(stage_v);
+        (void)hipFree(stage_i);
         chip_kktsystem_destroy(sys);
         chip_kkt_destroy(kkt);
     }
@@ -116,6 +127,8 @@ struct chip_solver {
     void check_convergence(bool almost);
     int backtrack_step_to_barrier(double alpha_init, double *alpha_out);
     int post_process();
+    int update_work();
+    int update(int which, const int64_t *idx_dev, const double *vals_dev, int k);
     double out5[5] = {0, 0, 0, 0, 0}; // r_tau, dot_qx, dot_bz, dot_sz, dot_xPx of the last residual update
     double t_solve0 = 0;
 };
@@ -604,5 +617,202 @@ int32_t chip_solver_get_equilibration(chip_solver *h, double *d, double *e, doub
     if (d && h->n) CHIP_HIP(hipMemcpy(d, h->d, (size_t)h->n * 8, hipMemcpyDeviceToHost));
     if (e && h->m) CHIP_HIP(hipMemcpy(e, h->e, (size_t)h->m * 8, hipMemcpyDeviceToHost));
     if (c) *c = h->c;
+    return CHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Data updates (default/data_updating.rs): new values on the fixed patterns, scaled with the equilibration of the
+// setup (d, e, c are never recomputed), written into the solver's arrays and from there, on the device, into K's
+// store, the L3 mirrors and vectors, with the norms and max |P_ii| that setup derived from the values.  The host forms
+// upload into the handle's staging and take the device path.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+enum { UPD_P = 0, UPD_A = 1, UPD_Q = 2, UPD_B = 3 };
+const char *const UPD_NAME[4] = {"chip_problem_update_P", "chip_problem_update_A", "chip_problem_update_q",
+                                 "chip_problem_update_b"};
+
+int64_t update_len(const chip_solver *h, int which) {
+    return which == UPD_P ? h->M.nnzP : which == UPD_A ? h->M.nnzA : which == UPD_Q ? h->n : h->m;
+}
+} // namespace
+
+int chip_solver::update_work() {
+    if (flag) return CHIP_OK;
+    const size_t len = (size_t)std::max({M.nnzP, M.nnzA, n, m});
+    int rc;
+    if ((rc = mem.alloc(&pos, len)) || (rc = mem.alloc(&npart, (size_t)dev::pu_norm_partials())) ||
+        (rc = mem.alloc(&nout, 3)) || (rc = mem.alloc(&flag, 1)))
+        return rc;
+    CHIP_HIP(hipMemset(pos, 0xff, std::max<size_t>(len, 1) * sizeof(int))); // every slot -1
+    return CHIP_OK;
+}
+
+// one update of P, A, q or b: idx_dev == nullptr is the full form (k == the length, checked by the caller)
+int chip_solver::update(int which, const int64_t *idx_dev, const double *vals_dev, int k) {
+    int rc;
+    if ((rc = update_work())) return rc;
+    const int64_t len = update_len(this, which);
+    hipStream_t s = stream;
+    if (idx_dev) { // the whole index list is checked before anything is written
+        int bad = 0;
+        CHIP_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
+        dev::pu_validate(s, idx_dev, k, len, flag);
+        CHIP_HIP(hipGetLastError());
+        CHIP_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, s));
+        CHIP_HIP(hipStreamSynchronize(s));
+        if (bad) return fails(CHIP_ERR_DIM, std::string(UPD_NAME[which]) + ": an index is out of range (nothing changed)");
+    }
+    dev::PuTarget t{};
+    switch (which) { // update_P / _A / _q / _b (data_updating.rs:96-170)
+    case UPD_P: t = {M.Px, (int)len, M.Prow, M.Pcol, d, d, c, true}; break;
+    case UPD_A: t = {M.Ax, (int)len, M.Arow, M.Acol, e, d, 1.0, false}; break;
+    case UPD_Q: t = {q, (int)len, nullptr, nullptr, d, nullptr, c, true}; break;
+    default: t = {b, (int)len, nullptr, nullptr, e, nullptr, 1.0, false}; break;
+    }
+    if (idx_dev) dev::pu_write_partial(s, t, idx_dev, vals_dev, k, pos);
+    else dev::pu_write_full(s, t, vals_dev);
+    CHIP_HIP(hipGetLastError());
+    // the copies the loop reads: K's values (only the touched entries of a partial update), the L3 mirrors and vectors
+    if (which == UPD_P || which == UPD_A) {
+        const double *src = which == UPD_P ? M.Px : M.Ax;
+        if ((rc = kkt_update_values_dev(kkt, which, src, idx_dev, idx_dev ? k : (int)len))) return rc;
+    }
+    if ((rc = kktsystem_update_data_dev(sys, which == UPD_P ? M.Px : nullptr, which == UPD_A ? M.Ax : nullptr,
+                                        which == UPD_Q ? q : nullptr, which == UPD_B ? b : nullptr)))
+        return rc;
+    // the scalars setup derived from the values: normq / normb as the lazy getters recompute them (problemdata.rs:
+    // 168-189) and max |P_ii| of the static regulariser; read back in the call's one synchronisation
+    const int mask = which == UPD_Q ? 1 : which == UPD_B ? 2 : which == UPD_P ? 4 : 0;
+    double hn[3] = {0, 0, 0};
+    if (mask) {
+        dev::pu_norms(s, mask, q, dinv, n, b, einv, m, M.Prow, M.Pcol, M.Px, M.nnzP, npart, nout);
+        CHIP_HIP(hipGetLastError());
+        CHIP_HIP(hipMemcpyAsync(hn, nout, sizeof(hn), hipMemcpyDeviceToHost, s));
+    }
+    CHIP_HIP(hipStreamSynchronize(s));
+    if (mask & 1) normq = hn[0] * (1.0 / c);
+    if (mask & 2) normb = hn[1];
+    if (mask & 4) kkt_set_static_diag_max(kkt, hn[2]);
+    return CHIP_OK;
+}
+
+namespace {
+// the checks shared by both forms: CHIP_ERR_ARG before any device is touched, k == 0 a no-op (returns 1)
+int update_args(chip_solver *h, int which, const void *idx, const double *vals, int64_t k) {
+    if (!h || k < 0 || (k > 0 && !vals)) return fails(CHIP_ERR_ARG, std::string(UPD_NAME[which]) + ": bad argument");
+    if (k == 0) return 1;
+    if (k >= (1ll << 31)) return fails(CHIP_ERR_DIM, std::string(UPD_NAME[which]) + ": more than 2^31 values");
+    if (!idx && k != update_len(h, which))
+        return fails(CHIP_ERR_DIM, std::string(UPD_NAME[which]) + ": the full form needs one value per entry");
+    return 0;
+}
+
+int update_host(chip_solver *h, int which, const uint64_t *idx, const double *vals, int64_t k) {
+    int rc = update_args(h, which, idx, vals, k);
+    if (rc) return rc < 0 ? rc : CHIP_OK;
+    CHIP_HIP(hipSetDevice(h->device));
+    if ((size_t)k > h->stage_cap) {
+        CHIP_HIP(hipStreamSynchronize(h->stream));
+        (void)hipFree(h->stage_v);
+        (void)hipFree(h->stage_i);
+        h->stage_v = nullptr;
+        h->stage_i = nullptr;
+        h->stage_cap = 0;
+        CHIP_HIP(hipMalloc(&h->stage_v, (size_t)k * sizeof(double)));
+        CHIP_HIP(hipMalloc(&h->stage_i, (size_t)k * sizeof(int64_t)));
+        h->stage_cap = (size_t)k;
+    }
+    CHIP_HIP(hipMemcpyAsync(h->stage_v, vals, (size_t)k * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    // (an index past 2^63 - 1 reads as negative and is refused like any other out-of-range index)
+    if (idx) CHIP_HIP(hipMemcpyAsync(h->stage_i, idx, (size_t)k * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    return h->update(which, idx ? h->stage_i : nullptr, h->stage_v, (int)k);
+}
+
+int update_dev(chip_solver *h, int which, const int64_t *idx, const double *vals, int64_t k) {
+    int rc = update_args(h, which, idx, vals, k);
+    if (rc) return rc < 0 ? rc : CHIP_OK;
+    CHIP_HIP(hipSetDevice(h->device));
+    return h->update(which, idx, vals, (int)k);
+}
+} // namespace
+
+int32_t chip_problem_update_P(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k) {
+    return update_host(h, UPD_P, index_or_null, values, k);
+}
+int32_t chip_problem_update_A(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k) {
+    return update_host(h, UPD_A, index_or_null, values, k);
+}
+int32_t chip_problem_update_q(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k) {
+    return update_host(h, UPD_Q, index_or_null, values, k);
+}
+int32_t chip_problem_update_b(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k) {
+    return update_host(h, UPD_B, index_or_null, values, k);
+}
+int32_t chip_problem_update_P_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
+    return update_dev(h, UPD_P, index_dev_or_null, values_dev, k);
+}
+int32_t chip_problem_update_A_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
+    return update_dev(h, UPD_A, index_dev_or_null, values_dev, k);
+}
+int32_t chip_problem_update_q_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
+    return update_dev(h, UPD_Q, index_dev_or_null, values_dev, k);
+}
+int32_t chip_problem_update_b_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
+    return update_dev(h, UPD_B, index_dev_or_null, values_dev, k);
+}
+
+// DefaultSolver::update_settings (core/solver.rs:207) with validate_as_update (settings.rs:307): the equilibration
+// fields as in the reference, and every field chip_kkt keeps its own copy of (all of linsys, with the two line-search
+// fields create copies into it)
+int32_t chip_problem_update_settings(chip_solver *h, const chip_solver_settings *settings) {
+    if (!h || !settings) return fails(CHIP_ERR_ARG, "chip_problem_update_settings: bad argument");
+    chip_solver_settings nw = *settings;
+    nw.linsys.linesearch_backtrack_step = nw.linesearch_backtrack_step;
+    nw.linsys.min_terminate_step_length = nw.min_terminate_step_length;
+    const chip_solver_settings &o = h->st;
+    const chip_settings &a = nw.linsys, &l = o.linsys;
+#define IMMUTABLE(cond, name) \
+    if (cond) return fails(CHIP_ERR_ARG, "chip_problem_update_settings: " name " cannot change after setup")
+    IMMUTABLE(nw.equilibrate_enable != o.equilibrate_enable, "equilibrate_enable");
+    IMMUTABLE(nw.equilibrate_max_iter != o.equilibrate_max_iter, "equilibrate_max_iter");
+    IMMUTABLE(std::memcmp(&nw.equilibrate_min_scaling, &o.equilibrate_min_scaling, 8), "equilibrate_min_scaling");
+    IMMUTABLE(std::memcmp(&nw.equilibrate_max_scaling, &o.equilibrate_max_scaling, 8), "equilibrate_max_scaling");
+    IMMUTABLE(std::memcmp(&nw.linesearch_backtrack_step, &o.linesearch_backtrack_step, 8), "linesearch_backtrack_step");
+    IMMUTABLE(std::memcmp(&nw.min_terminate_step_length, &o.min_terminate_step_length, 8), "min_terminate_step_length");
+#define IMMUTABLE_LIN(f) IMMUTABLE(std::memcmp(&a.f, &l.f, sizeof(a.f)), "linsys." #f)
+    IMMUTABLE_LIN(static_regularization_enable);
+    IMMUTABLE_LIN(static_regularization_constant);
+    IMMUTABLE_LIN(static_regularization_proportional);
+    IMMUTABLE_LIN(dynamic_regularization_enable);
+    IMMUTABLE_LIN(dynamic_regularization_eps);
+    IMMUTABLE_LIN(dynamic_regularization_delta);
+    IMMUTABLE_LIN(iterative_refinement_enable);
+    IMMUTABLE_LIN(iterative_refinement_reltol);
+    IMMUTABLE_LIN(iterative_refinement_abstol);
+    IMMUTABLE_LIN(iterative_refinement_max_iter);
+    IMMUTABLE_LIN(iterative_refinement_stop_ratio);
+    IMMUTABLE_LIN(device);
+    IMMUTABLE_LIN(amd_dense_scale);
+    IMMUTABLE_LIN(use_graph);
+#undef IMMUTABLE_LIN
+#undef IMMUTABLE
+    h->st = nw;
+    return CHIP_OK;
+}
+
+int32_t chip_problem_update_allowed(const chip_solver *h, int32_t *allowed) {
+    if (!h || !allowed) return fails(CHIP_ERR_ARG, "chip_problem_update_allowed: bad argument");
+    *allowed = 1; // no presolve, no chordal decomposition, no dropped structural zeros
+    return CHIP_OK;
+}
+
+int32_t chip_problem_get_scaled(chip_solver *h, double *Px, double *Ax, double *q, double *b) {
+    if (!h) return fails(CHIP_ERR_ARG, "chip_problem_get_scaled: bad argument");
+    CHIP_HIP(hipSetDevice(h->device));
+    CHIP_HIP(hipStreamSynchronize(h->stream));
+    if (Px && h->M.nnzP) CHIP_HIP(hipMemcpy(Px, h->M.Px, (size_t)h->M.nnzP * 8, hipMemcpyDeviceToHost));
+    if (Ax && h->M.nnzA) CHIP_HIP(hipMemcpy(Ax, h->M.Ax, (size_t)h->M.nnzA * 8, hipMemcpyDeviceToHost));
+    if (q && h->n) CHIP_HIP(hipMemcpy(q, h->q, (size_t)h->n * 8, hipMemcpyDeviceToHost));
+    if (b && h->m) CHIP_HIP(hipMemcpy(b, h->b, (size_t)h->m * 8, hipMemcpyDeviceToHost));
     return CHIP_OK;
 }

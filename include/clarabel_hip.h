@@ -598,6 +598,43 @@ int32_t chip_solver_get_solution_dev(chip_solver *h, double **x_dev, double **s_
 /* the equilibration of DefaultEquilibrationData: d[n], e[m] (host copies, either may be NULL) and c */
 int32_t chip_solver_get_equilibration(chip_solver *h, double *d, double *e, double *c);
 
+/* ---- data updates: DefaultSolver::update_P / update_A / update_q / update_b / update_settings
+ * (default/data_updating.rs, core/solver.rs:207) on a chip_solver handle.  The patterns are fixed; the new values are
+ * scaled with the equilibration of chip_solver_create (d, e and c are never recomputed), written into the solver's
+ * data and, on the device, into every copy the next solve reads.  The next chip_solver_solve restarts from
+ * default_start, as a second solve does.  Every update is allowed here: no presolve, no chordal decomposition, no
+ * dropped structural zeros.
+ *   full form     index == NULL: k must be nnz(P) / nnz(A) / n / m, else CHIP_ERR_DIM.
+ *                 P = (v * (d[row] * d[col])) * c, A = v * (e[row] * d[col])  (lrscale, then scale(c))
+ *   partial form  index != NULL: the reference's zip(index, values); a repeated index: the last occurrence wins.
+ *                 P = ((d[row] * d[col]) * c) * v, A = (e[row] * d[col]) * v  (the reference's order for Zip)
+ *   vectors       both forms: q = (v * d[i]) * c, b = v * e[i].  b is NOT capped at 1e20 here (the reference caps
+ *                 only in ProblemData::new).
+ *   k == 0        a no-op.
+ * An index >= the length (or negative, device form) gives CHIP_ERR_DIM and changes NOTHING -- stricter than the
+ * reference, which writes the entries before the bad one.  A refused call changes nothing.  A NULL handle, a NULL
+ * values pointer with k > 0 or k < 0 give CHIP_ERR_ARG without touching a device.  The stored norms of q and b
+ * (problemdata.rs:168-189) and max |P_ii| of the static regulariser are recomputed from the new scaled data. */
+int32_t chip_problem_update_P(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k);
+int32_t chip_problem_update_A(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k);
+int32_t chip_problem_update_q(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k);
+int32_t chip_problem_update_b(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k);
+/* the same with index / values in device memory (int64 indices: torch's index dtype).  The call returns once the
+ * device has consumed them; the caller must have finished writing them before the call. */
+int32_t chip_problem_update_P_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k);
+int32_t chip_problem_update_A_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k);
+int32_t chip_problem_update_q_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k);
+int32_t chip_problem_update_b_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k);
+/* DefaultSolver::update_settings with validate_as_update (settings.rs:307): CHIP_ERR_ARG, settings unchanged, when an
+ * immutable field differs -- equilibrate_enable / _max_iter / _min_scaling / _max_scaling as in the reference, and here
+ * also every field of linsys and linesearch_backtrack_step / min_terminate_step_length (the KKT handle keeps its own
+ * copy of them).  The rest (max_iter, time_limit, the tolerances, the step fractions) takes effect at the next solve. */
+int32_t chip_problem_update_settings(chip_solver *h, const chip_solver_settings *settings);
+/* DefaultSolver::is_data_update_allowed: always 1 here */
+int32_t chip_problem_update_allowed(const chip_solver *h, int32_t *allowed);
+/* solver.data as the solver holds it (P, A, q, b after equilibration): host copies, any pointer may be NULL */
+int32_t chip_problem_get_scaled(chip_solver *h, double *Px, double *Ax, double *q, double *b);
+
 /* ===========================================================================
  * Sharded path: one process per GPU, whole connected components of the elimination
  * forest per rank (BASELINE config 4: 1024 independent SOCPs, 128 per GPU at 8 GPUs).  Factorisation,
