@@ -44,9 +44,10 @@ P_I32 = C.POINTER(C.c_int32)
 # chip_status
 OK, ERR_DIM, ERR_EMPTY_COLUMN, ERR_NOT_TRIU, ERR_ZERO_PIVOT, ERR_BAD_PERM = 0, -1, -2, -3, -4, -5
 ERR_NOT_FACTORED, ERR_NO_DEVICE, ERR_HIP, ERR_ARG, ERR_UNSUPPORTED = -6, -7, -8, -9, -10
+ERR_UPDATE_NOT_ALLOWED = -11
 STATUS_NAMES = {0: "ok", -1: "IncompatibleDimension", -2: "EmptyColumn", -3: "NotUpperTriangular",
                 -4: "ZeroPivot", -5: "InvalidPermutation", -6: "NotFactored", -7: "NoDevice", -8: "HipError",
-                -9: "BadArgument", -10: "Unsupported"}
+                -9: "BadArgument", -10: "Unsupported", -11: "UpdateNotAllowed"}
 DEVICE_HOST_ONLY = -2
 
 # SupportedConeT tags
@@ -149,7 +150,14 @@ def _pf(a):
     return a.ctypes.data_as(P_F64)
 
 
+class UpdateNotAllowedError(ChipError):
+    """a data update refused because presolve or chordal decomposition changed the problem (the reference's
+    DataUpdateError::PresolveIsActive / ChordalDecompositionIsActive); code == ERR_UPDATE_NOT_ALLOWED"""
+
+
 def _check(rc, where):
+    if rc == ERR_UPDATE_NOT_ALLOWED:
+        raise UpdateNotAllowedError(rc, where)
     if rc < 0:
         raise ChipError(rc, where)
     return rc
@@ -766,21 +774,51 @@ class SolverSettings(C.Structure):
                 ("reduced_tol_ktratio", C.c_double), ("equilibrate_max_iter", C.c_int32), ("reserved0", C.c_int32),
                 ("equilibrate_min_scaling", C.c_double), ("equilibrate_max_scaling", C.c_double),
                 ("linesearch_backtrack_step", C.c_double), ("min_switch_step_length", C.c_double),
-                ("min_terminate_step_length", C.c_double)]
+                ("min_terminate_step_length", C.c_double), ("presolve_enable", C.c_int32),
+                ("chordal_decomposition_enable", C.c_int32), ("chordal_decomposition_merge_method", C.c_int32),
+                ("chordal_decomposition_compact", C.c_int32), ("chordal_decomposition_complete_dual", C.c_int32),
+                ("reserved1", C.c_int32)]
 
     @staticmethod
     def default(**kw):
         """DefaultSettings::default(); keyword arguments override fields (`device=` and the other linear-system
-        fields go to .linsys)"""
+        fields go to .linsys).  Unlike the reference, presolve_enable and chordal_decomposition_enable default to 0.
+        chordal_decomposition_merge_method takes the reference's strings ("none", "parent_child", "clique_graph") or
+        the MERGE_* values; another string raises ValueError (settings.rs validation)."""
         s = SolverSettings()
         lib().chip_solver_settings_default(C.byref(s))
-        own = {f[0] for f in SolverSettings._fields_}
-        lin = {f[0] for f in Settings._fields_}
-        for k, v in kw.items():
-            if k not in own and k not in lin:
-                raise TypeError("SolverSettings.default: no setting named %r" % k)
-            setattr(s if k in own else s.linsys, k, v)
+        _apply_settings(s, kw, "SolverSettings.default")
         return s
+
+
+# chordal_decomposition_merge_method (CHIP_MERGE_*)
+MERGE_NONE, MERGE_PARENT_CHILD, MERGE_CLIQUE_GRAPH = 0, 1, 2
+MERGE_METHODS = {"none": MERGE_NONE, "parent_child": MERGE_PARENT_CHILD, "clique_graph": MERGE_CLIQUE_GRAPH}
+
+
+def _apply_settings(s, kw, where):
+    own = {f[0] for f in SolverSettings._fields_}
+    lin = {f[0] for f in Settings._fields_}
+    for k, v in kw.items():
+        if k not in own and k not in lin:
+            raise TypeError("%s: no setting named %r" % (where, k))
+        if k == "chordal_decomposition_merge_method":
+            if isinstance(v, str):
+                if v not in MERGE_METHODS:
+                    raise ValueError("%s: unknown chordal_decomposition_merge_method %r (one of %s)"
+                                     % (where, v, ", ".join(sorted(MERGE_METHODS))))
+                v = MERGE_METHODS[v]
+            elif int(v) not in MERGE_METHODS.values():
+                raise ValueError("%s: unknown chordal_decomposition_merge_method %r" % (where, v))
+        setattr(s if k in own else s.linsys, k, v)
+
+
+class TransformInfo(C.Structure):
+    """chip_transform_info"""
+    _fields_ = [("m_full", C.c_int64), ("m_reduced", C.c_int64), ("n_internal", C.c_int64), ("m_internal", C.c_int64),
+                ("nnzA_internal", C.c_int64), ("psd_cones_decomposed", C.c_int64), ("psd_cones_added", C.c_int64),
+                ("psd_cones_added_premerge", C.c_int64), ("largest_clique", C.c_int64),
+                ("transform_time", C.c_double), ("completion_time", C.c_double)]
 
 
 class SolutionInfo(C.Structure):
@@ -846,7 +884,8 @@ class HipSolver:
             self._h = C.c_void_p()
 
     def solve(self):
-        """IPSolver::solve -> Solution (a second call restarts from default_start)"""
+        """IPSolver::solve -> Solution (a second call restarts from default_start).  x, s, z have the sizes of the
+        problem passed in, whatever presolve or chordal decomposition did."""
         _check(lib().chip_solver_solve(self._h), "chip_solver_solve")
         x, s, z = np.zeros(self.n), np.zeros(self.m), np.zeros(self.m)
         info = SolutionInfo()
@@ -863,8 +902,9 @@ class HipSolver:
                 DeviceArray.view(pz.value, self.m))
 
     def equilibration(self):
-        """DefaultEquilibrationData: (d, e, c)"""
-        d, e, c = np.zeros(self.n), np.zeros(self.m), C.c_double()
+        """DefaultEquilibrationData: (d, e, c) of the internal problem (n_internal, m_internal of transform_info)"""
+        t = self.transform_info()
+        d, e, c = np.zeros(t["n_internal"]), np.zeros(t["m_internal"]), C.c_double()
         _check(lib().chip_solver_get_equilibration(self._h, _pf(d), _pf(e), C.byref(c)),
                "chip_solver_get_equilibration")
         return d, e, c.value
@@ -876,6 +916,7 @@ class HipSolver:
         GPU (float64 values, int64 index).  Every piece is classified before any is applied; they are then applied in
         the order P, q, A, b, settings, and the first refusal raises ChipError (the pieces before it stay applied, as
         in the reference)."""
+        self._check_update_allowed()
         forms = [(k, classify_update(k, v, self._len[k], self._pattern.get(k)))
                  for k, v in (("P", P), ("q", q), ("A", A), ("b", b)) if v is not None]
         for k, f in forms:
@@ -895,7 +936,12 @@ class HipSolver:
     def update_b(self, data):
         self._apply_update("b", classify_update("b", data, self._len["b"]))
 
+    def _check_update_allowed(self):
+        if not self.is_data_update_allowed():  # data_updating.rs: checked before the data is looked at
+            raise UpdateNotAllowedError(ERR_UPDATE_NOT_ALLOWED, "update: presolve or chordal decomposition is active")
+
     def _apply_update(self, key, form):
+        self._check_update_allowed()
         kind = form[0]
         if kind == "none":
             return
@@ -917,26 +963,120 @@ class HipSolver:
         (linear-system fields go to .linsys).  An immutable field that differs raises ChipError(ERR_ARG) and the
         settings stay as they were."""
         new = SolverSettings.from_buffer_copy(settings if settings is not None else self.settings)
-        own = {f[0] for f in SolverSettings._fields_}
-        lin = {f[0] for f in Settings._fields_}
-        for k, v in kw.items():
-            if k not in own and k not in lin:
-                raise TypeError("update_settings: no setting named %r" % k)
-            setattr(new if k in own else new.linsys, k, v)
+        _apply_settings(new, kw, "update_settings")
         _check(lib().chip_problem_update_settings(self._h, C.byref(new)), "chip_problem_update_settings")
         self.settings = new
+
+    def transform_info(self):
+        """what presolve and chordal decomposition did at setup (chip_transform_get_info) as a dict"""
+        t = TransformInfo()
+        _check(lib().chip_transform_get_info(self._h, C.byref(t)), "chip_transform_get_info")
+        return {f[0]: getattr(t, f[0]) for f in TransformInfo._fields_}
 
     def is_data_update_allowed(self):
         allowed = C.c_int32()
         _check(lib().chip_problem_update_allowed(self._h, C.byref(allowed)), "chip_problem_update_allowed")
         return bool(allowed.value)
 
+    def internal_solution(self):
+        """test hook: the internal variables of the last solve, unscaled: (x2, s2, z2) of n_internal / m_internal"""
+        t = self.transform_info()
+        x, s, z = np.zeros(t["n_internal"]), np.zeros(t["m_internal"]), np.zeros(t["m_internal"])
+        _check(lib().chip_debug_solver_internal_solution(self._h, _pf(x), _pf(s), _pf(z)),
+               "chip_debug_solver_internal_solution")
+        return x, s, z
+
     def scaled_data(self):
-        """solver.data as the solver holds it, after equilibration: (P.nzval, A.nzval, q, b)"""
-        Px, Ax = np.zeros(self._len["P"]), np.zeros(self._len["A"])
-        q, b = np.zeros(self.n), np.zeros(self.m)
+        """solver.data as the solver holds it, after the transforms and the equilibration: (P.nzval, A.nzval, q, b)
+        of the internal problem (the original sizes unless a transform is active)"""
+        t = self.transform_info()
+        if t["m_internal"] == self.m and t["n_internal"] == self.n:
+            Px, Ax = np.zeros(self._len["P"]), np.zeros(self._len["A"])
+        else:  # P keeps its entries (zero-padded columns); A is the internal one
+            Px, Ax = np.zeros(self._len["P"]), np.zeros(t["nnzA_internal"])
+        q, b = np.zeros(t["n_internal"]), np.zeros(t["m_internal"])
         _check(lib().chip_problem_get_scaled(self._h, _pf(Px), _pf(Ax), _pf(q), _pf(b)), "chip_problem_get_scaled")
         return Px, Ax, q, b
+
+
+def _cone_arrays(cones):
+    cones = [tuple(c) for c in cones]
+    tags = np.array([c[0] for c in cones], dtype=np.int32)
+    dims = np.array([c[1] for c in cones], dtype=np.int64)
+    dims2 = np.array([c[2] if len(c) > 2 else 0 for c in cones], dtype=np.int64)
+    alphas = np.array([c[3] if (len(c) > 3 and c[0] == PowerConeT) else 0.5 for c in cones], dtype=np.float64)
+    return tags, dims, dims2, alphas
+
+
+class TransformDebug:
+    """the presolve / chordal-decomposition transform of chip_solver_create alone, on the host (test hooks of
+    include/clarabel_hip_testing.h: a library built with TESTING=1).  Arguments as HipSolver."""
+
+    _INT = {"sizes", "keep", "Pp", "Pi", "Ap", "Ai", "dims", "dims2", "tags", "mode", "ptr", "src", "H_row"}
+
+    def __init__(self, P, q, A, b, cones, settings=None):
+        self.n, self.m = P.n, A.m
+        self.settings = settings or SolverSettings.default()
+        tags, dims, dims2, alphas = _cone_arrays(cones)
+        self._h = C.c_void_p()
+        _check(lib().chip_debug_transform_create(C.byref(self._h), C.c_int64(P.n), C.c_int64(A.m), _pu(P.colptr),
+                                                 _pu(P.rowval), _pf(P.nzval), _pf(_f(q)), _pu(A.colptr),
+                                                 _pu(A.rowval), _pf(A.nzval), _pf(_f(b)), C.c_int64(len(tags)),
+                                                 tags.ctypes.data_as(P_I32), dims.ctypes.data_as(P_I64),
+                                                 dims2.ctypes.data_as(P_I64), _pf(alphas), C.byref(self.settings)),
+               "chip_debug_transform_create")
+        sz = self.get("sizes")
+        (self.active, _, _, self.m_reduced, self.n2, self.m2, self.npatterns, self.premerge_added, self.final_added,
+         self.largest_clique) = [int(v) for v in sz]
+        self.active = bool(self.active)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().chip_debug_transform_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def get(self, name):
+        n = C.c_int64()
+        L = lib()
+        _check(L.chip_debug_transform_get(self._h, name.encode(), C.byref(n), None), "chip_debug_transform_get")
+        is_int = name in self._INT or (name.startswith("pattern") and not name.endswith(("Px", "q", "Ax", "b")))
+        out = np.zeros(n.value, dtype=np.int64 if is_int else np.float64)
+        _check(L.chip_debug_transform_get(self._h, name.encode(), C.byref(n), out.ctypes.data_as(C.c_void_p)),
+               "chip_debug_transform_get")
+        return out
+
+    def problem(self):
+        """the transformed (P, q, A, b, cones) as CscMatrix / arrays / cone tuples"""
+        P = CscMatrix(self.n2, self.n2, self.get("Pp"), self.get("Pi"), self.get("Px"))
+        A = CscMatrix(self.m2, self.n2, self.get("Ap"), self.get("Ai"), self.get("Ax"))
+        cones = [(int(t), int(d), int(d2)) if t == GenPowerConeT or d2 else (int(t), int(d))
+                 for t, d, d2 in zip(self.get("tags"), self.get("dims"), self.get("dims2"))]
+        al = self.get("alphas")
+        cones = [(c[0], c[1], 0, float(al[i])) if c[0] == PowerConeT else c for i, c in enumerate(cones)]
+        return P, self.get("q"), A, self.get("b"), cones
+
+    def patterns(self):
+        """every decomposed cone: dict(cone, row_orig, row_pre, side, premerge_cliques, ordering, snode_start,
+        snode_len, parent, sep = [...], cliques = [sorted original vertices of each clique, in post order])"""
+        out = []
+        for k in range(self.npatterns):
+            info = self.get("pattern%d.info" % k)
+            p = dict(zip(("cone", "row_orig", "row_pre", "side", "premerge_cliques"), [int(v) for v in info]))
+            for f in ("ordering", "snode_start", "snode_len", "parent"):
+                p[f] = self.get("pattern%d.%s" % (k, f))
+            p["sep"] = [self.get("pattern%d.sep%d" % (k, j)) for j in range(len(p["snode_start"]))]
+            order = p["ordering"]
+            p["cliques"] = [sorted([int(order[v]) for v in range(a, a + ln)] + [int(order[v]) for v in sp])
+                            for a, ln, sp in zip(p["snode_start"], p["snode_len"], p["sep"])]
+            out.append(p)
+        return out
+
+    def reverse(self, x2, s2, z2):
+        """chip_debug_transform_reverse: (x, s, z) of the original problem from unscaled internal vectors"""
+        x, s, z = np.zeros(self.n), np.zeros(self.m), np.zeros(self.m)
+        _check(lib().chip_debug_transform_reverse(self._h, _pf(_f(x2)), _pf(_f(s2)), _pf(_f(z2)), _pf(x), _pf(s),
+                                                  _pf(z)), "chip_debug_transform_reverse")
+        return x, s, z
 
 
 def _is_torch(x):

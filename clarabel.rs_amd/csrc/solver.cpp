@@ -14,6 +14,7 @@
 
 #include "engine.hpp"
 #include "equilibrate.hpp"
+#include "problem_transform.hpp"
 #include "problem_update.hpp"
 
 using namespace chip;
@@ -84,7 +85,14 @@ struct chip_solver {
     int64_t degree = 0;
     chip_vars vars{}, lhs{}, rhs{}, prev{};
     double *rx = nullptr, *rz = nullptr, *rx_inf = nullptr, *rz_inf = nullptr, *Pxv = nullptr;
-    double *xo = nullptr, *so = nullptr, *zo = nullptr; // the unscaled solution
+    double *xo = nullptr, *so = nullptr, *zo = nullptr; // the unscaled solution (original sizes n_out, m_out)
+    // presolve / chordal decomposition (problem_transform.cpp): tf is null unless one of them changed the problem; then
+    // n, m above are the internal sizes and the reverse maps live on the device
+    std::unique_ptr<ProblemTransform> tf;
+    int n_out = 0, m_out = 0;
+    int32_t *rv_mode = nullptr;
+    int64_t *rv_ptr = nullptr, *rv_src = nullptr;
+    double transform_time = 0, completion_time = 0;
     InfoState info;
     double setup_time = 0, equilibration_time = 0, iteration_time = 0;
     double obj_val = 0, obj_val_dual = 0;
@@ -158,6 +166,13 @@ void chip_solver_settings_default(chip_solver_settings *s) {
     s->linesearch_backtrack_step = 0.8;
     s->min_switch_step_length = 0.1;
     s->min_terminate_step_length = 1e-4;
+    // the reference enables presolve and chordal decomposition by default; here both stay off until measured, so that a
+    // caller gets the problem it passes in
+    s->presolve_enable = 0;
+    s->chordal_decomposition_enable = 0;
+    s->chordal_decomposition_merge_method = CHIP_MERGE_CLIQUE_GRAPH;
+    s->chordal_decomposition_compact = 1;
+    s->chordal_decomposition_complete_dual = 1;
 }
 
 // DefaultProblemData::equilibrate (problemdata.rs:231-312): every Ruiz step enqueued without a host synchronisation,
@@ -233,9 +248,41 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
     st.linsys.min_terminate_step_length = st.min_terminate_step_length;
     if (st.linsys.device == CHIP_DEVICE_HOST_ONLY || chip_device_count() < 1)
         return fails(CHIP_ERR_NO_DEVICE, "chip_solver_create: no HIP device (the product has no CPU fallback)");
-    const uint64_t nnzP = Pcolptr[n], nnzA = Acolptr[n];
-    if ((nnzP && (!Prowval || !Pnzval)) || (nnzA && (!Arowval || !Anzval)) || (n && !q) || (m && !b))
+    if ((Pcolptr[n] && (!Prowval || !Pnzval)) || (Acolptr[n] && (!Arowval || !Anzval)) || (n && !q) || (m && !b))
         return fails(CHIP_ERR_ARG, "chip_solver_create: missing data");
+    h->n_out = (int)std::min<int64_t>(n, INT32_MAX);
+    h->m_out = (int)std::min<int64_t>(m, INT32_MAX);
+    // ---- presolve and chordal decomposition (problemdata.rs:59-165): everything below sees the transformed problem
+    if (st.presolve_enable || st.chordal_decomposition_enable) {
+        if (n >= (1ll << 31) || m >= (1ll << 31)) return fails(CHIP_ERR_DIM, "chip_solver_create: sizes out of int32 range");
+        for (uint64_t k = 0; k < Acolptr[n]; k++)
+            if ((int64_t)Arowval[k] >= m) return fails(CHIP_ERR_DIM, "A row index out of range");
+        std::unique_ptr<ProblemTransform> tf(new ProblemTransform());
+        int rc0 = transform_build(n, m, Pcolptr, Prowval, Pnzval, q, Acolptr, Arowval, Anzval, b, ncones, cone_tags,
+                                  cone_dims, cone_dims2, cone_alphas_or_null, transform_options(st), *tf);
+        if (rc0) return rc0;
+        h->transform_time = tf->transform_time;
+        if (tf->active()) {
+            const ProblemTransform &t = *tf;
+            n = t.n2;
+            m = t.m2;
+            Pcolptr = t.Pp.data();
+            Prowval = t.Pi.data();
+            Pnzval = t.Px.data();
+            q = t.q.data();
+            Acolptr = t.Ap.data();
+            Arowval = t.Ai.data();
+            Anzval = t.Ax.data();
+            b = t.b.data();
+            ncones = (int64_t)t.tags.size();
+            cone_tags = t.tags.data();
+            cone_dims = t.dims.data();
+            cone_dims2 = t.dims2.data();
+            cone_alphas_or_null = t.alphas.data();
+            h->tf = std::move(tf);
+        }
+    }
+    const uint64_t nnzP = Pcolptr[n], nnzA = Acolptr[n];
     // the entry-parallel passes of equilibrate.hip index P and A together, and A with b / e, in int32
     if (nnzP + nnzA + (uint64_t)n + (uint64_t)m >= (1ull << 31) || n + 2 * m >= (1ll << 31))
         return fails(CHIP_ERR_DIM, "chip_solver_create: sizes out of int32 range");
@@ -321,9 +368,16 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
         return rc;
     if ((rc = mem.alloc(&h->rx, (size_t)n)) || (rc = mem.alloc(&h->rz, (size_t)m)) ||
         (rc = mem.alloc(&h->rx_inf, (size_t)n)) || (rc = mem.alloc(&h->rz_inf, (size_t)m)) ||
-        (rc = mem.alloc(&h->Pxv, (size_t)n)) || (rc = mem.alloc(&h->xo, (size_t)n)) ||
-        (rc = mem.alloc(&h->so, (size_t)m)) || (rc = mem.alloc(&h->zo, (size_t)m)))
+        (rc = mem.alloc(&h->Pxv, (size_t)n)) || (rc = mem.alloc(&h->xo, (size_t)h->n_out)) ||
+        (rc = mem.alloc(&h->so, (size_t)h->m_out)) || (rc = mem.alloc(&h->zo, (size_t)h->m_out)))
         return rc;
+    if (h->tf) {
+        const ProblemTransform &t = *h->tf;
+        if ((rc = mem.upload(&h->rv_mode, t.mode.data(), t.mode.size())) ||
+            (rc = mem.upload(&h->rv_ptr, t.ptr.data(), t.ptr.size())) ||
+            (rc = mem.upload(&h->rv_src, t.src.data(), t.src.size())))
+            return rc;
+    }
     h->setup_time = now_s() - t0;
     *out = h.release();
     return CHIP_OK;
@@ -446,9 +500,23 @@ int chip_solver::post_process() {
     obj_val = inf ? std::numeric_limits<double>::quiet_NaN() : info.cost_primal;
     obj_val_dual = inf ? std::numeric_limits<double>::quiet_NaN() : info.cost_dual;
     const double scaleinv = inf ? 1.0 / vars.kappa : 1.0 / vars.tau, cinv = 1.0 / c;
-    dev::unscale(stream, xo, vars.x, d, scaleinv, n, zo, vars.z, e, scaleinv * cinv, so, vars.s, einv, scaleinv, m);
+    if (!tf) {
+        dev::unscale(stream, xo, vars.x, d, scaleinv, n, zo, vars.z, e, scaleinv * cinv, so, vars.s, einv, scaleinv, m);
+    } else { // decomp_reverse + reverse_presolve (solution.rs:94-110) in one gather, straight from the scaled variables
+        const dev::RvMaps mp{rv_mode, rv_ptr, rv_src};
+        dev::transform_reverse(stream, mp, n_out, m_out, xo, vars.x, d, scaleinv, so, vars.s, einv, scaleinv, zo, vars.z,
+                               e, scaleinv * cinv);
+    }
     CHIP_HIP(hipGetLastError());
     CHIP_HIP(hipStreamSynchronize(stream));
+    if (tf && tf->decomposed() && tf->opt.complete_dual) { // psd_completion on the host: a few dense blocks per solve
+        const double tc = now_s();
+        std::vector<double> zh((size_t)m_out);
+        if (m_out) CHIP_HIP(hipMemcpy(zh.data(), zo, (size_t)m_out * 8, hipMemcpyDeviceToHost));
+        transform_complete_dual(*tf, zh.data());
+        if (m_out) CHIP_HIP(hipMemcpy(zo, zh.data(), (size_t)m_out * 8, hipMemcpyHostToDevice));
+        completion_time = now_s() - tc;
+    }
     info.solve_time = setup_time + (now_s() - t_solve0);
     return CHIP_OK;
 }
@@ -579,13 +647,13 @@ int32_t chip_solver_get_solution(chip_solver *h, double *x, double *s, double *z
     if (!h) return CHIP_ERR_ARG;
     CHIP_HIP(hipSetDevice(h->device));
     if (h->solved_once) {
-        if (x && h->n) CHIP_HIP(hipMemcpy(x, h->xo, (size_t)h->n * 8, hipMemcpyDeviceToHost));
-        if (s && h->m) CHIP_HIP(hipMemcpy(s, h->so, (size_t)h->m * 8, hipMemcpyDeviceToHost));
-        if (z && h->m) CHIP_HIP(hipMemcpy(z, h->zo, (size_t)h->m * 8, hipMemcpyDeviceToHost));
+        if (x && h->n_out) CHIP_HIP(hipMemcpy(x, h->xo, (size_t)h->n_out * 8, hipMemcpyDeviceToHost));
+        if (s && h->m_out) CHIP_HIP(hipMemcpy(s, h->so, (size_t)h->m_out * 8, hipMemcpyDeviceToHost));
+        if (z && h->m_out) CHIP_HIP(hipMemcpy(z, h->zo, (size_t)h->m_out * 8, hipMemcpyDeviceToHost));
     } else {
-        if (x) std::fill(x, x + h->n, 0.0);
-        if (s) std::fill(s, s + h->m, 0.0);
-        if (z) std::fill(z, z + h->m, 0.0);
+        if (x) std::fill(x, x + h->n_out, 0.0);
+        if (s) std::fill(s, s + h->m_out, 0.0);
+        if (z) std::fill(z, z + h->m_out, 0.0);
     }
     if (out) {
         std::memset(out, 0, sizeof(*out));
@@ -700,6 +768,9 @@ namespace {
 // the checks shared by both forms: CHIP_ERR_ARG before any device is touched, k == 0 a no-op (returns 1)
 int update_args(chip_solver *h, int which, const void *idx, const double *vals, int64_t k) {
     if (!h || k < 0 || (k > 0 && !vals)) return fails(CHIP_ERR_ARG, std::string(UPD_NAME[which]) + ": bad argument");
+    if (h->tf) // data_updating.rs: PresolveIsActive / ChordalDecompositionIsActive
+        return fails(CHIP_ERR_UPDATE_NOT_ALLOWED, std::string(UPD_NAME[which]) +
+                                                      ": presolve or chordal decomposition is active (nothing changed)");
     if (k == 0) return 1;
     if (k >= (1ll << 31)) return fails(CHIP_ERR_DIM, std::string(UPD_NAME[which]) + ": more than 2^31 values");
     if (!idx && k != update_len(h, which))
@@ -779,6 +850,13 @@ int32_t chip_problem_update_settings(chip_solver *h, const chip_solver_settings 
     IMMUTABLE(std::memcmp(&nw.equilibrate_max_scaling, &o.equilibrate_max_scaling, 8), "equilibrate_max_scaling");
     IMMUTABLE(std::memcmp(&nw.linesearch_backtrack_step, &o.linesearch_backtrack_step, 8), "linesearch_backtrack_step");
     IMMUTABLE(std::memcmp(&nw.min_terminate_step_length, &o.min_terminate_step_length, 8), "min_terminate_step_length");
+    IMMUTABLE(nw.presolve_enable != o.presolve_enable, "presolve_enable"); // settings.rs:317-325
+    IMMUTABLE(nw.chordal_decomposition_enable != o.chordal_decomposition_enable, "chordal_decomposition_enable");
+    IMMUTABLE(nw.chordal_decomposition_merge_method != o.chordal_decomposition_merge_method,
+              "chordal_decomposition_merge_method");
+    IMMUTABLE(nw.chordal_decomposition_compact != o.chordal_decomposition_compact, "chordal_decomposition_compact");
+    IMMUTABLE(nw.chordal_decomposition_complete_dual != o.chordal_decomposition_complete_dual,
+              "chordal_decomposition_complete_dual");
 #define IMMUTABLE_LIN(f) IMMUTABLE(std::memcmp(&a.f, &l.f, sizeof(a.f)), "linsys." #f)
     IMMUTABLE_LIN(static_regularization_enable);
     IMMUTABLE_LIN(static_regularization_constant);
@@ -802,7 +880,7 @@ int32_t chip_problem_update_settings(chip_solver *h, const chip_solver_settings 
 
 int32_t chip_problem_update_allowed(const chip_solver *h, int32_t *allowed) {
     if (!h || !allowed) return fails(CHIP_ERR_ARG, "chip_problem_update_allowed: bad argument");
-    *allowed = 1; // no presolve, no chordal decomposition, no dropped structural zeros
+    *allowed = h->tf ? 0 : 1; // an enabled transform that changed nothing keeps updates allowed (the reference's Option)
     return CHIP_OK;
 }
 
@@ -816,3 +894,46 @@ int32_t chip_problem_get_scaled(chip_solver *h, double *Px, double *Ax, double *
     if (b && h->m) CHIP_HIP(hipMemcpy(b, h->b, (size_t)h->m * 8, hipMemcpyDeviceToHost));
     return CHIP_OK;
 }
+
+int32_t chip_transform_get_info(const chip_solver *h, chip_transform_info *out) {
+    if (!h || !out) return fails(CHIP_ERR_ARG, "chip_transform_get_info: bad argument");
+    std::memset(out, 0, sizeof(*out));
+    const ProblemTransform *t = h->tf.get();
+    out->m_full = h->m_out;
+    out->m_reduced = t ? t->m_reduced : h->m_out;
+    out->n_internal = h->n;
+    out->m_internal = h->m;
+    out->nnzA_internal = h->M.nnzA;
+    out->psd_cones_decomposed = t ? (int64_t)t->patterns.size() : 0;
+    out->psd_cones_added = t ? t->final_added : 0;
+    out->psd_cones_added_premerge = t ? t->premerge_added : 0;
+    out->largest_clique = t ? t->largest_clique : 0;
+    out->transform_time = h->transform_time;
+    out->completion_time = h->completion_time;
+    return CHIP_OK;
+}
+
+#ifdef CHIP_TESTING
+#include "../../include/clarabel_hip_testing.h"
+int32_t chip_debug_solver_internal_solution(void *solver, double *x2, double *s2, double *z2) {
+    chip_solver *h = (chip_solver *)solver;
+    if (!h) return fails(CHIP_ERR_ARG, "chip_debug_solver_internal_solution: bad argument");
+    CHIP_HIP(hipSetDevice(h->device));
+    const int n = h->n, m = h->m;
+    const bool inf = is_infeasible(h->info.status);
+    const chip_vars &v = h->vars;
+    const double scaleinv = inf ? 1.0 / v.kappa : 1.0 / v.tau, cinv = 1.0 / h->c;
+    DevBuf tmp;
+    double *xo, *so, *zo;
+    int rc;
+    if ((rc = tmp.alloc(&xo, (size_t)n)) || (rc = tmp.alloc(&so, (size_t)m)) || (rc = tmp.alloc(&zo, (size_t)m)))
+        return rc;
+    dev::unscale(h->stream, xo, v.x, h->d, scaleinv, n, zo, v.z, h->e, scaleinv * cinv, so, v.s, h->einv, scaleinv, m);
+    CHIP_HIP(hipGetLastError());
+    CHIP_HIP(hipStreamSynchronize(h->stream));
+    if (x2 && n) CHIP_HIP(hipMemcpy(x2, xo, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (s2 && m) CHIP_HIP(hipMemcpy(s2, so, (size_t)m * 8, hipMemcpyDeviceToHost));
+    if (z2 && m) CHIP_HIP(hipMemcpy(z2, zo, (size_t)m * 8, hipMemcpyDeviceToHost));
+    return CHIP_OK;
+}
+#endif

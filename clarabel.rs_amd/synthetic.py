@@ -271,3 +271,27 @@ def mixed_conic(nexp=40, npow=30, nsoc=5, socdim=9, nn=50, seed=11):
     A = A + sp.csc_matrix((np.ones(min(m, n)), (np.arange(min(m, n)), np.arange(min(m, n)))), shape=(m, n))
     P = sp.diags(rng.uniform(0.5, 1.5, n)).tocsc()
     return dict(n=n, m=m, P=_csc(P), A=_csc(A), cones=cones, s=s, z=z)
+
+
+def banded_sdp(side=200, band=2, seed=1):
+    """a PSD cone of side `side` whose aggregate pattern in [A b] is banded (half-bandwidth `band`): one variable per
+    pattern entry, min 0.5 |x|^2 / 2 + q'x s.t. svec(B - sum_k x_k E_k) in PSDTriangle(side), B = side * I plus noise
+    on the band.  Chordal decomposition splits the cone into cliques of side ~band + 1; undecomposed, its Hs block
+    has tri(side)^2 entries."""
+    rng = np.random.default_rng(seed)
+    m = side * (side + 1) // 2
+    rows, cols, vals, q = [], [], [], []
+    b = np.zeros(m)
+    j = 0
+    for c in range(side):
+        for r in range(max(0, c - band), c + 1):
+            k = c * (c + 1) // 2 + r
+            rows.append(k)
+            cols.append(j)
+            vals.append(1.0 if r == c else np.sqrt(2.0))
+            b[k] = float(side) if r == c else np.sqrt(2.0) * rng.uniform(-0.5, 0.5)
+            q.append(rng.uniform(-1.0, 1.0))
+            j += 1
+    A = sp.csc_matrix((vals, (rows, cols)), shape=(m, j))
+    P = sp.identity(j, format="csc") * 0.5
+    return dict(n=j, m=m, P=_csc(P), A=_csc(A), q=np.array(q), b=b, cones=[(6, side)])

@@ -48,7 +48,8 @@ typedef enum {
     CHIP_ERR_NO_DEVICE = -7,      /* HIP runtime/device unavailable (the product has NO CPU fallback) */
     CHIP_ERR_HIP = -8,            /* a HIP call failed; see chip_last_error() */
     CHIP_ERR_ARG = -9,
-    CHIP_ERR_UNSUPPORTED = -10
+    CHIP_ERR_UNSUPPORTED = -10,
+    CHIP_ERR_UPDATE_NOT_ALLOWED = -11 /* a data update while presolve or chordal decomposition is active */
 } chip_status;
 
 /* SupportedConeT tags (solver/core/cones/supportedcone.rs) */
@@ -516,8 +517,16 @@ int32_t chip_vec_norms(chip_kktsystem *h, int32_t count, const double *const *ve
  * (src/solver/implementations/default/solver.rs, core/solver.rs:242-464) on one GPU, built on L3:
  *   setup   ProblemData::new + equilibrate (default/problemdata.rs:231-312, Ruiz scaling and the cones'
  *           rectification compositecone.rs:183-195) on the device, then chip_kkt / chip_kktsystem built from the
- *           equilibrated values.  No presolve: rows with infinite bounds are NOT dropped (b is only capped at
- *           1e20 like problemdata.rs:125-127); no chordal decomposition.
+ *           equilibrated values.  Optional transforms before all of that (both off by default, see
+ *           chip_solver_settings_default): presolve (default/presolver.rs) drops Nonnegative rows whose b exceeds
+ *           (1 - 10 eps) 1e20, and chordal decomposition (src/solver/chordal/) splits every sparse PSDTriangle cone of
+ *           side > 3 into one cone per clique of a chordal extension of its aggregate pattern in [A b] (compact or
+ *           standard augmentation).  The cap of b at 1e20 (problemdata.rs:125-127), the stored norms, the int32 size
+ *           check, the equilibration and the L2 / L3 handles then all see the TRANSFORMED problem (n_internal x
+ *           m_internal, chip_transform_get_info).  The chordal analysis runs on the presolved problem (the reference
+ *           analyses the unpresolved one, which does not compose when presolve removes a row in front of a
+ *           decomposable cone).  The solution is reversed on the device into the original sizes on every solve;
+ *           the PSD completion of the dual (complete_dual) runs on the host.
  *   solve   default_start, DefaultInfo::update with the scaled norms (info.rs:113-178), check_termination with the
  *           full and reduced tolerances and the poor-progress rules (info.rs:182-231, 277-389), the four strategy
  *           checkpoints incl. reset_to_prev_iterate and the switch to the dual scaling for nonsymmetric cones
@@ -564,7 +573,29 @@ typedef struct {
     double linesearch_backtrack_step;     /* 0.8 */
     double min_switch_step_length;        /* 0.1 */
     double min_terminate_step_length;     /* 1e-4 */
+    /* the transforms of ProblemData::new (problemdata.rs:59-165); both enables default to 0 here (the reference: true),
+     * so that existing callers get the problem they pass in.  Immutable after chip_solver_create. */
+    int32_t presolve_enable;                    /* 0 (reference: true) */
+    int32_t chordal_decomposition_enable;       /* 0 (reference: true) */
+    int32_t chordal_decomposition_merge_method; /* CHIP_MERGE_CLIQUE_GRAPH ("clique_graph") */
+    int32_t chordal_decomposition_compact;      /* 1 */
+    int32_t chordal_decomposition_complete_dual;/* 1 */
+    int32_t reserved1;                          /* padding to a multiple of 8 bytes */
 } chip_solver_settings;
+/* chordal_decomposition_merge_method (settings.rs: "none" / "parent_child" / "clique_graph") */
+enum { CHIP_MERGE_NONE = 0, CHIP_MERGE_PARENT_CHILD = 1, CHIP_MERGE_CLIQUE_GRAPH = 2 };
+/* what the transforms of chip_solver_create did (the reference prints these, info_print.rs) */
+typedef struct {
+    int64_t m_full, m_reduced;      /* rows before / after presolve */
+    int64_t n_internal, m_internal; /* the problem the interior-point loop solves */
+    int64_t nnzA_internal;
+    int64_t psd_cones_decomposed;   /* PSDTriangle cones split into cliques */
+    int64_t psd_cones_added;        /* final_psd_cones_added: cones added after merging */
+    int64_t psd_cones_added_premerge; /* premerge_psd_cones_added */
+    int64_t largest_clique;         /* side of the largest PSD cone made by the decomposition (0: none) */
+    double transform_time;          /* seconds of the host transform inside setup_time */
+    double completion_time;         /* seconds of the PSD completion of the last solve */
+} chip_transform_info;
 /* DefaultSolution's scalars (solution.rs) + DefaultInfo's timings */
 typedef struct {
     int32_t status;            /* chip_solver_status */
@@ -591,19 +622,25 @@ void chip_solver_destroy(chip_solver *h);
 /* runs the interior-point loop; returns CHIP_OK (the outcome is the status of chip_solver_get_solution) or a
  * negative chip_status when a HIP call failed */
 int32_t chip_solver_solve(chip_solver *h);
-/* host copies of the unscaled solution (any of x[n], s[m], z[m] may be NULL) and its scalars */
+/* host copies of the unscaled solution (any of x[n], s[m], z[m] may be NULL) and its scalars.  n and m are always
+ * those of the problem passed to chip_solver_create: with a transform active, the solution is reversed (the rows
+ * presolve removed get s = 1e20, z = 0) and, with complete_dual, z of a decomposed cone is PSD-completed. */
 int32_t chip_solver_get_solution(chip_solver *h, double *x, double *s, double *z, chip_solution_info *info);
 /* the same vectors on the device, owned by the handle (valid until the next solve or the destruction) */
 int32_t chip_solver_get_solution_dev(chip_solver *h, double **x_dev, double **s_dev, double **z_dev);
-/* the equilibration of DefaultEquilibrationData: d[n], e[m] (host copies, either may be NULL) and c */
+/* the equilibration of DefaultEquilibrationData: d[n_internal], e[m_internal] (host copies, either may be NULL) and c
+ * (n_internal = n and m_internal = m unless a transform is active) */
 int32_t chip_solver_get_equilibration(chip_solver *h, double *d, double *e, double *c);
+/* what presolve and chordal decomposition did at setup (everything is the identity when neither is active) */
+int32_t chip_transform_get_info(const chip_solver *h, chip_transform_info *out);
 
 /* ---- data updates: DefaultSolver::update_P / update_A / update_q / update_b / update_settings
  * (default/data_updating.rs, core/solver.rs:207) on a chip_solver handle.  The patterns are fixed; the new values are
  * scaled with the equilibration of chip_solver_create (d, e and c are never recomputed), written into the solver's
  * data and, on the device, into every copy the next solve reads.  The next chip_solver_solve restarts from
- * default_start, as a second solve does.  Every update is allowed here: no presolve, no chordal decomposition, no
- * dropped structural zeros.
+ * default_start, as a second solve does.  Updates are allowed when no transform is active (no dropped structural
+ * zeros here).  While presolve removed a row or a cone was decomposed, every update returns
+ * CHIP_ERR_UPDATE_NOT_ALLOWED and changes nothing (data_updating.rs: PresolveIsActive / ChordalDecompositionIsActive).
  *   full form     index == NULL: k must be nnz(P) / nnz(A) / n / m, else CHIP_ERR_DIM.
  *                 P = (v * (d[row] * d[col])) * c, A = v * (e[row] * d[col])  (lrscale, then scale(c))
  *   partial form  index != NULL: the reference's zip(index, values); a repeated index: the last occurrence wins.
@@ -628,11 +665,14 @@ int32_t chip_problem_update_b_dev(chip_solver *h, const int64_t *index_dev_or_nu
 /* DefaultSolver::update_settings with validate_as_update (settings.rs:307): CHIP_ERR_ARG, settings unchanged, when an
  * immutable field differs -- equilibrate_enable / _max_iter / _min_scaling / _max_scaling as in the reference, and here
  * also every field of linsys and linesearch_backtrack_step / min_terminate_step_length (the KKT handle keeps its own
- * copy of them).  The rest (max_iter, time_limit, the tolerances, the step fractions) takes effect at the next solve. */
+ * copy of them), and the five transform fields (settings.rs:317-325).  The rest (max_iter, time_limit, the tolerances,
+ * the step fractions) takes effect at the next solve. */
 int32_t chip_problem_update_settings(chip_solver *h, const chip_solver_settings *settings);
-/* DefaultSolver::is_data_update_allowed: always 1 here */
+/* DefaultSolver::is_data_update_allowed: 0 while presolve removed a row or a cone was decomposed (enabled but
+ * inactive transforms still allow updates), else 1 */
 int32_t chip_problem_update_allowed(const chip_solver *h, int32_t *allowed);
-/* solver.data as the solver holds it (P, A, q, b after equilibration): host copies, any pointer may be NULL */
+/* solver.data as the solver holds it (P, A, q, b after the transforms and the equilibration: n_internal /
+ * m_internal long, with the internal nnz): host copies, any pointer may be NULL */
 int32_t chip_problem_get_scaled(chip_solver *h, double *Px, double *Ax, double *q, double *b);
 
 /* ===========================================================================

@@ -27,6 +27,28 @@ int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out
  * the collective enqueued last; the communicator's completion event moves behind it.  On one GPU this stands in for
  * the time RCCL's ring kernel holds CUs when several ranks exchange (bench.py --coresident). */
 int32_t chip_comm_debug_spin(void *comm, int32_t blocks, int32_t threads, double usec);
+/* ---- the problem transforms of chip_solver_create (csrc/problem_transform.cpp), host only: no device is touched ----
+ * chip_debug_transform_create takes chip_solver_create's arguments (only the five transform fields of the settings are
+ * read) and returns a handle even when nothing is transformed (then "active" reads 0). */
+int32_t chip_debug_transform_create(void **out, int64_t n, int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval,
+                                    const double *Pnzval, const double *q, const uint64_t *Acolptr,
+                                    const uint64_t *Arowval, const double *Anzval, const double *b, int64_t ncones,
+                                    const int32_t *cone_tags, const int64_t *cone_dims, const int64_t *cone_dims2,
+                                    const double *cone_alphas_or_null, const void *solver_settings);
+void chip_debug_transform_destroy(void *h);
+/* one array of the transform by name; *len <- its length; out (may be NULL) receives it.  int64 arrays: "sizes"
+ * ({active, n, m, m_reduced, n2, m2, npatterns, premerge_added, final_added, largest_clique}), "keep", "Pp", "Pi", "Ap",
+ * "Ai", "dims", "dims2", "mode", "ptr", "src", "H_row", "tags" (int32 values widened); double arrays: "Px", "q", "Ax",
+ * "b", "alphas".  Pattern k: "pattern<k>.ordering", ".snode_start", ".snode_len", ".parent", ".info" ({cone, row_orig,
+ * row_pre, side, premerge_cliques}), ".sep<j>".  CHIP_ERR_ARG for an unknown name. */
+int32_t chip_debug_transform_get(const void *h, const char *name, int64_t *len, void *out);
+/* the host restatement of the device reverse, from UNSCALED internal vectors x2[n2], s2[m2], z2[m2]: x[n], s[m], z[m],
+ * with the PSD completion when complete_dual is set */
+int32_t chip_debug_transform_reverse(const void *h, const double *x2, const double *s2, const double *z2, double *x,
+                                     double *s, double *z);
+/* the internal variables of a chip_solver's last solve unscaled (dev::unscale's arithmetic): x2[n_internal],
+ * s2[m_internal], z2[m_internal] (any may be NULL) */
+int32_t chip_debug_solver_internal_solution(void *solver, double *x2, double *s2, double *z2);
 #ifdef __cplusplus
 }
 #endif
