@@ -999,6 +999,115 @@ class HipSolver:
         return Px, Ax, q, b
 
 
+def batch_stack(problems):
+    """the block-diagonal stack of a list of (P, q, A, b, cones) with CscMatrix P (n x n triu) and A (m x n): a dict
+    with n_part, m_part, n, m, P and A as (colptr, rowval, nzval) uint64 / float64 arrays, q, b and the concatenated
+    cones (csc/block_concatenate.rs's layout: member k's columns and rows follow those of members 0 .. k-1)"""
+    n_part, m_part, cones = [], [], []
+    pc, pr, pv, ac, ar, av, qs, bs = [np.zeros(1, dtype=u64)], [], [], [np.zeros(1, dtype=u64)], [], [], [], []
+    noff = moff = 0
+    pnz = anz = 0
+    for k, pb in enumerate(problems):
+        P, q, A, b, cn = pb
+        n, m = P.n, A.m
+        if P.m != n or A.n != n:
+            raise ValueError("batch member %d: P must be n x n and A m x n" % k)
+        q, b = _f(q), _f(b)
+        if len(q) != n or len(b) != m:
+            raise ValueError("batch member %d: q must have n and b m entries" % k)
+        pc.append(_u(P.colptr)[1:] + u64(pnz))
+        pr.append(_u(P.rowval) + u64(noff))
+        pv.append(_f(P.nzval))
+        ac.append(_u(A.colptr)[1:] + u64(anz))
+        ar.append(_u(A.rowval) + u64(moff))
+        av.append(_f(A.nzval))
+        qs.append(q)
+        bs.append(b)
+        cones.extend(tuple(c) for c in cn)
+        n_part.append(n)
+        m_part.append(m)
+        noff, moff, pnz, anz = noff + n, moff + m, pnz + P.nnz, anz + A.nnz
+    cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dtype=dt)  # noqa: E731
+    return dict(n_part=np.array(n_part, dtype=np.int64), m_part=np.array(m_part, dtype=np.int64), n=noff, m=moff,
+                P=(cat(pc, u64), cat(pr, u64), cat(pv, f64)), A=(cat(ac, u64), cat(ar, u64), cat(av, f64)),
+                q=cat(qs, f64), b=cat(bs, f64), cones=cones)
+
+
+class HipBatchSolver:
+    """many independent problems in ONE batched interior-point solve on the device (chip_batch_*): every member keeps
+    its own tau, kappa, mu, sigma, step length, termination and status.  problems: a list of (P, q, A, b, cones) as
+    HipSolver takes them, with Zero / Nonnegative / SecondOrder cones; one settings for every member."""
+
+    def __init__(self, problems, settings=None):
+        problems = list(problems)
+        st = batch_stack(problems)
+        self.stack = st
+        self.settings = settings or SolverSettings.default()
+        self.n_part, self.m_part = st["n_part"], st["m_part"]
+        tags, dims, dims2, alphas = _cone_arrays(st["cones"])
+        self._h = C.c_void_p()
+        Pp, Pi, Px = st["P"]
+        Ap, Ai, Ax = st["A"]
+        _check(lib().chip_batch_create(C.byref(self._h), C.c_int64(len(problems)),
+                                       self.n_part.ctypes.data_as(P_I64), self.m_part.ctypes.data_as(P_I64),
+                                       C.c_int64(st["n"]), C.c_int64(st["m"]), _pu(Pp), _pu(Pi), _pf(Px), _pf(st["q"]),
+                                       _pu(Ap), _pu(Ai), _pf(Ax), _pf(st["b"]), C.c_int64(len(tags)),
+                                       tags.ctypes.data_as(P_I32), dims.ctypes.data_as(P_I64),
+                                       dims2.ctypes.data_as(P_I64), _pf(alphas), None, C.byref(self.settings)),
+               "chip_batch_create")
+
+    def __len__(self):
+        return len(self.n_part)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().chip_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def solve(self):
+        """the batched IPSolver::solve -> one Solution per member, in input order"""
+        _check(lib().chip_batch_solve(self._h), "chip_batch_solve")
+        out = []
+        for k in range(len(self)):
+            x, s, z = np.zeros(self.n_part[k]), np.zeros(self.m_part[k]), np.zeros(self.m_part[k])
+            info = SolutionInfo()
+            _check(lib().chip_batch_get_solution(self._h, C.c_int64(k), _pf(x), _pf(s), _pf(z), C.byref(info)),
+                   "chip_batch_get_solution")
+            out.append(Solution(x, s, z, info))
+        return out
+
+    def infos(self):
+        """the members' chip_solution_info of the last solve"""
+        arr = (SolutionInfo * max(len(self), 1))()
+        _check(lib().chip_batch_get_info(self._h, arr), "chip_batch_get_info")
+        return [arr[k] for k in range(len(self))]
+
+    def solutions_dev(self):
+        """the stacked (x, s, z) of the last solve as non-owning DeviceArray views (valid until the next solve)"""
+        px, ps, pz = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().chip_batch_get_solution_dev(self._h, C.byref(px), C.byref(ps), C.byref(pz)),
+               "chip_batch_get_solution_dev")
+        return (DeviceArray.view(px.value, self.stack["n"]), DeviceArray.view(ps.value, self.stack["m"]),
+                DeviceArray.view(pz.value, self.stack["m"]))
+
+    def equilibration(self, k):
+        """member k's (d, e, c)"""
+        d, e, c = np.zeros(self.n_part[k]), np.zeros(self.m_part[k]), C.c_double()
+        _check(lib().chip_batch_get_equilibration(self._h, C.c_int64(k), _pf(d), _pf(e), C.byref(c)),
+               "chip_batch_get_equilibration")
+        return d, e, c.value
+
+    # ---- test hooks (include/clarabel_hip_testing.h) ----
+    def debug_inject_nan(self, member, iteration):
+        _check(lib().chip_debug_batch_inject_nan(self._h, C.c_int64(member), C.c_int32(iteration)),
+               "chip_debug_batch_inject_nan")
+
+    def debug_counter(self, name):
+        out = C.c_double()
+        _check(lib().chip_debug_batch_counter(self._h, name.encode(), C.byref(out)), "chip_debug_batch_counter")
+        return out.value
+
+
 def _cone_arrays(cones):
     cones = [tuple(c) for c in cones]
     tags = np.array([c[0] for c in cones], dtype=np.int32)

@@ -1,0 +1,1127 @@
+// batch.cpp -- the batched L4 solver (chip_batch_*): nprob independent problems of Zero / Nonnegative / SecondOrder
+// cones, stacked block-diagonally, solved by ONE interior-point loop whose scalars are kept per member:
+//   setup: Ruiz equilibration of the stack with one cost scale per member (batch.hip), the members' norms of q and b
+//          and cone degrees, one L2 chip_kkt on the equilibrated stack (its K is block-diagonal: one tree per member);
+//   solve: core/solver.rs:242-464 with tau, kappa, mu, sigma, the step length, DefaultInfo's scalars, the iteration
+//          count and the status of every member on the host, read back from one device-to-host copy per reduction
+//          pass.  Members that terminate are frozen: their step length is 0, selected per entry, and their part of
+//          every right-hand side is 0.  The per-member passes are segmented kernels (batch.hip), so the number of
+//          launches and host synchronisations per iteration does not depend on nprob.
+// The L2 cone operations without a scalar (affine ds, ds from dz, Hs products, scaling update, unit initialisation)
+// run on the whole stack as they are; combined_ds_shift runs with sigma mu = 0 and the member's sigma mu is then
+// subtracted at the unit vector's entries, which is the same arithmetic for Nonnegative and SecondOrder cones.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "batch.hpp"
+#include "engine.hpp"
+
+using namespace chip;
+
+namespace {
+
+int failb(int code, const std::string &msg) {
+    set_error(msg);
+    return code;
+}
+
+double now_s() {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+struct BDev {
+    std::vector<void *> ptrs;
+    template <typename T> int alloc(T **dst, size_t n) {
+        void *p = nullptr;
+        CHIP_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+        ptrs.push_back(p);
+        *dst = (T *)p;
+        return CHIP_OK;
+    }
+    template <typename T> int upload(T **dst, const T *src, size_t n) {
+        int rc = alloc(dst, n);
+        if (rc) return rc;
+        if (n) CHIP_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+        return CHIP_OK;
+    }
+    ~BDev() {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+};
+
+// DefaultInfo's scalars of one member (default/info.rs:12-64) and the dots of its last residual pass
+struct MInfo {
+    double cost_primal = 0, cost_dual = 0, res_primal = 0, res_dual = 0, res_primal_inf = 0, res_dual_inf = 0;
+    double gap_abs = 0, gap_rel = 0, ktratio = 0;
+    double prev_cost_primal = 0, prev_cost_dual = 0, prev_res_primal = 0, prev_res_dual = 0, prev_gap_abs = 0,
+           prev_gap_rel = 0;
+    double out5[5] = {0, 0, 0, 0, 0}; // r_tau, q'x, b'z, s'z, x'Px
+    int iterations = 0;
+    int status = CHIP_SOLVER_UNSOLVED;
+};
+
+bool is_infeasible(int s) {
+    return s == CHIP_SOLVER_PRIMAL_INFEASIBLE || s == CHIP_SOLVER_DUAL_INFEASIBLE ||
+           s == CHIP_SOLVER_ALMOST_PRIMAL_INFEASIBLE || s == CHIP_SOLVER_ALMOST_DUAL_INFEASIBLE;
+}
+
+// per-member device scalars (slot * nprob + k) and masks
+enum { S_TAU, S_INVTAU, S_DTAU, S_OMS, S_ALPHA, S_AMAX, S_SHIFT1, S_SHIFT2, S_NEGSM, S_SX, S_SZ, S_COUNT };
+enum { M_ACTIVE, M_QP, M_LP, M_SEL, M_SEL2, M_COUNT };
+// slots of the reduction output: the residual pass
+enum { R_QX, R_XPX, R_NX, R_NRXI, R_NPX, R_NRX, R_BADX, R_BZ, R_SZ, R_NZ, R_NS, R_NRZI, R_NRZ, R_BADSZ, R_COUNT };
+// the direction passes
+enum { D_QX1, D_BZ1, D_XIPX1, D_DPD, D_BAD, D_COUNT };
+
+} // namespace
+
+struct chip_batch {
+    int nprob = 0, n = 0, m = 0, device = 0;
+    chip_solver_settings st{};
+    BDev mem;
+    std::vector<int> xoff, zoff;
+    dev::BatchPlan plan{};
+    dev::EqMats M{};
+    double *q = nullptr, *b = nullptr, *d = nullptr, *e = nullptr, *dinv = nullptr, *einv = nullptr, *negq = nullptr;
+    std::vector<double> c, normq, normb;
+    std::vector<int64_t> degree;
+    std::vector<int> lp_init; // the member's P has no stored entry: the LP initial point (kktsystem.rs:197-215)
+    bool anyP = false, anyLP = false;
+    chip_kkt *kkt = nullptr;
+    chip_kktsystem *sys = nullptr; // its sparse operators only (kktsystem_spmv)
+    hipStream_t stream = nullptr;
+    // iterates: the current and previous one (swapped by the step), the held last finite iterate of members that ended
+    // NumericalError, the direction and right-hand side
+    double *vx = nullptr, *vs = nullptr, *vz = nullptr, *px = nullptr, *ps = nullptr, *pz = nullptr;
+    double *hx = nullptr, *hs = nullptr, *hz = nullptr;
+    double *lx = nullptr, *ls = nullptr, *lz = nullptr, *dx = nullptr, *ds = nullptr, *dz = nullptr;
+    double *x1 = nullptr, *z1 = nullptr, *x2 = nullptr, *z2 = nullptr, *workx = nullptr, *workx2 = nullptr,
+           *wn = nullptr, *wn2 = nullptr, *wn3 = nullptr, *workz = nullptr, *conicw = nullptr;
+    double *rx = nullptr, *rz = nullptr, *rx_inf = nullptr, *rz_inf = nullptr, *Pxv = nullptr;
+    double *xo = nullptr, *so = nullptr, *zo = nullptr;
+    double *dsc = nullptr, *dred = nullptr, *seg_scr = nullptr, *cone_scr = nullptr;
+    int *dmask = nullptr;
+    std::vector<double> hsc, hred;
+    std::vector<int> hmask;
+    // per member on the host
+    std::vector<double> tau, kappa, ptau, pkappa, htau, hkappa, mu, sigma, alpha, dtau, qx2, bz2, x2Px2;
+    std::vector<MInfo> info, pinfo, hinfo;
+    std::vector<char> active, held, held_done; // held: 1 = the current iterate, 2 = the previous one
+    std::vector<double> obj_val, obj_val_dual;
+    double setup_time = 0, equilibration_time = 0, iteration_time = 0, solve_time = 0;
+    double t_solve0 = 0;
+    bool solved_once = false;
+    // test hooks and counters
+    int64_t nan_member = -1;
+    int nan_iter = -1;
+    long syncs = 0, launches = 0, loop_iters = 0;
+
+    ~chip_batch() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        chip_kktsystem_destroy(sys);
+        chip_kkt_destroy(kkt);
+    }
+    double *sc(int slot) { return dsc + (size_t)slot * nprob; }
+    double &hs_(int slot, int k) { return hsc[(size_t)slot * nprob + k]; }
+    int *mk(int slot) { return dmask + (size_t)slot * nprob; }
+    int &hm(int slot, int k) { return hmask[(size_t)slot * nprob + k]; }
+    // the per-member scalars and masks travel in a ring of device (and host staging) slots: a kernel enqueued before
+    // the next upload keeps reading its own slot, and the loop synchronises far more often than the ring wraps
+    static constexpr int RING = 32;
+    double *dsc_ring = nullptr;
+    int *dmask_ring = nullptr;
+    std::vector<double> hsc_ring;
+    std::vector<int> hmask_ring;
+    int ring_s = 0, ring_m = 0;
+    int push_scalars() {
+        const size_t len = hsc.size();
+        ring_s = (ring_s + 1) % RING;
+        double *src = hsc_ring.data() + (size_t)ring_s * len;
+        std::memcpy(src, hsc.data(), len * 8);
+        dsc = dsc_ring + (size_t)ring_s * len;
+        launches++;
+        CHIP_HIP(hipMemcpyAsync(dsc, src, len * 8, hipMemcpyHostToDevice, stream));
+        return CHIP_OK;
+    }
+    int push_masks() {
+        const size_t len = hmask.size();
+        ring_m = (ring_m + 1) % RING;
+        int *src = hmask_ring.data() + (size_t)ring_m * len;
+        std::memcpy(src, hmask.data(), len * sizeof(int));
+        dmask = dmask_ring + (size_t)ring_m * len;
+        launches++;
+        CHIP_HIP(hipMemcpyAsync(dmask, src, len * sizeof(int), hipMemcpyHostToDevice, stream));
+        return CHIP_OK;
+    }
+    // one device-to-host copy of `count` doubles of the reduction output and one synchronisation
+    int read_red(size_t count) {
+        CHIP_HIP(hipGetLastError());
+        CHIP_HIP(hipMemcpyAsync(hred.data(), dred, count * 8, hipMemcpyDeviceToHost, stream));
+        CHIP_HIP(hipStreamSynchronize(stream));
+        launches++;
+        syncs++;
+        return CHIP_OK;
+    }
+    double red(int slot, int k) const { return hred[(size_t)slot * nprob + k]; }
+    void lin(double *w, const double *x, const double *y, const double *sa, const double *sb, double ca, double cb,
+             int space, const int *mask, int mode) {
+        dev::blin(stream, plan, dev::BLin{w, x, y, sa, sb, ca, cb, space, mask, mode});
+        launches++;
+    }
+    void copy_members(double *wx, double *ws, double *wz, const double *x, const double *s, const double *z,
+                      const int *mask) { // masked copy: members with mask[k] != 0 take (x, s, z)
+        lin(wx, x, nullptr, nullptr, nullptr, 1.0, 0.0, 0, mask, dev::MASK_KEEP);
+        lin(ws, s, nullptr, nullptr, nullptr, 1.0, 0.0, 1, mask, dev::MASK_KEEP);
+        lin(wz, z, nullptr, nullptr, nullptr, 1.0, 0.0, 1, mask, dev::MASK_KEEP);
+    }
+    int spmv(int which, double *y, const double *aux, double alpha_, const double *x) {
+        launches++;
+        return kktsystem_spmv(sys, which, y, aux, alpha_, x);
+    }
+    int equilibrate(const std::vector<ConeSpec> &cones);
+    int default_start();
+    int residual_pass();
+    void member_info(int k);
+    bool check_termination(int k, int iter);
+    void check_convergence(int k, bool almost);
+    int solve_direction(const double *conic, const std::vector<double> &rtau, const std::vector<double> &rkap,
+                        std::vector<double> &lkappa, bool *global_ok, int iter);
+    int step_length(const std::vector<double> &lkappa, bool combined);
+    int constant_rhs(bool *global_ok, int iter);
+    int hold_and_reset();
+    int post_process();
+    int end_member(int k, int status, int iterations, bool from_prev);
+};
+
+int chip_batch::equilibrate(const std::vector<ConeSpec> &cones) {
+    std::vector<double> ones((size_t)std::max(n, m), 1.0);
+    if (n) CHIP_HIP(hipMemcpy(d, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    if (m) CHIP_HIP(hipMemcpy(e, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
+    c.assign((size_t)nprob, 1.0);
+    if (!st.equilibrate_enable) {
+        if (n) CHIP_HIP(hipMemcpy(dinv, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+        if (m) CHIP_HIP(hipMemcpy(einv, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
+        return CHIP_OK;
+    }
+    BDev work;
+    unsigned long long *bits = nullptr;
+    double *cstate = nullptr, *colsum = nullptr, *delta = nullptr, *scr = nullptr;
+    const size_t nbits = dev::batch_eq_bits_words(n, m, nprob);
+    int rc;
+    if ((rc = work.alloc(&bits, nbits)) || (rc = work.alloc(&cstate, 2 * (size_t)nprob)) ||
+        (rc = work.alloc(&colsum, (size_t)nprob)) || (rc = work.alloc(&delta, (size_t)m)) ||
+        (rc = work.alloc(&scr, dev::seg_scratch_doubles(plan))))
+        return rc;
+    std::vector<double> c0(2 * (size_t)nprob, 1.0);
+    CHIP_HIP(hipMemcpy(cstate, c0.data(), c0.size() * 8, hipMemcpyHostToDevice));
+    hipStream_t s = stream;
+    for (int it = 0; it < st.equilibrate_max_iter; it++) {
+        CHIP_HIP(hipMemsetAsync(bits, 0, nbits * sizeof(unsigned long long), s));
+        dev::batch_eq_ruiz_step(s, plan, M, q, b, d, e, bits, scr, colsum, cstate, st.equilibrate_min_scaling,
+                                st.equilibrate_max_scaling);
+    }
+    // rectification of the second-order cones (compositecone.rs:183-195): per cone, so per member already
+    std::vector<int> sb, se;
+    for (const ConeSpec &cs : cones)
+        if (cs.tag == CHIP_CONE_SECONDORDER && cs.numel > 0) {
+            sb.push_back((int)cs.start);
+            se.push_back((int)(cs.start + cs.numel));
+        }
+    int *dsb = nullptr, *dse = nullptr;
+    if (!sb.empty()) {
+        if ((rc = work.upload(&dsb, sb.data(), sb.size())) || (rc = work.upload(&dse, se.data(), se.size()))) return rc;
+        dev::eq_rectify(s, M, b, e, m, dsb, dse, (int)sb.size(), delta);
+    }
+    dev::eq_invert(s, d, dinv, n, e, einv, m);
+    CHIP_HIP(hipGetLastError());
+    CHIP_HIP(hipMemcpyAsync(c0.data(), cstate, (size_t)nprob * 8, hipMemcpyDeviceToHost, s));
+    CHIP_HIP(hipStreamSynchronize(s));
+    for (int k = 0; k < nprob; k++) c[k] = c0[k];
+    return CHIP_OK;
+}
+
+int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n,
+                          int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval, const double *Pnzval,
+                          const double *q, const uint64_t *Acolptr, const uint64_t *Arowval, const double *Anzval,
+                          const double *b, int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims,
+                          const int64_t *cone_dims2, const double *cone_alphas_or_null,
+                          const double *genpow_alphas_or_null, const chip_solver_settings *settings) {
+    (void)cone_alphas_or_null;
+    (void)genpow_alphas_or_null;
+    if (!out) return failb(CHIP_ERR_ARG, "chip_batch_create: bad argument");
+    *out = nullptr;
+    if (nprob < 1 || !n_part || !m_part || n < 0 || m < 0 || !Pcolptr || !Acolptr || ncones < 0 ||
+        (ncones && (!cone_tags || !cone_dims)))
+        return failb(CHIP_ERR_ARG, "chip_batch_create: bad argument");
+    if ((Pcolptr[n] && (!Prowval || !Pnzval)) || (Acolptr[n] && (!Arowval || !Anzval)) || (n && !q) || (m && !b))
+        return failb(CHIP_ERR_ARG, "chip_batch_create: missing data");
+    const double t0 = now_s();
+    std::unique_ptr<chip_batch> h(new chip_batch());
+    if (settings) h->st = *settings;
+    else chip_solver_settings_default(&h->st);
+    chip_solver_settings &st = h->st;
+    st.linsys.linesearch_backtrack_step = st.linesearch_backtrack_step;
+    st.linsys.min_terminate_step_length = st.min_terminate_step_length;
+    if (st.presolve_enable || st.chordal_decomposition_enable)
+        return failb(CHIP_ERR_UNSUPPORTED, "chip_batch_create: presolve and chordal decomposition are not supported");
+    for (int64_t i = 0; i < ncones; i++)
+        if (cone_tags[i] != CHIP_CONE_ZERO && cone_tags[i] != CHIP_CONE_NONNEGATIVE &&
+            cone_tags[i] != CHIP_CONE_SECONDORDER)
+            return failb(CHIP_ERR_UNSUPPORTED, "chip_batch_create: only Zero, Nonnegative and SecondOrder cones");
+    if (nprob >= (1ll << 31)) return failb(CHIP_ERR_DIM, "chip_batch_create: sizes out of int32 range");
+    const uint64_t nnzP = Pcolptr[n], nnzA = Acolptr[n];
+    if (n >= (1ll << 31) || m >= (1ll << 31) || nnzP + nnzA + (uint64_t)n + (uint64_t)m >= (1ull << 31) ||
+        n + 2 * m >= (1ll << 31))
+        return failb(CHIP_ERR_DIM, "chip_batch_create: sizes out of int32 range");
+    // ---- the partition and the checks that every entry and cone stays inside its member
+    const int np = (int)nprob;
+    std::vector<int> xoff((size_t)np + 1, 0), zoff((size_t)np + 1, 0);
+    for (int k = 0; k < np; k++) {
+        if (n_part[k] < 0 || m_part[k] < 0) return failb(CHIP_ERR_ARG, "chip_batch_create: negative part");
+        const int64_t xn = (int64_t)xoff[k] + n_part[k], zn = (int64_t)zoff[k] + m_part[k];
+        if (xn > n || zn > m) return failb(CHIP_ERR_ARG, "chip_batch_create: the parts exceed n or m");
+        xoff[k + 1] = (int)xn;
+        zoff[k + 1] = (int)zn;
+    }
+    if (xoff[np] != n || zoff[np] != m) return failb(CHIP_ERR_ARG, "chip_batch_create: the parts do not add up to n, m");
+    std::vector<int> xmem((size_t)n), zmem((size_t)m);
+    for (int k = 0; k < np; k++) {
+        for (int j = xoff[k]; j < xoff[k + 1]; j++) xmem[j] = k;
+        for (int i = zoff[k]; i < zoff[k + 1]; i++) zmem[i] = k;
+    }
+    std::vector<int> Prow(nnzP), Pcol(nnzP), Arow(nnzA), Acol(nnzA);
+    std::vector<int> lp_init((size_t)np, 1);
+    for (int64_t j = 0; j < n; j++) {
+        const int k = xmem[j];
+        for (uint64_t p = Pcolptr[j]; p < Pcolptr[j + 1]; p++) {
+            const int64_t r = (int64_t)Prowval[p];
+            if (r > j) return failb(CHIP_ERR_NOT_TRIU, "P is not upper triangular");
+            if (r < xoff[k]) return failb(CHIP_ERR_ARG, "chip_batch_create: an entry of P crosses two members' blocks");
+            Prow[p] = (int)r;
+            Pcol[p] = (int)j;
+            lp_init[k] = 0;
+        }
+        for (uint64_t p = Acolptr[j]; p < Acolptr[j + 1]; p++) {
+            const int64_t r = (int64_t)Arowval[p];
+            if (r >= m) return failb(CHIP_ERR_DIM, "A row index out of range");
+            if (zmem[r] != k) return failb(CHIP_ERR_ARG, "chip_batch_create: an entry of A crosses two members' blocks");
+            Arow[p] = (int)r;
+            Acol[p] = (int)j;
+        }
+    }
+    std::vector<ConeSpec> cones;
+    int64_t mm = 0, pdim = 0, nHs = 0;
+    if (build_cone_specs(ncones, cone_tags, cone_dims, cone_dims2, cones, mm, pdim, nHs))
+        return failb(CHIP_ERR_ARG, "chip_batch_create: bad cone");
+    if (mm != m) return failb(CHIP_ERR_DIM, "chip_batch_create: cone dimensions do not add up to m");
+    std::vector<int> rtype((size_t)m, dev::ROW_ZERO);
+    std::vector<int64_t> degree((size_t)np, 0);
+    std::vector<int> it_beg, it_end, it_type, it_mem;
+    for (const ConeSpec &cs : cones) {
+        if (cs.numel == 0) continue;
+        const int r0 = (int)cs.start, r1 = (int)(cs.start + cs.numel), k = zmem[r0];
+        if (zmem[r1 - 1] != k) return failb(CHIP_ERR_ARG, "chip_batch_create: a cone crosses a member's rows");
+        if (cs.tag == CHIP_CONE_NONNEGATIVE) {
+            for (int i = r0; i < r1; i++) rtype[i] = dev::ROW_NN;
+            degree[k] += cs.numel;
+            for (int i = r0; i < r1; i += dev::BATCH_CHUNK) {
+                it_beg.push_back(i);
+                it_end.push_back(std::min(r1, i + dev::BATCH_CHUNK));
+                it_type.push_back(dev::ITEM_NN);
+                it_mem.push_back(k);
+            }
+        } else if (cs.tag == CHIP_CONE_SECONDORDER) {
+            rtype[r0] = dev::ROW_SOC_HEAD;
+            for (int i = r0 + 1; i < r1; i++) rtype[i] = dev::ROW_SOC_TAIL;
+            degree[k] += 1;
+            it_beg.push_back(r0);
+            it_end.push_back(r1);
+            it_type.push_back(dev::ITEM_SOC);
+            it_mem.push_back(k);
+        }
+    }
+    // cones are in row order, so the items are sorted by member
+    std::vector<int> it_first((size_t)np + 1, 0);
+    for (int k : it_mem) it_first[k + 1]++;
+    for (int k = 0; k < np; k++) it_first[k + 1] += it_first[k];
+    std::vector<int> ch_beg, ch_end, cx_first((size_t)np + 1, 0), cz_first((size_t)np + 1, 0);
+    for (int k = 0; k < np; k++) {
+        for (int j = xoff[k]; j < xoff[k + 1]; j += dev::BATCH_CHUNK) {
+            ch_beg.push_back(j);
+            ch_end.push_back(std::min(xoff[k + 1], j + dev::BATCH_CHUNK));
+        }
+        cx_first[k + 1] = (int)ch_beg.size();
+    }
+    const int ncx = (int)ch_beg.size();
+    for (int k = 0; k < np; k++) {
+        for (int i = zoff[k]; i < zoff[k + 1]; i += dev::BATCH_CHUNK) {
+            ch_beg.push_back(i);
+            ch_end.push_back(std::min(zoff[k + 1], i + dev::BATCH_CHUNK));
+        }
+        cz_first[k + 1] = (int)ch_beg.size() - ncx;
+    }
+    // ---- the device
+    if (st.linsys.device == CHIP_DEVICE_HOST_ONLY || chip_device_count() < 1)
+        return failb(CHIP_ERR_NO_DEVICE, "chip_batch_create: no HIP device (the product has no CPU fallback)");
+    if (st.linsys.device >= 0) CHIP_HIP(hipSetDevice(st.linsys.device));
+    CHIP_HIP(hipGetDevice(&h->device));
+    h->nprob = np;
+    h->n = (int)n;
+    h->m = (int)m;
+    h->xoff = xoff;
+    h->zoff = zoff;
+    h->degree = degree;
+    h->lp_init = lp_init;
+    h->anyP = nnzP > 0;
+    h->anyLP = std::find(lp_init.begin(), lp_init.end(), 1) != lp_init.end();
+    BDev &mem = h->mem;
+    int rc;
+    dev::BatchPlan &pl = h->plan;
+    int *d_xoff, *d_zoff, *d_xmem, *d_zmem, *d_chb, *d_che, *d_cxf, *d_czf, *d_itb, *d_ite, *d_itt, *d_itf, *d_rt;
+    if ((rc = mem.upload(&d_xoff, xoff.data(), xoff.size())) || (rc = mem.upload(&d_zoff, zoff.data(), zoff.size())) ||
+        (rc = mem.upload(&d_xmem, xmem.data(), xmem.size())) || (rc = mem.upload(&d_zmem, zmem.data(), zmem.size())) ||
+        (rc = mem.upload(&d_chb, ch_beg.data(), ch_beg.size())) ||
+        (rc = mem.upload(&d_che, ch_end.data(), ch_end.size())) ||
+        (rc = mem.upload(&d_cxf, cx_first.data(), cx_first.size())) ||
+        (rc = mem.upload(&d_czf, cz_first.data(), cz_first.size())) ||
+        (rc = mem.upload(&d_itb, it_beg.data(), it_beg.size())) ||
+        (rc = mem.upload(&d_ite, it_end.data(), it_end.size())) ||
+        (rc = mem.upload(&d_itt, it_type.data(), it_type.size())) ||
+        (rc = mem.upload(&d_itf, it_first.data(), it_first.size())) ||
+        (rc = mem.upload(&d_rt, rtype.data(), rtype.size())))
+        return rc;
+    pl = dev::BatchPlan{np,    (int)n, (int)m, d_xoff, d_zoff, d_xmem, d_zmem, d_chb,  d_che, d_cxf,
+                        d_czf, ncx,    (int)ch_beg.size() - ncx, d_itb, d_ite, d_itt, d_itf, (int)it_beg.size(), d_rt};
+    // ---- the data: b capped at the reference's infinity; per member the norms of the unequilibrated q and b
+    std::vector<double> bcap(b, b + m);
+    for (double &v : bcap) v = std::min(v, 1e20); // problemdata.rs:125-127
+    h->normq.assign((size_t)np, 0.0);
+    h->normb.assign((size_t)np, 0.0);
+    for (int k = 0; k < np; k++) {
+        double nq = 0.0, nb = 0.0;
+        for (int j = xoff[k]; j < xoff[k + 1]; j++) nq = std::isnan(q[j]) ? q[j] : std::max(nq, std::fabs(q[j]));
+        for (int i = zoff[k]; i < zoff[k + 1]; i++) nb = std::isnan(bcap[i]) ? bcap[i] : std::max(nb, std::fabs(bcap[i]));
+        h->normq[k] = nq;
+        h->normb[k] = nb;
+    }
+    dev::EqMats &M = h->M;
+    int *dPr, *dPc, *dAr, *dAc;
+    if ((rc = mem.upload(&dPr, Prow.data(), nnzP)) || (rc = mem.upload(&dPc, Pcol.data(), nnzP)) ||
+        (rc = mem.upload(&M.Px, Pnzval, nnzP)) || (rc = mem.upload(&dAr, Arow.data(), nnzA)) ||
+        (rc = mem.upload(&dAc, Acol.data(), nnzA)) || (rc = mem.upload(&M.Ax, Anzval, nnzA)) ||
+        (rc = mem.upload(&h->q, q, (size_t)n)) || (rc = mem.upload(&h->b, bcap.data(), (size_t)m)))
+        return rc;
+    M.Prow = dPr;
+    M.Pcol = dPc;
+    M.Arow = dAr;
+    M.Acol = dAc;
+    M.nnzP = (int)nnzP;
+    M.nnzA = (int)nnzA;
+    if ((rc = mem.alloc(&h->d, (size_t)n)) || (rc = mem.alloc(&h->e, (size_t)m)) ||
+        (rc = mem.alloc(&h->dinv, (size_t)n)) || (rc = mem.alloc(&h->einv, (size_t)m)) ||
+        (rc = mem.alloc(&h->negq, (size_t)n)))
+        return rc;
+    CHIP_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); // replaced by the KKT handle's below
+    hipStream_t s_eq = h->stream;
+    const double te = now_s();
+    rc = h->equilibrate(cones);
+    (void)hipStreamDestroy(s_eq);
+    h->stream = nullptr;
+    if (rc) return rc;
+    h->equilibration_time = now_s() - te;
+    // ---- one KKT system of the equilibrated stack (block-diagonal K)
+    std::vector<double> Px(nnzP), Ax(nnzA), qs(n), bs(m);
+    if (nnzP) CHIP_HIP(hipMemcpy(Px.data(), M.Px, nnzP * 8, hipMemcpyDeviceToHost));
+    if (nnzA) CHIP_HIP(hipMemcpy(Ax.data(), M.Ax, nnzA * 8, hipMemcpyDeviceToHost));
+    if (n) CHIP_HIP(hipMemcpy(qs.data(), h->q, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (m) CHIP_HIP(hipMemcpy(bs.data(), h->b, (size_t)m * 8, hipMemcpyDeviceToHost));
+    if ((rc = chip_kkt_create(&h->kkt, n, m, Pcolptr, Prowval, Px.data(), Acolptr, Arowval, Ax.data(), ncones,
+                              cone_tags, cone_dims, cone_dims2, nullptr, &st.linsys, nullptr)))
+        return rc;
+    if ((rc = chip_kktsystem_create(&h->sys, h->kkt, Pcolptr, Prowval, Px.data(), Acolptr, Arowval, Ax.data(),
+                                    qs.data(), bs.data())))
+        return rc;
+    h->stream = (hipStream_t)chip_kkt_stream(h->kkt);
+    const size_t N = (size_t)n, Mm = (size_t)m;
+    if ((rc = mem.alloc(&h->vx, N)) || (rc = mem.alloc(&h->vs, Mm)) || (rc = mem.alloc(&h->vz, Mm)) ||
+        (rc = mem.alloc(&h->px, N)) || (rc = mem.alloc(&h->ps, Mm)) || (rc = mem.alloc(&h->pz, Mm)) ||
+        (rc = mem.alloc(&h->hx, N)) || (rc = mem.alloc(&h->hs, Mm)) || (rc = mem.alloc(&h->hz, Mm)) ||
+        (rc = mem.alloc(&h->lx, N)) || (rc = mem.alloc(&h->ls, Mm)) || (rc = mem.alloc(&h->lz, Mm)) ||
+        (rc = mem.alloc(&h->dx, N)) || (rc = mem.alloc(&h->ds, Mm)) || (rc = mem.alloc(&h->dz, Mm)) ||
+        (rc = mem.alloc(&h->x1, N)) || (rc = mem.alloc(&h->z1, Mm)) || (rc = mem.alloc(&h->x2, N)) ||
+        (rc = mem.alloc(&h->z2, Mm)) || (rc = mem.alloc(&h->workx, N)) || (rc = mem.alloc(&h->workx2, N)) ||
+        (rc = mem.alloc(&h->wn, N)) || (rc = mem.alloc(&h->wn2, N)) || (rc = mem.alloc(&h->wn3, N)) || (rc = mem.alloc(&h->workz, Mm)) ||
+        (rc = mem.alloc(&h->conicw, Mm)) || (rc = mem.alloc(&h->rx, N)) || (rc = mem.alloc(&h->rz, Mm)) ||
+        (rc = mem.alloc(&h->rx_inf, N)) || (rc = mem.alloc(&h->rz_inf, Mm)) || (rc = mem.alloc(&h->Pxv, N)) ||
+        (rc = mem.alloc(&h->xo, N)) || (rc = mem.alloc(&h->so, Mm)) || (rc = mem.alloc(&h->zo, Mm)))
+        return rc;
+    const size_t red_len = (size_t)(R_COUNT + 2) * np; // + the interior minima
+    if ((rc = mem.alloc(&h->dsc_ring, (size_t)chip_batch::RING * S_COUNT * np)) ||
+        (rc = mem.alloc(&h->dmask_ring, (size_t)chip_batch::RING * M_COUNT * np)) ||
+        (rc = mem.alloc(&h->dred, red_len)) || (rc = mem.alloc(&h->seg_scr, dev::seg_scratch_doubles(pl))) ||
+        (rc = mem.alloc(&h->cone_scr, dev::cone_scratch_doubles(pl))))
+        return rc;
+    h->hsc.assign((size_t)S_COUNT * np, 0.0);
+    h->hmask.assign((size_t)M_COUNT * np, 0);
+    h->hred.assign(red_len, 0.0);
+    h->hsc_ring.assign((size_t)chip_batch::RING * S_COUNT * np, 0.0);
+    h->hmask_ring.assign((size_t)chip_batch::RING * M_COUNT * np, 0);
+    h->dsc = h->dsc_ring;
+    h->dmask = h->dmask_ring;
+    dev::waxpby(h->stream, h->negq, -1.0, h->q, 0.0, nullptr, h->n);
+    CHIP_HIP(hipGetLastError());
+    CHIP_HIP(hipStreamSynchronize(h->stream));
+    h->setup_time = now_s() - t0;
+    *out = h.release();
+    return CHIP_OK;
+}
+
+void chip_batch_destroy(chip_batch *h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    delete h;
+}
+
+// default_start (core/solver.rs:525-541) for symmetric cones, per member: the initial point of kktsystem.rs:197-231
+// (QP members from [-q; b], LP members from [0; b] and [-q; 0]) and _shift_to_cone_interior (variables.rs:231-256)
+// with the member's margins and degree
+int chip_batch::default_start() {
+    int rc;
+    hipStream_t s = stream;
+    if ((rc = chip_kkt_unit_initialization_dev(kkt, dz, ds))) return rc;
+    if ((rc = chip_kkt_update_scaling_dev(kkt, dz, dz, 1.0, 0)) < 0) return rc;
+    if ((rc = chip_kkt_update(kkt, nullptr)) < 0) return rc; // (the reference ignores the bool here)
+    for (int k = 0; k < nprob; k++) {
+        hm(M_QP, k) = !lp_init[k];
+        hm(M_LP, k) = lp_init[k];
+    }
+    if ((rc = push_masks())) return rc;
+    lin(workx, negq, nullptr, nullptr, nullptr, 1.0, 0.0, 0, mk(M_QP), dev::MASK_ZERO); // QP: -q, LP: 0
+    if ((rc = chip_kkt_setrhs_dev(kkt, workx, b))) return rc;
+    if ((rc = chip_kkt_solve_dev(kkt, vx, vz)) < 0) return rc;
+    dev::waxpby(s, vs, -1.0, vz, 0.0, nullptr, m); // QP: s = -z; LP: s = -(the z part of [0; b])
+    if (anyLP) {
+        lin(workx, negq, nullptr, nullptr, nullptr, 1.0, 0.0, 0, mk(M_LP), dev::MASK_ZERO);
+        CHIP_HIP(hipMemsetAsync(workz, 0, std::max<size_t>((size_t)m, 1) * 8, s));
+        if ((rc = chip_kkt_setrhs_dev(kkt, workx, workz))) return rc;
+        if ((rc = chip_kkt_solve_dev(kkt, x1, z1)) < 0) return rc;
+        lin(vz, z1, nullptr, nullptr, nullptr, 1.0, 0.0, 1, mk(M_LP), dev::MASK_KEEP);
+    }
+    // the shifts of s (primal) and z (dual)
+    for (int pass = 0; pass < 2; pass++) {
+        double *v = pass == 0 ? vs : vz;
+        dev::cone_minima(s, plan, dev::CONE_MARGINS, nullptr, nullptr, v, nullptr, nullptr, dred, dred + nprob,
+                         cone_scr);
+        if ((rc = read_red(2 * (size_t)nprob))) return rc;
+        for (int k = 0; k < nprob; k++) {
+            const double mn = red(0, k), pos = red(1, k);
+            const double target = std::max(1.0, (pos * 0.1) / (double)degree[k]);
+            double a1 = 0.0, a2 = 0.0;
+            if (mn <= 0.0) {
+                a1 = -mn;
+                a2 = target;
+            } else if (mn < target) {
+                a1 = target - mn;
+            }
+            hs_(S_SHIFT1, k) = a1;
+            hs_(S_SHIFT2, k) = a2;
+        }
+        if ((rc = push_scalars())) return rc;
+        dev::bunit_shift(s, plan, v, sc(S_SHIFT1), pass == 0, nullptr);
+        dev::bunit_shift(s, plan, v, sc(S_SHIFT2), pass == 0, nullptr);
+    }
+    for (int k = 0; k < nprob; k++) tau[k] = kappa[k] = 1.0;
+    // the previous iterate starts as the initial one (a member that fails before its first step reports it)
+    if (n) CHIP_HIP(hipMemcpyAsync(px, vx, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+    if (m) CHIP_HIP(hipMemcpyAsync(ps, vs, (size_t)m * 8, hipMemcpyDeviceToDevice, s));
+    if (m) CHIP_HIP(hipMemcpyAsync(pz, vz, (size_t)m * 8, hipMemcpyDeviceToDevice, s));
+    CHIP_HIP(hipGetLastError());
+    return CHIP_OK;
+}
+
+// Residuals::update + DefaultInfo::update's norms and dots for every member, the finiteness counts and the interior
+// minima of (s, z): one segmented pass, one cone pass, ONE device-to-host copy
+int chip_batch::residual_pass() {
+    int rc;
+    for (int k = 0; k < nprob; k++) hs_(S_TAU, k) = tau[k];
+    if ((rc = push_scalars())) return rc;
+    if (anyP) {
+        if ((rc = spmv(0, Pxv, nullptr, 1.0, vx))) return rc;
+    } else if (n) {
+        CHIP_HIP(hipMemsetAsync(Pxv, 0, (size_t)n * 8, stream));
+    }
+    if ((rc = spmv(2, rx_inf, nullptr, -1.0, vz))) return rc; // rx_inf = -A' z
+    if ((rc = spmv(1, rz_inf, vs, 1.0, vx))) return rc;       // rz_inf = A x + s
+    dev::bresid(stream, plan, rx, rx_inf, Pxv, q, rz, rz_inf, b, sc(S_TAU));
+    dev::SegBatch bt{};
+    auto add = [&](const double *a, const double *w, int kind, int space, int slot) {
+        bt.s[bt.count++] = dev::SegSpec{a, w, kind, space, slot};
+    };
+    add(q, vx, dev::SEG_DOT, 0, R_QX);
+    add(vx, Pxv, dev::SEG_DOT, 0, R_XPX);
+    add(vx, d, dev::SEG_WSQ, 0, R_NX);
+    add(rx_inf, dinv, dev::SEG_WSQ, 0, R_NRXI);
+    add(Pxv, dinv, dev::SEG_WSQ, 0, R_NPX);
+    add(rx, dinv, dev::SEG_WSQ, 0, R_NRX);
+    add(vx, nullptr, dev::SEG_NONFINITE, 0, R_BADX);
+    add(b, vz, dev::SEG_DOT, 1, R_BZ);
+    add(vs, vz, dev::SEG_DOT, 1, R_SZ);
+    add(vz, e, dev::SEG_WSQ, 1, R_NZ);
+    add(vs, einv, dev::SEG_WSQ, 1, R_NS);
+    add(rz_inf, einv, dev::SEG_WSQ, 1, R_NRZI);
+    add(rz, einv, dev::SEG_WSQ, 1, R_NRZ);
+    add(vs, vz, dev::SEG_NONFINITE, 1, R_BADSZ);
+    dev::seg_reduce(stream, plan, bt, dred, seg_scr);
+    dev::cone_minima(stream, plan, dev::CONE_INTERIOR, nullptr, nullptr, vz, vs, nullptr, dred + (size_t)R_COUNT * nprob,
+                     nullptr, cone_scr);
+    launches += 4;
+    return read_red((size_t)(R_COUNT + 1) * nprob);
+}
+
+// DefaultInfo::update (info.rs:113-178) of member k from the residual pass
+void chip_batch::member_info(int k) {
+    MInfo &I = info[k];
+    const double t = tau[k];
+    const double qx = red(R_QX, k), bz = red(R_BZ, k), sz = red(R_SZ, k), xPx = anyP ? red(R_XPX, k) : 0.0;
+    I.out5[0] = qx + bz + kappa[k] + xPx / t;
+    I.out5[1] = qx;
+    I.out5[2] = bz;
+    I.out5[3] = sz;
+    I.out5[4] = xPx;
+    double nrm[8];
+    const int slots[8] = {R_NX, R_NZ, R_NS, R_NRXI, R_NPX, R_NRZI, R_NRZ, R_NRX};
+    for (int j = 0; j < 8; j++) nrm[j] = std::sqrt(red(slots[j], k));
+    const double tinv = 1.0 / t, cinv = 1.0 / c[k];
+    const double xPx2 = xPx * tinv * tinv / 2.0;
+    I.cost_primal = (qx * tinv + xPx2) * cinv;
+    I.cost_dual = (-bz * tinv - xPx2) * cinv;
+    double normx = nrm[0], normz = nrm[1] * cinv, norms = nrm[2];
+    I.res_primal_inf = (nrm[3] * cinv) / std::max(1.0, normz);
+    I.res_dual_inf = std::max(nrm[4] / std::max(1.0, normx), nrm[5] / std::max(1.0, normx + norms));
+    normx *= tinv;
+    normz *= tinv;
+    norms *= tinv;
+    I.res_primal = nrm[6] * tinv / std::max(1.0, normb[k] + normx + norms);
+    I.res_dual = nrm[7] * tinv * cinv / std::max(1.0, normq[k] + normx + normz);
+    I.gap_abs = std::fabs(I.cost_primal - I.cost_dual);
+    I.gap_rel = I.gap_abs / std::max(1.0, std::min(std::fabs(I.cost_primal), std::fabs(I.cost_dual)));
+    I.ktratio = kappa[k] * tinv;
+    mu[k] = (sz + tau[k] * kappa[k]) / (double)(degree[k] + 1); // variables.rs:63-66
+}
+
+// check_convergence_full / _almost (info.rs:277-389)
+void chip_batch::check_convergence(int k, bool almost) {
+    MInfo &I = info[k];
+    const double tga = almost ? st.reduced_tol_gap_abs : st.tol_gap_abs;
+    const double tgr = almost ? st.reduced_tol_gap_rel : st.tol_gap_rel;
+    const double tf = almost ? st.reduced_tol_feas : st.tol_feas;
+    const double tia = almost ? st.reduced_tol_infeas_abs : st.tol_infeas_abs;
+    const double tir = almost ? st.reduced_tol_infeas_rel : st.tol_infeas_rel;
+    const double tkt = almost ? st.reduced_tol_ktratio : st.tol_ktratio;
+    const double dot_qx = I.out5[1], dot_bz = I.out5[2];
+    if (I.ktratio <= 1.0 && (I.gap_abs < tga || I.gap_rel < tgr) && I.res_primal < tf && I.res_dual < tf) {
+        I.status = almost ? CHIP_SOLVER_ALMOST_SOLVED : CHIP_SOLVER_SOLVED;
+    } else if (I.ktratio > (1.0 / tkt) * 1000.0) {
+        if (dot_bz < -tia && I.res_primal_inf < -tir * dot_bz)
+            I.status = almost ? CHIP_SOLVER_ALMOST_PRIMAL_INFEASIBLE : CHIP_SOLVER_PRIMAL_INFEASIBLE;
+        else if (dot_qx < -tia && I.res_dual_inf < -tir * dot_qx)
+            I.status = almost ? CHIP_SOLVER_ALMOST_DUAL_INFEASIBLE : CHIP_SOLVER_DUAL_INFEASIBLE;
+    }
+}
+
+// check_termination (info.rs:182-231) of member k
+bool chip_batch::check_termination(int k, int iter) {
+    MInfo &I = info[k];
+    check_convergence(k, false);
+    if (I.status == CHIP_SOLVER_UNSOLVED && iter > 1 && (I.res_dual > I.prev_res_dual || I.res_primal > I.prev_res_primal)) {
+        if (I.ktratio < std::numeric_limits<double>::epsilon() * 100.0 &&
+            (I.prev_gap_abs < st.tol_gap_abs || I.prev_gap_rel < st.tol_gap_rel))
+            I.status = CHIP_SOLVER_INSUFFICIENT_PROGRESS;
+        if (I.ktratio < 1.0) {
+            if ((I.res_dual > st.tol_feas * 100.0 && I.res_dual > I.prev_res_dual * 100.0) ||
+                (I.res_primal > st.tol_feas * 100.0 && I.res_primal > I.prev_res_primal * 100.0))
+                I.status = CHIP_SOLVER_INSUFFICIENT_PROGRESS;
+        }
+    }
+    if (I.status == CHIP_SOLVER_UNSOLVED) {
+        if (st.max_iter == I.iterations) I.status = CHIP_SOLVER_MAX_ITERATIONS;
+        else if (solve_time > st.time_limit) I.status = CHIP_SOLVER_MAX_TIME;
+    }
+    return I.status != CHIP_SOLVER_UNSOLVED;
+}
+
+// member k ends NumericalError: its reported solution is its last finite iterate (the previous one when the current
+// one is not finite), held aside; its s and z become the cones' unit vector so that its block of K stays well posed
+int chip_batch::end_member(int k, int status, int iterations, bool from_prev) {
+    info[k].status = status;
+    info[k].iterations = iterations;
+    active[k] = 0;
+    held[k] = from_prev ? 2 : 1;
+    return CHIP_OK;
+}
+
+// the KKT solve of one direction with the member-wise tau step (kktsystem.rs:127-195): right-hand side (dx, ds, dz)
+// and rtau / rkappa per member; the result in (lx, ls, lz) and dtau / lkappa per member.  conic: the constant term of
+// Hs dz + ds = -conic.  Members whose part of the solution is not finite end NumericalError; *global_ok is the
+// engine's verdict
+int chip_batch::solve_direction(const double *conic, const std::vector<double> &rtau, const std::vector<double> &rkap,
+                                std::vector<double> &lkappa, bool *global_ok, int iter) {
+    int rc;
+    hipStream_t s = stream;
+    // frozen members contribute a zero right-hand side, so their part of the solution is 0 and stays finite
+    lin(workz, conic, dz, nullptr, nullptr, 1.0, -1.0, 1, mk(M_ACTIVE), dev::MASK_ZERO);
+    lin(workx, dx, nullptr, nullptr, nullptr, 1.0, 0.0, 0, mk(M_ACTIVE), dev::MASK_ZERO);
+    if ((rc = chip_kkt_setrhs_dev(kkt, workx, workz))) return rc;
+    rc = chip_kkt_solve_dev(kkt, x1, z1);
+    syncs++;
+    launches++;
+    if (rc < 0) return rc;
+    *global_ok = rc == 1;
+    // the dots of the tau numerator and denominator per member and the finiteness of (x1, z1), one copy
+    for (int k = 0; k < nprob; k++) hs_(S_INVTAU, k) = 1.0 / tau[k];
+    if ((rc = push_scalars())) return rc;
+    dev::SegBatch bt{};
+    bt.s[bt.count++] = dev::SegSpec{q, x1, dev::SEG_DOT, 0, D_QX1};
+    bt.s[bt.count++] = dev::SegSpec{b, z1, dev::SEG_DOT, 1, D_BZ1};
+    if (anyP) {
+        lin(wn2, vx, nullptr, sc(S_INVTAU), nullptr, 1.0, 0.0, 0, nullptr, 0); // xi = x / tau
+        if ((rc = spmv(0, wn, nullptr, 1.0, x1))) return rc;                   // P x1
+        dev::waxpby(s, workx2, -1.0, x2, 1.0, wn2, n);                         // xi - x2
+        if ((rc = spmv(0, wn3, nullptr, 1.0, workx2))) return rc;
+        launches++;
+        bt.s[bt.count++] = dev::SegSpec{wn2, wn, dev::SEG_DOT, 0, D_XIPX1};
+        bt.s[bt.count++] = dev::SegSpec{workx2, wn3, dev::SEG_DOT, 0, D_DPD};
+    }
+    bt.s[bt.count++] = dev::SegSpec{x1, nullptr, dev::SEG_NONFINITE, 0, D_BAD};
+    bt.s[bt.count++] = dev::SegSpec{z1, nullptr, dev::SEG_NONFINITE, 1, D_BAD + 1};
+    dev::seg_reduce(s, plan, bt, dred, seg_scr);
+    launches += 2;
+    if ((rc = read_red((size_t)(D_COUNT + 1) * nprob))) return rc;
+    for (int k = 0; k < nprob; k++) {
+        dtau[k] = 0.0;
+        lkappa[k] = 0.0;
+        if (!active[k]) continue;
+        const double t = tau[k], kp = kappa[k];
+        const double xiPx1 = anyP ? red(D_XIPX1, k) : 0.0, dPd = anyP ? red(D_DPD, k) : 0.0;
+        const double tau_num = rtau[k] - rkap[k] / t + red(D_QX1, k) + red(D_BZ1, k) + 2.0 * xiPx1;
+        double tau_den = kp / t - qx2[k] - bz2[k];
+        tau_den += dPd - x2Px2[k];
+        const double lt = tau_num / tau_den;
+        if (red(D_BAD, k) != 0.0 || red(D_BAD + 1, k) != 0.0 || !std::isfinite(lt)) {
+            end_member(k, CHIP_SOLVER_NUMERICAL_ERROR, iter, false);
+            continue;
+        }
+        dtau[k] = lt;
+        lkappa[k] = -(rkap[k] + kp * lt) / t;
+    }
+    for (int k = 0; k < nprob; k++) {
+        hs_(S_DTAU, k) = dtau[k];
+        hm(M_ACTIVE, k) = active[k];
+    }
+    if ((rc = push_scalars()) || (rc = push_masks())) return rc;
+    lin(lx, x1, x2, nullptr, sc(S_DTAU), 1.0, 0.0, 0, nullptr, 0); // x1 + dtau x2
+    lin(lz, z1, z2, nullptr, sc(S_DTAU), 1.0, 0.0, 1, nullptr, 0);
+    if ((rc = chip_kkt_mul_Hs_dev(kkt, ls, lz))) return rc; // ds = -(Hs dz + conic)
+    dev::waxpby(s, ls, -1.0, conic, -1.0, ls, m);
+    launches += 2;
+    CHIP_HIP(hipGetLastError());
+    return CHIP_OK;
+}
+
+// calc_step_length (variables.rs:120-160) per member: the tau / kappa bounds on the host, the cones on the device
+int chip_batch::step_length(const std::vector<double> &lkappa, bool combined) {
+    int rc;
+    const double big = std::numeric_limits<double>::max();
+    for (int k = 0; k < nprob; k++) {
+        const double a_tau = dtau[k] < 0.0 ? -tau[k] / dtau[k] : big;
+        const double a_kap = lkappa[k] < 0.0 ? -kappa[k] / lkappa[k] : big;
+        hs_(S_AMAX, k) = std::min(std::min(a_tau, a_kap), 1.0);
+    }
+    if ((rc = push_scalars())) return rc;
+    dev::cone_minima(stream, plan, dev::CONE_STEP, lz, ls, vz, vs, sc(S_AMAX), dred, nullptr, cone_scr);
+    launches += 2;
+    if ((rc = read_red((size_t)nprob))) return rc;
+    for (int k = 0; k < nprob; k++) {
+        double a = red(0, k);
+        if (combined) a *= st.max_step_fraction;
+        alpha[k] = active[k] ? a : 0.0;
+    }
+    return CHIP_OK;
+}
+
+// the constant right-hand side [-q; b] after each KKT update (kktsystem.rs:108-125) and its dots per member
+int chip_batch::constant_rhs(bool *global_ok, int iter) {
+    int rc;
+    if ((rc = chip_kkt_setrhs_dev(kkt, negq, b))) return rc;
+    rc = chip_kkt_solve_dev(kkt, x2, z2);
+    syncs++;
+    launches++;
+    if (rc < 0) return rc;
+    *global_ok = rc == 1;
+    dev::SegBatch bt{};
+    bt.s[bt.count++] = dev::SegSpec{q, x2, dev::SEG_DOT, 0, 0};
+    bt.s[bt.count++] = dev::SegSpec{b, z2, dev::SEG_DOT, 1, 1};
+    if (anyP) {
+        if ((rc = spmv(0, wn, nullptr, 1.0, x2))) return rc;
+        bt.s[bt.count++] = dev::SegSpec{x2, wn, dev::SEG_DOT, 0, 2};
+    }
+    bt.s[bt.count++] = dev::SegSpec{x2, nullptr, dev::SEG_NONFINITE, 0, 3};
+    bt.s[bt.count++] = dev::SegSpec{z2, nullptr, dev::SEG_NONFINITE, 1, 4};
+    dev::seg_reduce(stream, plan, bt, dred, seg_scr);
+    launches += 2;
+    if ((rc = read_red(5 * (size_t)nprob))) return rc;
+    for (int k = 0; k < nprob; k++) {
+        qx2[k] = red(0, k);
+        bz2[k] = red(1, k);
+        x2Px2[k] = anyP ? red(2, k) : 0.0;
+        if (active[k] && (red(3, k) != 0.0 || red(4, k) != 0.0)) end_member(k, CHIP_SOLVER_NUMERICAL_ERROR, iter, false);
+    }
+    return CHIP_OK;
+}
+
+// the held iterates of the members that ended NumericalError this iteration (the current one, or the previous one
+// when the current one is not finite), then their s and z reset to the unit vector
+int chip_batch::hold_and_reset() {
+    bool any = false;
+    for (int k = 0; k < nprob; k++) {
+        hm(M_SEL, k) = held[k] == 1 && !held_done[k];
+        hm(M_SEL2, k) = held[k] == 2 && !held_done[k];
+        any = any || hm(M_SEL, k) || hm(M_SEL2, k);
+    }
+    if (!any) return CHIP_OK;
+    for (int k = 0; k < nprob; k++) {
+        if (!hm(M_SEL, k) && !hm(M_SEL2, k)) continue;
+        const bool prev = hm(M_SEL2, k);
+        htau[k] = prev ? ptau[k] : tau[k];
+        hkappa[k] = prev ? pkappa[k] : kappa[k];
+        const int status = info[k].status, iterations = info[k].iterations;
+        hinfo[k] = prev ? pinfo[k] : info[k];
+        hinfo[k].status = status;
+        hinfo[k].iterations = iterations;
+        held_done[k] = 1;
+    }
+    int rc;
+    if ((rc = push_masks())) return rc;
+    copy_members(hx, hs, hz, vx, vs, vz, mk(M_SEL));
+    copy_members(hx, hs, hz, px, ps, pz, mk(M_SEL2));
+    for (int k = 0; k < nprob; k++) hm(M_SEL, k) = hm(M_SEL, k) || hm(M_SEL2, k);
+    if ((rc = push_masks())) return rc;
+    dev::bunit_reset(stream, plan, vx, vs, vz, mk(M_SEL));
+    launches++;
+    CHIP_HIP(hipGetLastError());
+    return CHIP_OK;
+}
+
+// info.post_process (info.rs:95-105) and solution.post_process (solution.rs:68-111) per member, one segmented unscale
+int chip_batch::post_process() {
+    int rc;
+    for (int k = 0; k < nprob; k++) {
+        hm(M_SEL, k) = held[k] != 0;
+        if (held[k]) {
+            info[k] = hinfo[k];
+            tau[k] = htau[k];
+            kappa[k] = hkappa[k];
+        }
+    }
+    if ((rc = push_masks())) return rc;
+    copy_members(vx, vs, vz, hx, hs, hz, mk(M_SEL));
+    for (int k = 0; k < nprob; k++) {
+        MInfo &I = info[k];
+        const int s = I.status;
+        if (s == CHIP_SOLVER_NUMERICAL_ERROR || s == CHIP_SOLVER_INSUFFICIENT_PROGRESS || s == CHIP_SOLVER_MAX_ITERATIONS ||
+            s == CHIP_SOLVER_MAX_TIME)
+            check_convergence(k, true);
+        const bool inf = is_infeasible(I.status);
+        obj_val[k] = inf ? std::numeric_limits<double>::quiet_NaN() : I.cost_primal;
+        obj_val_dual[k] = inf ? std::numeric_limits<double>::quiet_NaN() : I.cost_dual;
+        const double scaleinv = inf ? 1.0 / kappa[k] : 1.0 / tau[k];
+        hs_(S_SX, k) = scaleinv;
+        hs_(S_SZ, k) = scaleinv * (1.0 / c[k]);
+    }
+    if ((rc = push_scalars())) return rc;
+    dev::bunscale(stream, plan, xo, vx, d, zo, vz, e, so, vs, einv, sc(S_SX), sc(S_SZ));
+    CHIP_HIP(hipGetLastError());
+    CHIP_HIP(hipStreamSynchronize(stream));
+    return CHIP_OK;
+}
+
+// IPSolver::solve (core/solver.rs:242-464) with every scalar indexed by member
+int32_t chip_batch_solve(chip_batch *h) {
+    if (!h) return failb(CHIP_ERR_ARG, "chip_batch_solve: bad argument");
+    CHIP_HIP(hipSetDevice(h->device));
+    const int np = h->nprob;
+    const chip_solver_settings &st = h->st;
+    auto zeros = [np](std::vector<double> &v) { v.assign((size_t)np, 0.0); };
+    for (auto *v : {&h->tau, &h->kappa, &h->ptau, &h->pkappa, &h->htau, &h->hkappa, &h->mu, &h->sigma, &h->alpha,
+                    &h->dtau, &h->obj_val, &h->obj_val_dual, &h->qx2, &h->bz2, &h->x2Px2})
+        zeros(*v);
+    h->info.assign((size_t)np, MInfo());
+    h->pinfo.assign((size_t)np, MInfo());
+    h->hinfo.assign((size_t)np, MInfo());
+    h->active.assign((size_t)np, 1);
+    h->held.assign((size_t)np, 0);
+    h->held_done.assign((size_t)np, 0);
+    h->t_solve0 = now_s();
+    h->solve_time = h->setup_time;
+    int rc;
+    if ((rc = h->default_start())) return rc;
+    for (int k = 0; k < np; k++) h->hm(M_ACTIVE, k) = 1;
+    if ((rc = h->push_masks())) return rc;
+    CHIP_HIP(hipStreamSynchronize(h->stream));
+    h->syncs = h->launches = h->loop_iters = 0;
+    const double t_loop0 = now_s();
+    int iter = 0;
+    std::vector<double> rtau((size_t)np), rkap((size_t)np), lkappa((size_t)np);
+    std::vector<char> restore((size_t)np);
+    while (true) {
+#ifdef CHIP_TESTING
+        if (h->nan_member >= 0 && h->nan_member < np && iter == h->nan_iter && h->zoff[h->nan_member + 1] > h->zoff[h->nan_member]) {
+            const double nan = std::numeric_limits<double>::quiet_NaN();
+            CHIP_HIP(hipMemcpyAsync(h->vz + h->zoff[h->nan_member], &nan, 8, hipMemcpyHostToDevice, h->stream));
+            CHIP_HIP(hipStreamSynchronize(h->stream));
+        }
+#endif
+        if ((rc = h->residual_pass())) return rc;
+        h->solve_time = h->setup_time + (now_s() - h->t_solve0);
+        bool any_restore = false;
+        for (int k = 0; k < np; k++) {
+            if (!h->active[k]) continue;
+            MInfo &I = h->info[k];
+            h->member_info(k);
+            I.iterations = iter;
+            if (h->check_termination(k, iter)) {
+                h->active[k] = 0;
+                if (I.status == CHIP_SOLVER_INSUFFICIENT_PROGRESS) { // reset_to_prev_iterate (info.rs:244-253)
+                    I.cost_primal = I.prev_cost_primal;
+                    I.cost_dual = I.prev_cost_dual;
+                    I.res_primal = I.prev_res_primal;
+                    I.res_dual = I.prev_res_dual;
+                    I.gap_abs = I.prev_gap_abs;
+                    I.gap_rel = I.prev_gap_rel;
+                    restore[k] = 1;
+                    any_restore = true;
+                    h->tau[k] = h->ptau[k];
+                    h->kappa[k] = h->pkappa[k];
+                }
+                continue;
+            }
+            // the pre-update check: s and z finite and strictly interior, x finite
+            const bool nonfin = h->red(R_BADX, k) != 0.0 || h->red(R_BADSZ, k) != 0.0;
+            const double margin = h->red(R_COUNT, k);
+            if (nonfin || !(margin > 0.0)) h->end_member(k, CHIP_SOLVER_NUMERICAL_ERROR, iter, nonfin);
+        }
+        if (any_restore) {
+            for (int k = 0; k < np; k++) h->hm(M_SEL, k) = restore[k];
+            if ((rc = h->push_masks())) return rc;
+            h->copy_members(h->vx, h->vs, h->vz, h->px, h->ps, h->pz, h->mk(M_SEL));
+            std::fill(restore.begin(), restore.end(), 0);
+        }
+        if ((rc = h->hold_and_reset())) return rc;
+        bool any_active = false;
+        for (int k = 0; k < np; k++) {
+            h->hm(M_ACTIVE, k) = h->active[k];
+            any_active = any_active || h->active[k];
+        }
+        if (!any_active) break;
+        if ((rc = h->push_masks())) return rc;
+        h->loop_iters++;
+        // scale cones and refactor (NN and SOC scalings do not read mu)
+        if ((rc = chip_kkt_update_scaling_dev(h->kkt, h->vs, h->vz, 1.0, 0)) < 0) return rc;
+        iter++;
+        rc = chip_kkt_update(h->kkt, nullptr);
+        h->syncs++;
+        h->launches++;
+        if (rc < 0) return rc;
+        bool ok = rc == 1;
+        if (ok && (rc = h->constant_rhs(&ok, iter))) return rc;
+        if (!ok) { // a failed factorisation that no member accounts for (the reference stops before counting it)
+            for (int k = 0; k < np; k++)
+                if (h->active[k]) h->end_member(k, CHIP_SOLVER_NUMERICAL_ERROR, iter - 1, false);
+            if ((rc = h->hold_and_reset())) return rc;
+            break;
+        }
+        if ((rc = h->hold_and_reset())) return rc;
+        // affine step rhs (variables.rs:68-79)
+        for (int k = 0; k < np; k++) {
+            h->hm(M_ACTIVE, k) = h->active[k];
+            rtau[k] = h->info[k].out5[0];
+            rkap[k] = h->tau[k] * h->kappa[k];
+        }
+        if ((rc = h->push_masks())) return rc;
+        h->lin(h->dx, h->rx, nullptr, nullptr, nullptr, 1.0, 0.0, 0, nullptr, 0);
+        h->lin(h->dz, h->rz, nullptr, nullptr, nullptr, 1.0, 0.0, 1, nullptr, 0);
+        if ((rc = chip_kkt_affine_ds_dev(h->kkt, h->ds, h->vs))) return rc;
+        ok = true;
+        if ((rc = h->solve_direction(h->vs, rtau, rkap, lkappa, &ok, iter))) return rc;
+        bool any_flag = false;
+        for (int k = 0; k < np; k++) any_flag = any_flag || (h->held[k] && !h->held_done[k]);
+        if (!ok && !any_flag) {
+            for (int k = 0; k < np; k++)
+                if (h->active[k]) h->end_member(k, CHIP_SOLVER_NUMERICAL_ERROR, iter, false);
+            if ((rc = h->hold_and_reset())) return rc;
+            break;
+        }
+        if ((rc = h->hold_and_reset())) return rc;
+        if ((rc = h->step_length(lkappa, false))) return rc;
+        // combined step rhs (variables.rs:81-118)
+        for (int k = 0; k < np; k++) {
+            const double a = h->alpha[k];
+            h->sigma[k] = std::pow(1.0 - a, 3);
+            const double mscale = iter > 1 ? 1.0 : a;
+            const double sm = h->sigma[k] * h->mu[k];
+            h->hs_(S_OMS, k) = 1.0 - h->sigma[k];
+            h->hs_(S_ALPHA, k) = mscale;
+            h->hs_(S_NEGSM, k) = -sm;
+            rkap[k] = -sm + mscale * h->dtau[k] * lkappa[k] + h->tau[k] * h->kappa[k];
+            rtau[k] = (1.0 - h->sigma[k]) * h->info[k].out5[0];
+        }
+        if ((rc = h->push_scalars())) return rc;
+        h->lin(h->dx, h->rx, nullptr, h->sc(S_OMS), nullptr, 1.0, 0.0, 0, nullptr, 0);
+        if (iter == 1) h->lin(h->lz, h->lz, nullptr, h->sc(S_ALPHA), nullptr, 1.0, 0.0, 1, nullptr, 0);
+        if ((rc = chip_kkt_combined_ds_shift_dev(h->kkt, h->dz, h->lz, h->ls, 0.0))) return rc; // dz is work
+        dev::bunit_shift(h->stream, h->plan, h->dz, h->sc(S_NEGSM), 0, nullptr);                 // - sigma_mu e
+        dev::waxpby(h->stream, h->ds, 1.0, h->ds, 1.0, h->dz, h->m);
+        h->lin(h->dz, h->rz, nullptr, h->sc(S_OMS), nullptr, 1.0, 0.0, 1, nullptr, 0);
+        if ((rc = chip_kkt_ds_from_dz_offset_dev(h->kkt, h->conicw, h->ds, h->vz))) return rc;
+        h->launches += 4;
+        ok = true;
+        if ((rc = h->solve_direction(h->conicw, rtau, rkap, lkappa, &ok, iter))) return rc;
+        any_flag = false;
+        for (int k = 0; k < np; k++) any_flag = any_flag || (h->held[k] && !h->held_done[k]);
+        if (!ok && !any_flag) {
+            for (int k = 0; k < np; k++)
+                if (h->active[k]) h->end_member(k, CHIP_SOLVER_NUMERICAL_ERROR, iter, false);
+            if ((rc = h->hold_and_reset())) return rc;
+            break;
+        }
+        if ((rc = h->hold_and_reset())) return rc;
+        if ((rc = h->step_length(lkappa, true))) return rc;
+        // strategy_checkpoint_small_step (core/solver.rs:630-654) per member
+        for (int k = 0; k < np; k++) {
+            if (!h->active[k]) {
+                h->alpha[k] = 0.0;
+                continue;
+            }
+            if (h->alpha[k] <= std::max(0.0, st.min_terminate_step_length)) {
+                h->alpha[k] = 0.0;
+                h->info[k].status = CHIP_SOLVER_INSUFFICIENT_PROGRESS;
+                h->info[k].iterations = iter;
+                h->active[k] = 0;
+            }
+        }
+        // save_prev_iterate + add_step: the new iterate goes into the previous iterate's buffers and the two swap;
+        // frozen members copy their iterate (a select, never 0 * step)
+        for (int k = 0; k < np; k++) {
+            h->hm(M_ACTIVE, k) = h->active[k];
+            h->hs_(S_ALPHA, k) = h->alpha[k];
+            if (!h->active[k]) continue;
+            MInfo &I = h->info[k];
+            h->pinfo[k] = I;
+            I.prev_cost_primal = I.cost_primal;
+            I.prev_cost_dual = I.cost_dual;
+            I.prev_res_primal = I.res_primal;
+            I.prev_res_dual = I.res_dual;
+            I.prev_gap_abs = I.gap_abs;
+            I.prev_gap_rel = I.gap_rel;
+            h->ptau[k] = h->tau[k];
+            h->pkappa[k] = h->kappa[k];
+            h->tau[k] = h->tau[k] + h->alpha[k] * h->dtau[k];
+            h->kappa[k] = h->kappa[k] + h->alpha[k] * lkappa[k];
+        }
+        if ((rc = h->push_scalars()) || (rc = h->push_masks())) return rc;
+        h->lin(h->px, h->lx, h->vx, h->sc(S_ALPHA), nullptr, 1.0, 1.0, 0, h->mk(M_ACTIVE), dev::MASK_Y);
+        h->lin(h->ps, h->ls, h->vs, h->sc(S_ALPHA), nullptr, 1.0, 1.0, 1, h->mk(M_ACTIVE), dev::MASK_Y);
+        h->lin(h->pz, h->lz, h->vz, h->sc(S_ALPHA), nullptr, 1.0, 1.0, 1, h->mk(M_ACTIVE), dev::MASK_Y);
+        CHIP_HIP(hipGetLastError());
+        std::swap(h->vx, h->px);
+        std::swap(h->vs, h->ps);
+        std::swap(h->vz, h->pz);
+    }
+    h->iteration_time = now_s() - t_loop0;
+    if ((rc = h->post_process())) return rc;
+    h->solve_time = h->setup_time + (now_s() - h->t_solve0);
+    h->solved_once = true;
+    return CHIP_OK;
+}
+
+static void fill_info(const chip_batch *h, int k, chip_solution_info *out) {
+    std::memset(out, 0, sizeof(*out));
+    out->status = h->solved_once ? h->info[k].status : CHIP_SOLVER_UNSOLVED;
+    out->iterations = h->solved_once ? h->info[k].iterations : 0;
+    out->obj_val = h->solved_once ? h->obj_val[k] : 0.0;
+    out->obj_val_dual = h->solved_once ? h->obj_val_dual[k] : 0.0;
+    out->r_prim = h->solved_once ? h->info[k].res_primal : 0.0;
+    out->r_dual = h->solved_once ? h->info[k].res_dual : 0.0;
+    out->solve_time = h->solve_time;
+    out->setup_time = h->setup_time;
+    out->equilibration_time = h->equilibration_time;
+    out->iteration_time = h->iteration_time;
+}
+
+int32_t chip_batch_get_info(chip_batch *h, chip_solution_info *infos) {
+    if (!h || !infos) return failb(CHIP_ERR_ARG, "chip_batch_get_info: bad argument");
+    for (int k = 0; k < h->nprob; k++) fill_info(h, k, infos + k);
+    return CHIP_OK;
+}
+
+int32_t chip_batch_get_solution(chip_batch *h, int64_t k, double *x, double *s, double *z, chip_solution_info *info) {
+    if (!h || k < 0 || k >= h->nprob) return failb(CHIP_ERR_ARG, "chip_batch_get_solution: bad argument");
+    CHIP_HIP(hipSetDevice(h->device));
+    const int x0 = h->xoff[k], nk = h->xoff[k + 1] - x0, z0 = h->zoff[k], mk_ = h->zoff[k + 1] - z0;
+    if (h->solved_once) {
+        if (x && nk) CHIP_HIP(hipMemcpy(x, h->xo + x0, (size_t)nk * 8, hipMemcpyDeviceToHost));
+        if (s && mk_) CHIP_HIP(hipMemcpy(s, h->so + z0, (size_t)mk_ * 8, hipMemcpyDeviceToHost));
+        if (z && mk_) CHIP_HIP(hipMemcpy(z, h->zo + z0, (size_t)mk_ * 8, hipMemcpyDeviceToHost));
+    } else {
+        if (x) std::fill(x, x + nk, 0.0);
+        if (s) std::fill(s, s + mk_, 0.0);
+        if (z) std::fill(z, z + mk_, 0.0);
+    }
+    if (info) fill_info(h, (int)k, info);
+    return CHIP_OK;
+}
+
+int32_t chip_batch_get_solution_dev(chip_batch *h, double **x_dev, double **s_dev, double **z_dev) {
+    if (!h) return failb(CHIP_ERR_ARG, "chip_batch_get_solution_dev: bad argument");
+    if (x_dev) *x_dev = h->xo;
+    if (s_dev) *s_dev = h->so;
+    if (z_dev) *z_dev = h->zo;
+    return CHIP_OK;
+}
+
+int32_t chip_batch_get_equilibration(chip_batch *h, int64_t k, double *d, double *e, double *c) {
+    if (!h || k < 0 || k >= h->nprob) return failb(CHIP_ERR_ARG, "chip_batch_get_equilibration: bad argument");
+    CHIP_HIP(hipSetDevice(h->device));
+    const int x0 = h->xoff[k], nk = h->xoff[k + 1] - x0, z0 = h->zoff[k], mk_ = h->zoff[k + 1] - z0;
+    if (d && nk) CHIP_HIP(hipMemcpy(d, h->d + x0, (size_t)nk * 8, hipMemcpyDeviceToHost));
+    if (e && mk_) CHIP_HIP(hipMemcpy(e, h->e + z0, (size_t)mk_ * 8, hipMemcpyDeviceToHost));
+    if (c) *c = h->c[k];
+    return CHIP_OK;
+}
+
+#ifdef CHIP_TESTING
+#include "../../include/clarabel_hip_testing.h"
+int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration) {
+    chip_batch *h = (chip_batch *)batch;
+    if (!h) return failb(CHIP_ERR_ARG, "chip_debug_batch_inject_nan: bad argument");
+    h->nan_member = member;
+    h->nan_iter = iteration;
+    return CHIP_OK;
+}
+int32_t chip_debug_batch_counter(void *batch, const char *name, double *out) {
+    chip_batch *h = (chip_batch *)batch;
+    if (!h || !name || !out) return failb(CHIP_ERR_ARG, "chip_debug_batch_counter: bad argument");
+    const std::string nm(name);
+    if (nm == "host_syncs") *out = (double)h->syncs;
+    else if (nm == "launches") *out = (double)h->launches;
+    else if (nm == "loop_iterations") *out = (double)h->loop_iters;
+    else return failb(CHIP_ERR_ARG, "chip_debug_batch_counter: unknown name");
+    return CHIP_OK;
+}
+#endif

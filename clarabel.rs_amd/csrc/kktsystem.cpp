@@ -12,6 +12,7 @@
 
 #include "engine.hpp"
 #include "equilibrate.hpp"
+#include "batch.hpp"
 #include "problem_update.hpp"
 
 using namespace chip;
@@ -289,6 +290,16 @@ int chip::kktsystem_update_data_dev(chip_kktsystem *h, const double *P, const do
         dev::waxpby(h->stream, h->negq, -1.0, h->q, 0.0, nullptr, h->n);
     }
     if (b && h->m) CHIP_HIP(hipMemcpyAsync(h->b, b, (size_t)h->m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    CHIP_HIP(hipGetLastError());
+    return CHIP_OK;
+}
+
+// the batched solver (batch.cpp) applies the handle's operators to the whole stack; a P without entries gives y = aux
+// (or 0), as the gather kernels write every row
+int chip::kktsystem_spmv(chip_kktsystem *h, int which, double *y, const double *aux, double alpha, const double *x) {
+    if (!h || which < 0 || which > 2) return CHIP_ERR_ARG;
+    const SpMat &M = which == 0 ? h->Psym : which == 1 ? h->Arow : h->Acol;
+    if (M.rows) h->spmv(M, y, aux, alpha, x);
     CHIP_HIP(hipGetLastError());
     return CHIP_OK;
 }

@@ -676,6 +676,46 @@ int32_t chip_problem_update_allowed(const chip_solver *h, int32_t *allowed);
 int32_t chip_problem_get_scaled(chip_solver *h, double *Px, double *Ax, double *q, double *b);
 
 /* ===========================================================================
+ * Batched L4 solver: nprob INDEPENDENT problems solved in one interior-point loop on one GPU, each with its own tau,
+ * kappa, mu, sigma, step length, termination and status (core/solver.rs:242-464 with every scalar indexed by member).
+ * The problems are handed over as ONE block-diagonal stack plus its partition: member k owns the columns
+ * [sum n_part[<k], + n_part[k]) and the rows [sum m_part[<k], + m_part[k]).  P, q, A, b and the cone arrays are as for
+ * chip_solver_create; one chip_solver_settings applies to every member.  The KKT matrix of the stack is factored once
+ * per iteration (one elimination tree per member); the per-member passes run in launches whose number does not depend
+ * on nprob.  DESIGN.md 4.13 lists where the result can differ from solving the members one by one (the regularisers
+ * and the refinement stop are taken over the whole stack).
+ * Refusals of chip_batch_create:
+ *   CHIP_ERR_ARG          a NULL handle or array, nprob < 1, a negative part, parts that do not add up to n / m, an
+ *                         entry of P or A that crosses two members' blocks, a cone that crosses a member's rows
+ *   CHIP_ERR_UNSUPPORTED  a cone other than Zero / Nonnegative / SecondOrder, presolve or chordal decomposition enabled
+ *   CHIP_ERR_NO_DEVICE    no device (or a CHIP_DEVICE_HOST_ONLY setting): there is no CPU fallback
+ *   CHIP_ERR_DIM          the sizes of chip_solver_create's int32 check
+ * Numerical failures are attributed to members: before every KKT update a member whose s or z is not finite or not
+ * strictly interior, and after every solve a member whose part of the direction is not finite, ends NumericalError
+ * with its last finite iterate as its solution; the others go on.  A failed factorisation or solve that no member
+ * accounts for ends every member still running with NumericalError.  max_iter and time_limit apply to the batch.
+ * ===========================================================================*/
+typedef struct chip_batch chip_batch;
+int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n,
+                          int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval, const double *Pnzval,
+                          const double *q, const uint64_t *Acolptr, const uint64_t *Arowval, const double *Anzval,
+                          const double *b, int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims,
+                          const int64_t *cone_dims2, const double *cone_alphas_or_null,
+                          const double *genpow_alphas_or_null, const chip_solver_settings *settings);
+void chip_batch_destroy(chip_batch *h);
+/* runs the batched loop; CHIP_OK (the outcomes are the members' statuses) or a negative chip_status */
+int32_t chip_batch_solve(chip_batch *h);
+/* the nprob members' chip_solution_info in member order: status, iterations, obj_val, obj_val_dual, r_prim, r_dual
+ * of the member; solve_time, setup_time, equilibration_time and iteration_time of the batch */
+int32_t chip_batch_get_info(chip_batch *h, chip_solution_info *infos);
+/* member k's unscaled solution (x[n_part[k]], s[m_part[k]], z[m_part[k]], any may be NULL) and info (may be NULL) */
+int32_t chip_batch_get_solution(chip_batch *h, int64_t k, double *x, double *s, double *z, chip_solution_info *info);
+/* the stacked solution on the device (n, m, m doubles), owned by the handle (valid until the next solve) */
+int32_t chip_batch_get_solution_dev(chip_batch *h, double **x_dev, double **s_dev, double **z_dev);
+/* member k's equilibration: d[n_part[k]], e[m_part[k]] (host copies, either may be NULL) and its cost scale c */
+int32_t chip_batch_get_equilibration(chip_batch *h, int64_t k, double *d, double *e, double *c);
+
+/* ===========================================================================
  * Sharded path: one process per GPU, whole connected components of the elimination
  * forest per rank (BASELINE config 4: 1024 independent SOCPs, 128 per GPU at 8 GPUs).  Factorisation,
  * substitutions and refinement of a rank's blocks need no exchange; the exchange step is ONE RCCL

@@ -49,6 +49,13 @@ int32_t chip_debug_transform_reverse(const void *h, const double *x2, const doub
 /* the internal variables of a chip_solver's last solve unscaled (dev::unscale's arithmetic): x2[n_internal],
  * s2[m_internal], z2[m_internal] (any may be NULL) */
 int32_t chip_debug_solver_internal_solution(void *solver, double *x2, double *s2, double *z2);
+/* ---- the batched solver (csrc/batch.cpp) ----
+ * chip_debug_batch_inject_nan: at the start of iteration `iteration` of the next solves, before the residual pass and
+ * the pre-update check, z[first row of member `member`] of the stacked iterate becomes NaN (member < 0: off).
+ * chip_debug_batch_counter: "host_syncs" / "launches" (host synchronisations / kernel and copy enqueues of the last
+ * solve's iterations, default_start and post-processing excluded), "loop_iterations" (iterations run). */
+int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration);
+int32_t chip_debug_batch_counter(void *batch, const char *name, double *out);
 #ifdef __cplusplus
 }
 #endif
