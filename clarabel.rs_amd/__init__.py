@@ -1044,6 +1044,16 @@ class HipBatchSolver:
         self.stack = st
         self.settings = settings or SolverSettings.default()
         self.n_part, self.m_part = st["n_part"], st["m_part"]
+        # for update(): the stack's lengths and patterns, and the members' offsets, lengths and patterns
+        n, m = st["n"], st["m"]
+        self._len = {"P": len(st["P"][2]), "A": len(st["A"][2]), "q": n, "b": m}
+        self._pattern = {"P": (n, n, st["P"][0], st["P"][1]), "A": (m, n, st["A"][0], st["A"][1])}
+        part = {"P": [pb[0].nnz for pb in problems], "A": [pb[2].nnz for pb in problems], "q": self.n_part,
+                "b": self.m_part}
+        self._offsets = {k: np.concatenate([[0], np.cumsum(np.asarray(v, dtype=np.int64))]).astype(np.int64)
+                         for k, v in part.items()}
+        self._mpattern = {"P": [(pb[0].m, pb[0].n, pb[0].colptr.copy(), pb[0].rowval.copy()) for pb in problems],
+                          "A": [(pb[2].m, pb[2].n, pb[2].colptr.copy(), pb[2].rowval.copy()) for pb in problems]}
         tags, dims, dims2, alphas = _cone_arrays(st["cones"])
         self._h = C.c_void_p()
         Pp, Pi, Px = st["P"]
@@ -1096,6 +1106,72 @@ class HipBatchSolver:
         _check(lib().chip_batch_get_equilibration(self._h, C.c_int64(k), _pf(d), _pf(e), C.byref(c)),
                "chip_batch_get_equilibration")
         return d, e, c.value
+
+    # ---- data updates (chip_bdata_*): new values on the stack's fixed patterns, then solve() again ----------------
+    def update(self, P=None, q=None, A=None, b=None, settings=None):
+        """batch.update(P=..., q=..., A=..., b=..., settings=...): each piece is a stacked value vector (or a
+        CscMatrix with the stack's pattern), an (index, values) tuple of stack positions, an empty vector (no-op),
+        torch tensors on the GPU (float64 values, int64 index) -- or a LIST with one entry per member, each None
+        (member untouched), a value vector of the member's own length (or its CscMatrix) or a member-local
+        (index, values); the list is translated with the stack's offsets into one partial update, so updating 3 of
+        1024 members moves only their values.  Every piece is classified before any is applied; they are applied in
+        the order P, q, A, b, settings, and the first refusal raises ChipError (the pieces before it stay applied)."""
+        forms = [(k, self._classify(k, v)) for k, v in (("P", P), ("q", q), ("A", A), ("b", b)) if v is not None]
+        for k, f in forms:
+            self._apply_update(k, f)
+        if settings is not None:
+            self.update_settings(settings)
+
+    def update_P(self, data):
+        self._apply_update("P", self._classify("P", data))
+
+    def update_A(self, data):
+        self._apply_update("A", self._classify("A", data))
+
+    def update_q(self, data):
+        self._apply_update("q", self._classify("q", data))
+
+    def update_b(self, data):
+        self._apply_update("b", self._classify("b", data))
+
+    def _classify(self, key, data):
+        if isinstance(data, list) and len(data) > 0 and not np.isscalar(data[0]):
+            return batch_list_update(key, data, self._offsets[key], self._mpattern.get(key))
+        return classify_update(key, data, self._len[key], self._pattern.get(key))
+
+    def _apply_update(self, key, form):
+        kind = form[0]
+        if kind == "none":
+            return
+        idx, vals = form[1], form[2]
+        if kind in ("full", "partial"):
+            fn = getattr(lib(), "chip_bdata_update_" + key)
+            _check(fn(self._h, None if idx is None else _pu(idx), _pf(vals), C.c_int64(len(vals))),
+                   "chip_bdata_update_" + key)
+            return
+        import torch
+        torch.cuda.current_stream(vals.device).synchronize()  # the values are written before the call reads them
+        fn = getattr(lib(), "chip_bdata_update_%s_dev" % key)
+        _check(fn(self._h, None if idx is None else C.c_void_p(idx.data_ptr()), C.c_void_p(vals.data_ptr()),
+                  C.c_int64(vals.numel())), "chip_bdata_update_%s_dev" % key)
+
+    def update_settings(self, settings=None, **kw):
+        """update_settings for every member: a SolverSettings, or keyword overrides of the current settings.  An
+        immutable field that differs raises ChipError(ERR_ARG) and the settings stay as they were."""
+        new = SolverSettings.from_buffer_copy(settings if settings is not None else self.settings)
+        _apply_settings(new, kw, "update_settings")
+        _check(lib().chip_bdata_update_settings(self._h, C.byref(new)), "chip_bdata_update_settings")
+        self.settings = new
+
+    def scaled_data(self):
+        """the stack's data as the handle holds it after the equilibration, and the members' norms of the unscaled
+        q and b: (P.nzval, A.nzval, q, b, normq, normb)"""
+        Px, Ax = np.zeros(self._len["P"]), np.zeros(self._len["A"])
+        q, b = np.zeros(self._len["q"]), np.zeros(self._len["b"])
+        nq, nb = np.zeros(len(self)), np.zeros(len(self))
+        _check(lib().chip_bdata_get_scaled(self._h, _pf(Px), _pf(Ax), _pf(q), _pf(b), _pf(nq), _pf(nb)),
+               "chip_bdata_get_scaled")
+        return Px, Ax, q, b, nq, nb
 
     # ---- test hooks (include/clarabel_hip_testing.h) ----
     def debug_inject_nan(self, member, iteration):
@@ -1268,6 +1344,37 @@ def classify_update(key, data, length, pattern=None):
     if vals.size != length:
         raise ChipError(ERR_DIM, "update %s: %d values for %d entries" % (key, vals.size, length))
     return ("full", None, _f(vals))
+
+
+def batch_list_update(key, pieces, offsets, patterns=None):
+    """The per-member list form of HipBatchSolver.update as ONE partial update of the stack (no GPU touched).  pieces:
+    one entry per member -- None (untouched), a value vector of the member's own length (or a CscMatrix with the
+    member's pattern) or a member-local (index, values) of host arrays; offsets[k] is where member k's entries start
+    in the stacked nzval / vector (nprob + 1 entries); patterns: the members' (m, n, colptr, rowval) for P / A.
+    Returns ("none",) or ("partial", index, values) with stack positions in member order (uint64 / float64).
+    ChipError(ERR_DIM) for a list of the wrong length, a vector of the wrong length or a member-local index outside
+    the member (it must not reach another member's entries)."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    if len(pieces) != len(offsets) - 1:
+        raise ChipError(ERR_DIM, "update %s: %d list entries for %d members" % (key, len(pieces), len(offsets) - 1))
+    idxs, vals = [], []
+    for k, piece in enumerate(pieces):
+        length = int(offsets[k + 1] - offsets[k])
+        form = classify_update(key, piece, length, None if patterns is None else patterns[k])
+        if form[0] == "none":
+            continue
+        if form[0] == "full":
+            idxs.append(offsets[k] + np.arange(length, dtype=np.int64))
+        elif form[0] == "partial":
+            if np.any(form[1] >= np.uint64(length)):
+                raise ChipError(ERR_DIM, "update %s: member %d: an index is out of the member's range" % (key, k))
+            idxs.append(offsets[k] + form[1].astype(np.int64))
+        else:
+            raise TypeError("update %s: member %d: the entries of a list are host arrays" % (key, k))
+        vals.append(form[2])
+    if not idxs:
+        return ("none",)
+    return ("partial", _u(np.concatenate(idxs)), _f(np.concatenate(vals)))
 
 
 # ---------------------------------------------------------------------------

@@ -20,7 +20,9 @@
 #include <vector>
 
 #include "batch.hpp"
+#include "batch_update.hpp"
 #include "engine.hpp"
+#include "problem_update.hpp"
 
 using namespace chip;
 
@@ -89,6 +91,9 @@ struct chip_batch {
     dev::BatchPlan plan{};
     dev::EqMats M{};
     double *q = nullptr, *b = nullptr, *d = nullptr, *e = nullptr, *dinv = nullptr, *einv = nullptr, *negq = nullptr;
+    // for the data updates (chip_bdata_*): the unscaled q and b (the members' norms are taken from them, as create
+    // takes them from the user's data) and the members' cost scales on the device
+    double *uq = nullptr, *ub = nullptr, *dc = nullptr;
     std::vector<double> c, normq, normb;
     std::vector<int64_t> degree;
     std::vector<int> lp_init; // the member's P has no stored entry: the LP initial point (kktsystem.rs:197-215)
@@ -121,9 +126,21 @@ struct chip_batch {
     int64_t nan_member = -1;
     int nan_iter = -1;
     long syncs = 0, launches = 0, loop_iters = 0;
+    // work buffers of the data updates, allocated by the first one; the staging of the host forms grows on demand
+    int *upos = nullptr, *uflag = nullptr;
+    unsigned long long *unpart = nullptr, *ubpart = nullptr;
+    double *unout = nullptr, *ubout = nullptr;
+    double *stage_v = nullptr;
+    int64_t *stage_i = nullptr, *clean = nullptr;
+    size_t stage_v_cap = 0, stage_i_cap = 0, clean_cap = 0;
+    std::vector<double> unorm;
+    long upd_syncs = 0, upd_launches = 0; // of the last update call
 
     ~chip_batch() {
         if (stream) (void)hipStreamSynchronize(stream);
+        (void)hipFree(stage_v);
+        (void)hipFree(stage_i);
+        (void)hipFree(clean);
         chip_kktsystem_destroy(sys);
         chip_kkt_destroy(kkt);
     }
@@ -197,6 +214,9 @@ struct chip_batch {
     int hold_and_reset();
     int post_process();
     int end_member(int k, int status, int iterations, bool from_prev);
+    int update_work();
+    template <typename T> int grow(T **buf, size_t *cap, size_t need);
+    int update(int which, const int64_t *idx_dev, const double *vals_dev, int k);
 };
 
 int chip_batch::equilibrate(const std::vector<ConeSpec> &cones) {
@@ -415,7 +435,8 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     if ((rc = mem.upload(&dPr, Prow.data(), nnzP)) || (rc = mem.upload(&dPc, Pcol.data(), nnzP)) ||
         (rc = mem.upload(&M.Px, Pnzval, nnzP)) || (rc = mem.upload(&dAr, Arow.data(), nnzA)) ||
         (rc = mem.upload(&dAc, Acol.data(), nnzA)) || (rc = mem.upload(&M.Ax, Anzval, nnzA)) ||
-        (rc = mem.upload(&h->q, q, (size_t)n)) || (rc = mem.upload(&h->b, bcap.data(), (size_t)m)))
+        (rc = mem.upload(&h->q, q, (size_t)n)) || (rc = mem.upload(&h->b, bcap.data(), (size_t)m)) ||
+        (rc = mem.upload(&h->uq, q, (size_t)n)) || (rc = mem.upload(&h->ub, bcap.data(), (size_t)m)))
         return rc;
     M.Prow = dPr;
     M.Pcol = dPc;
@@ -435,6 +456,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     h->stream = nullptr;
     if (rc) return rc;
     h->equilibration_time = now_s() - te;
+    if ((rc = mem.upload(&h->dc, h->c.data(), (size_t)np))) return rc;
     // ---- one KKT system of the equilibrated stack (block-diagonal K)
     std::vector<double> Px(nnzP), Ax(nnzA), qs(n), bs(m);
     if (nnzP) CHIP_HIP(hipMemcpy(Px.data(), M.Px, nnzP * 8, hipMemcpyDeviceToHost));
@@ -1105,6 +1127,237 @@ int32_t chip_batch_get_equilibration(chip_batch *h, int64_t k, double *d, double
     return CHIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Data updates of the stack (chip_bdata_*; default/data_updating.rs with one cost scale per member): new values on the
+// fixed patterns, scaled on the device with the setup's d, e and the members' c_k, then every copy the loop reads is
+// refreshed.  What create derives from the values and the loop reads: the scaled M.Px / M.Ax, q, b
+// and negq; K's device store; the L3 handle's mirrors of P and A (kktsystem_spmv) and its q, b; max |P_ii| of the
+// static regulariser over the whole stack; normq[k] and normb[k] of the members' UNSCALED q and b.  One call is a
+// fixed number of launches and ONE host synchronisation: a partial form's writes read the word the index check
+// raised on the device, so a refused call has written nothing when the host learns of it.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+enum { BU_P = 0, BU_A = 1, BU_Q = 2, BU_B = 3 };
+const char *const BU_NAME[4] = {"chip_bdata_update_P", "chip_bdata_update_A", "chip_bdata_update_q",
+                                "chip_bdata_update_b"};
+} // namespace
+
+int chip_batch::update_work() {
+    if (uflag) return CHIP_OK;
+    const size_t len = (size_t)std::max({M.nnzP, M.nnzA, n, m, 1});
+    int rc;
+    if ((rc = mem.alloc(&upos, len)) || (rc = mem.alloc(&unpart, (size_t)dev::pu_norm_partials())) ||
+        (rc = mem.alloc(&unout, 3)) || (rc = mem.alloc(&ubpart, (size_t)(plan.ncx + plan.ncz))) ||
+        (rc = mem.alloc(&ubout, (size_t)nprob)) || (rc = mem.alloc(&uflag, 1)))
+        return rc;
+    unorm.assign((size_t)nprob, 0.0);
+    CHIP_HIP(hipMemsetAsync(upos, 0xff, len * sizeof(int), stream)); // every slot -1
+    CHIP_HIP(hipMemsetAsync(uflag, 0, sizeof(int), stream));
+    upd_launches += 2;
+    return CHIP_OK;
+}
+
+template <typename T> int chip_batch::grow(T **buf, size_t *cap, size_t need) {
+    if (need <= *cap) return CHIP_OK;
+    if (*buf) { // (work enqueued earlier may still read the old buffer)
+        CHIP_HIP(hipStreamSynchronize(stream));
+        upd_syncs++;
+        (void)hipFree(*buf);
+        *buf = nullptr;
+        *cap = 0;
+    }
+    CHIP_HIP(hipMalloc((void **)buf, need * sizeof(T)));
+    *cap = need;
+    return CHIP_OK;
+}
+
+// one update of P, A, q or b: idx_dev == nullptr is the full form (k == the length, checked by the caller)
+int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev, int k) {
+    int rc;
+    if ((rc = update_work())) return rc;
+    const int len = which == BU_P ? M.nnzP : which == BU_A ? M.nnzA : which == BU_Q ? n : m;
+    hipStream_t s = stream;
+    if (idx_dev) { // the whole index list is checked on the device before any pass writes
+        if ((rc = grow(&clean, &clean_cap, (size_t)k))) return rc;
+        CHIP_HIP(hipMemsetAsync(uflag, 0, sizeof(int), s));
+        dev::pu_validate(s, idx_dev, k, len, uflag);
+        upd_launches += 2;
+    }
+    dev::BuTarget t{};
+    switch (which) {
+    case BU_P: t = {M.Px, nullptr, nullptr, len, M.Prow, M.Pcol, d, d, dc, plan.xmem}; break;
+    case BU_A: t = {M.Ax, nullptr, nullptr, len, M.Arow, M.Acol, e, d, nullptr, plan.xmem}; break;
+    case BU_Q: t = {q, uq, negq, len, nullptr, nullptr, d, nullptr, dc, plan.xmem}; break;
+    default: t = {b, ub, nullptr, len, nullptr, nullptr, e, nullptr, nullptr, plan.zmem}; break;
+    }
+    if (idx_dev) {
+        dev::bu_write_partial(s, t, idx_dev, vals_dev, k, upos, uflag, clean);
+        upd_launches += 3;
+    } else {
+        dev::bu_write_full(s, t, vals_dev);
+        upd_launches++;
+    }
+    CHIP_HIP(hipGetLastError());
+    // the copies the loop reads: K's values (only the touched entries of a partial form; a refused one rewrites
+    // entry 0 with its own value), the L3 mirrors and vectors
+    if (which == BU_P || which == BU_A) {
+        const double *src = which == BU_P ? M.Px : M.Ax;
+        if ((rc = kkt_update_values_dev(kkt, which, src, idx_dev ? clean : nullptr, idx_dev ? k : len))) return rc;
+        upd_launches++;
+    }
+    if ((rc = kktsystem_update_data_dev(sys, which == BU_P ? M.Px : nullptr, which == BU_A ? M.Ax : nullptr,
+                                        which == BU_Q ? q : nullptr, which == BU_B ? b : nullptr)))
+        return rc;
+    upd_launches += (which == BU_A || which == BU_Q) ? 2 : 1; // A: two mirrors; q: the copy and its negation
+    // the scalars create derived from the values: the members' norms of the unscaled q / b, max |P_ii| of the stack
+    double pmax[3] = {0, 0, 0};
+    if (which == BU_Q || which == BU_B) {
+        dev::bu_norms(s, plan, which == BU_Q ? 0 : 1, which == BU_Q ? uq : ub, ubpart, ubout);
+        CHIP_HIP(hipGetLastError());
+        CHIP_HIP(hipMemcpyAsync(unorm.data(), ubout, (size_t)nprob * 8, hipMemcpyDeviceToHost, s));
+        upd_launches += 3;
+    } else if (which == BU_P) {
+        dev::pu_norms(s, 4, nullptr, nullptr, 0, nullptr, nullptr, 0, M.Prow, M.Pcol, M.Px, M.nnzP, unpart, unout);
+        CHIP_HIP(hipGetLastError());
+        CHIP_HIP(hipMemcpyAsync(pmax, unout, sizeof(pmax), hipMemcpyDeviceToHost, s));
+        upd_launches += 3;
+    }
+    int bad = 0;
+    if (idx_dev) {
+        CHIP_HIP(hipMemcpyAsync(&bad, uflag, sizeof(int), hipMemcpyDeviceToHost, s));
+        upd_launches++;
+    }
+    CHIP_HIP(hipStreamSynchronize(s));
+    upd_syncs++;
+    if (bad) return failb(CHIP_ERR_DIM, std::string(BU_NAME[which]) + ": an index is out of range (nothing changed)");
+    if (which == BU_Q) normq = unorm;
+    if (which == BU_B) normb = unorm;
+    if (which == BU_P) kkt_set_static_diag_max(kkt, pmax[2]);
+    return CHIP_OK;
+}
+
+namespace {
+// the checks shared by both forms: CHIP_ERR_ARG before any device is touched, k == 0 a no-op (returns 1)
+int bu_args(chip_batch *h, int which, const void *idx, const double *vals, int64_t k) {
+    if (!h || k < 0 || (k > 0 && !vals)) return failb(CHIP_ERR_ARG, std::string(BU_NAME[which]) + ": bad argument");
+    h->upd_syncs = h->upd_launches = 0;
+    if (k == 0) return 1;
+    if (k >= (1ll << 31)) return failb(CHIP_ERR_DIM, std::string(BU_NAME[which]) + ": more than 2^31 values");
+    const int64_t len = which == BU_P ? h->M.nnzP : which == BU_A ? h->M.nnzA : which == BU_Q ? h->n : h->m;
+    if (!idx && k != len)
+        return failb(CHIP_ERR_DIM, std::string(BU_NAME[which]) + ": the full form needs one value per entry");
+    if (idx && len == 0) // (every index is out of range)
+        return failb(CHIP_ERR_DIM, std::string(BU_NAME[which]) + ": an index is out of range (nothing changed)");
+    return 0;
+}
+
+int bu_host(chip_batch *h, int which, const uint64_t *idx, const double *vals, int64_t k) {
+    int rc = bu_args(h, which, idx, vals, k);
+    if (rc) return rc < 0 ? rc : CHIP_OK;
+    CHIP_HIP(hipSetDevice(h->device));
+    if ((rc = h->grow(&h->stage_v, &h->stage_v_cap, (size_t)k))) return rc;
+    if (idx && (rc = h->grow(&h->stage_i, &h->stage_i_cap, (size_t)k))) return rc;
+    CHIP_HIP(hipMemcpyAsync(h->stage_v, vals, (size_t)k * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    h->upd_launches++;
+    // (an index past 2^63 - 1 reads as negative and is refused like any other out-of-range index)
+    if (idx) {
+        CHIP_HIP(hipMemcpyAsync(h->stage_i, idx, (size_t)k * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+        h->upd_launches++;
+    }
+    return h->update(which, idx ? h->stage_i : nullptr, h->stage_v, (int)k);
+}
+
+int bu_dev(chip_batch *h, int which, const int64_t *idx, const double *vals, int64_t k) {
+    int rc = bu_args(h, which, idx, vals, k);
+    if (rc) return rc < 0 ? rc : CHIP_OK;
+    CHIP_HIP(hipSetDevice(h->device));
+    return h->update(which, idx, vals, (int)k);
+}
+} // namespace
+
+int32_t chip_bdata_update_P(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k) {
+    return bu_host(h, BU_P, index_or_null, values, k);
+}
+int32_t chip_bdata_update_A(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k) {
+    return bu_host(h, BU_A, index_or_null, values, k);
+}
+int32_t chip_bdata_update_q(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k) {
+    return bu_host(h, BU_Q, index_or_null, values, k);
+}
+int32_t chip_bdata_update_b(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k) {
+    return bu_host(h, BU_B, index_or_null, values, k);
+}
+int32_t chip_bdata_update_P_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
+    return bu_dev(h, BU_P, index_dev_or_null, values_dev, k);
+}
+int32_t chip_bdata_update_A_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
+    return bu_dev(h, BU_A, index_dev_or_null, values_dev, k);
+}
+int32_t chip_bdata_update_q_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
+    return bu_dev(h, BU_Q, index_dev_or_null, values_dev, k);
+}
+int32_t chip_bdata_update_b_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
+    return bu_dev(h, BU_B, index_dev_or_null, values_dev, k);
+}
+
+// update_settings with validate_as_update (settings.rs:307): the immutable fields of chip_problem_update_settings
+int32_t chip_bdata_update_settings(chip_batch *h, const chip_solver_settings *settings) {
+    if (!h || !settings) return failb(CHIP_ERR_ARG, "chip_bdata_update_settings: bad argument");
+    chip_solver_settings nw = *settings;
+    nw.linsys.linesearch_backtrack_step = nw.linesearch_backtrack_step;
+    nw.linsys.min_terminate_step_length = nw.min_terminate_step_length;
+    const chip_solver_settings &o = h->st;
+    const chip_settings &a = nw.linsys, &l = o.linsys;
+#define IMMUTABLE(cond, name) \
+    if (cond) return failb(CHIP_ERR_ARG, "chip_bdata_update_settings: " name " cannot change after setup")
+    IMMUTABLE(nw.equilibrate_enable != o.equilibrate_enable, "equilibrate_enable");
+    IMMUTABLE(nw.equilibrate_max_iter != o.equilibrate_max_iter, "equilibrate_max_iter");
+    IMMUTABLE(std::memcmp(&nw.equilibrate_min_scaling, &o.equilibrate_min_scaling, 8), "equilibrate_min_scaling");
+    IMMUTABLE(std::memcmp(&nw.equilibrate_max_scaling, &o.equilibrate_max_scaling, 8), "equilibrate_max_scaling");
+    IMMUTABLE(std::memcmp(&nw.linesearch_backtrack_step, &o.linesearch_backtrack_step, 8), "linesearch_backtrack_step");
+    IMMUTABLE(std::memcmp(&nw.min_terminate_step_length, &o.min_terminate_step_length, 8), "min_terminate_step_length");
+    IMMUTABLE(nw.presolve_enable != o.presolve_enable, "presolve_enable");
+    IMMUTABLE(nw.chordal_decomposition_enable != o.chordal_decomposition_enable, "chordal_decomposition_enable");
+    IMMUTABLE(nw.chordal_decomposition_merge_method != o.chordal_decomposition_merge_method,
+              "chordal_decomposition_merge_method");
+    IMMUTABLE(nw.chordal_decomposition_compact != o.chordal_decomposition_compact, "chordal_decomposition_compact");
+    IMMUTABLE(nw.chordal_decomposition_complete_dual != o.chordal_decomposition_complete_dual,
+              "chordal_decomposition_complete_dual");
+#define IMMUTABLE_LIN(f) IMMUTABLE(std::memcmp(&a.f, &l.f, sizeof(a.f)), "linsys." #f)
+    IMMUTABLE_LIN(static_regularization_enable);
+    IMMUTABLE_LIN(static_regularization_constant);
+    IMMUTABLE_LIN(static_regularization_proportional);
+    IMMUTABLE_LIN(dynamic_regularization_enable);
+    IMMUTABLE_LIN(dynamic_regularization_eps);
+    IMMUTABLE_LIN(dynamic_regularization_delta);
+    IMMUTABLE_LIN(iterative_refinement_enable);
+    IMMUTABLE_LIN(iterative_refinement_reltol);
+    IMMUTABLE_LIN(iterative_refinement_abstol);
+    IMMUTABLE_LIN(iterative_refinement_max_iter);
+    IMMUTABLE_LIN(iterative_refinement_stop_ratio);
+    IMMUTABLE_LIN(device);
+    IMMUTABLE_LIN(amd_dense_scale);
+    IMMUTABLE_LIN(use_graph);
+#undef IMMUTABLE_LIN
+#undef IMMUTABLE
+    h->st = nw;
+    return CHIP_OK;
+}
+
+int32_t chip_bdata_get_scaled(chip_batch *h, double *Px, double *Ax, double *q, double *b, double *normq,
+                              double *normb) {
+    if (!h) return failb(CHIP_ERR_ARG, "chip_bdata_get_scaled: bad argument");
+    CHIP_HIP(hipSetDevice(h->device));
+    CHIP_HIP(hipStreamSynchronize(h->stream));
+    if (Px && h->M.nnzP) CHIP_HIP(hipMemcpy(Px, h->M.Px, (size_t)h->M.nnzP * 8, hipMemcpyDeviceToHost));
+    if (Ax && h->M.nnzA) CHIP_HIP(hipMemcpy(Ax, h->M.Ax, (size_t)h->M.nnzA * 8, hipMemcpyDeviceToHost));
+    if (q && h->n) CHIP_HIP(hipMemcpy(q, h->q, (size_t)h->n * 8, hipMemcpyDeviceToHost));
+    if (b && h->m) CHIP_HIP(hipMemcpy(b, h->b, (size_t)h->m * 8, hipMemcpyDeviceToHost));
+    if (normq) std::copy(h->normq.begin(), h->normq.end(), normq);
+    if (normb) std::copy(h->normb.begin(), h->normb.end(), normb);
+    return CHIP_OK;
+}
+
 #ifdef CHIP_TESTING
 #include "../../include/clarabel_hip_testing.h"
 int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration) {
@@ -1121,6 +1374,8 @@ int32_t chip_debug_batch_counter(void *batch, const char *name, double *out) {
     if (nm == "host_syncs") *out = (double)h->syncs;
     else if (nm == "launches") *out = (double)h->launches;
     else if (nm == "loop_iterations") *out = (double)h->loop_iters;
+    else if (nm == "update_launches") *out = (double)h->upd_launches;
+    else if (nm == "update_host_syncs") *out = (double)h->upd_syncs;
     else return failb(CHIP_ERR_ARG, "chip_debug_batch_counter: unknown name");
     return CHIP_OK;
 }

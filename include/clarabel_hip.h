@@ -715,6 +715,44 @@ int32_t chip_batch_get_solution_dev(chip_batch *h, double **x_dev, double **s_de
 /* member k's equilibration: d[n_part[k]], e[m_part[k]] (host copies, either may be NULL) and its cost scale c */
 int32_t chip_batch_get_equilibration(chip_batch *h, int64_t k, double *d, double *e, double *c);
 
+/* ---- data updates of a batch: DefaultSolver::update_P / update_A / update_q / update_b / update_settings
+ * (default/data_updating.rs, core/solver.rs:207) on a chip_batch handle, then the batch is solved again.  The
+ * semantics are those of the single solver's data updates above, applied to the STACK: an index is a position in the
+ * stacked nzval of P / A or in the stacked q / b, so one call can touch any subset of the members.  The patterns are
+ * fixed; the new values are scaled on the device with the d, e of the setup and the cost scale c_k of the member that
+ * owns the entry's column (the equilibration is never recomputed), and every copy the next solve reads is refreshed.
+ *   full form     index == NULL: k must be nnz(P) / nnz(A) / n / m of the stack, else CHIP_ERR_DIM.
+ *                 P = (v * (d[row] * d[col])) * c_k, A = v * (e[row] * d[col])
+ *   partial form  index != NULL: the reference's zip(index, values); a repeated index: the last occurrence wins.
+ *                 P = ((d[row] * d[col]) * c_k) * v, A = (e[row] * d[col]) * v
+ *   vectors       both forms: q = (v * d[j]) * c_k, b = v * e[i].  b is NOT capped at 1e20 by an update.
+ *   k == 0        CHIP_OK, nothing changes.
+ * An index >= the length (or negative, device form) gives CHIP_ERR_DIM and changes NOTHING.  A NULL handle, a NULL
+ * values pointer with k > 0 or k < 0 give CHIP_ERR_ARG without touching a device.  After an update the handle also
+ * holds max |P_ii| of the static regulariser over the whole stack and, per member, the norms of q and b that
+ * termination reads: max |q_k| and max |b_k| of the member's current UNSCALED values (a NaN wins), as create takes
+ * them.  One call costs a number of launches and one host synchronisation, whatever nprob and however many members
+ * the indices touch. */
+int32_t chip_bdata_update_P(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k);
+int32_t chip_bdata_update_A(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k);
+int32_t chip_bdata_update_q(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k);
+int32_t chip_bdata_update_b(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k);
+/* the same with index / values in device memory (int64 indices: torch's index dtype).  The call returns once the
+ * device has consumed them; the caller must have finished writing them before the call. */
+int32_t chip_bdata_update_P_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k);
+int32_t chip_bdata_update_A_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k);
+int32_t chip_bdata_update_q_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k);
+int32_t chip_bdata_update_b_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k);
+/* validate_as_update (settings.rs:307) with the immutable fields of the single solver's settings update: the four
+ * equilibration fields, every field of linsys, linesearch_backtrack_step / min_terminate_step_length and the five
+ * transform fields.  A refused call (CHIP_ERR_ARG) leaves the settings as they were; the rest takes effect at the next
+ * solve. */
+int32_t chip_bdata_update_settings(chip_batch *h, const chip_solver_settings *settings);
+/* the stack's data as the handle holds it after the equilibration (Px[nnz(P)], Ax[nnz(A)], q[n], b[m]) and the
+ * members' norms (normq[nprob], normb[nprob]): host copies, any pointer may be NULL */
+int32_t chip_bdata_get_scaled(chip_batch *h, double *Px, double *Ax, double *q, double *b, double *normq,
+                              double *normb);
+
 /* ===========================================================================
  * Sharded path: one process per GPU, whole connected components of the elimination
  * forest per rank (BASELINE config 4: 1024 independent SOCPs, 128 per GPU at 8 GPUs).  Factorisation,
