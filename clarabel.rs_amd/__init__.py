@@ -1054,6 +1054,7 @@ class HipBatchSolver:
                          for k, v in part.items()}
         self._mpattern = {"P": [(pb[0].m, pb[0].n, pb[0].colptr.copy(), pb[0].rowval.copy()) for pb in problems],
                           "A": [(pb[2].m, pb[2].n, pb[2].colptr.copy(), pb[2].rowval.copy()) for pb in problems]}
+        self.generation = 0  # counts the solves (layer.BatchQPFunction checks that its backward meets its own solve)
         tags, dims, dims2, alphas = _cone_arrays(st["cones"])
         self._h = C.c_void_p()
         Pp, Pi, Px = st["P"]
@@ -1074,9 +1075,13 @@ class HipBatchSolver:
             lib().chip_batch_destroy(self._h)
             self._h = C.c_void_p()
 
+    def _solve(self):
+        _check(lib().chip_batch_solve(self._h), "chip_batch_solve")
+        self.generation += 1
+
     def solve(self):
         """the batched IPSolver::solve -> one Solution per member, in input order"""
-        _check(lib().chip_batch_solve(self._h), "chip_batch_solve")
+        self._solve()
         out = []
         for k in range(len(self)):
             x, s, z = np.zeros(self.n_part[k]), np.zeros(self.m_part[k]), np.zeros(self.m_part[k])
@@ -1173,6 +1178,84 @@ class HipBatchSolver:
                "chip_bdata_get_scaled")
         return Px, Ax, q, b, nq, nb
 
+    # ---- gradients (chip_bgrad_*): dL/d(x, z, s) of every member -> dL/d(q, b, P, A) of every member --------------
+    def solve_torch(self):
+        """solve() without the per-member host copies: the stacked (x, s, z) as torch tensors on the GPU (copies of
+        the handle's buffers, so they outlive the next solve); statuses with infos()"""
+        self._solve()
+        px, ps, pz = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().chip_batch_get_solution_dev(self._h, C.byref(px), C.byref(ps), C.byref(pz)),
+               "chip_batch_get_solution_dev")
+        n, m = self._len["q"], self._len["b"]
+        return _torch_copy(px.value, n, "float64"), _torch_copy(ps.value, m, "float64"), \
+            _torch_copy(pz.value, m, "float64")
+
+    def _grad_input(self, name, g, key):
+        """one incoming gradient -> ("none", None), ("host", float64 array) or ("dev", contiguous GPU tensor)"""
+        length = self._len[key]
+        if g is None:
+            return ("none", None)
+        if isinstance(g, list) and len(g) > 0 and not np.isscalar(g[0]):
+            off = self._offsets[key]
+            if len(g) != len(self):
+                raise ChipError(ERR_DIM, "backward %s: %d list entries for %d members" % (name, len(g), len(self)))
+            out = np.zeros(length)
+            for k, piece in enumerate(g):
+                if piece is None:
+                    continue
+                if _is_torch(piece) and piece.is_cuda:
+                    raise TypeError("backward %s: member %d: the entries of a list are host arrays" % (name, k))
+                v = _host_array(piece, name, False)
+                if v.size != off[k + 1] - off[k]:
+                    raise ChipError(ERR_DIM, "backward %s: member %d: %d values for %d entries"
+                                    % (name, k, v.size, off[k + 1] - off[k]))
+                out[off[k]:off[k + 1]] = v
+            return ("host", out)
+        if _is_torch(g) and g.is_cuda:
+            import torch
+            if g.dtype != torch.float64:
+                raise TypeError("backward %s: GPU values must be float64, not %s" % (name, g.dtype))
+            if g.dim() != 1 or g.numel() != length:
+                raise ChipError(ERR_DIM, "backward %s: a vector of %d values is needed" % (name, length))
+            return ("dev", g.detach().contiguous())
+        v = _host_array(g, name, False)
+        if v.size != length:
+            raise ChipError(ERR_DIM, "backward %s: %d values for %d entries" % (name, v.size, length))
+        return ("host", _f(v))
+
+    def backward(self, gx=None, gz=None, gs=None):
+        """the gradients of a loss with respect to q, b, P and A of every member from its gradients with respect to
+        the members' x, z and s of the last solve() (stacked vectors; None = zeros): numpy arrays, torch tensors on
+        the GPU (float64; the result then holds torch tensors on the GPU and nothing crosses to the host), or a list
+        with one entry per member (None = zeros for that member; the entries are HOST vectors, as in update()'s list
+        form -- gradients that live on the GPU go in as stacked tensors).  Returns a BatchGradient.  Members that did not end
+        Solved, or own a SecondOrder cone, have valid[k] = 0 and exact zeros.  ChipError(ERR_ARG) before a solve and
+        after an update that was not followed by a solve."""
+        forms = [self._grad_input(nm, g, key) for nm, g, key in (("gx", gx, "q"), ("gz", gz, "b"), ("gs", gs, "b"))]
+        kinds = {f[0] for f in forms} - {"none"}
+        if len(kinds) > 1:
+            raise TypeError("backward: gx, gz and gs must all be host arrays or all GPU tensors")
+        n, m, nP, nA = self._len["q"], self._len["b"], self._len["P"], self._len["A"]
+        valid = np.zeros(len(self), dtype=np.int32)
+        if kinds == {"dev"}:
+            import torch
+            dev = [f[1] for f in forms if f[0] == "dev"][0].device
+            torch.cuda.current_stream(dev).synchronize()  # the values are written before the call reads them
+            ptr = [None if f[0] == "none" else C.c_void_p(f[1].data_ptr()) for f in forms]
+            _check(lib().chip_bgrad_backward_dev(self._h, *ptr), "chip_bgrad_backward_dev")
+            out = [C.c_void_p() for _ in range(4)]
+            _check(lib().chip_bgrad_get_dev(self._h, *[C.byref(o) for o in out], None), "chip_bgrad_get_dev")
+            _check(lib().chip_bgrad_get(self._h, None, None, None, None, valid.ctypes.data_as(P_I32)),
+                   "chip_bgrad_get")
+            dq, db, dP, dA = [_torch_copy(o.value, ln, "float64", dev) for o, ln in zip(out, (n, m, nP, nA))]
+            return BatchGradient(dq, db, dP, dA, valid, self._offsets)
+        ptr = [None if f[0] == "none" else _pf(f[1]) for f in forms]
+        _check(lib().chip_bgrad_backward(self._h, *ptr), "chip_bgrad_backward")
+        dq, db, dP, dA = np.zeros(n), np.zeros(m), np.zeros(nP), np.zeros(nA)
+        _check(lib().chip_bgrad_get(self._h, _pf(dq), _pf(db), _pf(dP), _pf(dA), valid.ctypes.data_as(P_I32)),
+               "chip_bgrad_get")
+        return BatchGradient(dq, db, dP, dA, valid, self._offsets)
+
     # ---- test hooks (include/clarabel_hip_testing.h) ----
     def debug_inject_nan(self, member, iteration):
         _check(lib().chip_debug_batch_inject_nan(self._h, C.c_int64(member), C.c_int32(iteration)),
@@ -1182,6 +1265,36 @@ class HipBatchSolver:
         out = C.c_double()
         _check(lib().chip_debug_batch_counter(self._h, name.encode(), C.byref(out)), "chip_debug_batch_counter")
         return out.value
+
+
+class BatchGradient:
+    """the result of HipBatchSolver.backward: dq[n], db[m], dP[nnz(P)], dA[nnz(A)] of the stack (dP, dA in the order
+    of the stack's nzval, the positions update_P / update_A index) as numpy arrays or torch GPU tensors, and
+    valid[nprob] (numpy int32): 1 where the member has a gradient, else its entries are exact zeros"""
+
+    def __init__(self, dq, db, dP, dA, valid, offsets):
+        self.dq, self.db, self.dP, self.dA, self.valid = dq, db, dP, dA, valid
+        self._offsets = offsets
+
+    def per_member(self, k):
+        """member k's (dq, db, dP, dA): slices of the stacked vectors"""
+        o = self._offsets
+        return tuple(v[int(o[key][k]):int(o[key][k + 1])]
+                     for v, key in ((self.dq, "q"), (self.db, "b"), (self.dP, "P"), (self.dA, "A")))
+
+
+def _torch_copy(ptr, n, dtype, device=None):
+    """a torch tensor on the GPU holding a copy of n values at device address `ptr`"""
+    import torch
+    t = torch.empty(int(n), dtype=getattr(torch, dtype), device=device if device is not None else "cuda")
+    if n:
+        rt = _hiprt()
+        rc = rt.hipMemcpy(C.c_void_p(t.data_ptr()), C.c_void_p(ptr), C.c_size_t(int(n) * t.element_size()), C.c_int(3))
+        if rc == 0:
+            rc = rt.hipDeviceSynchronize()
+        if rc != 0:
+            raise RuntimeError("hipMemcpy D2D failed: %d" % rc)
+    return t
 
 
 def _cone_arrays(cones):

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "batch.hpp"
+#include "batch_adjoint.hpp"
 #include "batch_update.hpp"
 #include "engine.hpp"
 #include "problem_update.hpp"
@@ -135,6 +136,15 @@ struct chip_batch {
     size_t stage_v_cap = 0, stage_i_cap = 0, clean_cap = 0;
     std::vector<double> unorm;
     long upd_syncs = 0, upd_launches = 0; // of the last update call
+    // the gradients (chip_bgrad_*): solve_current: the last solve ran on the data the handle holds now; grad_done: the
+    // buffers below hold the result of a backward since that solve.  Allocated by the first backward
+    std::vector<char> has_soc; // the member owns a SecondOrder cone: no gradient
+    std::vector<int32_t> gvalid;
+    bool solve_current = false, grad_done = false;
+    int *g_valid = nullptr;
+    double *g_dq = nullptr, *g_db = nullptr, *g_dP = nullptr, *g_dA = nullptr;
+    double *g_in[3] = {nullptr, nullptr, nullptr}; // the staging of the host form's gx, gz, gs
+    long grad_syncs = 0, grad_launches = 0;        // of the last backward
 
     ~chip_batch() {
         if (stream) (void)hipStreamSynchronize(stream);
@@ -217,6 +227,8 @@ struct chip_batch {
     int update_work();
     template <typename T> int grow(T **buf, size_t *cap, size_t need);
     int update(int which, const int64_t *idx_dev, const double *vals_dev, int k);
+    int backward_work();
+    int backward(const double *gx_dev, const double *gz_dev, const double *gs_dev);
 };
 
 int chip_batch::equilibrate(const std::vector<ConeSpec> &cones) {
@@ -342,6 +354,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     if (mm != m) return failb(CHIP_ERR_DIM, "chip_batch_create: cone dimensions do not add up to m");
     std::vector<int> rtype((size_t)m, dev::ROW_ZERO);
     std::vector<int64_t> degree((size_t)np, 0);
+    std::vector<char> has_soc((size_t)np, 0);
     std::vector<int> it_beg, it_end, it_type, it_mem;
     for (const ConeSpec &cs : cones) {
         if (cs.numel == 0) continue;
@@ -357,6 +370,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
                 it_mem.push_back(k);
             }
         } else if (cs.tag == CHIP_CONE_SECONDORDER) {
+            has_soc[k] = 1;
             rtype[r0] = dev::ROW_SOC_HEAD;
             for (int i = r0 + 1; i < r1; i++) rtype[i] = dev::ROW_SOC_TAIL;
             degree[k] += 1;
@@ -397,6 +411,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     h->xoff = xoff;
     h->zoff = zoff;
     h->degree = degree;
+    h->has_soc = has_soc;
     h->lp_init = lp_init;
     h->anyP = nnzP > 0;
     h->anyLP = std::find(lp_init.begin(), lp_init.end(), 1) != lp_init.end();
@@ -891,6 +906,7 @@ int32_t chip_batch_solve(chip_batch *h) {
     h->held_done.assign((size_t)np, 0);
     h->t_solve0 = now_s();
     h->solve_time = h->setup_time;
+    h->solve_current = h->grad_done = false;
     int rc;
     if ((rc = h->default_start())) return rc;
     for (int k = 0; k < np; k++) h->hm(M_ACTIVE, k) = 1;
@@ -1069,6 +1085,7 @@ int32_t chip_batch_solve(chip_batch *h) {
     if ((rc = h->post_process())) return rc;
     h->solve_time = h->setup_time + (now_s() - h->t_solve0);
     h->solved_once = true;
+    h->solve_current = true;
     return CHIP_OK;
 }
 
@@ -1175,6 +1192,10 @@ template <typename T> int chip_batch::grow(T **buf, size_t *cap, size_t need) {
 int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev, int k) {
     int rc;
     if ((rc = update_work())) return rc;
+    // from the first write on the last solve's iterate no longer belongs to the data: no gradient until the next solve
+    // (chip_bgrad_*).  Only the refusal that has changed nothing puts the flag back; a call that fails on the way does not
+    const bool was_current = solve_current;
+    solve_current = false;
     const int len = which == BU_P ? M.nnzP : which == BU_A ? M.nnzA : which == BU_Q ? n : m;
     hipStream_t s = stream;
     if (idx_dev) { // the whole index list is checked on the device before any pass writes
@@ -1229,7 +1250,10 @@ int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev
     }
     CHIP_HIP(hipStreamSynchronize(s));
     upd_syncs++;
-    if (bad) return failb(CHIP_ERR_DIM, std::string(BU_NAME[which]) + ": an index is out of range (nothing changed)");
+    if (bad) {
+        solve_current = was_current;
+        return failb(CHIP_ERR_DIM, std::string(BU_NAME[which]) + ": an index is out of range (nothing changed)");
+    }
     if (which == BU_Q) normq = unorm;
     if (which == BU_B) normb = unorm;
     if (which == BU_P) kkt_set_static_diag_max(kkt, pmax[2]);
@@ -1358,6 +1382,129 @@ int32_t chip_bdata_get_scaled(chip_batch *h, double *Px, double *Ax, double *q, 
     return CHIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Gradients of the members' solutions (chip_bgrad_*).  With the incoming gradients (gx, gz, gs) of a
+// member's unscaled (x, z, s), its adjoint is ONE KKT solve at the final iterate,
+//     [vx; vz] = K^-1 [gx - A' gs; gz],   K = [P A'; A -H],   H = diag(s / z) on Nonnegative rows, 0 on Zero rows,
+// which is the matrix chip_kkt factors after a scaling update with (s, z).  The solve runs in the equilibrated space
+// of the stack (x = D x^, z = E z^ / c_k, s = E^-1 s^; P^ = c_k D P D, q^ = c_k D q, A^ = E A D, b^ = E b), where the
+// incoming gradients are D gx, E gz / c_k and E^-1 gs; its solution multiplied back, ux = c_k D vx^ and uz = E vz^,
+// is the adjoint pair of the unscaled problem, so the four gradients are the unscaled formulas on the unscaled
+// solution the solve has already written (xo, zo).  H is s / z of the internal iterate: tau cancels.
+// One backward: a fixed number of enqueues (counted as batch.cpp counts them everywhere: one per kernel, copy or call
+// into the KKT layer, whatever that call launches itself), the synchronisations of one chip_kkt_update and one
+// chip_kkt_solve_dev and one at the end.  It leaves K factored at the final iterate and overwrites work vectors only; chip_batch_solve starts
+// from default_start, which rescales and refactors, so a following solve does not see it.
+// ---------------------------------------------------------------------------------------------------------------
+int chip_batch::backward_work() {
+    if (g_valid) return CHIP_OK;
+    int rc;
+    if ((rc = mem.alloc(&g_dq, (size_t)n)) || (rc = mem.alloc(&g_db, (size_t)m)) ||
+        (rc = mem.alloc(&g_dP, (size_t)M.nnzP)) || (rc = mem.alloc(&g_dA, (size_t)M.nnzA)) ||
+        (rc = mem.alloc(&g_in[0], (size_t)n)) || (rc = mem.alloc(&g_in[1], (size_t)m)) ||
+        (rc = mem.alloc(&g_in[2], (size_t)m)) || (rc = mem.alloc(&g_valid, (size_t)nprob)))
+        return rc;
+    gvalid.assign((size_t)nprob, 0);
+    return CHIP_OK;
+}
+
+int chip_batch::backward(const double *gx, const double *gz, const double *gs) {
+    int rc;
+    hipStream_t s = stream;
+    grad_done = false; // (a backward that fails part-way leaves no result behind)
+    // a gradient exists for the members that ended Solved and own only Zero / Nonnegative cones; every other member
+    // takes the cones' unit vector for (s, z), as a member that ended NumericalError does in the loop, and a zero
+    // right-hand side: its block of K stays well posed and its part of the solution is 0
+    for (int k = 0; k < nprob; k++) gvalid[k] = info[k].status == CHIP_SOLVER_SOLVED && !has_soc[k];
+    CHIP_HIP(hipMemcpyAsync(g_valid, gvalid.data(), (size_t)nprob * sizeof(int), hipMemcpyHostToDevice, s));
+    dev::ba_rhs(s, plan, dev::BaRhs{g_valid, gx, gz, gs, d, e, dc, vs, vz, wn, conicw, workz, ds, dz});
+    grad_launches += 2;
+    if ((rc = kktsystem_spmv(sys, 2, workx, wn, -1.0, conicw))) return rc; // D gx - A^' (gs / e)
+    grad_launches++;
+    if ((rc = chip_kkt_update_scaling_dev(kkt, ds, dz, 1.0, 0)) < 0) return rc;
+    rc = chip_kkt_update(kkt, nullptr);
+    grad_syncs++;
+    grad_launches += 2;
+    if (rc < 0) return rc;
+    if (rc != 1) return failb(CHIP_ERR_ZERO_PIVOT, "chip_bgrad_backward: the factorisation at the final iterate failed");
+    if ((rc = chip_kkt_setrhs_dev(kkt, workx, workz))) return rc;
+    rc = chip_kkt_solve_dev(kkt, x1, z1);
+    grad_syncs++;
+    grad_launches++;
+    if (rc < 0) return rc;
+    if (rc != 1) return failb(CHIP_ERR_ZERO_PIVOT, "chip_bgrad_backward: the solve at the final iterate failed");
+    const dev::BaGrad g{g_valid, x1, z1, gs, d, e, dc, xo, zo, x2, z2, g_dq, g_db, g_dP, g_dA};
+    dev::ba_grad_vectors(s, plan, g);
+    dev::ba_grad_matrices(s, plan, M, g);
+    grad_launches += 2;
+    CHIP_HIP(hipGetLastError());
+    CHIP_HIP(hipStreamSynchronize(s));
+    grad_syncs++;
+    grad_done = true;
+    return CHIP_OK;
+}
+
+namespace {
+int bg_ready(chip_batch *h, const char *fn) {
+    if (!h) return failb(CHIP_ERR_ARG, std::string(fn) + ": bad argument");
+    if (!h->solve_current)
+        return failb(CHIP_ERR_ARG, std::string(fn) + ": needs a finished chip_batch_solve on the current data");
+    return CHIP_OK;
+}
+} // namespace
+
+int32_t chip_bgrad_backward(chip_batch *h, const double *gx, const double *gz, const double *gs) {
+    int rc = bg_ready(h, "chip_bgrad_backward");
+    if (rc) return rc;
+    CHIP_HIP(hipSetDevice(h->device));
+    h->grad_syncs = h->grad_launches = 0;
+    if ((rc = h->backward_work())) return rc;
+    const double *src[3] = {gx, gz, gs};
+    const double *in[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; i++) {
+        const size_t len = (size_t)(i == 0 ? h->n : h->m);
+        if (!src[i]) continue;
+        in[i] = h->g_in[i];
+        if (!len) continue;
+        CHIP_HIP(hipMemcpyAsync(h->g_in[i], src[i], len * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        h->grad_launches++;
+    }
+    return h->backward(in[0], in[1], in[2]);
+}
+
+int32_t chip_bgrad_backward_dev(chip_batch *h, const double *gx_dev, const double *gz_dev, const double *gs_dev) {
+    int rc = bg_ready(h, "chip_bgrad_backward_dev");
+    if (rc) return rc;
+    CHIP_HIP(hipSetDevice(h->device));
+    h->grad_syncs = h->grad_launches = 0;
+    if ((rc = h->backward_work())) return rc;
+    return h->backward(gx_dev, gz_dev, gs_dev);
+}
+
+int32_t chip_bgrad_get(chip_batch *h, double *dq, double *db, double *dPx, double *dAx, int32_t *valid) {
+    if (!h) return failb(CHIP_ERR_ARG, "chip_bgrad_get: bad argument");
+    if (!h->grad_done) return failb(CHIP_ERR_ARG, "chip_bgrad_get: no chip_bgrad_backward since the last solve");
+    CHIP_HIP(hipSetDevice(h->device));
+    if (dq && h->n) CHIP_HIP(hipMemcpy(dq, h->g_dq, (size_t)h->n * 8, hipMemcpyDeviceToHost));
+    if (db && h->m) CHIP_HIP(hipMemcpy(db, h->g_db, (size_t)h->m * 8, hipMemcpyDeviceToHost));
+    if (dPx && h->M.nnzP) CHIP_HIP(hipMemcpy(dPx, h->g_dP, (size_t)h->M.nnzP * 8, hipMemcpyDeviceToHost));
+    if (dAx && h->M.nnzA) CHIP_HIP(hipMemcpy(dAx, h->g_dA, (size_t)h->M.nnzA * 8, hipMemcpyDeviceToHost));
+    if (valid) std::copy(h->gvalid.begin(), h->gvalid.end(), valid);
+    return CHIP_OK;
+}
+
+int32_t chip_bgrad_get_dev(chip_batch *h, double **dq_dev, double **db_dev, double **dPx_dev, double **dAx_dev,
+                           int32_t **valid_dev) {
+    if (!h) return failb(CHIP_ERR_ARG, "chip_bgrad_get_dev: bad argument");
+    if (!h->grad_done) return failb(CHIP_ERR_ARG, "chip_bgrad_get_dev: no chip_bgrad_backward since the last solve");
+    if (dq_dev) *dq_dev = h->g_dq;
+    if (db_dev) *db_dev = h->g_db;
+    if (dPx_dev) *dPx_dev = h->g_dP;
+    if (dAx_dev) *dAx_dev = h->g_dA;
+    if (valid_dev) *valid_dev = h->g_valid;
+    return CHIP_OK;
+}
+
 #ifdef CHIP_TESTING
 #include "../../include/clarabel_hip_testing.h"
 int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration) {
@@ -1376,6 +1523,8 @@ int32_t chip_debug_batch_counter(void *batch, const char *name, double *out) {
     else if (nm == "loop_iterations") *out = (double)h->loop_iters;
     else if (nm == "update_launches") *out = (double)h->upd_launches;
     else if (nm == "update_host_syncs") *out = (double)h->upd_syncs;
+    else if (nm == "backward_launches") *out = (double)h->grad_launches;
+    else if (nm == "backward_host_syncs") *out = (double)h->grad_syncs;
     else return failb(CHIP_ERR_ARG, "chip_debug_batch_counter: unknown name");
     return CHIP_OK;
 }

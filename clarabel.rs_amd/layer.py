@@ -1,0 +1,42 @@
+"""A batch of QPs / LPs as a differentiable torch layer: q, b and the values of P and A come from a model, the
+members' solutions feed a loss.  Forward is HipBatchSolver.update + one batched solve, backward is
+HipBatchSolver.backward (chip_bgrad_*: one KKT update and one KKT solve at the final iterates); with
+tensors on the GPU nothing crosses to the host in either direction.
+
+    solver = HipBatchSolver(problems)                    # the patterns and the initial values
+    x, z, s = BatchQPFunction.apply(q, b, Px, Ax, solver)
+    loss(x, z, s).backward()                             # fills q.grad, b.grad, Px.grad, Ax.grad
+
+q[n], b[m], Px[nnz(P)], Ax[nnz(A)] are stacked float64 vectors in the stack's order (the positions update_P /
+update_A index); any of them may be None: that piece keeps the solver's current values and gets no gradient.  Members
+that did not end Solved, or own a SecondOrder cone, get zero gradients (solver.last_gradient.valid tells which)."""
+import torch
+
+
+class BatchQPFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, b, Px, Ax, solver):
+        pieces = {"P": Px, "q": q, "A": Ax, "b": b}
+        solver.update(**{k: (None if v is None else v.detach()) for k, v in pieces.items()})
+        x, s, z = solver.solve_torch()
+        ctx.solver = solver
+        ctx.generation = solver.generation  # backward differentiates the LAST solve of the handle: which one this was
+        ctx.device = x.device
+        ctx.like = [None if v is None else (v.device, v.dtype) for v in (q, b, Px, Ax)]
+        return x, z, s
+
+    @staticmethod
+    def backward(ctx, gx, gz, gs):
+        solver = ctx.solver
+        if solver.generation != ctx.generation:
+            raise RuntimeError("BatchQPFunction.backward: the solver has been solved again since this forward")
+        dev = ctx.device
+        prep = lambda g: None if g is None else g.detach().to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
+        if gx is None and gz is None and gs is None:
+            gx = torch.zeros(solver.stack["n"], dtype=torch.float64, device=dev)
+        g = solver.backward(gx=prep(gx), gz=prep(gz), gs=prep(gs))
+        solver.last_gradient = g
+        outs = (g.dq, g.db, g.dP, g.dA)
+        grads = [None if like is None or not need else o.to(device=like[0], dtype=like[1])
+                 for o, like, need in zip(outs, ctx.like, ctx.needs_input_grad[:4])]
+        return grads[0], grads[1], grads[2], grads[3], None

@@ -115,6 +115,32 @@ def portfolio_problem(nblocks=1000, blocksize=1000, seed=3):
     return pr
 
 
+def portfolio_qp(n_assets=2000, n_factors=20, seed=5):
+    """a long-only factor-model portfolio QP (Zero / Nonnegative cones only, so a batch of them has gradients):
+        min 1/2 (x'Dx + y'y) - mu'x   s.t.  y = F'x,  1'x = 1,  0 <= x <= cap
+    variables [x (n_assets); y (n_factors)]; rows: Zero(n_factors) y - F'x = 0, Zero(1) budget,
+    NN(n_assets) -x <= 0, NN(n_assets) x <= cap.  D: idiosyncratic variances (diagonal), F: n_assets x n_factors
+    loadings, cap = 10 / n_assets (capped at 1).  P is diagonal.  Also returns F, D, mu and cap."""
+    rng = np.random.default_rng(seed)
+    na, nf = int(n_assets), int(n_factors)
+    F = rng.standard_normal((na, nf)) / np.sqrt(max(nf, 1))
+    D = rng.uniform(0.05, 0.5, na)
+    mu = rng.uniform(0.0, 0.3, na)
+    cap = min(1.0, 10.0 / na)
+    n, m = na + nf, nf + 1 + 2 * na
+    I = sp.identity(na, format="csc")
+    A = sp.bmat([[-sp.csc_matrix(F.T), sp.identity(nf, format="csc")],
+                 [sp.csc_matrix(np.ones((1, na))), None],
+                 [-I, None],
+                 [I, None]], format="csc")
+    P = sp.diags(np.concatenate([D, np.ones(nf)]), format="csc")
+    q = np.concatenate([-mu, np.zeros(nf)])
+    b = np.concatenate([np.zeros(nf), [1.0], np.zeros(na), np.full(na, cap)])
+    cones = [(ZERO, nf + 1), (NN, 2 * na)]
+    s, z = _interior(rng, cones)
+    return dict(n=n, m=m, P=_csc(P), A=_csc(A), cones=cones, q=q, b=b, s=s, z=z, F=F, D=D, mu=mu, cap=cap)
+
+
 def batched_socp(nbatch=1024, n_b=2000, blocks_per=2, seed=100, late=False):
     """C4: `nbatch` independent copies of a small C3-pattern SOCP, concatenated block
     diagonally (csc/block_concatenate.rs:22) -> elimination forest with nbatch roots."""

@@ -753,6 +753,31 @@ int32_t chip_bdata_update_settings(chip_batch *h, const chip_solver_settings *se
 int32_t chip_bdata_get_scaled(chip_batch *h, double *Px, double *Ax, double *q, double *b, double *normq,
                               double *normb);
 
+/* ---- gradients of a batch's solutions: given dL/dx, dL/dz, dL/ds of every member's (unscaled) solution, dL/dq,
+ * dL/db, dL/dP and dL/dA of every member -- what a QP / LP layer inside a model needs for its backward pass.  With
+ * H = diag(s_i / z_i) on the Nonnegative rows and 0 on the Zero rows of the final iterate and K = [P A'; A -H]:
+ *     [vx; vz] = K^-1 [gx - A' gs; gz]
+ *     dL/dq = -vx                      dL/dA_ij = -(z_i vx_j + vz_i x_j) - gs_i x_j   on A's stored entries
+ *     dL/db =  vz + gs                 dL/dP_ij = -(vx_i x_j + vx_j x_i) (i < j), -vx_i x_i (i = j)   on P's stored triu
+ * One call costs one KKT update, one refined KKT solve and entry-parallel passes, whatever nprob.
+ *   chip_bgrad_backward  gx[n], gz[m], gs[m]: stacked host vectors, any may be NULL (= zeros); _dev: device pointers
+ *                        (the caller must have finished writing them before the call).  Needs a finished
+ *                        chip_batch_solve on the data the handle holds now: before the first solve, or after a
+ *                        chip_bdata_update_{P,A,q,b} that changed something, CHIP_ERR_ARG and nothing changes.
+ *   chip_bgrad_get       host copies (any may be NULL): dq[n], db[m], dPx[nnz(P)], dAx[nnz(A)] in the order of the
+ *                        stack's nzval -- the positions chip_bdata_update_P / _A index -- and valid[nprob].
+ *                        _dev: the handle's own device buffers, valid until the next backward, solve or destroy.
+ *                        CHIP_ERR_ARG when no backward has run since the last solve.
+ *   valid[k] = 1 iff member k ended CHIP_SOLVER_SOLVED and owns only Zero / Nonnegative cones.  Every other member
+ *   (AlmostSolved, infeasible, NumericalError, MaxIterations, ..., any SecondOrder cone) has valid[k] = 0 and exact
+ *   zeros in all four gradients, and does not disturb the others.  A member without strict complementarity gets
+ *   whatever the regularised system gives.  A following chip_batch_solve behaves as if backward had not run. */
+int32_t chip_bgrad_backward(chip_batch *h, const double *gx, const double *gz, const double *gs);
+int32_t chip_bgrad_backward_dev(chip_batch *h, const double *gx_dev, const double *gz_dev, const double *gs_dev);
+int32_t chip_bgrad_get(chip_batch *h, double *dq, double *db, double *dPx, double *dAx, int32_t *valid);
+int32_t chip_bgrad_get_dev(chip_batch *h, double **dq_dev, double **db_dev, double **dPx_dev, double **dAx_dev,
+                           int32_t **valid_dev);
+
 /* ===========================================================================
  * Sharded path: one process per GPU, whole connected components of the elimination
  * forest per rank (BASELINE config 4: 1024 independent SOCPs, 128 per GPU at 8 GPUs).  Factorisation,

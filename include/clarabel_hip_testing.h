@@ -55,7 +55,8 @@ int32_t chip_debug_solver_internal_solution(void *solver, double *x2, double *s2
  * chip_debug_batch_counter: "host_syncs" / "launches" (host synchronisations / kernel and copy enqueues of the last
  * solve's iterations, default_start and post-processing excluded), "loop_iterations" (iterations run);
  * "update_launches" / "update_host_syncs" (kernel, memset and copy enqueues / host synchronisations of the last
- * chip_bdata_update_* call). */
+ * chip_bdata_update_* call); "backward_launches" / "backward_host_syncs" (the same of the last chip_bgrad_backward*
+ * call). */
 int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration);
 int32_t chip_debug_batch_counter(void *batch, const char *name, double *out);
 #ifdef __cplusplus
