@@ -844,11 +844,81 @@ class Solution:
         return "Solution(status=%s, iterations=%d, obj_val=%r)" % (self.status, self.iterations, self.obj_val)
 
 
-class HipSolver:
+class _DataUpdates:
+    """the data updates of HipSolver and HipBatchSolver (default/data_updating.rs, python/impl_default_py.rs:699):
+    update(), update_P / _A / _q / _b and update_settings over the C entry points <_UPDATE_PREFIX>P .. b, their _dev
+    forms and <_UPDATE_PREFIX>settings.  The class has _h, settings, _len and _pattern; it may override _classify (a
+    piece -> a form of classify_update) and _check_update_allowed (raises when the handle takes no updates)."""
+
+    _UPDATE_PREFIX = None
+
+    def update(self, P=None, q=None, A=None, b=None, settings=None):
+        """solver.update(P=..., q=..., A=..., b=..., settings=...): each piece may be a CscMatrix with the setup's
+        pattern (P, A), a full value vector, an (index, values) tuple, an empty vector (no-op) or torch tensors on the
+        GPU (float64 values, int64 index); for a HipBatchSolver these address the stack, and a piece may also be a
+        LIST with one entry per member (see HipBatchSolver).  Every piece is classified before any is applied; they
+        are then applied in the order P, q, A, b, settings, and the first refusal raises ChipError (the pieces before
+        it stay applied, as in the reference)."""
+        self._check_update_allowed()
+        forms = [(k, self._classify(k, v)) for k, v in (("P", P), ("q", q), ("A", A), ("b", b)) if v is not None]
+        for k, f in forms:
+            self._apply_update(k, f)
+        if settings is not None:
+            self.update_settings(settings)
+
+    def update_P(self, data):
+        self._apply_update("P", self._classify("P", data))
+
+    def update_A(self, data):
+        self._apply_update("A", self._classify("A", data))
+
+    def update_q(self, data):
+        self._apply_update("q", self._classify("q", data))
+
+    def update_b(self, data):
+        self._apply_update("b", self._classify("b", data))
+
+    def _classify(self, key, data):
+        return classify_update(key, data, self._len[key], self._pattern.get(key))
+
+    def _check_update_allowed(self):
+        pass
+
+    def _apply_update(self, key, form):
+        self._check_update_allowed()
+        kind = form[0]
+        if kind == "none":
+            return
+        idx, vals = form[1], form[2]
+        name = self._UPDATE_PREFIX + key
+        if kind in ("full", "partial"):
+            _check(getattr(lib(), name)(self._h, None if idx is None else _pu(idx), _pf(vals), C.c_int64(len(vals))),
+                   name)
+            return
+        import torch
+        torch.cuda.current_stream(vals.device).synchronize()  # the values are written before the call reads them
+        name += "_dev"
+        _check(getattr(lib(), name)(self._h, None if idx is None else C.c_void_p(idx.data_ptr()),
+                                    C.c_void_p(vals.data_ptr()), C.c_int64(vals.numel())), name)
+
+    def update_settings(self, settings=None, **kw):
+        """DefaultSolver::update_settings (for a HipBatchSolver: of every member): a SolverSettings, or keyword
+        overrides of the current settings (linear-system fields go to .linsys).  An immutable field that differs
+        raises ChipError(ERR_ARG) and the settings stay as they were."""
+        new = SolverSettings.from_buffer_copy(settings if settings is not None else self.settings)
+        _apply_settings(new, kw, "update_settings")
+        name = self._UPDATE_PREFIX + "settings"
+        _check(getattr(lib(), name)(self._h, C.byref(new)), name)
+        self.settings = new
+
+
+class HipSolver(_DataUpdates):
     """DefaultSolver::new(P, q, A, b, cones, settings) (default/solver.rs) with every layer on the device: Ruiz
     equilibration, the interior-point loop, termination and the status.  P: n x n triu CscMatrix, A: m x n CscMatrix,
     cones as in HipKKTSolver ((tag, dim), (tag, dim, dim2), (tag, dim, dim2, alpha); GenPowerConeT =
     (5, len(alpha), dim2, alpha))."""
+
+    _UPDATE_PREFIX = "chip_problem_update_"
 
     def __init__(self, P, q, A, b, cones, settings=None):
         n, m = P.n, A.m
@@ -909,63 +979,9 @@ class HipSolver:
                "chip_solver_get_equilibration")
         return d, e, c.value
 
-    # ---- data updates (default/data_updating.rs, python/impl_default_py.rs:699) ------------------------------------
-    def update(self, P=None, q=None, A=None, b=None, settings=None):
-        """solver.update(P=..., q=..., A=..., b=..., settings=...): each piece may be a CscMatrix with the setup's
-        pattern (P, A), a full value vector, an (index, values) tuple, an empty vector (no-op) or torch tensors on the
-        GPU (float64 values, int64 index).  Every piece is classified before any is applied; they are then applied in
-        the order P, q, A, b, settings, and the first refusal raises ChipError (the pieces before it stay applied, as
-        in the reference)."""
-        self._check_update_allowed()
-        forms = [(k, classify_update(k, v, self._len[k], self._pattern.get(k)))
-                 for k, v in (("P", P), ("q", q), ("A", A), ("b", b)) if v is not None]
-        for k, f in forms:
-            self._apply_update(k, f)
-        if settings is not None:
-            self.update_settings(settings)
-
-    def update_P(self, data):
-        self._apply_update("P", classify_update("P", data, self._len["P"], self._pattern["P"]))
-
-    def update_A(self, data):
-        self._apply_update("A", classify_update("A", data, self._len["A"], self._pattern["A"]))
-
-    def update_q(self, data):
-        self._apply_update("q", classify_update("q", data, self._len["q"]))
-
-    def update_b(self, data):
-        self._apply_update("b", classify_update("b", data, self._len["b"]))
-
     def _check_update_allowed(self):
         if not self.is_data_update_allowed():  # data_updating.rs: checked before the data is looked at
             raise UpdateNotAllowedError(ERR_UPDATE_NOT_ALLOWED, "update: presolve or chordal decomposition is active")
-
-    def _apply_update(self, key, form):
-        self._check_update_allowed()
-        kind = form[0]
-        if kind == "none":
-            return
-        if kind in ("full", "partial"):
-            idx, vals = form[1], form[2]
-            fn = getattr(lib(), "chip_problem_update_" + key)
-            _check(fn(self._h, None if idx is None else _pu(idx), _pf(vals), C.c_int64(len(vals))),
-                   "chip_problem_update_" + key)
-            return
-        import torch
-        idx, vals = form[1], form[2]
-        torch.cuda.current_stream(vals.device).synchronize()  # the values are written before the call reads them
-        fn = getattr(lib(), "chip_problem_update_%s_dev" % key)
-        _check(fn(self._h, None if idx is None else C.c_void_p(idx.data_ptr()), C.c_void_p(vals.data_ptr()),
-                  C.c_int64(vals.numel())), "chip_problem_update_%s_dev" % key)
-
-    def update_settings(self, settings=None, **kw):
-        """DefaultSolver::update_settings: a SolverSettings, or keyword overrides of the current settings
-        (linear-system fields go to .linsys).  An immutable field that differs raises ChipError(ERR_ARG) and the
-        settings stay as they were."""
-        new = SolverSettings.from_buffer_copy(settings if settings is not None else self.settings)
-        _apply_settings(new, kw, "update_settings")
-        _check(lib().chip_problem_update_settings(self._h, C.byref(new)), "chip_problem_update_settings")
-        self.settings = new
 
     def transform_info(self):
         """what presolve and chordal decomposition did at setup (chip_transform_get_info) as a dict"""
@@ -1033,10 +1049,19 @@ def batch_stack(problems):
                 q=cat(qs, f64), b=cat(bs, f64), cones=cones)
 
 
-class HipBatchSolver:
+class HipBatchSolver(_DataUpdates):
     """many independent problems in ONE batched interior-point solve on the device (chip_batch_*): every member keeps
     its own tau, kappa, mu, sigma, step length, termination and status.  problems: a list of (P, q, A, b, cones) as
-    HipSolver takes them, with Zero / Nonnegative / SecondOrder cones; one settings for every member."""
+    HipSolver takes them, with Zero / Nonnegative / SecondOrder cones; one settings for every member.
+
+    Data updates (chip_bdata_*; update(), update_P / _A / _q / _b): new values on the stack's fixed patterns, then
+    solve() again.  Each piece is a stacked value vector (or a CscMatrix with the stack's pattern), an (index, values)
+    tuple of stack positions, an empty vector (no-op), torch tensors on the GPU -- or a LIST with one entry per member,
+    each None (member untouched), a value vector of the member's own length (or its CscMatrix) or a member-local
+    (index, values); the list is translated with the stack's offsets into one partial update, so updating 3 of 1024
+    members moves only their values."""
+
+    _UPDATE_PREFIX = "chip_bdata_update_"
 
     def __init__(self, problems, settings=None):
         problems = list(problems)
@@ -1112,61 +1137,10 @@ class HipBatchSolver:
                "chip_batch_get_equilibration")
         return d, e, c.value
 
-    # ---- data updates (chip_bdata_*): new values on the stack's fixed patterns, then solve() again ----------------
-    def update(self, P=None, q=None, A=None, b=None, settings=None):
-        """batch.update(P=..., q=..., A=..., b=..., settings=...): each piece is a stacked value vector (or a
-        CscMatrix with the stack's pattern), an (index, values) tuple of stack positions, an empty vector (no-op),
-        torch tensors on the GPU (float64 values, int64 index) -- or a LIST with one entry per member, each None
-        (member untouched), a value vector of the member's own length (or its CscMatrix) or a member-local
-        (index, values); the list is translated with the stack's offsets into one partial update, so updating 3 of
-        1024 members moves only their values.  Every piece is classified before any is applied; they are applied in
-        the order P, q, A, b, settings, and the first refusal raises ChipError (the pieces before it stay applied)."""
-        forms = [(k, self._classify(k, v)) for k, v in (("P", P), ("q", q), ("A", A), ("b", b)) if v is not None]
-        for k, f in forms:
-            self._apply_update(k, f)
-        if settings is not None:
-            self.update_settings(settings)
-
-    def update_P(self, data):
-        self._apply_update("P", self._classify("P", data))
-
-    def update_A(self, data):
-        self._apply_update("A", self._classify("A", data))
-
-    def update_q(self, data):
-        self._apply_update("q", self._classify("q", data))
-
-    def update_b(self, data):
-        self._apply_update("b", self._classify("b", data))
-
     def _classify(self, key, data):
         if isinstance(data, list) and len(data) > 0 and not np.isscalar(data[0]):
             return batch_list_update(key, data, self._offsets[key], self._mpattern.get(key))
-        return classify_update(key, data, self._len[key], self._pattern.get(key))
-
-    def _apply_update(self, key, form):
-        kind = form[0]
-        if kind == "none":
-            return
-        idx, vals = form[1], form[2]
-        if kind in ("full", "partial"):
-            fn = getattr(lib(), "chip_bdata_update_" + key)
-            _check(fn(self._h, None if idx is None else _pu(idx), _pf(vals), C.c_int64(len(vals))),
-                   "chip_bdata_update_" + key)
-            return
-        import torch
-        torch.cuda.current_stream(vals.device).synchronize()  # the values are written before the call reads them
-        fn = getattr(lib(), "chip_bdata_update_%s_dev" % key)
-        _check(fn(self._h, None if idx is None else C.c_void_p(idx.data_ptr()), C.c_void_p(vals.data_ptr()),
-                  C.c_int64(vals.numel())), "chip_bdata_update_%s_dev" % key)
-
-    def update_settings(self, settings=None, **kw):
-        """update_settings for every member: a SolverSettings, or keyword overrides of the current settings.  An
-        immutable field that differs raises ChipError(ERR_ARG) and the settings stay as they were."""
-        new = SolverSettings.from_buffer_copy(settings if settings is not None else self.settings)
-        _apply_settings(new, kw, "update_settings")
-        _check(lib().chip_bdata_update_settings(self._h, C.byref(new)), "chip_bdata_update_settings")
-        self.settings = new
+        return super()._classify(key, data)
 
     def scaled_data(self):
         """the stack's data as the handle holds it after the equilibration, and the members' norms of the unscaled

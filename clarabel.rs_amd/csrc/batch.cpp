@@ -11,7 +11,6 @@
 // run on the whole stack as they are; combined_ds_shift runs with sigma mu = 0 and the member's sigma mu is then
 // subtracted at the unit vector's entries, which is the same arithmetic for Nonnegative and SecondOrder cones.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -23,57 +22,13 @@
 #include "batch_adjoint.hpp"
 #include "batch_update.hpp"
 #include "engine.hpp"
+#include "host_util.hpp"
+#include "ipm_info.hpp"
 #include "problem_update.hpp"
 
 using namespace chip;
 
 namespace {
-
-int failb(int code, const std::string &msg) {
-    set_error(msg);
-    return code;
-}
-
-double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-struct BDev {
-    std::vector<void *> ptrs;
-    template <typename T> int alloc(T **dst, size_t n) {
-        void *p = nullptr;
-        CHIP_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        ptrs.push_back(p);
-        *dst = (T *)p;
-        return CHIP_OK;
-    }
-    template <typename T> int upload(T **dst, const T *src, size_t n) {
-        int rc = alloc(dst, n);
-        if (rc) return rc;
-        if (n) CHIP_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-        return CHIP_OK;
-    }
-    ~BDev() {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-};
-
-// DefaultInfo's scalars of one member (default/info.rs:12-64) and the dots of its last residual pass
-struct MInfo {
-    double cost_primal = 0, cost_dual = 0, res_primal = 0, res_dual = 0, res_primal_inf = 0, res_dual_inf = 0;
-    double gap_abs = 0, gap_rel = 0, ktratio = 0;
-    double prev_cost_primal = 0, prev_cost_dual = 0, prev_res_primal = 0, prev_res_dual = 0, prev_gap_abs = 0,
-           prev_gap_rel = 0;
-    double out5[5] = {0, 0, 0, 0, 0}; // r_tau, q'x, b'z, s'z, x'Px
-    int iterations = 0;
-    int status = CHIP_SOLVER_UNSOLVED;
-};
-
-bool is_infeasible(int s) {
-    return s == CHIP_SOLVER_PRIMAL_INFEASIBLE || s == CHIP_SOLVER_DUAL_INFEASIBLE ||
-           s == CHIP_SOLVER_ALMOST_PRIMAL_INFEASIBLE || s == CHIP_SOLVER_ALMOST_DUAL_INFEASIBLE;
-}
-
 // per-member device scalars (slot * nprob + k) and masks
 enum { S_TAU, S_INVTAU, S_DTAU, S_OMS, S_ALPHA, S_AMAX, S_SHIFT1, S_SHIFT2, S_NEGSM, S_SX, S_SZ, S_COUNT };
 enum { M_ACTIVE, M_QP, M_LP, M_SEL, M_SEL2, M_COUNT };
@@ -81,13 +36,12 @@ enum { M_ACTIVE, M_QP, M_LP, M_SEL, M_SEL2, M_COUNT };
 enum { R_QX, R_XPX, R_NX, R_NRXI, R_NPX, R_NRX, R_BADX, R_BZ, R_SZ, R_NZ, R_NS, R_NRZI, R_NRZ, R_BADSZ, R_COUNT };
 // the direction passes
 enum { D_QX1, D_BZ1, D_XIPX1, D_DPD, D_BAD, D_COUNT };
-
 } // namespace
 
 struct chip_batch {
     int nprob = 0, n = 0, m = 0, device = 0;
     chip_solver_settings st{};
-    BDev mem;
+    DevPool mem;
     std::vector<int> xoff, zoff;
     dev::BatchPlan plan{};
     dev::EqMats M{};
@@ -117,7 +71,7 @@ struct chip_batch {
     std::vector<int> hmask;
     // per member on the host
     std::vector<double> tau, kappa, ptau, pkappa, htau, hkappa, mu, sigma, alpha, dtau, qx2, bz2, x2Px2;
-    std::vector<MInfo> info, pinfo, hinfo;
+    std::vector<IpmInfo> info, pinfo, hinfo; // (out5 of a member: the dots of its last residual pass)
     std::vector<char> active, held, held_done; // held: 1 = the current iterate, 2 = the previous one
     std::vector<double> obj_val, obj_val_dual;
     double setup_time = 0, equilibration_time = 0, iteration_time = 0, solve_time = 0;
@@ -131,9 +85,9 @@ struct chip_batch {
     int *upos = nullptr, *uflag = nullptr;
     unsigned long long *unpart = nullptr, *ubpart = nullptr;
     double *unout = nullptr, *ubout = nullptr;
-    double *stage_v = nullptr;
-    int64_t *stage_i = nullptr, *clean = nullptr;
-    size_t stage_v_cap = 0, stage_i_cap = 0, clean_cap = 0;
+    UpdateStage stage;
+    int64_t *clean = nullptr;
+    size_t clean_cap = 0;
     std::vector<double> unorm;
     long upd_syncs = 0, upd_launches = 0; // of the last update call
     // the gradients (chip_bgrad_*): solve_current: the last solve ran on the data the handle holds now; grad_done: the
@@ -148,8 +102,6 @@ struct chip_batch {
 
     ~chip_batch() {
         if (stream) (void)hipStreamSynchronize(stream);
-        (void)hipFree(stage_v);
-        (void)hipFree(stage_i);
         (void)hipFree(clean);
         chip_kktsystem_destroy(sys);
         chip_kkt_destroy(kkt);
@@ -215,8 +167,6 @@ struct chip_batch {
     int default_start();
     int residual_pass();
     void member_info(int k);
-    bool check_termination(int k, int iter);
-    void check_convergence(int k, bool almost);
     int solve_direction(const double *conic, const std::vector<double> &rtau, const std::vector<double> &rkap,
                         std::vector<double> &lkappa, bool *global_ok, int iter);
     int step_length(const std::vector<double> &lkappa, bool combined);
@@ -225,7 +175,12 @@ struct chip_batch {
     int post_process();
     int end_member(int k, int status, int iterations, bool from_prev);
     int update_work();
-    template <typename T> int grow(T **buf, size_t *cap, size_t need);
+    static constexpr const char *UPD_PREFIX = "chip_bdata_update_";
+    int update_len(int which) const { return which == UPD_P ? M.nnzP : which == UPD_A ? M.nnzA : which == UPD_Q ? n : m; }
+    static int update_args(chip_batch *h, int which, const void *idx, const double *vals, int64_t k);
+    int stage_upload(const uint64_t *idx, const double *vals, size_t k) {
+        return stage.upload(stream, idx, vals, k, &upd_launches, &upd_syncs);
+    }
     int update(int which, const int64_t *idx_dev, const double *vals_dev, int k);
     int backward_work();
     int backward(const double *gx_dev, const double *gz_dev, const double *gs_dev);
@@ -241,7 +196,7 @@ int chip_batch::equilibrate(const std::vector<ConeSpec> &cones) {
         if (m) CHIP_HIP(hipMemcpy(einv, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
         return CHIP_OK;
     }
-    BDev work;
+    DevPool work;
     unsigned long long *bits = nullptr;
     double *cstate = nullptr, *colsum = nullptr, *delta = nullptr, *scr = nullptr;
     const size_t nbits = dev::batch_eq_bits_words(n, m, nprob);
@@ -286,13 +241,13 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
                           const double *genpow_alphas_or_null, const chip_solver_settings *settings) {
     (void)cone_alphas_or_null;
     (void)genpow_alphas_or_null;
-    if (!out) return failb(CHIP_ERR_ARG, "chip_batch_create: bad argument");
+    if (!out) return fail(CHIP_ERR_ARG, "chip_batch_create: bad argument");
     *out = nullptr;
     if (nprob < 1 || !n_part || !m_part || n < 0 || m < 0 || !Pcolptr || !Acolptr || ncones < 0 ||
         (ncones && (!cone_tags || !cone_dims)))
-        return failb(CHIP_ERR_ARG, "chip_batch_create: bad argument");
+        return fail(CHIP_ERR_ARG, "chip_batch_create: bad argument");
     if ((Pcolptr[n] && (!Prowval || !Pnzval)) || (Acolptr[n] && (!Arowval || !Anzval)) || (n && !q) || (m && !b))
-        return failb(CHIP_ERR_ARG, "chip_batch_create: missing data");
+        return fail(CHIP_ERR_ARG, "chip_batch_create: missing data");
     const double t0 = now_s();
     std::unique_ptr<chip_batch> h(new chip_batch());
     if (settings) h->st = *settings;
@@ -301,27 +256,27 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     st.linsys.linesearch_backtrack_step = st.linesearch_backtrack_step;
     st.linsys.min_terminate_step_length = st.min_terminate_step_length;
     if (st.presolve_enable || st.chordal_decomposition_enable)
-        return failb(CHIP_ERR_UNSUPPORTED, "chip_batch_create: presolve and chordal decomposition are not supported");
+        return fail(CHIP_ERR_UNSUPPORTED, "chip_batch_create: presolve and chordal decomposition are not supported");
     for (int64_t i = 0; i < ncones; i++)
         if (cone_tags[i] != CHIP_CONE_ZERO && cone_tags[i] != CHIP_CONE_NONNEGATIVE &&
             cone_tags[i] != CHIP_CONE_SECONDORDER)
-            return failb(CHIP_ERR_UNSUPPORTED, "chip_batch_create: only Zero, Nonnegative and SecondOrder cones");
-    if (nprob >= (1ll << 31)) return failb(CHIP_ERR_DIM, "chip_batch_create: sizes out of int32 range");
+            return fail(CHIP_ERR_UNSUPPORTED, "chip_batch_create: only Zero, Nonnegative and SecondOrder cones");
+    if (nprob >= (1ll << 31)) return fail(CHIP_ERR_DIM, "chip_batch_create: sizes out of int32 range");
     const uint64_t nnzP = Pcolptr[n], nnzA = Acolptr[n];
     if (n >= (1ll << 31) || m >= (1ll << 31) || nnzP + nnzA + (uint64_t)n + (uint64_t)m >= (1ull << 31) ||
         n + 2 * m >= (1ll << 31))
-        return failb(CHIP_ERR_DIM, "chip_batch_create: sizes out of int32 range");
+        return fail(CHIP_ERR_DIM, "chip_batch_create: sizes out of int32 range");
     // ---- the partition and the checks that every entry and cone stays inside its member
     const int np = (int)nprob;
     std::vector<int> xoff((size_t)np + 1, 0), zoff((size_t)np + 1, 0);
     for (int k = 0; k < np; k++) {
-        if (n_part[k] < 0 || m_part[k] < 0) return failb(CHIP_ERR_ARG, "chip_batch_create: negative part");
+        if (n_part[k] < 0 || m_part[k] < 0) return fail(CHIP_ERR_ARG, "chip_batch_create: negative part");
         const int64_t xn = (int64_t)xoff[k] + n_part[k], zn = (int64_t)zoff[k] + m_part[k];
-        if (xn > n || zn > m) return failb(CHIP_ERR_ARG, "chip_batch_create: the parts exceed n or m");
+        if (xn > n || zn > m) return fail(CHIP_ERR_ARG, "chip_batch_create: the parts exceed n or m");
         xoff[k + 1] = (int)xn;
         zoff[k + 1] = (int)zn;
     }
-    if (xoff[np] != n || zoff[np] != m) return failb(CHIP_ERR_ARG, "chip_batch_create: the parts do not add up to n, m");
+    if (xoff[np] != n || zoff[np] != m) return fail(CHIP_ERR_ARG, "chip_batch_create: the parts do not add up to n, m");
     std::vector<int> xmem((size_t)n), zmem((size_t)m);
     for (int k = 0; k < np; k++) {
         for (int j = xoff[k]; j < xoff[k + 1]; j++) xmem[j] = k;
@@ -333,16 +288,16 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
         const int k = xmem[j];
         for (uint64_t p = Pcolptr[j]; p < Pcolptr[j + 1]; p++) {
             const int64_t r = (int64_t)Prowval[p];
-            if (r > j) return failb(CHIP_ERR_NOT_TRIU, "P is not upper triangular");
-            if (r < xoff[k]) return failb(CHIP_ERR_ARG, "chip_batch_create: an entry of P crosses two members' blocks");
+            if (r > j) return fail(CHIP_ERR_NOT_TRIU, "P is not upper triangular");
+            if (r < xoff[k]) return fail(CHIP_ERR_ARG, "chip_batch_create: an entry of P crosses two members' blocks");
             Prow[p] = (int)r;
             Pcol[p] = (int)j;
             lp_init[k] = 0;
         }
         for (uint64_t p = Acolptr[j]; p < Acolptr[j + 1]; p++) {
             const int64_t r = (int64_t)Arowval[p];
-            if (r >= m) return failb(CHIP_ERR_DIM, "A row index out of range");
-            if (zmem[r] != k) return failb(CHIP_ERR_ARG, "chip_batch_create: an entry of A crosses two members' blocks");
+            if (r >= m) return fail(CHIP_ERR_DIM, "A row index out of range");
+            if (zmem[r] != k) return fail(CHIP_ERR_ARG, "chip_batch_create: an entry of A crosses two members' blocks");
             Arow[p] = (int)r;
             Acol[p] = (int)j;
         }
@@ -350,8 +305,8 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     std::vector<ConeSpec> cones;
     int64_t mm = 0, pdim = 0, nHs = 0;
     if (build_cone_specs(ncones, cone_tags, cone_dims, cone_dims2, cones, mm, pdim, nHs))
-        return failb(CHIP_ERR_ARG, "chip_batch_create: bad cone");
-    if (mm != m) return failb(CHIP_ERR_DIM, "chip_batch_create: cone dimensions do not add up to m");
+        return fail(CHIP_ERR_ARG, "chip_batch_create: bad cone");
+    if (mm != m) return fail(CHIP_ERR_DIM, "chip_batch_create: cone dimensions do not add up to m");
     std::vector<int> rtype((size_t)m, dev::ROW_ZERO);
     std::vector<int64_t> degree((size_t)np, 0);
     std::vector<char> has_soc((size_t)np, 0);
@@ -359,7 +314,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     for (const ConeSpec &cs : cones) {
         if (cs.numel == 0) continue;
         const int r0 = (int)cs.start, r1 = (int)(cs.start + cs.numel), k = zmem[r0];
-        if (zmem[r1 - 1] != k) return failb(CHIP_ERR_ARG, "chip_batch_create: a cone crosses a member's rows");
+        if (zmem[r1 - 1] != k) return fail(CHIP_ERR_ARG, "chip_batch_create: a cone crosses a member's rows");
         if (cs.tag == CHIP_CONE_NONNEGATIVE) {
             for (int i = r0; i < r1; i++) rtype[i] = dev::ROW_NN;
             degree[k] += cs.numel;
@@ -402,7 +357,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     }
     // ---- the device
     if (st.linsys.device == CHIP_DEVICE_HOST_ONLY || chip_device_count() < 1)
-        return failb(CHIP_ERR_NO_DEVICE, "chip_batch_create: no HIP device (the product has no CPU fallback)");
+        return fail(CHIP_ERR_NO_DEVICE, "chip_batch_create: no HIP device (the product has no CPU fallback)");
     if (st.linsys.device >= 0) CHIP_HIP(hipSetDevice(st.linsys.device));
     CHIP_HIP(hipGetDevice(&h->device));
     h->nprob = np;
@@ -415,7 +370,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     h->lp_init = lp_init;
     h->anyP = nnzP > 0;
     h->anyLP = std::find(lp_init.begin(), lp_init.end(), 1) != lp_init.end();
-    BDev &mem = h->mem;
+    DevPool &mem = h->mem;
     int rc;
     dev::BatchPlan &pl = h->plan;
     int *d_xoff, *d_zoff, *d_xmem, *d_zmem, *d_chb, *d_che, *d_cxf, *d_czf, *d_itb, *d_ite, *d_itt, *d_itf, *d_rt;
@@ -621,76 +576,20 @@ int chip_batch::residual_pass() {
     return read_red((size_t)(R_COUNT + 1) * nprob);
 }
 
-// DefaultInfo::update (info.rs:113-178) of member k from the residual pass
+// the dots and squared norms of member k from the residual pass into DefaultInfo::update (ipm_info.hpp), and its mu
 void chip_batch::member_info(int k) {
-    MInfo &I = info[k];
-    const double t = tau[k];
+    IpmInfo &I = info[k];
     const double qx = red(R_QX, k), bz = red(R_BZ, k), sz = red(R_SZ, k), xPx = anyP ? red(R_XPX, k) : 0.0;
-    I.out5[0] = qx + bz + kappa[k] + xPx / t;
+    I.out5[0] = qx + bz + kappa[k] + xPx / tau[k];
     I.out5[1] = qx;
     I.out5[2] = bz;
     I.out5[3] = sz;
     I.out5[4] = xPx;
-    double nrm[8];
     const int slots[8] = {R_NX, R_NZ, R_NS, R_NRXI, R_NPX, R_NRZI, R_NRZ, R_NRX};
-    for (int j = 0; j < 8; j++) nrm[j] = std::sqrt(red(slots[j], k));
-    const double tinv = 1.0 / t, cinv = 1.0 / c[k];
-    const double xPx2 = xPx * tinv * tinv / 2.0;
-    I.cost_primal = (qx * tinv + xPx2) * cinv;
-    I.cost_dual = (-bz * tinv - xPx2) * cinv;
-    double normx = nrm[0], normz = nrm[1] * cinv, norms = nrm[2];
-    I.res_primal_inf = (nrm[3] * cinv) / std::max(1.0, normz);
-    I.res_dual_inf = std::max(nrm[4] / std::max(1.0, normx), nrm[5] / std::max(1.0, normx + norms));
-    normx *= tinv;
-    normz *= tinv;
-    norms *= tinv;
-    I.res_primal = nrm[6] * tinv / std::max(1.0, normb[k] + normx + norms);
-    I.res_dual = nrm[7] * tinv * cinv / std::max(1.0, normq[k] + normx + normz);
-    I.gap_abs = std::fabs(I.cost_primal - I.cost_dual);
-    I.gap_rel = I.gap_abs / std::max(1.0, std::min(std::fabs(I.cost_primal), std::fabs(I.cost_dual)));
-    I.ktratio = kappa[k] * tinv;
+    double sq[8];
+    for (int j = 0; j < 8; j++) sq[j] = red(slots[j], k);
+    ipm_info_update(I, sq, tau[k], kappa[k], c[k], normq[k], normb[k]);
     mu[k] = (sz + tau[k] * kappa[k]) / (double)(degree[k] + 1); // variables.rs:63-66
-}
-
-// check_convergence_full / _almost (info.rs:277-389)
-void chip_batch::check_convergence(int k, bool almost) {
-    MInfo &I = info[k];
-    const double tga = almost ? st.reduced_tol_gap_abs : st.tol_gap_abs;
-    const double tgr = almost ? st.reduced_tol_gap_rel : st.tol_gap_rel;
-    const double tf = almost ? st.reduced_tol_feas : st.tol_feas;
-    const double tia = almost ? st.reduced_tol_infeas_abs : st.tol_infeas_abs;
-    const double tir = almost ? st.reduced_tol_infeas_rel : st.tol_infeas_rel;
-    const double tkt = almost ? st.reduced_tol_ktratio : st.tol_ktratio;
-    const double dot_qx = I.out5[1], dot_bz = I.out5[2];
-    if (I.ktratio <= 1.0 && (I.gap_abs < tga || I.gap_rel < tgr) && I.res_primal < tf && I.res_dual < tf) {
-        I.status = almost ? CHIP_SOLVER_ALMOST_SOLVED : CHIP_SOLVER_SOLVED;
-    } else if (I.ktratio > (1.0 / tkt) * 1000.0) {
-        if (dot_bz < -tia && I.res_primal_inf < -tir * dot_bz)
-            I.status = almost ? CHIP_SOLVER_ALMOST_PRIMAL_INFEASIBLE : CHIP_SOLVER_PRIMAL_INFEASIBLE;
-        else if (dot_qx < -tia && I.res_dual_inf < -tir * dot_qx)
-            I.status = almost ? CHIP_SOLVER_ALMOST_DUAL_INFEASIBLE : CHIP_SOLVER_DUAL_INFEASIBLE;
-    }
-}
-
-// check_termination (info.rs:182-231) of member k
-bool chip_batch::check_termination(int k, int iter) {
-    MInfo &I = info[k];
-    check_convergence(k, false);
-    if (I.status == CHIP_SOLVER_UNSOLVED && iter > 1 && (I.res_dual > I.prev_res_dual || I.res_primal > I.prev_res_primal)) {
-        if (I.ktratio < std::numeric_limits<double>::epsilon() * 100.0 &&
-            (I.prev_gap_abs < st.tol_gap_abs || I.prev_gap_rel < st.tol_gap_rel))
-            I.status = CHIP_SOLVER_INSUFFICIENT_PROGRESS;
-        if (I.ktratio < 1.0) {
-            if ((I.res_dual > st.tol_feas * 100.0 && I.res_dual > I.prev_res_dual * 100.0) ||
-                (I.res_primal > st.tol_feas * 100.0 && I.res_primal > I.prev_res_primal * 100.0))
-                I.status = CHIP_SOLVER_INSUFFICIENT_PROGRESS;
-        }
-    }
-    if (I.status == CHIP_SOLVER_UNSOLVED) {
-        if (st.max_iter == I.iterations) I.status = CHIP_SOLVER_MAX_ITERATIONS;
-        else if (solve_time > st.time_limit) I.status = CHIP_SOLVER_MAX_TIME;
-    }
-    return I.status != CHIP_SOLVER_UNSOLVED;
 }
 
 // member k ends NumericalError: its reported solution is its last finite iterate (the previous one when the current
@@ -868,19 +767,8 @@ int chip_batch::post_process() {
     }
     if ((rc = push_masks())) return rc;
     copy_members(vx, vs, vz, hx, hs, hz, mk(M_SEL));
-    for (int k = 0; k < nprob; k++) {
-        MInfo &I = info[k];
-        const int s = I.status;
-        if (s == CHIP_SOLVER_NUMERICAL_ERROR || s == CHIP_SOLVER_INSUFFICIENT_PROGRESS || s == CHIP_SOLVER_MAX_ITERATIONS ||
-            s == CHIP_SOLVER_MAX_TIME)
-            check_convergence(k, true);
-        const bool inf = is_infeasible(I.status);
-        obj_val[k] = inf ? std::numeric_limits<double>::quiet_NaN() : I.cost_primal;
-        obj_val_dual[k] = inf ? std::numeric_limits<double>::quiet_NaN() : I.cost_dual;
-        const double scaleinv = inf ? 1.0 / kappa[k] : 1.0 / tau[k];
-        hs_(S_SX, k) = scaleinv;
-        hs_(S_SZ, k) = scaleinv * (1.0 / c[k]);
-    }
+    for (int k = 0; k < nprob; k++)
+        ipm_post_process(info[k], st, tau[k], kappa[k], c[k], &obj_val[k], &obj_val_dual[k], &hs_(S_SX, k), &hs_(S_SZ, k));
     if ((rc = push_scalars())) return rc;
     dev::bunscale(stream, plan, xo, vx, d, zo, vz, e, so, vs, einv, sc(S_SX), sc(S_SZ));
     CHIP_HIP(hipGetLastError());
@@ -890,7 +778,7 @@ int chip_batch::post_process() {
 
 // IPSolver::solve (core/solver.rs:242-464) with every scalar indexed by member
 int32_t chip_batch_solve(chip_batch *h) {
-    if (!h) return failb(CHIP_ERR_ARG, "chip_batch_solve: bad argument");
+    if (!h) return fail(CHIP_ERR_ARG, "chip_batch_solve: bad argument");
     CHIP_HIP(hipSetDevice(h->device));
     const int np = h->nprob;
     const chip_solver_settings &st = h->st;
@@ -898,9 +786,9 @@ int32_t chip_batch_solve(chip_batch *h) {
     for (auto *v : {&h->tau, &h->kappa, &h->ptau, &h->pkappa, &h->htau, &h->hkappa, &h->mu, &h->sigma, &h->alpha,
                     &h->dtau, &h->obj_val, &h->obj_val_dual, &h->qx2, &h->bz2, &h->x2Px2})
         zeros(*v);
-    h->info.assign((size_t)np, MInfo());
-    h->pinfo.assign((size_t)np, MInfo());
-    h->hinfo.assign((size_t)np, MInfo());
+    h->info.assign((size_t)np, IpmInfo());
+    h->pinfo.assign((size_t)np, IpmInfo());
+    h->hinfo.assign((size_t)np, IpmInfo());
     h->active.assign((size_t)np, 1);
     h->held.assign((size_t)np, 0);
     h->held_done.assign((size_t)np, 0);
@@ -930,18 +818,13 @@ int32_t chip_batch_solve(chip_batch *h) {
         bool any_restore = false;
         for (int k = 0; k < np; k++) {
             if (!h->active[k]) continue;
-            MInfo &I = h->info[k];
+            IpmInfo &I = h->info[k];
             h->member_info(k);
             I.iterations = iter;
-            if (h->check_termination(k, iter)) {
+            if (ipm_check_termination(I, st, iter, h->solve_time)) {
                 h->active[k] = 0;
                 if (I.status == CHIP_SOLVER_INSUFFICIENT_PROGRESS) { // reset_to_prev_iterate (info.rs:244-253)
-                    I.cost_primal = I.prev_cost_primal;
-                    I.cost_dual = I.prev_cost_dual;
-                    I.res_primal = I.prev_res_primal;
-                    I.res_dual = I.prev_res_dual;
-                    I.gap_abs = I.prev_gap_abs;
-                    I.gap_rel = I.prev_gap_rel;
+                    ipm_reset_to_prev(I);
                     restore[k] = 1;
                     any_restore = true;
                     h->tau[k] = h->ptau[k];
@@ -1059,14 +942,9 @@ int32_t chip_batch_solve(chip_batch *h) {
             h->hm(M_ACTIVE, k) = h->active[k];
             h->hs_(S_ALPHA, k) = h->alpha[k];
             if (!h->active[k]) continue;
-            MInfo &I = h->info[k];
+            IpmInfo &I = h->info[k];
             h->pinfo[k] = I;
-            I.prev_cost_primal = I.cost_primal;
-            I.prev_cost_dual = I.cost_dual;
-            I.prev_res_primal = I.res_primal;
-            I.prev_res_dual = I.res_dual;
-            I.prev_gap_abs = I.gap_abs;
-            I.prev_gap_rel = I.gap_rel;
+            ipm_save_prev(I);
             h->ptau[k] = h->tau[k];
             h->pkappa[k] = h->kappa[k];
             h->tau[k] = h->tau[k] + h->alpha[k] * h->dtau[k];
@@ -1104,13 +982,13 @@ static void fill_info(const chip_batch *h, int k, chip_solution_info *out) {
 }
 
 int32_t chip_batch_get_info(chip_batch *h, chip_solution_info *infos) {
-    if (!h || !infos) return failb(CHIP_ERR_ARG, "chip_batch_get_info: bad argument");
+    if (!h || !infos) return fail(CHIP_ERR_ARG, "chip_batch_get_info: bad argument");
     for (int k = 0; k < h->nprob; k++) fill_info(h, k, infos + k);
     return CHIP_OK;
 }
 
 int32_t chip_batch_get_solution(chip_batch *h, int64_t k, double *x, double *s, double *z, chip_solution_info *info) {
-    if (!h || k < 0 || k >= h->nprob) return failb(CHIP_ERR_ARG, "chip_batch_get_solution: bad argument");
+    if (!h || k < 0 || k >= h->nprob) return fail(CHIP_ERR_ARG, "chip_batch_get_solution: bad argument");
     CHIP_HIP(hipSetDevice(h->device));
     const int x0 = h->xoff[k], nk = h->xoff[k + 1] - x0, z0 = h->zoff[k], mk_ = h->zoff[k + 1] - z0;
     if (h->solved_once) {
@@ -1127,7 +1005,7 @@ int32_t chip_batch_get_solution(chip_batch *h, int64_t k, double *x, double *s, 
 }
 
 int32_t chip_batch_get_solution_dev(chip_batch *h, double **x_dev, double **s_dev, double **z_dev) {
-    if (!h) return failb(CHIP_ERR_ARG, "chip_batch_get_solution_dev: bad argument");
+    if (!h) return fail(CHIP_ERR_ARG, "chip_batch_get_solution_dev: bad argument");
     if (x_dev) *x_dev = h->xo;
     if (s_dev) *s_dev = h->so;
     if (z_dev) *z_dev = h->zo;
@@ -1135,7 +1013,7 @@ int32_t chip_batch_get_solution_dev(chip_batch *h, double **x_dev, double **s_de
 }
 
 int32_t chip_batch_get_equilibration(chip_batch *h, int64_t k, double *d, double *e, double *c) {
-    if (!h || k < 0 || k >= h->nprob) return failb(CHIP_ERR_ARG, "chip_batch_get_equilibration: bad argument");
+    if (!h || k < 0 || k >= h->nprob) return fail(CHIP_ERR_ARG, "chip_batch_get_equilibration: bad argument");
     CHIP_HIP(hipSetDevice(h->device));
     const int x0 = h->xoff[k], nk = h->xoff[k + 1] - x0, z0 = h->zoff[k], mk_ = h->zoff[k + 1] - z0;
     if (d && nk) CHIP_HIP(hipMemcpy(d, h->d + x0, (size_t)nk * 8, hipMemcpyDeviceToHost));
@@ -1153,12 +1031,6 @@ int32_t chip_batch_get_equilibration(chip_batch *h, int64_t k, double *d, double
 // fixed number of launches and ONE host synchronisation: a partial form's writes read the word the index check
 // raised on the device, so a refused call has written nothing when the host learns of it.
 // ---------------------------------------------------------------------------------------------------------------
-namespace {
-enum { BU_P = 0, BU_A = 1, BU_Q = 2, BU_B = 3 };
-const char *const BU_NAME[4] = {"chip_bdata_update_P", "chip_bdata_update_A", "chip_bdata_update_q",
-                                "chip_bdata_update_b"};
-} // namespace
-
 int chip_batch::update_work() {
     if (uflag) return CHIP_OK;
     const size_t len = (size_t)std::max({M.nnzP, M.nnzA, n, m, 1});
@@ -1174,20 +1046,6 @@ int chip_batch::update_work() {
     return CHIP_OK;
 }
 
-template <typename T> int chip_batch::grow(T **buf, size_t *cap, size_t need) {
-    if (need <= *cap) return CHIP_OK;
-    if (*buf) { // (work enqueued earlier may still read the old buffer)
-        CHIP_HIP(hipStreamSynchronize(stream));
-        upd_syncs++;
-        (void)hipFree(*buf);
-        *buf = nullptr;
-        *cap = 0;
-    }
-    CHIP_HIP(hipMalloc((void **)buf, need * sizeof(T)));
-    *cap = need;
-    return CHIP_OK;
-}
-
 // one update of P, A, q or b: idx_dev == nullptr is the full form (k == the length, checked by the caller)
 int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev, int k) {
     int rc;
@@ -1196,19 +1054,19 @@ int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev
     // (chip_bgrad_*).  Only the refusal that has changed nothing puts the flag back; a call that fails on the way does not
     const bool was_current = solve_current;
     solve_current = false;
-    const int len = which == BU_P ? M.nnzP : which == BU_A ? M.nnzA : which == BU_Q ? n : m;
+    const int len = update_len(which);
     hipStream_t s = stream;
     if (idx_dev) { // the whole index list is checked on the device before any pass writes
-        if ((rc = grow(&clean, &clean_cap, (size_t)k))) return rc;
+        if ((rc = grow_dev(&clean, &clean_cap, (size_t)k, s, &upd_syncs))) return rc;
         CHIP_HIP(hipMemsetAsync(uflag, 0, sizeof(int), s));
         dev::pu_validate(s, idx_dev, k, len, uflag);
         upd_launches += 2;
     }
     dev::BuTarget t{};
     switch (which) {
-    case BU_P: t = {M.Px, nullptr, nullptr, len, M.Prow, M.Pcol, d, d, dc, plan.xmem}; break;
-    case BU_A: t = {M.Ax, nullptr, nullptr, len, M.Arow, M.Acol, e, d, nullptr, plan.xmem}; break;
-    case BU_Q: t = {q, uq, negq, len, nullptr, nullptr, d, nullptr, dc, plan.xmem}; break;
+    case UPD_P: t = {M.Px, nullptr, nullptr, len, M.Prow, M.Pcol, d, d, dc, plan.xmem}; break;
+    case UPD_A: t = {M.Ax, nullptr, nullptr, len, M.Arow, M.Acol, e, d, nullptr, plan.xmem}; break;
+    case UPD_Q: t = {q, uq, negq, len, nullptr, nullptr, d, nullptr, dc, plan.xmem}; break;
     default: t = {b, ub, nullptr, len, nullptr, nullptr, e, nullptr, nullptr, plan.zmem}; break;
     }
     if (idx_dev) {
@@ -1221,23 +1079,23 @@ int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev
     CHIP_HIP(hipGetLastError());
     // the copies the loop reads: K's values (only the touched entries of a partial form; a refused one rewrites
     // entry 0 with its own value), the L3 mirrors and vectors
-    if (which == BU_P || which == BU_A) {
-        const double *src = which == BU_P ? M.Px : M.Ax;
+    if (which == UPD_P || which == UPD_A) {
+        const double *src = which == UPD_P ? M.Px : M.Ax;
         if ((rc = kkt_update_values_dev(kkt, which, src, idx_dev ? clean : nullptr, idx_dev ? k : len))) return rc;
         upd_launches++;
     }
-    if ((rc = kktsystem_update_data_dev(sys, which == BU_P ? M.Px : nullptr, which == BU_A ? M.Ax : nullptr,
-                                        which == BU_Q ? q : nullptr, which == BU_B ? b : nullptr)))
+    if ((rc = kktsystem_update_data_dev(sys, which == UPD_P ? M.Px : nullptr, which == UPD_A ? M.Ax : nullptr,
+                                        which == UPD_Q ? q : nullptr, which == UPD_B ? b : nullptr)))
         return rc;
-    upd_launches += (which == BU_A || which == BU_Q) ? 2 : 1; // A: two mirrors; q: the copy and its negation
+    upd_launches += (which == UPD_A || which == UPD_Q) ? 2 : 1; // A: two mirrors; q: the copy and its negation
     // the scalars create derived from the values: the members' norms of the unscaled q / b, max |P_ii| of the stack
     double pmax[3] = {0, 0, 0};
-    if (which == BU_Q || which == BU_B) {
-        dev::bu_norms(s, plan, which == BU_Q ? 0 : 1, which == BU_Q ? uq : ub, ubpart, ubout);
+    if (which == UPD_Q || which == UPD_B) {
+        dev::bu_norms(s, plan, which == UPD_Q ? 0 : 1, which == UPD_Q ? uq : ub, ubpart, ubout);
         CHIP_HIP(hipGetLastError());
         CHIP_HIP(hipMemcpyAsync(unorm.data(), ubout, (size_t)nprob * 8, hipMemcpyDeviceToHost, s));
         upd_launches += 3;
-    } else if (which == BU_P) {
+    } else if (which == UPD_P) {
         dev::pu_norms(s, 4, nullptr, nullptr, 0, nullptr, nullptr, 0, M.Prow, M.Pcol, M.Px, M.nnzP, unpart, unout);
         CHIP_HIP(hipGetLastError());
         CHIP_HIP(hipMemcpyAsync(pmax, unout, sizeof(pmax), hipMemcpyDeviceToHost, s));
@@ -1252,125 +1110,40 @@ int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev
     upd_syncs++;
     if (bad) {
         solve_current = was_current;
-        return failb(CHIP_ERR_DIM, std::string(BU_NAME[which]) + ": an index is out of range (nothing changed)");
+        return fail(CHIP_ERR_DIM, update_fn(UPD_PREFIX, which) + ": an index is out of range (nothing changed)");
     }
-    if (which == BU_Q) normq = unorm;
-    if (which == BU_B) normb = unorm;
-    if (which == BU_P) kkt_set_static_diag_max(kkt, pmax[2]);
+    if (which == UPD_Q) normq = unorm;
+    if (which == UPD_B) normb = unorm;
+    if (which == UPD_P) kkt_set_static_diag_max(kkt, pmax[2]);
     return CHIP_OK;
 }
 
-namespace {
-// the checks shared by both forms: CHIP_ERR_ARG before any device is touched, k == 0 a no-op (returns 1)
-int bu_args(chip_batch *h, int which, const void *idx, const double *vals, int64_t k) {
-    if (!h || k < 0 || (k > 0 && !vals)) return failb(CHIP_ERR_ARG, std::string(BU_NAME[which]) + ": bad argument");
-    h->upd_syncs = h->upd_launches = 0;
-    if (k == 0) return 1;
-    if (k >= (1ll << 31)) return failb(CHIP_ERR_DIM, std::string(BU_NAME[which]) + ": more than 2^31 values");
-    const int64_t len = which == BU_P ? h->M.nnzP : which == BU_A ? h->M.nnzA : which == BU_Q ? h->n : h->m;
-    if (!idx && k != len)
-        return failb(CHIP_ERR_DIM, std::string(BU_NAME[which]) + ": the full form needs one value per entry");
-    if (idx && len == 0) // (every index is out of range)
-        return failb(CHIP_ERR_DIM, std::string(BU_NAME[which]) + ": an index is out of range (nothing changed)");
-    return 0;
+int chip_batch::update_args(chip_batch *h, int which, const void *idx, const double *vals, int64_t k) {
+    const std::string fn = update_fn(UPD_PREFIX, which);
+    const int64_t len = h ? h->update_len(which) : 0;
+    const int rc = chip::update_args(fn, h, idx, vals, k, len, [&] {
+        h->upd_syncs = h->upd_launches = 0;
+        return 0;
+    });
+    if (rc == 0 && idx && len == 0) // (every index is out of range)
+        return fail(CHIP_ERR_DIM, fn + ": an index is out of range (nothing changed)");
+    return rc;
 }
 
-int bu_host(chip_batch *h, int which, const uint64_t *idx, const double *vals, int64_t k) {
-    int rc = bu_args(h, which, idx, vals, k);
-    if (rc) return rc < 0 ? rc : CHIP_OK;
-    CHIP_HIP(hipSetDevice(h->device));
-    if ((rc = h->grow(&h->stage_v, &h->stage_v_cap, (size_t)k))) return rc;
-    if (idx && (rc = h->grow(&h->stage_i, &h->stage_i_cap, (size_t)k))) return rc;
-    CHIP_HIP(hipMemcpyAsync(h->stage_v, vals, (size_t)k * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    h->upd_launches++;
-    // (an index past 2^63 - 1 reads as negative and is refused like any other out-of-range index)
-    if (idx) {
-        CHIP_HIP(hipMemcpyAsync(h->stage_i, idx, (size_t)k * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-        h->upd_launches++;
-    }
-    return h->update(which, idx ? h->stage_i : nullptr, h->stage_v, (int)k);
-}
-
-int bu_dev(chip_batch *h, int which, const int64_t *idx, const double *vals, int64_t k) {
-    int rc = bu_args(h, which, idx, vals, k);
-    if (rc) return rc < 0 ? rc : CHIP_OK;
-    CHIP_HIP(hipSetDevice(h->device));
-    return h->update(which, idx, vals, (int)k);
-}
-} // namespace
-
-int32_t chip_bdata_update_P(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k) {
-    return bu_host(h, BU_P, index_or_null, values, k);
-}
-int32_t chip_bdata_update_A(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k) {
-    return bu_host(h, BU_A, index_or_null, values, k);
-}
-int32_t chip_bdata_update_q(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k) {
-    return bu_host(h, BU_Q, index_or_null, values, k);
-}
-int32_t chip_bdata_update_b(chip_batch *h, const uint64_t *index_or_null, const double *values, int64_t k) {
-    return bu_host(h, BU_B, index_or_null, values, k);
-}
-int32_t chip_bdata_update_P_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
-    return bu_dev(h, BU_P, index_dev_or_null, values_dev, k);
-}
-int32_t chip_bdata_update_A_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
-    return bu_dev(h, BU_A, index_dev_or_null, values_dev, k);
-}
-int32_t chip_bdata_update_q_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
-    return bu_dev(h, BU_Q, index_dev_or_null, values_dev, k);
-}
-int32_t chip_bdata_update_b_dev(chip_batch *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
-    return bu_dev(h, BU_B, index_dev_or_null, values_dev, k);
-}
+CHIP_UPDATE_ENTRIES(chip_bdata_update_, chip_batch)
 
 // update_settings with validate_as_update (settings.rs:307): the immutable fields of chip_problem_update_settings
 int32_t chip_bdata_update_settings(chip_batch *h, const chip_solver_settings *settings) {
-    if (!h || !settings) return failb(CHIP_ERR_ARG, "chip_bdata_update_settings: bad argument");
+    if (!h || !settings) return fail(CHIP_ERR_ARG, "chip_bdata_update_settings: bad argument");
     chip_solver_settings nw = *settings;
-    nw.linsys.linesearch_backtrack_step = nw.linesearch_backtrack_step;
-    nw.linsys.min_terminate_step_length = nw.min_terminate_step_length;
-    const chip_solver_settings &o = h->st;
-    const chip_settings &a = nw.linsys, &l = o.linsys;
-#define IMMUTABLE(cond, name) \
-    if (cond) return failb(CHIP_ERR_ARG, "chip_bdata_update_settings: " name " cannot change after setup")
-    IMMUTABLE(nw.equilibrate_enable != o.equilibrate_enable, "equilibrate_enable");
-    IMMUTABLE(nw.equilibrate_max_iter != o.equilibrate_max_iter, "equilibrate_max_iter");
-    IMMUTABLE(std::memcmp(&nw.equilibrate_min_scaling, &o.equilibrate_min_scaling, 8), "equilibrate_min_scaling");
-    IMMUTABLE(std::memcmp(&nw.equilibrate_max_scaling, &o.equilibrate_max_scaling, 8), "equilibrate_max_scaling");
-    IMMUTABLE(std::memcmp(&nw.linesearch_backtrack_step, &o.linesearch_backtrack_step, 8), "linesearch_backtrack_step");
-    IMMUTABLE(std::memcmp(&nw.min_terminate_step_length, &o.min_terminate_step_length, 8), "min_terminate_step_length");
-    IMMUTABLE(nw.presolve_enable != o.presolve_enable, "presolve_enable");
-    IMMUTABLE(nw.chordal_decomposition_enable != o.chordal_decomposition_enable, "chordal_decomposition_enable");
-    IMMUTABLE(nw.chordal_decomposition_merge_method != o.chordal_decomposition_merge_method,
-              "chordal_decomposition_merge_method");
-    IMMUTABLE(nw.chordal_decomposition_compact != o.chordal_decomposition_compact, "chordal_decomposition_compact");
-    IMMUTABLE(nw.chordal_decomposition_complete_dual != o.chordal_decomposition_complete_dual,
-              "chordal_decomposition_complete_dual");
-#define IMMUTABLE_LIN(f) IMMUTABLE(std::memcmp(&a.f, &l.f, sizeof(a.f)), "linsys." #f)
-    IMMUTABLE_LIN(static_regularization_enable);
-    IMMUTABLE_LIN(static_regularization_constant);
-    IMMUTABLE_LIN(static_regularization_proportional);
-    IMMUTABLE_LIN(dynamic_regularization_enable);
-    IMMUTABLE_LIN(dynamic_regularization_eps);
-    IMMUTABLE_LIN(dynamic_regularization_delta);
-    IMMUTABLE_LIN(iterative_refinement_enable);
-    IMMUTABLE_LIN(iterative_refinement_reltol);
-    IMMUTABLE_LIN(iterative_refinement_abstol);
-    IMMUTABLE_LIN(iterative_refinement_max_iter);
-    IMMUTABLE_LIN(iterative_refinement_stop_ratio);
-    IMMUTABLE_LIN(device);
-    IMMUTABLE_LIN(amd_dense_scale);
-    IMMUTABLE_LIN(use_graph);
-#undef IMMUTABLE_LIN
-#undef IMMUTABLE
+    if (int rc = validate_settings_update(h->st, nw, "chip_bdata_update_settings")) return rc;
     h->st = nw;
     return CHIP_OK;
 }
 
 int32_t chip_bdata_get_scaled(chip_batch *h, double *Px, double *Ax, double *q, double *b, double *normq,
                               double *normb) {
-    if (!h) return failb(CHIP_ERR_ARG, "chip_bdata_get_scaled: bad argument");
+    if (!h) return fail(CHIP_ERR_ARG, "chip_bdata_get_scaled: bad argument");
     CHIP_HIP(hipSetDevice(h->device));
     CHIP_HIP(hipStreamSynchronize(h->stream));
     if (Px && h->M.nnzP) CHIP_HIP(hipMemcpy(Px, h->M.Px, (size_t)h->M.nnzP * 8, hipMemcpyDeviceToHost));
@@ -1426,13 +1199,13 @@ int chip_batch::backward(const double *gx, const double *gz, const double *gs) {
     grad_syncs++;
     grad_launches += 2;
     if (rc < 0) return rc;
-    if (rc != 1) return failb(CHIP_ERR_ZERO_PIVOT, "chip_bgrad_backward: the factorisation at the final iterate failed");
+    if (rc != 1) return fail(CHIP_ERR_ZERO_PIVOT, "chip_bgrad_backward: the factorisation at the final iterate failed");
     if ((rc = chip_kkt_setrhs_dev(kkt, workx, workz))) return rc;
     rc = chip_kkt_solve_dev(kkt, x1, z1);
     grad_syncs++;
     grad_launches++;
     if (rc < 0) return rc;
-    if (rc != 1) return failb(CHIP_ERR_ZERO_PIVOT, "chip_bgrad_backward: the solve at the final iterate failed");
+    if (rc != 1) return fail(CHIP_ERR_ZERO_PIVOT, "chip_bgrad_backward: the solve at the final iterate failed");
     const dev::BaGrad g{g_valid, x1, z1, gs, d, e, dc, xo, zo, x2, z2, g_dq, g_db, g_dP, g_dA};
     dev::ba_grad_vectors(s, plan, g);
     dev::ba_grad_matrices(s, plan, M, g);
@@ -1446,9 +1219,9 @@ int chip_batch::backward(const double *gx, const double *gz, const double *gs) {
 
 namespace {
 int bg_ready(chip_batch *h, const char *fn) {
-    if (!h) return failb(CHIP_ERR_ARG, std::string(fn) + ": bad argument");
+    if (!h) return fail(CHIP_ERR_ARG, std::string(fn) + ": bad argument");
     if (!h->solve_current)
-        return failb(CHIP_ERR_ARG, std::string(fn) + ": needs a finished chip_batch_solve on the current data");
+        return fail(CHIP_ERR_ARG, std::string(fn) + ": needs a finished chip_batch_solve on the current data");
     return CHIP_OK;
 }
 } // namespace
@@ -1482,8 +1255,8 @@ int32_t chip_bgrad_backward_dev(chip_batch *h, const double *gx_dev, const doubl
 }
 
 int32_t chip_bgrad_get(chip_batch *h, double *dq, double *db, double *dPx, double *dAx, int32_t *valid) {
-    if (!h) return failb(CHIP_ERR_ARG, "chip_bgrad_get: bad argument");
-    if (!h->grad_done) return failb(CHIP_ERR_ARG, "chip_bgrad_get: no chip_bgrad_backward since the last solve");
+    if (!h) return fail(CHIP_ERR_ARG, "chip_bgrad_get: bad argument");
+    if (!h->grad_done) return fail(CHIP_ERR_ARG, "chip_bgrad_get: no chip_bgrad_backward since the last solve");
     CHIP_HIP(hipSetDevice(h->device));
     if (dq && h->n) CHIP_HIP(hipMemcpy(dq, h->g_dq, (size_t)h->n * 8, hipMemcpyDeviceToHost));
     if (db && h->m) CHIP_HIP(hipMemcpy(db, h->g_db, (size_t)h->m * 8, hipMemcpyDeviceToHost));
@@ -1495,8 +1268,8 @@ int32_t chip_bgrad_get(chip_batch *h, double *dq, double *db, double *dPx, doubl
 
 int32_t chip_bgrad_get_dev(chip_batch *h, double **dq_dev, double **db_dev, double **dPx_dev, double **dAx_dev,
                            int32_t **valid_dev) {
-    if (!h) return failb(CHIP_ERR_ARG, "chip_bgrad_get_dev: bad argument");
-    if (!h->grad_done) return failb(CHIP_ERR_ARG, "chip_bgrad_get_dev: no chip_bgrad_backward since the last solve");
+    if (!h) return fail(CHIP_ERR_ARG, "chip_bgrad_get_dev: bad argument");
+    if (!h->grad_done) return fail(CHIP_ERR_ARG, "chip_bgrad_get_dev: no chip_bgrad_backward since the last solve");
     if (dq_dev) *dq_dev = h->g_dq;
     if (db_dev) *db_dev = h->g_db;
     if (dPx_dev) *dPx_dev = h->g_dP;
@@ -1509,14 +1282,14 @@ int32_t chip_bgrad_get_dev(chip_batch *h, double **dq_dev, double **db_dev, doub
 #include "../../include/clarabel_hip_testing.h"
 int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration) {
     chip_batch *h = (chip_batch *)batch;
-    if (!h) return failb(CHIP_ERR_ARG, "chip_debug_batch_inject_nan: bad argument");
+    if (!h) return fail(CHIP_ERR_ARG, "chip_debug_batch_inject_nan: bad argument");
     h->nan_member = member;
     h->nan_iter = iteration;
     return CHIP_OK;
 }
 int32_t chip_debug_batch_counter(void *batch, const char *name, double *out) {
     chip_batch *h = (chip_batch *)batch;
-    if (!h || !name || !out) return failb(CHIP_ERR_ARG, "chip_debug_batch_counter: bad argument");
+    if (!h || !name || !out) return fail(CHIP_ERR_ARG, "chip_debug_batch_counter: bad argument");
     const std::string nm(name);
     if (nm == "host_syncs") *out = (double)h->syncs;
     else if (nm == "launches") *out = (double)h->launches;
@@ -1525,7 +1298,7 @@ int32_t chip_debug_batch_counter(void *batch, const char *name, double *out) {
     else if (nm == "update_host_syncs") *out = (double)h->upd_syncs;
     else if (nm == "backward_launches") *out = (double)h->grad_launches;
     else if (nm == "backward_host_syncs") *out = (double)h->grad_syncs;
-    else return failb(CHIP_ERR_ARG, "chip_debug_batch_counter: unknown name");
+    else return fail(CHIP_ERR_ARG, "chip_debug_batch_counter: unknown name");
     return CHIP_OK;
 }
 #endif

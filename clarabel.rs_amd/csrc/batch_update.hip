@@ -111,9 +111,6 @@ __global__ __launch_bounds__(WG) void k_bu_release(const int64_t *__restrict__ i
     for (int t = blockIdx.x * WG + threadIdx.x; t < k; t += gridDim.x * WG) pos[idx[t]] = -1;
 }
 
-__device__ __forceinline__ unsigned long long bu_abs_bits(double x) {
-    return (unsigned long long)__double_as_longlong(fabs(x));
-}
 // one workgroup per chunk of the plan (chunk0: the first chunk of the space): the maximum of the bits of |raw|
 __global__ __launch_bounds__(WG) void k_bu_norm_partial(const double *__restrict__ raw, const int *__restrict__ ch_beg,
                                                         const int *__restrict__ ch_end, int chunk0,
@@ -122,16 +119,11 @@ __global__ __launch_bounds__(WG) void k_bu_norm_partial(const double *__restrict
     const int ch = chunk0 + blockIdx.x;
     unsigned long long acc = 0;
     for (int i = ch_beg[ch] + threadIdx.x, e = ch_end[ch]; i < e; i += WG) {
-        const unsigned long long v = bu_abs_bits(raw[i]);
+        const unsigned long long v = abs_bits(raw[i]);
         acc = v > acc ? v : acc;
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = WG / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] > red[threadIdx.x + w] ? red[threadIdx.x] : red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partials[ch] = red[0];
+    acc = block_max_u64(acc, red);
+    if (threadIdx.x == 0) partials[ch] = acc;
 }
 // one thread per member: the maximum over its chunks (a member without entries: 0, as create's loop gives)
 __global__ __launch_bounds__(WG) void k_bu_norm_final(const int *__restrict__ cfirst, int chunk0, int nprob,

@@ -19,11 +19,6 @@ namespace {
 
 thread_local std::string g_last;
 
-int fail(int code, const std::string &msg) {
-    set_error(msg);
-    return code;
-}
-
 const i64 *as_i64(const uint64_t *p) { return reinterpret_cast<const i64 *>(p); }
 
 void fill_info(const Engine &E, chip_info *info) {

@@ -269,6 +269,22 @@ __device__ __forceinline__ void fold_norm(unsigned long long *nrm, int *nan, dou
     }
 }
 
+// the bits of |x|: for x that is not NaN they order as unsigned integers the way the values do, so a maximum of
+// magnitudes can be reduced (and taken atomically) on 64-bit words
+__device__ __forceinline__ unsigned long long abs_bits(double x) {
+    return (unsigned long long)__double_as_longlong(fabs(x));
+}
+// the maximum of v over a workgroup of WG threads, in every thread; red: WG words of LDS
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long *red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = WG / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] > red[threadIdx.x + w] ? red[threadIdx.x] : red[threadIdx.x + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
 __device__ __forceinline__ double nanmax(double a, double b) { return (a != a || b != b) ? (a != a ? a : b) : fmax(a, b); }
 
 } // namespace

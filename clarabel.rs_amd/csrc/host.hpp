@@ -282,6 +282,15 @@ int assemble_kkt_triu(i64 n, i64 m, const i64 *Pp, const i64 *Pi, const double *
                       const i64 *Ai, const double *Ax, KktLayout &K);
 
 void set_error(const std::string &msg);
+// records the text chip_last_error returns and hands the code back: `return fail(CHIP_ERR_ARG, "...")`
+inline int fail(int code, const std::string &msg) {
+    set_error(msg);
+    return code;
+}
+// monotonic wall clock in seconds (the timers of the setup and solve figures)
+inline double now_s() {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 
 // CHIP_TIMING=1: wall-clock of the analysis phases on stderr
 struct PhaseClock {

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "host_util.hpp"
 #include "equilibrate.hpp"
 #include "batch.hpp"
 #include "problem_update.hpp"
@@ -18,11 +19,6 @@
 using namespace chip;
 
 namespace {
-
-int failk(int code, const std::string &msg) {
-    set_error(msg);
-    return code;
-}
 
 constexpr int T_MAX = 32, B_MIN = 16384, B_CHUNK = 4096; // same classes as symbolic.cpp
 
@@ -34,27 +30,6 @@ struct SpMat {
     size_t nnz = 0;
     int *t_idx = nullptr, *w_idx = nullptr, *b_row = nullptr, *b_beg = nullptr, *b_end = nullptr, *br_idx = nullptr;
     int nt = 0, nw = 0, nbc = 0, nbr = 0;
-};
-
-struct DevPool {
-    std::vector<void *> allocs;
-    template <typename T> int alloc(T **dst, size_t n) {
-        *dst = nullptr;
-        void *p = nullptr;
-        CHIP_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        allocs.push_back(p);
-        *dst = (T *)p;
-        return CHIP_OK;
-    }
-    template <typename T> int upload(T **dst, const std::vector<T> &src) {
-        int rc = alloc(dst, src.size());
-        if (rc) return rc;
-        if (!src.empty()) CHIP_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-        return CHIP_OK;
-    }
-    ~DevPool() {
-        for (void *p : allocs) (void)hipFree(p);
-    }
 };
 
 int build_spmat(DevPool &pool, SpMat &M, int rows, const std::vector<int> &ptr, const std::vector<int> &idx,
@@ -175,13 +150,13 @@ int32_t chip_kktsystem_create(chip_kktsystem **out, chip_kkt *kkt, const uint64_
                               const double *Anzval, const double *q, const double *b) {
     if (!out || !kkt || !Pcolptr || !Acolptr) return CHIP_ERR_ARG;
     *out = nullptr;
-    if (kkt_host_only(kkt)) return failk(CHIP_ERR_NO_DEVICE, "host-only handle: no numeric work without a GPU");
+    if (kkt_host_only(kkt)) return fail(CHIP_ERR_NO_DEVICE, "host-only handle: no numeric work without a GPU");
     int64_t dims[8];
     int rc = chip_kkt_dims(kkt, dims);
     if (rc) return rc;
     const int64_t n = dims[0], m = dims[1];
     const uint64_t nnzP = Pcolptr[n], nnzA = Acolptr[n];
-    if (nnzP >= (1ull << 31) || nnzA >= (1ull << 31)) return failk(CHIP_ERR_DIM, "nnz out of int32 range");
+    if (nnzP >= (1ull << 31) || nnzA >= (1ull << 31)) return fail(CHIP_ERR_DIM, "nnz out of int32 range");
     if ((nnzP && (!Prowval || !Pnzval)) || (nnzA && (!Arowval || !Anzval)) || (n && !q) || (m && !b))
         return CHIP_ERR_ARG;
     std::unique_ptr<chip_kktsystem> h(new chip_kktsystem());
@@ -199,7 +174,7 @@ int32_t chip_kktsystem_create(chip_kktsystem **out, chip_kkt *kkt, const uint64_
         for (int64_t c = 0; c < n; c++)
             for (uint64_t p = Pcolptr[c]; p < Pcolptr[c + 1]; p++) {
                 const int64_t r = (int64_t)Prowval[p];
-                if (r > c || r < 0) return failk(CHIP_ERR_NOT_TRIU, "P is not upper triangular");
+                if (r > c || r < 0) return fail(CHIP_ERR_NOT_TRIU, "P is not upper triangular");
                 ptr[r + 1]++;
                 if (r != c) ptr[c + 1]++;
             }
@@ -221,7 +196,7 @@ int32_t chip_kktsystem_create(chip_kktsystem **out, chip_kkt *kkt, const uint64_
     {
         std::vector<int> ptr((size_t)m + 1, 0);
         for (uint64_t p = 0; p < nnzA; p++) {
-            if (Arowval[p] >= (uint64_t)m) return failk(CHIP_ERR_DIM, "A row index out of range");
+            if (Arowval[p] >= (uint64_t)m) return fail(CHIP_ERR_DIM, "A row index out of range");
             ptr[Arowval[p] + 1]++;
         }
         for (int64_t i = 0; i < m; i++) ptr[i + 1] += ptr[i];

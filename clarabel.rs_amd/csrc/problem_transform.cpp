@@ -12,7 +12,6 @@
 #include "problem_transform.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <limits>
 #include <map>
@@ -367,10 +366,6 @@ void to_csc(int64_t ncols, std::vector<Triplet> &t, std::vector<uint64_t> &cp, s
         vx[k] = t[k].v;
     }
     for (int64_t j = 0; j < ncols; j++) cp[(size_t)j + 1] += cp[(size_t)j];
-}
-
-double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 } // namespace

@@ -98,18 +98,6 @@ __global__ __launch_bounds__(WG) void k_pu_scatter(double *Kx, const int *__rest
     }
 }
 
-__device__ __forceinline__ unsigned long long abs_bits(double x) {
-    return (unsigned long long)__double_as_longlong(fabs(x));
-}
-__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long *red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = WG / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] > red[threadIdx.x + w] ? red[threadIdx.x] : red[threadIdx.x + w];
-        __syncthreads();
-    }
-    return red[0];
-}
 // blockIdx.y: 0 = |q dinv|, 1 = |b einv|, 2 = |P_ii|
 __global__ __launch_bounds__(WG) void k_pu_norm_partial(int mask, const double *__restrict__ q,
                                                         const double *__restrict__ dinv, int n,

@@ -5,7 +5,6 @@
 //          check_termination / post_process (default/info.rs:80-389) and DefaultSolution::post_process
 //          (default/solution.rs:68-111) on the host: only scalars cross the boundary per iteration.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -14,66 +13,21 @@
 
 #include "engine.hpp"
 #include "equilibrate.hpp"
+#include "host_util.hpp"
+#include "ipm_info.hpp"
 #include "problem_transform.hpp"
 #include "problem_update.hpp"
 
 using namespace chip;
 
 namespace {
-
-int fails(int code, const std::string &msg) {
-    set_error(msg);
-    return code;
-}
-
-double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 enum { PRIMAL_DUAL = 0, DUAL = 1 }; // ScalingStrategy (core/solver.rs:77-80)
-
-struct DevBuf {
-    std::vector<void *> ptrs;
-    template <typename T> int alloc(T **dst, size_t n) {
-        void *p = nullptr;
-        CHIP_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        ptrs.push_back(p);
-        *dst = (T *)p;
-        return CHIP_OK;
-    }
-    template <typename T> int upload(T **dst, const T *src, size_t n) {
-        int rc = alloc(dst, n);
-        if (rc) return rc;
-        if (n) CHIP_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-        return CHIP_OK;
-    }
-    ~DevBuf() {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-};
-
-// the scalars of DefaultInfo (default/info.rs:12-64) the loop reads and writes
-struct InfoState {
-    double cost_primal = 0, cost_dual = 0, res_primal = 0, res_dual = 0, res_primal_inf = 0, res_dual_inf = 0;
-    double gap_abs = 0, gap_rel = 0, ktratio = 0;
-    double prev_cost_primal = 0, prev_cost_dual = 0, prev_res_primal = 0, prev_res_dual = 0, prev_gap_abs = 0,
-           prev_gap_rel = 0;
-    double solve_time = 0;
-    int iterations = 0;
-    int status = CHIP_SOLVER_UNSOLVED;
-};
-
-bool is_infeasible(int s) {
-    return s == CHIP_SOLVER_PRIMAL_INFEASIBLE || s == CHIP_SOLVER_DUAL_INFEASIBLE ||
-           s == CHIP_SOLVER_ALMOST_PRIMAL_INFEASIBLE || s == CHIP_SOLVER_ALMOST_DUAL_INFEASIBLE;
-}
-
 } // namespace
 
 struct chip_solver {
     int n = 0, m = 0, device = 0;
     chip_solver_settings st{};
-    DevBuf mem;
+    DevPool mem;
     // the problem data: patterns in coordinate form, equilibrated values, scalings
     dev::EqMats M{};
     double *q = nullptr, *b = nullptr, *d = nullptr, *e = nullptr, *dinv = nullptr, *einv = nullptr;
@@ -93,23 +47,20 @@ struct chip_solver {
     int32_t *rv_mode = nullptr;
     int64_t *rv_ptr = nullptr, *rv_src = nullptr;
     double transform_time = 0, completion_time = 0;
-    InfoState info;
+    IpmInfo info; // (its out5: r_tau, dot_qx, dot_bz, dot_sz, dot_xPx of the last residual update)
+    double solve_time = 0;
     double setup_time = 0, equilibration_time = 0, iteration_time = 0;
     double obj_val = 0, obj_val_dual = 0;
     bool solved_once = false;
     // the data updates (problem_update.hip), allocated by the first one: host-form staging (grown to the longest
     // update), the last-occurrence scratch (-1 between updates), the index check's flag and the reductions
-    double *stage_v = nullptr;
-    int64_t *stage_i = nullptr;
-    size_t stage_cap = 0;
+    UpdateStage stage;
     int *pos = nullptr, *flag = nullptr;
     unsigned long long *npart = nullptr;
     double *nout = nullptr;
 
     ~chip_solver() {
         if (stream) (void)hipStreamSynchronize(stream);
-        (void)hipFree(stage_v);
-        (void)hipFree(stage_i);
         chip_kktsystem_destroy(sys);
         chip_kkt_destroy(kkt);
     }
@@ -131,13 +82,14 @@ struct chip_solver {
     int equilibrate(const std::vector<ConeSpec> &cones);
     int default_start();
     int residuals_and_info();
-    bool check_termination(int iter);
-    void check_convergence(bool almost);
     int backtrack_step_to_barrier(double alpha_init, double *alpha_out);
     int post_process();
     int update_work();
+    static constexpr const char *UPD_PREFIX = "chip_problem_update_";
+    int64_t update_len(int which) const { return which == UPD_P ? M.nnzP : which == UPD_A ? M.nnzA : which == UPD_Q ? n : m; }
+    static int update_args(chip_solver *h, int which, const void *idx, const double *vals, int64_t k);
+    int stage_upload(const uint64_t *idx, const double *vals, size_t k) { return stage.upload(stream, idx, vals, k); }
     int update(int which, const int64_t *idx_dev, const double *vals_dev, int k);
-    double out5[5] = {0, 0, 0, 0, 0}; // r_tau, dot_qx, dot_bz, dot_sz, dot_xPx of the last residual update
     double t_solve0 = 0;
 };
 
@@ -187,7 +139,7 @@ int chip_solver::equilibrate(const std::vector<ConeSpec> &cones) {
         if (m) CHIP_HIP(hipMemcpy(einv, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
         return CHIP_OK;
     }
-    DevBuf work;
+    DevPool work;
     unsigned long long *bits = nullptr;
     double *partials = nullptr, *cstate = nullptr, *delta = nullptr;
     const size_t nbits = dev::eq_bits_words(n, m);
@@ -226,7 +178,7 @@ int chip_solver::equilibrate(const std::vector<ConeSpec> &cones) {
     if (err == hipSuccess) err = hipGetLastError();
     if (err == hipSuccess) err = hipStreamSynchronize(s);
     (void)hipStreamDestroy(s);
-    if (err != hipSuccess) return fails(CHIP_ERR_HIP, hip_err(err, "equilibrate"));
+    if (err != hipSuccess) return fail(CHIP_ERR_HIP, hip_err(err, "equilibrate"));
     c = hc[0];
     return CHIP_OK;
 }
@@ -237,7 +189,7 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
                            const int64_t *cone_dims, const int64_t *cone_dims2, const double *cone_alphas_or_null,
                            const double *genpow_alphas_or_null, const chip_solver_settings *settings) {
     if (!out || n < 0 || m < 0 || !Pcolptr || !Acolptr || ncones < 0 || (ncones && (!cone_tags || !cone_dims)))
-        return fails(CHIP_ERR_ARG, "chip_solver_create: bad argument");
+        return fail(CHIP_ERR_ARG, "chip_solver_create: bad argument");
     *out = nullptr;
     const double t0 = now_s();
     std::unique_ptr<chip_solver> h(new chip_solver());
@@ -247,16 +199,16 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
     st.linsys.linesearch_backtrack_step = st.linesearch_backtrack_step;
     st.linsys.min_terminate_step_length = st.min_terminate_step_length;
     if (st.linsys.device == CHIP_DEVICE_HOST_ONLY || chip_device_count() < 1)
-        return fails(CHIP_ERR_NO_DEVICE, "chip_solver_create: no HIP device (the product has no CPU fallback)");
+        return fail(CHIP_ERR_NO_DEVICE, "chip_solver_create: no HIP device (the product has no CPU fallback)");
     if ((Pcolptr[n] && (!Prowval || !Pnzval)) || (Acolptr[n] && (!Arowval || !Anzval)) || (n && !q) || (m && !b))
-        return fails(CHIP_ERR_ARG, "chip_solver_create: missing data");
+        return fail(CHIP_ERR_ARG, "chip_solver_create: missing data");
     h->n_out = (int)std::min<int64_t>(n, INT32_MAX);
     h->m_out = (int)std::min<int64_t>(m, INT32_MAX);
     // ---- presolve and chordal decomposition (problemdata.rs:59-165): everything below sees the transformed problem
     if (st.presolve_enable || st.chordal_decomposition_enable) {
-        if (n >= (1ll << 31) || m >= (1ll << 31)) return fails(CHIP_ERR_DIM, "chip_solver_create: sizes out of int32 range");
+        if (n >= (1ll << 31) || m >= (1ll << 31)) return fail(CHIP_ERR_DIM, "chip_solver_create: sizes out of int32 range");
         for (uint64_t k = 0; k < Acolptr[n]; k++)
-            if ((int64_t)Arowval[k] >= m) return fails(CHIP_ERR_DIM, "A row index out of range");
+            if ((int64_t)Arowval[k] >= m) return fail(CHIP_ERR_DIM, "A row index out of range");
         std::unique_ptr<ProblemTransform> tf(new ProblemTransform());
         int rc0 = transform_build(n, m, Pcolptr, Prowval, Pnzval, q, Acolptr, Arowval, Anzval, b, ncones, cone_tags,
                                   cone_dims, cone_dims2, cone_alphas_or_null, transform_options(st), *tf);
@@ -285,12 +237,12 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
     const uint64_t nnzP = Pcolptr[n], nnzA = Acolptr[n];
     // the entry-parallel passes of equilibrate.hip index P and A together, and A with b / e, in int32
     if (nnzP + nnzA + (uint64_t)n + (uint64_t)m >= (1ull << 31) || n + 2 * m >= (1ll << 31))
-        return fails(CHIP_ERR_DIM, "chip_solver_create: sizes out of int32 range");
+        return fail(CHIP_ERR_DIM, "chip_solver_create: sizes out of int32 range");
     std::vector<ConeSpec> cones;
     int64_t mm = 0, p = 0, nHs = 0;
     if (build_cone_specs(ncones, cone_tags, cone_dims, cone_dims2, cones, mm, p, nHs))
-        return fails(CHIP_ERR_ARG, "chip_solver_create: bad cone");
-    if (mm != m) return fails(CHIP_ERR_DIM, "chip_solver_create: cone dimensions do not add up to m");
+        return fail(CHIP_ERR_ARG, "chip_solver_create: bad cone");
+    if (mm != m) return fail(CHIP_ERR_DIM, "chip_solver_create: cone dimensions do not add up to m");
     h->n = (int)n;
     h->m = (int)m;
     if (st.linsys.device >= 0) CHIP_HIP(hipSetDevice(st.linsys.device));
@@ -299,12 +251,12 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
     std::vector<int> Prow(nnzP), Pcol(nnzP), Arow(nnzA), Acol(nnzA);
     for (int64_t j = 0; j < n; j++) {
         for (uint64_t k = Pcolptr[j]; k < Pcolptr[j + 1]; k++) {
-            if ((int64_t)Prowval[k] > j) return fails(CHIP_ERR_NOT_TRIU, "P is not upper triangular");
+            if ((int64_t)Prowval[k] > j) return fail(CHIP_ERR_NOT_TRIU, "P is not upper triangular");
             Prow[k] = (int)Prowval[k];
             Pcol[k] = (int)j;
         }
         for (uint64_t k = Acolptr[j]; k < Acolptr[j + 1]; k++) {
-            if ((int64_t)Arowval[k] >= m) return fails(CHIP_ERR_DIM, "A row index out of range");
+            if ((int64_t)Arowval[k] >= m) return fail(CHIP_ERR_DIM, "A row index out of range");
             Arow[k] = (int)Arowval[k];
             Acol[k] = (int)j;
         }
@@ -316,7 +268,7 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
     for (double v : bcap) nb = std::isnan(v) ? v : std::max(nb, std::fabs(v));
     h->normq = nq;
     h->normb = nb;
-    DevBuf &mem = h->mem;
+    DevPool &mem = h->mem;
     int rc;
     dev::EqMats &M = h->M;
     int *dPr, *dPc, *dAr, *dAc;
@@ -350,7 +302,7 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
     const double *ga = genpow_alphas_or_null;
     for (int64_t i = 0; i < ncones; i++) {
         if (cone_tags[i] == CHIP_CONE_GENPOWER) {
-            if (!ga) return fails(CHIP_ERR_ARG, "chip_solver_create: GenPow cone without its powers");
+            if (!ga) return fail(CHIP_ERR_ARG, "chip_solver_create: GenPow cone without its powers");
             if ((rc = chip_kkt_set_genpow_alpha(h->kkt, i, ga))) return rc;
             ga += cone_dims[i];
         }
@@ -412,68 +364,11 @@ int chip_solver::residuals_and_info() {
     for (int k = 0; k < 8; k++) wn.s[k] = specs[k];
     wn.count = 8;
     double sq[8];
-    int rc = residuals_update_wnorms(sys, &vars, rx, rz, rx_inf, rz_inf, Pxv, out5, &wn, sq);
+    int rc = residuals_update_wnorms(sys, &vars, rx, rz, rx_inf, rz_inf, Pxv, info.out5, &wn, sq);
     if (rc) return rc;
-    double nrm[8];
-    for (int k = 0; k < 8; k++) nrm[k] = std::sqrt(sq[k]);
-    const double tinv = 1.0 / vars.tau, cinv = 1.0 / c;
-    const double dot_qx = out5[1], dot_bz = out5[2], dot_xPx = out5[4];
-    const double xPx2 = dot_xPx * tinv * tinv / 2.0;
-    info.cost_primal = (dot_qx * tinv + xPx2) * cinv;
-    info.cost_dual = (-dot_bz * tinv - xPx2) * cinv;
-    double normx = nrm[0], normz = nrm[1] * cinv, norms = nrm[2];
-    info.res_primal_inf = (nrm[3] * cinv) / std::max(1.0, normz);
-    info.res_dual_inf = std::max(nrm[4] / std::max(1.0, normx), nrm[5] / std::max(1.0, normx + norms));
-    normx *= tinv;
-    normz *= tinv;
-    norms *= tinv;
-    info.res_primal = nrm[6] * tinv / std::max(1.0, normb + normx + norms);
-    info.res_dual = nrm[7] * tinv * cinv / std::max(1.0, normq + normx + normz);
-    info.gap_abs = std::fabs(info.cost_primal - info.cost_dual);
-    info.gap_rel = info.gap_abs / std::max(1.0, std::min(std::fabs(info.cost_primal), std::fabs(info.cost_dual)));
-    info.ktratio = vars.kappa * tinv;
-    info.solve_time = setup_time + (now_s() - t_solve0);
+    ipm_info_update(info, sq, vars.tau, vars.kappa, c, normq, normb);
+    solve_time = setup_time + (now_s() - t_solve0);
     return CHIP_OK;
-}
-
-// check_convergence_full / _almost (info.rs:277-389)
-void chip_solver::check_convergence(bool almost) {
-    const double tga = almost ? st.reduced_tol_gap_abs : st.tol_gap_abs;
-    const double tgr = almost ? st.reduced_tol_gap_rel : st.tol_gap_rel;
-    const double tf = almost ? st.reduced_tol_feas : st.tol_feas;
-    const double tia = almost ? st.reduced_tol_infeas_abs : st.tol_infeas_abs;
-    const double tir = almost ? st.reduced_tol_infeas_rel : st.tol_infeas_rel;
-    const double tkt = almost ? st.reduced_tol_ktratio : st.tol_ktratio;
-    const double dot_qx = out5[1], dot_bz = out5[2];
-    if (info.ktratio <= 1.0 && (info.gap_abs < tga || info.gap_rel < tgr) && info.res_primal < tf && info.res_dual < tf) {
-        info.status = almost ? CHIP_SOLVER_ALMOST_SOLVED : CHIP_SOLVER_SOLVED;
-    } else if (info.ktratio > (1.0 / tkt) * 1000.0) {
-        if (dot_bz < -tia && info.res_primal_inf < -tir * dot_bz)
-            info.status = almost ? CHIP_SOLVER_ALMOST_PRIMAL_INFEASIBLE : CHIP_SOLVER_PRIMAL_INFEASIBLE;
-        else if (dot_qx < -tia && info.res_dual_inf < -tir * dot_qx)
-            info.status = almost ? CHIP_SOLVER_ALMOST_DUAL_INFEASIBLE : CHIP_SOLVER_DUAL_INFEASIBLE;
-    }
-}
-
-// check_termination (info.rs:182-231)
-bool chip_solver::check_termination(int iter) {
-    check_convergence(false);
-    if (info.status == CHIP_SOLVER_UNSOLVED && iter > 1 &&
-        (info.res_dual > info.prev_res_dual || info.res_primal > info.prev_res_primal)) {
-        if (info.ktratio < std::numeric_limits<double>::epsilon() * 100.0 &&
-            (info.prev_gap_abs < st.tol_gap_abs || info.prev_gap_rel < st.tol_gap_rel))
-            info.status = CHIP_SOLVER_INSUFFICIENT_PROGRESS;
-        if (info.ktratio < 1.0) {
-            if ((info.res_dual > st.tol_feas * 100.0 && info.res_dual > info.prev_res_dual * 100.0) ||
-                (info.res_primal > st.tol_feas * 100.0 && info.res_primal > info.prev_res_primal * 100.0))
-                info.status = CHIP_SOLVER_INSUFFICIENT_PROGRESS;
-        }
-    }
-    if (info.status == CHIP_SOLVER_UNSOLVED) {
-        if (st.max_iter == info.iterations) info.status = CHIP_SOLVER_MAX_ITERATIONS;
-        else if (info.solve_time > st.time_limit) info.status = CHIP_SOLVER_MAX_TIME;
-    }
-    return info.status != CHIP_SOLVER_UNSOLVED;
 }
 
 // backtrack_step_to_barrier (core/solver.rs:571-584)
@@ -492,20 +387,14 @@ int chip_solver::backtrack_step_to_barrier(double alpha_init, double *alpha_out)
 
 // info.post_process (info.rs:95-105) + solution.post_process (solution.rs:68-111) with variables.unscale
 int chip_solver::post_process() {
-    const int s = info.status;
-    if (s == CHIP_SOLVER_NUMERICAL_ERROR || s == CHIP_SOLVER_INSUFFICIENT_PROGRESS || s == CHIP_SOLVER_MAX_ITERATIONS ||
-        s == CHIP_SOLVER_MAX_TIME)
-        check_convergence(true);
-    const bool inf = is_infeasible(info.status);
-    obj_val = inf ? std::numeric_limits<double>::quiet_NaN() : info.cost_primal;
-    obj_val_dual = inf ? std::numeric_limits<double>::quiet_NaN() : info.cost_dual;
-    const double scaleinv = inf ? 1.0 / vars.kappa : 1.0 / vars.tau, cinv = 1.0 / c;
+    double scaleinv, scale_z;
+    ipm_post_process(info, st, vars.tau, vars.kappa, c, &obj_val, &obj_val_dual, &scaleinv, &scale_z);
     if (!tf) {
-        dev::unscale(stream, xo, vars.x, d, scaleinv, n, zo, vars.z, e, scaleinv * cinv, so, vars.s, einv, scaleinv, m);
+        dev::unscale(stream, xo, vars.x, d, scaleinv, n, zo, vars.z, e, scale_z, so, vars.s, einv, scaleinv, m);
     } else { // decomp_reverse + reverse_presolve (solution.rs:94-110) in one gather, straight from the scaled variables
         const dev::RvMaps mp{rv_mode, rv_ptr, rv_src};
         dev::transform_reverse(stream, mp, n_out, m_out, xo, vars.x, d, scaleinv, so, vars.s, einv, scaleinv, zo, vars.z,
-                               e, scaleinv * cinv);
+                               e, scale_z);
     }
     CHIP_HIP(hipGetLastError());
     CHIP_HIP(hipStreamSynchronize(stream));
@@ -517,7 +406,7 @@ int chip_solver::post_process() {
         if (m_out) CHIP_HIP(hipMemcpy(zo, zh.data(), (size_t)m_out * 8, hipMemcpyHostToDevice));
         completion_time = now_s() - tc;
     }
-    info.solve_time = setup_time + (now_s() - t_solve0);
+    solve_time = setup_time + (now_s() - t_solve0);
     return CHIP_OK;
 }
 
@@ -525,8 +414,9 @@ int chip_solver::post_process() {
 int32_t chip_solver_solve(chip_solver *h) {
     if (!h) return CHIP_ERR_ARG;
     CHIP_HIP(hipSetDevice(h->device));
-    InfoState &info = h->info;
-    info = InfoState(); // info.reset; the previous-iterate scalars start from the same values on every solve
+    IpmInfo &info = h->info;
+    info = IpmInfo(); // info.reset; the previous-iterate scalars start from the same values on every solve
+    h->solve_time = 0;
     h->t_solve0 = now_s();
     int rc;
     if ((rc = h->default_start()) < 0) return rc;
@@ -539,17 +429,12 @@ int32_t chip_solver_solve(chip_solver *h) {
     const chip_solver_settings &st = h->st;
     while (true) {
         if ((rc = h->residuals_and_info())) return rc;
-        if ((rc = chip_variables_calc_mu(h->sys, &h->vars, h->out5[3], &mu))) return rc;
+        if ((rc = chip_variables_calc_mu(h->sys, &h->vars, info.out5[3], &mu))) return rc;
         info.iterations = iter; // save_scalars
-        if (h->check_termination(iter)) {
+        if (ipm_check_termination(info, st, iter, h->solve_time)) {
             // strategy_checkpoint_insufficient_progress (core/solver.rs:586-608)
             if (info.status != CHIP_SOLVER_INSUFFICIENT_PROGRESS) break;
-            info.cost_primal = info.prev_cost_primal; // reset_to_prev_iterate (info.rs:244-253)
-            info.cost_dual = info.prev_cost_dual;
-            info.res_primal = info.prev_res_primal;
-            info.res_dual = info.prev_res_dual;
-            info.gap_abs = info.prev_gap_abs;
-            info.gap_rel = info.prev_gap_rel;
+            ipm_reset_to_prev(info);
             if ((rc = h->copy_vars(h->vars, h->prev))) return rc;
             if (!sym && scaling == PRIMAL_DUAL) { // Update(s) => {scaling = s; continue}: alpha is kept here
                 info.status = CHIP_SOLVER_UNSOLVED; // (core/solver.rs:322), unlike the two checkpoints below
@@ -573,7 +458,7 @@ int32_t chip_solver_solve(chip_solver *h) {
                 break;
             }
         }
-        if ((rc = chip_variables_affine_step_rhs(h->sys, &h->rhs, h->rx, h->rz, h->out5[0], &h->vars))) return rc;
+        if ((rc = chip_variables_affine_step_rhs(h->sys, &h->rhs, h->rx, h->rz, info.out5[0], &h->vars))) return rc;
         if (ok) {
             rc = chip_kktsystem_solve(h->sys, &h->lhs, &h->rhs, &h->vars, CHIP_STEP_AFFINE);
             if (rc < 0) return rc;
@@ -585,7 +470,7 @@ int32_t chip_solver_solve(chip_solver *h) {
                 return rc;
             sigma = std::pow(1.0 - alpha, 3);
             const double mm = iter > 1 ? 1.0 : alpha;
-            if ((rc = chip_variables_combined_step_rhs(h->sys, &h->rhs, h->rx, h->rz, h->out5[0], &h->vars, &h->lhs,
+            if ((rc = chip_variables_combined_step_rhs(h->sys, &h->rhs, h->rx, h->rz, info.out5[0], &h->vars, &h->lhs,
                                                        sigma, mu, mm)))
                 return rc;
             rc = chip_kktsystem_solve(h->sys, &h->lhs, &h->rhs, &h->vars, CHIP_STEP_COMBINED);
@@ -619,12 +504,7 @@ int32_t chip_solver_solve(chip_solver *h) {
         // save_prev_iterate (info.rs:233-242) + add_step (variables.rs:162-168): the new iterate is written into the
         // previous iterate's buffers (the arithmetic of chip_variables_add_step) and the two sets swap, so keeping the
         // previous iterate costs no copy
-        info.prev_cost_primal = info.cost_primal;
-        info.prev_cost_dual = info.cost_dual;
-        info.prev_res_primal = info.res_primal;
-        info.prev_res_dual = info.res_dual;
-        info.prev_gap_abs = info.gap_abs;
-        info.prev_gap_rel = info.gap_rel;
+        ipm_save_prev(info);
         chip_vars &nv = h->prev, &v = h->vars, &st_ = h->lhs;
         dev::waxpby(h->stream, nv.x, alpha, st_.x, 1.0, v.x, h->n);
         dev::waxpby(h->stream, nv.s, alpha, st_.s, 1.0, v.s, h->m);
@@ -663,7 +543,7 @@ int32_t chip_solver_get_solution(chip_solver *h, double *x, double *s, double *z
         out->obj_val_dual = h->obj_val_dual;
         out->r_prim = h->info.res_primal;
         out->r_dual = h->info.res_dual;
-        out->solve_time = h->info.solve_time;
+        out->solve_time = h->solve_time;
         out->setup_time = h->setup_time;
         out->equilibration_time = h->equilibration_time;
         out->iteration_time = h->iteration_time;
@@ -694,16 +574,6 @@ int32_t chip_solver_get_equilibration(chip_solver *h, double *d, double *e, doub
 // store, the L3 mirrors and vectors, with the norms and max |P_ii| that setup derived from the values.  The host forms
 // upload into the handle's staging and take the device path.
 // ---------------------------------------------------------------------------------------------------------------
-namespace {
-enum { UPD_P = 0, UPD_A = 1, UPD_Q = 2, UPD_B = 3 };
-const char *const UPD_NAME[4] = {"chip_problem_update_P", "chip_problem_update_A", "chip_problem_update_q",
-                                 "chip_problem_update_b"};
-
-int64_t update_len(const chip_solver *h, int which) {
-    return which == UPD_P ? h->M.nnzP : which == UPD_A ? h->M.nnzA : which == UPD_Q ? h->n : h->m;
-}
-} // namespace
-
 int chip_solver::update_work() {
     if (flag) return CHIP_OK;
     const size_t len = (size_t)std::max({M.nnzP, M.nnzA, n, m});
@@ -719,7 +589,7 @@ int chip_solver::update_work() {
 int chip_solver::update(int which, const int64_t *idx_dev, const double *vals_dev, int k) {
     int rc;
     if ((rc = update_work())) return rc;
-    const int64_t len = update_len(this, which);
+    const int64_t len = update_len(which);
     hipStream_t s = stream;
     if (idx_dev) { // the whole index list is checked before anything is written
         int bad = 0;
@@ -728,7 +598,7 @@ int chip_solver::update(int which, const int64_t *idx_dev, const double *vals_de
         CHIP_HIP(hipGetLastError());
         CHIP_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, s));
         CHIP_HIP(hipStreamSynchronize(s));
-        if (bad) return fails(CHIP_ERR_DIM, std::string(UPD_NAME[which]) + ": an index is out of range (nothing changed)");
+        if (bad) return fail(CHIP_ERR_DIM, update_fn(UPD_PREFIX, which) + ": an index is out of range (nothing changed)");
     }
     dev::PuTarget t{};
     switch (which) { // update_P / _A / _q / _b (data_updating.rs:96-170)
@@ -764,86 +634,26 @@ int chip_solver::update(int which, const int64_t *idx_dev, const double *vals_de
     return CHIP_OK;
 }
 
-namespace {
-// the checks shared by both forms: CHIP_ERR_ARG before any device is touched, k == 0 a no-op (returns 1)
-int update_args(chip_solver *h, int which, const void *idx, const double *vals, int64_t k) {
-    if (!h || k < 0 || (k > 0 && !vals)) return fails(CHIP_ERR_ARG, std::string(UPD_NAME[which]) + ": bad argument");
-    if (h->tf) // data_updating.rs: PresolveIsActive / ChordalDecompositionIsActive
-        return fails(CHIP_ERR_UPDATE_NOT_ALLOWED, std::string(UPD_NAME[which]) +
-                                                      ": presolve or chordal decomposition is active (nothing changed)");
-    if (k == 0) return 1;
-    if (k >= (1ll << 31)) return fails(CHIP_ERR_DIM, std::string(UPD_NAME[which]) + ": more than 2^31 values");
-    if (!idx && k != update_len(h, which))
-        return fails(CHIP_ERR_DIM, std::string(UPD_NAME[which]) + ": the full form needs one value per entry");
-    return 0;
+int chip_solver::update_args(chip_solver *h, int which, const void *idx, const double *vals, int64_t k) {
+    const std::string fn = update_fn(UPD_PREFIX, which);
+    return chip::update_args(fn, h, idx, vals, k, h ? h->update_len(which) : 0, [&] {
+        if (h->tf) // data_updating.rs: PresolveIsActive / ChordalDecompositionIsActive
+            return fail(CHIP_ERR_UPDATE_NOT_ALLOWED, fn + ": presolve or chordal decomposition is active (nothing changed)");
+        return 0;
+    });
 }
 
-int update_host(chip_solver *h, int which, const uint64_t *idx, const double *vals, int64_t k) {
-    int rc = update_args(h, which, idx, vals, k);
-    if (rc) return rc < 0 ? rc : CHIP_OK;
-    CHIP_HIP(hipSetDevice(h->device));
-    if ((size_t)k > h->stage_cap) {
-        CHIP_HIP(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->stage_v);
-        (void)hipFree(h->stage_i);
-        h->stage_v = nullptr;
-        h->stage_i = nullptr;
-        h->stage_cap = 0;
-        CHIP_HIP(hipMalloc(&h->stage_v, (size_t)k * sizeof(double)));
-        CHIP_HIP(hipMalloc(&h->stage_i, (size_t)k * sizeof(int64_t)));
-        h->stage_cap = (size_t)k;
-    }
-    CHIP_HIP(hipMemcpyAsync(h->stage_v, vals, (size_t)k * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    // (an index past 2^63 - 1 reads as negative and is refused like any other out-of-range index)
-    if (idx) CHIP_HIP(hipMemcpyAsync(h->stage_i, idx, (size_t)k * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    return h->update(which, idx ? h->stage_i : nullptr, h->stage_v, (int)k);
-}
-
-int update_dev(chip_solver *h, int which, const int64_t *idx, const double *vals, int64_t k) {
-    int rc = update_args(h, which, idx, vals, k);
-    if (rc) return rc < 0 ? rc : CHIP_OK;
-    CHIP_HIP(hipSetDevice(h->device));
-    return h->update(which, idx, vals, (int)k);
-}
-} // namespace
-
-int32_t chip_problem_update_P(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k) {
-    return update_host(h, UPD_P, index_or_null, values, k);
-}
-int32_t chip_problem_update_A(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k) {
-    return update_host(h, UPD_A, index_or_null, values, k);
-}
-int32_t chip_problem_update_q(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k) {
-    return update_host(h, UPD_Q, index_or_null, values, k);
-}
-int32_t chip_problem_update_b(chip_solver *h, const uint64_t *index_or_null, const double *values, int64_t k) {
-    return update_host(h, UPD_B, index_or_null, values, k);
-}
-int32_t chip_problem_update_P_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
-    return update_dev(h, UPD_P, index_dev_or_null, values_dev, k);
-}
-int32_t chip_problem_update_A_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
-    return update_dev(h, UPD_A, index_dev_or_null, values_dev, k);
-}
-int32_t chip_problem_update_q_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
-    return update_dev(h, UPD_Q, index_dev_or_null, values_dev, k);
-}
-int32_t chip_problem_update_b_dev(chip_solver *h, const int64_t *index_dev_or_null, const double *values_dev, int64_t k) {
-    return update_dev(h, UPD_B, index_dev_or_null, values_dev, k);
-}
+CHIP_UPDATE_ENTRIES(chip_problem_update_, chip_solver)
 
 // DefaultSolver::update_settings (core/solver.rs:207) with validate_as_update (settings.rs:307): the equilibration
 // fields as in the reference, and every field chip_kkt keeps its own copy of (all of linsys, with the two line-search
 // fields create copies into it)
-int32_t chip_problem_update_settings(chip_solver *h, const chip_solver_settings *settings) {
-    if (!h || !settings) return fails(CHIP_ERR_ARG, "chip_problem_update_settings: bad argument");
-    chip_solver_settings nw = *settings;
+int chip::validate_settings_update(const chip_solver_settings &o, chip_solver_settings &nw, const char *fn) {
     nw.linsys.linesearch_backtrack_step = nw.linesearch_backtrack_step;
     nw.linsys.min_terminate_step_length = nw.min_terminate_step_length;
-    const chip_solver_settings &o = h->st;
     const chip_settings &a = nw.linsys, &l = o.linsys;
 #define IMMUTABLE(cond, name) \
-    if (cond) return fails(CHIP_ERR_ARG, "chip_problem_update_settings: " name " cannot change after setup")
+    if (cond) return fail(CHIP_ERR_ARG, std::string(fn) + ": " name " cannot change after setup")
     IMMUTABLE(nw.equilibrate_enable != o.equilibrate_enable, "equilibrate_enable");
     IMMUTABLE(nw.equilibrate_max_iter != o.equilibrate_max_iter, "equilibrate_max_iter");
     IMMUTABLE(std::memcmp(&nw.equilibrate_min_scaling, &o.equilibrate_min_scaling, 8), "equilibrate_min_scaling");
@@ -874,18 +684,25 @@ int32_t chip_problem_update_settings(chip_solver *h, const chip_solver_settings 
     IMMUTABLE_LIN(use_graph);
 #undef IMMUTABLE_LIN
 #undef IMMUTABLE
+    return CHIP_OK;
+}
+
+int32_t chip_problem_update_settings(chip_solver *h, const chip_solver_settings *settings) {
+    if (!h || !settings) return fail(CHIP_ERR_ARG, "chip_problem_update_settings: bad argument");
+    chip_solver_settings nw = *settings;
+    if (int rc = validate_settings_update(h->st, nw, "chip_problem_update_settings")) return rc;
     h->st = nw;
     return CHIP_OK;
 }
 
 int32_t chip_problem_update_allowed(const chip_solver *h, int32_t *allowed) {
-    if (!h || !allowed) return fails(CHIP_ERR_ARG, "chip_problem_update_allowed: bad argument");
+    if (!h || !allowed) return fail(CHIP_ERR_ARG, "chip_problem_update_allowed: bad argument");
     *allowed = h->tf ? 0 : 1; // an enabled transform that changed nothing keeps updates allowed (the reference's Option)
     return CHIP_OK;
 }
 
 int32_t chip_problem_get_scaled(chip_solver *h, double *Px, double *Ax, double *q, double *b) {
-    if (!h) return fails(CHIP_ERR_ARG, "chip_problem_get_scaled: bad argument");
+    if (!h) return fail(CHIP_ERR_ARG, "chip_problem_get_scaled: bad argument");
     CHIP_HIP(hipSetDevice(h->device));
     CHIP_HIP(hipStreamSynchronize(h->stream));
     if (Px && h->M.nnzP) CHIP_HIP(hipMemcpy(Px, h->M.Px, (size_t)h->M.nnzP * 8, hipMemcpyDeviceToHost));
@@ -896,7 +713,7 @@ int32_t chip_problem_get_scaled(chip_solver *h, double *Px, double *Ax, double *
 }
 
 int32_t chip_transform_get_info(const chip_solver *h, chip_transform_info *out) {
-    if (!h || !out) return fails(CHIP_ERR_ARG, "chip_transform_get_info: bad argument");
+    if (!h || !out) return fail(CHIP_ERR_ARG, "chip_transform_get_info: bad argument");
     std::memset(out, 0, sizeof(*out));
     const ProblemTransform *t = h->tf.get();
     out->m_full = h->m_out;
@@ -917,13 +734,13 @@ int32_t chip_transform_get_info(const chip_solver *h, chip_transform_info *out) 
 #include "../../include/clarabel_hip_testing.h"
 int32_t chip_debug_solver_internal_solution(void *solver, double *x2, double *s2, double *z2) {
     chip_solver *h = (chip_solver *)solver;
-    if (!h) return fails(CHIP_ERR_ARG, "chip_debug_solver_internal_solution: bad argument");
+    if (!h) return fail(CHIP_ERR_ARG, "chip_debug_solver_internal_solution: bad argument");
     CHIP_HIP(hipSetDevice(h->device));
     const int n = h->n, m = h->m;
-    const bool inf = is_infeasible(h->info.status);
+    const bool inf = ipm_is_infeasible(h->info.status);
     const chip_vars &v = h->vars;
     const double scaleinv = inf ? 1.0 / v.kappa : 1.0 / v.tau, cinv = 1.0 / h->c;
-    DevBuf tmp;
+    DevPool tmp;
     double *xo, *so, *zo;
     int rc;
     if ((rc = tmp.alloc(&xo, (size_t)n)) || (rc = tmp.alloc(&so, (size_t)m)) || (rc = tmp.alloc(&zo, (size_t)m)))
@@ -934,6 +751,41 @@ int32_t chip_debug_solver_internal_solution(void *solver, double *x2, double *s2
     if (x2 && n) CHIP_HIP(hipMemcpy(x2, xo, (size_t)n * 8, hipMemcpyDeviceToHost));
     if (s2 && m) CHIP_HIP(hipMemcpy(s2, so, (size_t)m * 8, hipMemcpyDeviceToHost));
     if (z2 && m) CHIP_HIP(hipMemcpy(z2, zo, (size_t)m * 8, hipMemcpyDeviceToHost));
+    return CHIP_OK;
+}
+
+namespace {
+// the flat form of an IpmInfo the two hooks below exchange (clarabel_hip_testing.h): these 15 scalars, then out5
+constexpr double IpmInfo::*IPM_FIELD[15] = {
+    &IpmInfo::cost_primal,      &IpmInfo::cost_dual,      &IpmInfo::res_primal,      &IpmInfo::res_dual,
+    &IpmInfo::res_primal_inf,   &IpmInfo::res_dual_inf,   &IpmInfo::gap_abs,         &IpmInfo::gap_rel,
+    &IpmInfo::ktratio,          &IpmInfo::prev_cost_primal, &IpmInfo::prev_cost_dual, &IpmInfo::prev_res_primal,
+    &IpmInfo::prev_res_dual,    &IpmInfo::prev_gap_abs,   &IpmInfo::prev_gap_rel};
+IpmInfo ipm_from_flat(const double *info) {
+    IpmInfo I;
+    for (int k = 0; k < 15; k++) I.*IPM_FIELD[k] = info[k];
+    std::copy(info + 15, info + 20, I.out5);
+    return I;
+}
+} // namespace
+int32_t chip_debug_ipm_termination(const void *solver_settings, const double *info, int32_t iter, int32_t iterations,
+                                   double solve_time, int32_t almost_post_process) {
+    if (!solver_settings || !info) return fail(CHIP_ERR_ARG, "chip_debug_ipm_termination: bad argument");
+    const chip_solver_settings &st = *(const chip_solver_settings *)solver_settings;
+    IpmInfo I = ipm_from_flat(info);
+    I.status = (int)info[20];
+    I.iterations = iterations;
+    double unused[4];
+    if (almost_post_process) ipm_post_process(I, st, 1.0, 1.0, 1.0, &unused[0], &unused[1], &unused[2], &unused[3]);
+    else ipm_check_termination(I, st, iter, solve_time);
+    return I.status;
+}
+int32_t chip_debug_ipm_info_update(double *info, const double *sq, double tau, double kappa, double c, double normq,
+                                   double normb) {
+    if (!info || !sq) return fail(CHIP_ERR_ARG, "chip_debug_ipm_info_update: bad argument");
+    IpmInfo I = ipm_from_flat(info);
+    ipm_info_update(I, sq, tau, kappa, c, normq, normb);
+    for (int k = 0; k < 9; k++) info[k] = I.*IPM_FIELD[k];
     return CHIP_OK;
 }
 #endif

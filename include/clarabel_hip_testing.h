@@ -49,6 +49,18 @@ int32_t chip_debug_transform_reverse(const void *h, const double *x2, const doub
 /* the internal variables of a chip_solver's last solve unscaled (dev::unscale's arithmetic): x2[n_internal],
  * s2[m_internal], z2[m_internal] (any may be NULL) */
 int32_t chip_debug_solver_internal_solution(void *solver, double *x2, double *s2, double *z2);
+/* ---- the interior-point loop's scalar logic (csrc/ipm_info.hpp), host only: no device is touched ----
+ * info[21]: cost_primal, cost_dual, res_primal, res_dual, res_primal_inf, res_dual_inf, gap_abs, gap_rel, ktratio; the six
+ * prev_ scalars in the same order (cost_primal .. gap_rel); r_tau, q'x, b'z, s'z, x'Px of the residuals; the status.
+ * chip_debug_ipm_termination returns the status after check_termination at iteration `iter` of an info with those
+ * scalars whose iteration count is `iterations` and whose solve time so far is `solve_time` (almost_post_process == 0),
+ * or after post_process alone (!= 0); CHIP_ERR_ARG (negative) for a NULL argument.
+ * chip_debug_ipm_info_update: DefaultInfo::update from the SQUARED weighted norms sq[8] of (x, d), (z, e), (s, einv),
+ * (rx_inf, dinv), (Px, dinv), (rz_inf, einv), (rz, einv), (rx, dinv) and the dots in info[15..19]; writes info[0..8]. */
+int32_t chip_debug_ipm_termination(const void *solver_settings, const double *info, int32_t iter, int32_t iterations,
+                                   double solve_time, int32_t almost_post_process);
+int32_t chip_debug_ipm_info_update(double *info, const double *sq, double tau, double kappa, double c, double normq,
+                                   double normb);
 /* ---- the batched solver (csrc/batch.cpp) ----
  * chip_debug_batch_inject_nan: at the start of iteration `iteration` of the next solves, before the residual pass and
  * the pre-update check, z[first row of member `member`] of the stacked iterate becomes NaN (member < 0: off).
