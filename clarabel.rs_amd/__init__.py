@@ -1351,6 +1351,152 @@ class TransformDebug:
         return x, s, z
 
 
+class BatchPlanDebug:
+    """the partition of the batched solver alone (chip_debug_bplan_*; test hooks of include/clarabel_hip_testing.h: a
+    library built with TESTING=1), and one launch of each device pass of csrc/batch.hpp on host arrays.  n_part /
+    m_part: the members' columns / rows; cones: (tag, dim) tuples in row order.  Creating it and get() need no GPU;
+    the first pass uploads the plan.  Every pass returns copies and leaves its arguments alone, except where an
+    argument IS the output (blin's w, bunit_shift's z, bunit_reset's x / s / z: updated in place and returned)."""
+
+    NAMES = ("xoff", "zoff", "xmem", "zmem", "ch_beg", "ch_end", "cx_first", "cz_first", "it_beg", "it_end", "it_type",
+             "it_first", "rtype")
+    SEG_DOT, SEG_WSQ, SEG_SUM, SEG_NONFINITE = range(4)
+    CONE_STEP, CONE_MARGINS, CONE_INTERIOR = range(3)
+    MASK_ZERO, MASK_Y, MASK_KEEP = range(3)
+    ROW_ZERO, ROW_NN, ROW_SOC_HEAD, ROW_SOC_TAIL = range(4)
+    ITEM_NN, ITEM_SOC = range(2)
+    CHUNK, SEG_MAX = 4096, 16
+
+    def __init__(self, n_part, m_part, cones):
+        n_part = np.ascontiguousarray(n_part, dtype=np.int64)
+        m_part = np.ascontiguousarray(m_part, dtype=np.int64)
+        tags, dims, _, _ = _cone_arrays(cones)
+        self._h = C.c_void_p()
+        _check(lib().chip_debug_bplan_create(C.byref(self._h), C.c_int64(len(n_part)), n_part.ctypes.data_as(P_I64),
+                                             m_part.ctypes.data_as(P_I64), C.c_int64(len(tags)),
+                                             tags.ctypes.data_as(P_I32), dims.ctypes.data_as(P_I64)),
+               "chip_debug_bplan_create")
+        self.nprob, self.n, self.m, self.ncx, self.ncz, self.nitems = [int(v) for v in self.get("sizes")]
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().chip_debug_bplan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def get(self, name):
+        n = C.c_int64()
+        L = lib()
+        _check(L.chip_debug_bplan_get(self._h, name.encode(), C.byref(n), None), "chip_debug_bplan_get")
+        out = np.zeros(n.value, dtype=np.int32)
+        _check(L.chip_debug_bplan_get(self._h, name.encode(), C.byref(n), out.ctypes.data_as(P_I32)),
+               "chip_debug_bplan_get")
+        return out
+
+    def _vec(self, a, length, what, null_ok=False, dtype=f64):
+        if a is None:
+            if not null_ok:
+                raise ValueError("%s is required" % what)
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.shape != (length,):
+            raise ValueError("%s must have %d entries" % (what, length))
+        return a
+
+    @staticmethod
+    def _p(a, ptr=P_F64):
+        return None if a is None else a.ctypes.data_as(ptr)
+
+    def seg_reduce(self, specs, nslots, fill=0.0):
+        """specs: up to SEG_MAX tuples (kind, space, slot, a, b or None) -> out[nslots, nprob], `fill` where no spec
+        wrote.  Specs that name the same array object share one device buffer."""
+        cnt = len(specs)
+        kind = np.array([s[0] for s in specs], dtype=np.int32)
+        space = np.array([s[1] for s in specs], dtype=np.int32)
+        slot = np.array([s[2] for s in specs], dtype=np.int32)
+        keep = {}  # one contiguous copy per distinct array object
+
+        def arr(v, sp_, what):
+            if v is None:
+                return None
+            if id(v) not in keep:
+                keep[id(v)] = (v, self._vec(v, self.m if sp_ else self.n, what))
+            return keep[id(v)][1]
+        av = [arr(s[3], s[1], "a") for s in specs]
+        bv = [arr(s[4], s[1], "b") for s in specs]
+        pa = (C.c_void_p * max(cnt, 1))(*[None if v is None else v.ctypes.data for v in av])
+        pb = (C.c_void_p * max(cnt, 1))(*[None if v is None else v.ctypes.data for v in bv])
+        out = np.full((nslots, self.nprob), fill, dtype=f64)
+        _check(lib().chip_debug_bplan_seg_reduce(self._h, C.c_int32(cnt), self._p(kind, P_I32), self._p(space, P_I32),
+                                                 self._p(slot, P_I32), pa, pb, C.c_int32(nslots), _pf(out)),
+               "chip_debug_bplan_seg_reduce")
+        return out
+
+    def cone_minima(self, op, z, sv=None, dz=None, ds=None, amax=None, want_sum=True):
+        """-> (out_min[nprob], out_sum[nprob] or None)"""
+        m, k = self.m, self.nprob
+        z, sv = self._vec(z, m, "z"), self._vec(sv, m, "sv", True)
+        dz, ds = self._vec(dz, m, "dz", True), self._vec(ds, m, "ds", True)
+        amax = self._vec(amax, k, "amax", True)
+        omin = np.full(k, np.nan)
+        osum = np.full(k, np.nan) if want_sum else None
+        _check(lib().chip_debug_bplan_cone_minima(self._h, C.c_int32(op), self._p(dz), self._p(ds), self._p(z),
+                                                  self._p(sv), self._p(amax), _pf(omin), self._p(osum)),
+               "chip_debug_bplan_cone_minima")
+        return omin, osum
+
+    def blin(self, w, x, y=None, sa=None, sb=None, ca=0.0, cb=0.0, space=0, mask=None, mask_mode=0):
+        """w (a float64 array, updated in place) = a_k x + b_k y; pass w itself as x or y to alias them"""
+        ln, k = (self.m if space else self.n), self.nprob
+        if not (isinstance(w, np.ndarray) and w.dtype == f64 and w.flags.c_contiguous and w.shape == (ln,)):
+            raise ValueError("w must be a contiguous float64 array of %d entries" % ln)
+        xv = w if x is w else self._vec(x, ln, "x")
+        yv = w if y is w else self._vec(y, ln, "y", True)
+        sa, sb = self._vec(sa, k, "sa", True), self._vec(sb, k, "sb", True)
+        mask = self._vec(mask, k, "mask", True, np.int32)
+        _check(lib().chip_debug_bplan_blin(self._h, _pf(w), _pf(xv), self._p(yv), self._p(sa), self._p(sb),
+                                           C.c_double(ca), C.c_double(cb), C.c_int32(space), self._p(mask, P_I32),
+                                           C.c_int32(mask_mode)), "chip_debug_bplan_blin")
+        return w
+
+    def bresid(self, rx_inf, Px, q, rz_inf, b, tau):
+        """-> (rx, rz)"""
+        n, m = self.n, self.m
+        rx, rz = np.full(n, np.nan), np.full(m, np.nan)
+        _check(lib().chip_debug_bplan_bresid(self._h, _pf(rx), _pf(self._vec(rx_inf, n, "rx_inf")),
+                                             _pf(self._vec(Px, n, "Px")), _pf(self._vec(q, n, "q")), _pf(rz),
+                                             _pf(self._vec(rz_inf, m, "rz_inf")), _pf(self._vec(b, m, "b")),
+                                             _pf(self._vec(tau, self.nprob, "tau"))), "chip_debug_bplan_bresid")
+        return rx, rz
+
+    def bunit_shift(self, z, alpha, primal, mask=None):
+        """z (copied) += alpha_k e -> the new z"""
+        z = self._vec(z, self.m, "z").copy()
+        mask = self._vec(mask, self.nprob, "mask", True, np.int32)
+        _check(lib().chip_debug_bplan_bunit_shift(self._h, _pf(z), _pf(self._vec(alpha, self.nprob, "alpha")),
+                                                  C.c_int32(primal), self._p(mask, P_I32)),
+               "chip_debug_bplan_bunit_shift")
+        return z
+
+    def bunit_reset(self, x, sv, z, flag):
+        """-> the new (x, s, z) (copies)"""
+        x, sv, z = self._vec(x, self.n, "x").copy(), self._vec(sv, self.m, "sv").copy(), self._vec(z, self.m, "z").copy()
+        flag = self._vec(flag, self.nprob, "flag", False, np.int32)
+        _check(lib().chip_debug_bplan_bunit_reset(self._h, _pf(x), _pf(sv), _pf(z), self._p(flag, P_I32)),
+               "chip_debug_bplan_bunit_reset")
+        return x, sv, z
+
+    def bunscale(self, x, d, z, e, sv, einv, sx, sz):
+        """-> (xo, zo, so)"""
+        n, m, k = self.n, self.m, self.nprob
+        xo, zo, so = np.full(n, np.nan), np.full(m, np.nan), np.full(m, np.nan)
+        _check(lib().chip_debug_bplan_bunscale(self._h, _pf(xo), _pf(self._vec(x, n, "x")), _pf(self._vec(d, n, "d")),
+                                               _pf(zo), _pf(self._vec(z, m, "z")), _pf(self._vec(e, m, "e")), _pf(so),
+                                               _pf(self._vec(sv, m, "sv")), _pf(self._vec(einv, m, "einv")),
+                                               _pf(self._vec(sx, k, "sx")), _pf(self._vec(sz, k, "sz"))),
+               "chip_debug_bplan_bunscale")
+        return xo, zo, so
+
+
 def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
 

@@ -36,6 +36,127 @@ enum { M_ACTIVE, M_QP, M_LP, M_SEL, M_SEL2, M_COUNT };
 enum { R_QX, R_XPX, R_NX, R_NRXI, R_NPX, R_NRX, R_BADX, R_BZ, R_SZ, R_NZ, R_NS, R_NRZI, R_NRZ, R_BADSZ, R_COUNT };
 // the direction passes
 enum { D_QX1, D_BZ1, D_XIPX1, D_DPD, D_BAD, D_COUNT };
+
+// the fixed partition of a batch on the host (dev::BatchPlan, batch.hpp, is its device copy), with what the cones give
+// per member.  parts_ok: the parts themselves were accepted, so xoff / zoff / xmem / zmem are filled even when a cone
+// was refused after them
+struct HostPlan {
+    int nprob = 0, n = 0, m = 0, ncx = 0, ncz = 0;
+    std::vector<int> xoff, zoff, xmem, zmem, ch_beg, ch_end, cx_first, cz_first, it_beg, it_end, it_type, it_first, rtype;
+    std::vector<int64_t> degree;
+    std::vector<char> has_soc;
+    std::vector<ConeSpec> cones;
+    bool parts_ok = false;
+};
+
+int batch_cones_supported(int64_t ncones, const int32_t *cone_tags) {
+    for (int64_t i = 0; i < ncones; i++)
+        if (cone_tags[i] != CHIP_CONE_ZERO && cone_tags[i] != CHIP_CONE_NONNEGATIVE &&
+            cone_tags[i] != CHIP_CONE_SECONDORDER)
+            return fail(CHIP_ERR_UNSUPPORTED, "chip_batch_create: only Zero, Nonnegative and SecondOrder cones");
+    return CHIP_OK;
+}
+
+// the partition of nprob members with n_part[k] columns and m_part[k] rows (sizes already within int32), and the
+// checks that the parts add up and that every cone stays inside its member
+int host_plan_build(HostPlan &hp, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n, int64_t m,
+                    int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims, const int64_t *cone_dims2) {
+    const int np = (int)nprob;
+    hp.nprob = np;
+    hp.n = (int)n;
+    hp.m = (int)m;
+    std::vector<int> &xoff = hp.xoff, &zoff = hp.zoff, &xmem = hp.xmem, &zmem = hp.zmem;
+    xoff.assign((size_t)np + 1, 0);
+    zoff.assign((size_t)np + 1, 0);
+    for (int k = 0; k < np; k++) {
+        if (n_part[k] < 0 || m_part[k] < 0) return fail(CHIP_ERR_ARG, "chip_batch_create: negative part");
+        const int64_t xn = (int64_t)xoff[k] + n_part[k], zn = (int64_t)zoff[k] + m_part[k];
+        if (xn > n || zn > m) return fail(CHIP_ERR_ARG, "chip_batch_create: the parts exceed n or m");
+        xoff[k + 1] = (int)xn;
+        zoff[k + 1] = (int)zn;
+    }
+    if (xoff[np] != n || zoff[np] != m) return fail(CHIP_ERR_ARG, "chip_batch_create: the parts do not add up to n, m");
+    xmem.assign((size_t)n, 0);
+    zmem.assign((size_t)m, 0);
+    for (int k = 0; k < np; k++) {
+        for (int j = xoff[k]; j < xoff[k + 1]; j++) xmem[j] = k;
+        for (int i = zoff[k]; i < zoff[k + 1]; i++) zmem[i] = k;
+    }
+    hp.parts_ok = true;
+    int64_t mm = 0, pdim = 0, nHs = 0;
+    if (build_cone_specs(ncones, cone_tags, cone_dims, cone_dims2, hp.cones, mm, pdim, nHs))
+        return fail(CHIP_ERR_ARG, "chip_batch_create: bad cone");
+    if (mm != m) return fail(CHIP_ERR_DIM, "chip_batch_create: cone dimensions do not add up to m");
+    hp.rtype.assign((size_t)m, dev::ROW_ZERO);
+    hp.degree.assign((size_t)np, 0);
+    hp.has_soc.assign((size_t)np, 0);
+    std::vector<int> &it_beg = hp.it_beg, &it_end = hp.it_end, &it_type = hp.it_type, it_mem;
+    for (const ConeSpec &cs : hp.cones) {
+        if (cs.numel == 0) continue;
+        const int r0 = (int)cs.start, r1 = (int)(cs.start + cs.numel), k = zmem[r0];
+        if (zmem[r1 - 1] != k) return fail(CHIP_ERR_ARG, "chip_batch_create: a cone crosses a member's rows");
+        if (cs.tag == CHIP_CONE_NONNEGATIVE) {
+            for (int i = r0; i < r1; i++) hp.rtype[i] = dev::ROW_NN;
+            hp.degree[k] += cs.numel;
+            for (int i = r0; i < r1; i += dev::BATCH_CHUNK) {
+                it_beg.push_back(i);
+                it_end.push_back(std::min(r1, i + dev::BATCH_CHUNK));
+                it_type.push_back(dev::ITEM_NN);
+                it_mem.push_back(k);
+            }
+        } else if (cs.tag == CHIP_CONE_SECONDORDER) {
+            hp.has_soc[k] = 1;
+            hp.rtype[r0] = dev::ROW_SOC_HEAD;
+            for (int i = r0 + 1; i < r1; i++) hp.rtype[i] = dev::ROW_SOC_TAIL;
+            hp.degree[k] += 1;
+            it_beg.push_back(r0);
+            it_end.push_back(r1);
+            it_type.push_back(dev::ITEM_SOC);
+            it_mem.push_back(k);
+        }
+    }
+    // cones are in row order, so the items are sorted by member
+    hp.it_first.assign((size_t)np + 1, 0);
+    for (int k : it_mem) hp.it_first[k + 1]++;
+    for (int k = 0; k < np; k++) hp.it_first[k + 1] += hp.it_first[k];
+    std::vector<int> &ch_beg = hp.ch_beg, &ch_end = hp.ch_end;
+    hp.cx_first.assign((size_t)np + 1, 0);
+    hp.cz_first.assign((size_t)np + 1, 0);
+    for (int k = 0; k < np; k++) {
+        for (int j = xoff[k]; j < xoff[k + 1]; j += dev::BATCH_CHUNK) {
+            ch_beg.push_back(j);
+            ch_end.push_back(std::min(xoff[k + 1], j + dev::BATCH_CHUNK));
+        }
+        hp.cx_first[k + 1] = (int)ch_beg.size();
+    }
+    hp.ncx = (int)ch_beg.size();
+    for (int k = 0; k < np; k++) {
+        for (int i = zoff[k]; i < zoff[k + 1]; i += dev::BATCH_CHUNK) {
+            ch_beg.push_back(i);
+            ch_end.push_back(std::min(zoff[k + 1], i + dev::BATCH_CHUNK));
+        }
+        hp.cz_first[k + 1] = (int)ch_beg.size() - hp.ncx;
+    }
+    hp.ncz = (int)ch_beg.size() - hp.ncx;
+    return CHIP_OK;
+}
+
+// the device copy of a HostPlan, owned by `mem`
+int host_plan_upload(DevPool &mem, const HostPlan &hp, dev::BatchPlan *pl) {
+    int rc;
+    int *d_xoff, *d_zoff, *d_xmem, *d_zmem, *d_chb, *d_che, *d_cxf, *d_czf, *d_itb, *d_ite, *d_itt, *d_itf, *d_rt;
+    if ((rc = mem.upload(&d_xoff, hp.xoff)) || (rc = mem.upload(&d_zoff, hp.zoff)) ||
+        (rc = mem.upload(&d_xmem, hp.xmem)) || (rc = mem.upload(&d_zmem, hp.zmem)) ||
+        (rc = mem.upload(&d_chb, hp.ch_beg)) || (rc = mem.upload(&d_che, hp.ch_end)) ||
+        (rc = mem.upload(&d_cxf, hp.cx_first)) || (rc = mem.upload(&d_czf, hp.cz_first)) ||
+        (rc = mem.upload(&d_itb, hp.it_beg)) || (rc = mem.upload(&d_ite, hp.it_end)) ||
+        (rc = mem.upload(&d_itt, hp.it_type)) || (rc = mem.upload(&d_itf, hp.it_first)) ||
+        (rc = mem.upload(&d_rt, hp.rtype)))
+        return rc;
+    *pl = dev::BatchPlan{hp.nprob, hp.n, hp.m, d_xoff, d_zoff, d_xmem, d_zmem, d_chb,  d_che, d_cxf,
+                         d_czf,    hp.ncx, hp.ncz, d_itb, d_ite, d_itt, d_itf, (int)hp.it_beg.size(), d_rt};
+    return CHIP_OK;
+}
 } // namespace
 
 struct chip_batch {
@@ -257,10 +378,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     st.linsys.min_terminate_step_length = st.min_terminate_step_length;
     if (st.presolve_enable || st.chordal_decomposition_enable)
         return fail(CHIP_ERR_UNSUPPORTED, "chip_batch_create: presolve and chordal decomposition are not supported");
-    for (int64_t i = 0; i < ncones; i++)
-        if (cone_tags[i] != CHIP_CONE_ZERO && cone_tags[i] != CHIP_CONE_NONNEGATIVE &&
-            cone_tags[i] != CHIP_CONE_SECONDORDER)
-            return fail(CHIP_ERR_UNSUPPORTED, "chip_batch_create: only Zero, Nonnegative and SecondOrder cones");
+    if (int rc = batch_cones_supported(ncones, cone_tags)) return rc;
     if (nprob >= (1ll << 31)) return fail(CHIP_ERR_DIM, "chip_batch_create: sizes out of int32 range");
     const uint64_t nnzP = Pcolptr[n], nnzA = Acolptr[n];
     if (n >= (1ll << 31) || m >= (1ll << 31) || nnzP + nnzA + (uint64_t)n + (uint64_t)m >= (1ull << 31) ||
@@ -268,20 +386,10 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
         return fail(CHIP_ERR_DIM, "chip_batch_create: sizes out of int32 range");
     // ---- the partition and the checks that every entry and cone stays inside its member
     const int np = (int)nprob;
-    std::vector<int> xoff((size_t)np + 1, 0), zoff((size_t)np + 1, 0);
-    for (int k = 0; k < np; k++) {
-        if (n_part[k] < 0 || m_part[k] < 0) return fail(CHIP_ERR_ARG, "chip_batch_create: negative part");
-        const int64_t xn = (int64_t)xoff[k] + n_part[k], zn = (int64_t)zoff[k] + m_part[k];
-        if (xn > n || zn > m) return fail(CHIP_ERR_ARG, "chip_batch_create: the parts exceed n or m");
-        xoff[k + 1] = (int)xn;
-        zoff[k + 1] = (int)zn;
-    }
-    if (xoff[np] != n || zoff[np] != m) return fail(CHIP_ERR_ARG, "chip_batch_create: the parts do not add up to n, m");
-    std::vector<int> xmem((size_t)n), zmem((size_t)m);
-    for (int k = 0; k < np; k++) {
-        for (int j = xoff[k]; j < xoff[k + 1]; j++) xmem[j] = k;
-        for (int i = zoff[k]; i < zoff[k + 1]; i++) zmem[i] = k;
-    }
+    HostPlan hp;
+    const int plan_rc = host_plan_build(hp, nprob, n_part, m_part, n, m, ncones, cone_tags, cone_dims, cone_dims2);
+    if (plan_rc && !hp.parts_ok) return plan_rc;
+    const std::vector<int> &xoff = hp.xoff, &zoff = hp.zoff, &zmem = hp.zmem, &xmem = hp.xmem;
     std::vector<int> Prow(nnzP), Pcol(nnzP), Arow(nnzA), Acol(nnzA);
     std::vector<int> lp_init((size_t)np, 1);
     for (int64_t j = 0; j < n; j++) {
@@ -302,59 +410,8 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
             Acol[p] = (int)j;
         }
     }
-    std::vector<ConeSpec> cones;
-    int64_t mm = 0, pdim = 0, nHs = 0;
-    if (build_cone_specs(ncones, cone_tags, cone_dims, cone_dims2, cones, mm, pdim, nHs))
-        return fail(CHIP_ERR_ARG, "chip_batch_create: bad cone");
-    if (mm != m) return fail(CHIP_ERR_DIM, "chip_batch_create: cone dimensions do not add up to m");
-    std::vector<int> rtype((size_t)m, dev::ROW_ZERO);
-    std::vector<int64_t> degree((size_t)np, 0);
-    std::vector<char> has_soc((size_t)np, 0);
-    std::vector<int> it_beg, it_end, it_type, it_mem;
-    for (const ConeSpec &cs : cones) {
-        if (cs.numel == 0) continue;
-        const int r0 = (int)cs.start, r1 = (int)(cs.start + cs.numel), k = zmem[r0];
-        if (zmem[r1 - 1] != k) return fail(CHIP_ERR_ARG, "chip_batch_create: a cone crosses a member's rows");
-        if (cs.tag == CHIP_CONE_NONNEGATIVE) {
-            for (int i = r0; i < r1; i++) rtype[i] = dev::ROW_NN;
-            degree[k] += cs.numel;
-            for (int i = r0; i < r1; i += dev::BATCH_CHUNK) {
-                it_beg.push_back(i);
-                it_end.push_back(std::min(r1, i + dev::BATCH_CHUNK));
-                it_type.push_back(dev::ITEM_NN);
-                it_mem.push_back(k);
-            }
-        } else if (cs.tag == CHIP_CONE_SECONDORDER) {
-            has_soc[k] = 1;
-            rtype[r0] = dev::ROW_SOC_HEAD;
-            for (int i = r0 + 1; i < r1; i++) rtype[i] = dev::ROW_SOC_TAIL;
-            degree[k] += 1;
-            it_beg.push_back(r0);
-            it_end.push_back(r1);
-            it_type.push_back(dev::ITEM_SOC);
-            it_mem.push_back(k);
-        }
-    }
-    // cones are in row order, so the items are sorted by member
-    std::vector<int> it_first((size_t)np + 1, 0);
-    for (int k : it_mem) it_first[k + 1]++;
-    for (int k = 0; k < np; k++) it_first[k + 1] += it_first[k];
-    std::vector<int> ch_beg, ch_end, cx_first((size_t)np + 1, 0), cz_first((size_t)np + 1, 0);
-    for (int k = 0; k < np; k++) {
-        for (int j = xoff[k]; j < xoff[k + 1]; j += dev::BATCH_CHUNK) {
-            ch_beg.push_back(j);
-            ch_end.push_back(std::min(xoff[k + 1], j + dev::BATCH_CHUNK));
-        }
-        cx_first[k + 1] = (int)ch_beg.size();
-    }
-    const int ncx = (int)ch_beg.size();
-    for (int k = 0; k < np; k++) {
-        for (int i = zoff[k]; i < zoff[k + 1]; i += dev::BATCH_CHUNK) {
-            ch_beg.push_back(i);
-            ch_end.push_back(std::min(zoff[k + 1], i + dev::BATCH_CHUNK));
-        }
-        cz_first[k + 1] = (int)ch_beg.size() - ncx;
-    }
+    if (plan_rc) return plan_rc; // a refused cone: reported after the entries of P and A, its text still the last error
+    const std::vector<ConeSpec> &cones = hp.cones;
     // ---- the device
     if (st.linsys.device == CHIP_DEVICE_HOST_ONLY || chip_device_count() < 1)
         return fail(CHIP_ERR_NO_DEVICE, "chip_batch_create: no HIP device (the product has no CPU fallback)");
@@ -365,29 +422,15 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     h->m = (int)m;
     h->xoff = xoff;
     h->zoff = zoff;
-    h->degree = degree;
-    h->has_soc = has_soc;
+    h->degree = hp.degree;
+    h->has_soc = hp.has_soc;
     h->lp_init = lp_init;
     h->anyP = nnzP > 0;
     h->anyLP = std::find(lp_init.begin(), lp_init.end(), 1) != lp_init.end();
     DevPool &mem = h->mem;
     int rc;
     dev::BatchPlan &pl = h->plan;
-    int *d_xoff, *d_zoff, *d_xmem, *d_zmem, *d_chb, *d_che, *d_cxf, *d_czf, *d_itb, *d_ite, *d_itt, *d_itf, *d_rt;
-    if ((rc = mem.upload(&d_xoff, xoff.data(), xoff.size())) || (rc = mem.upload(&d_zoff, zoff.data(), zoff.size())) ||
-        (rc = mem.upload(&d_xmem, xmem.data(), xmem.size())) || (rc = mem.upload(&d_zmem, zmem.data(), zmem.size())) ||
-        (rc = mem.upload(&d_chb, ch_beg.data(), ch_beg.size())) ||
-        (rc = mem.upload(&d_che, ch_end.data(), ch_end.size())) ||
-        (rc = mem.upload(&d_cxf, cx_first.data(), cx_first.size())) ||
-        (rc = mem.upload(&d_czf, cz_first.data(), cz_first.size())) ||
-        (rc = mem.upload(&d_itb, it_beg.data(), it_beg.size())) ||
-        (rc = mem.upload(&d_ite, it_end.data(), it_end.size())) ||
-        (rc = mem.upload(&d_itt, it_type.data(), it_type.size())) ||
-        (rc = mem.upload(&d_itf, it_first.data(), it_first.size())) ||
-        (rc = mem.upload(&d_rt, rtype.data(), rtype.size())))
-        return rc;
-    pl = dev::BatchPlan{np,    (int)n, (int)m, d_xoff, d_zoff, d_xmem, d_zmem, d_chb,  d_che, d_cxf,
-                        d_czf, ncx,    (int)ch_beg.size() - ncx, d_itb, d_ite, d_itt, d_itf, (int)it_beg.size(), d_rt};
+    if ((rc = host_plan_upload(mem, hp, &pl))) return rc;
     // ---- the data: b capped at the reference's infinity; per member the norms of the unequilibrated q and b
     std::vector<double> bcap(b, b + m);
     for (double &v : bcap) v = std::min(v, 1e20); // problemdata.rs:125-127
@@ -1300,5 +1343,271 @@ int32_t chip_debug_batch_counter(void *batch, const char *name, double *out) {
     else if (nm == "backward_host_syncs") *out = (double)h->grad_syncs;
     else return fail(CHIP_ERR_ARG, "chip_debug_batch_counter: unknown name");
     return CHIP_OK;
+}
+
+// ---- the partition alone, and one launch of every launcher of batch.hpp on host arrays (tests/test_batch_plan_host.py,
+// tests/test_batch_passes_gpu.py).  The plan is the one chip_batch_create builds (host_plan_build / host_plan_upload)
+namespace {
+struct DebugPlan {
+    HostPlan hp;
+    DevPool mem;
+    dev::BatchPlan plan{};
+    bool uploaded = false;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    double *seg_scr = nullptr, *cone_scr = nullptr;
+    ~DebugPlan() {
+        if (stream) {
+            (void)hipStreamSynchronize(stream);
+            (void)hipStreamDestroy(stream);
+        }
+    }
+    int ready() { // the first runner uploads the plan; chip_debug_bplan_create itself touches no device
+        if (uploaded) {
+            CHIP_HIP(hipSetDevice(device));
+            return CHIP_OK;
+        }
+        if (chip_device_count() < 1) return fail(CHIP_ERR_NO_DEVICE, "chip_debug_bplan: no HIP device");
+        CHIP_HIP(hipGetDevice(&device));
+        int rc;
+        if ((rc = host_plan_upload(mem, hp, &plan)) || (rc = mem.alloc(&seg_scr, dev::seg_scratch_doubles(plan))) ||
+            (rc = mem.alloc(&cone_scr, dev::cone_scratch_doubles(plan))))
+            return rc;
+        CHIP_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        uploaded = true;
+        return CHIP_OK;
+    }
+};
+// the device buffers of one runner call: one per distinct host array (so operands that alias on the host alias on the
+// device), NULL stays NULL; out() arrays are uploaded too and copied back by finish()
+struct DebugStage {
+    DevPool mem;
+    struct Buf {
+        const void *host;
+        void *dev;
+        size_t bytes;
+        bool out;
+    };
+    std::vector<Buf> bufs;
+    template <typename T> int map(const T *host, size_t len, bool is_out, T **devp) {
+        *devp = nullptr;
+        if (!host) return CHIP_OK;
+        for (Buf &b : bufs)
+            if (b.host == (const void *)host) {
+                b.out = b.out || is_out;
+                *devp = (T *)b.dev;
+                return CHIP_OK;
+            }
+        int rc = mem.upload(devp, host, len);
+        if (rc) return rc;
+        bufs.push_back(Buf{host, *devp, len * sizeof(T), is_out});
+        return CHIP_OK;
+    }
+    template <typename T> int in(const T *host, size_t len, const T **devp) {
+        T *d;
+        int rc = map(host, len, false, &d);
+        *devp = d;
+        return rc;
+    }
+    template <typename T> int out(T *host, size_t len, T **devp) { return map(host, len, true, devp); }
+    int finish(hipStream_t s) {
+        CHIP_HIP(hipGetLastError());
+        CHIP_HIP(hipStreamSynchronize(s));
+        for (const Buf &b : bufs)
+            if (b.out && b.bytes) CHIP_HIP(hipMemcpy((void *)b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
+        return CHIP_OK;
+    }
+};
+} // namespace
+
+int32_t chip_debug_bplan_create(void **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t ncones,
+                                const int32_t *cone_tags, const int64_t *cone_dims) {
+    if (!out) return fail(CHIP_ERR_ARG, "chip_debug_bplan_create: bad argument");
+    *out = nullptr;
+    if (nprob < 1 || !n_part || !m_part || ncones < 0 || (ncones && (!cone_tags || !cone_dims)))
+        return fail(CHIP_ERR_ARG, "chip_debug_bplan_create: bad argument");
+    if (int rc = batch_cones_supported(ncones, cone_tags)) return rc;
+    if (nprob >= (1ll << 31)) return fail(CHIP_ERR_DIM, "chip_debug_bplan_create: sizes out of int32 range");
+    int64_t n = 0, m = 0;
+    for (int64_t k = 0; k < nprob; k++) {
+        if (n_part[k] < 0 || m_part[k] < 0) return fail(CHIP_ERR_ARG, "chip_debug_bplan_create: negative part");
+        n += n_part[k];
+        m += m_part[k];
+        if (n >= (1ll << 31) || m >= (1ll << 31) || n + 2 * m >= (1ll << 31))
+            return fail(CHIP_ERR_DIM, "chip_debug_bplan_create: sizes out of int32 range");
+    }
+    std::unique_ptr<DebugPlan> h(new DebugPlan());
+    std::vector<int64_t> dims2((size_t)ncones, 0);
+    if (int rc = host_plan_build(h->hp, nprob, n_part, m_part, n, m, ncones, cone_tags, cone_dims, dims2.data()))
+        return rc;
+    *out = h.release();
+    return CHIP_OK;
+}
+void chip_debug_bplan_destroy(void *h) { delete (DebugPlan *)h; }
+
+int32_t chip_debug_bplan_get(const void *handle, const char *name, int64_t *len, int32_t *out) {
+    const DebugPlan *h = (const DebugPlan *)handle;
+    if (!h || !name || !len) return fail(CHIP_ERR_ARG, "chip_debug_bplan_get: bad argument");
+    const HostPlan &hp = h->hp;
+    const std::string nm(name);
+    const std::vector<int> sizes{hp.nprob, hp.n, hp.m, hp.ncx, hp.ncz, (int)hp.it_beg.size()};
+    const std::vector<int> *v = nm == "sizes"      ? &sizes
+                                : nm == "xoff"     ? &hp.xoff
+                                : nm == "zoff"     ? &hp.zoff
+                                : nm == "xmem"     ? &hp.xmem
+                                : nm == "zmem"     ? &hp.zmem
+                                : nm == "ch_beg"   ? &hp.ch_beg
+                                : nm == "ch_end"   ? &hp.ch_end
+                                : nm == "cx_first" ? &hp.cx_first
+                                : nm == "cz_first" ? &hp.cz_first
+                                : nm == "it_beg"   ? &hp.it_beg
+                                : nm == "it_end"   ? &hp.it_end
+                                : nm == "it_type"  ? &hp.it_type
+                                : nm == "it_first" ? &hp.it_first
+                                : nm == "rtype"    ? &hp.rtype
+                                                   : nullptr;
+    if (!v) return fail(CHIP_ERR_ARG, "chip_debug_bplan_get: unknown name");
+    *len = (int64_t)v->size();
+    if (out && !v->empty()) std::memcpy(out, v->data(), v->size() * sizeof(int));
+    return CHIP_OK;
+}
+
+int32_t chip_debug_bplan_seg_reduce(void *handle, int32_t count, const int32_t *kind, const int32_t *space,
+                                    const int32_t *slot, const double *const *a, const double *const *b,
+                                    int32_t nslots, double *out) {
+    DebugPlan *h = (DebugPlan *)handle;
+    if (!h || count < 0 || count > dev::SEG_MAX || nslots < 0 || (count && (!kind || !space || !slot || !a || !b || !out)))
+        return fail(CHIP_ERR_ARG, "chip_debug_bplan_seg_reduce: bad argument");
+    for (int j = 0; j < count; j++)
+        if (kind[j] < dev::SEG_DOT || kind[j] > dev::SEG_NONFINITE || (space[j] != 0 && space[j] != 1) || slot[j] < 0 ||
+            slot[j] >= nslots || !a[j] || (!b[j] && (kind[j] == dev::SEG_DOT || kind[j] == dev::SEG_WSQ)))
+            return fail(CHIP_ERR_ARG, "chip_debug_bplan_seg_reduce: bad spec");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugStage st;
+    dev::SegBatch bt{};
+    bt.count = count;
+    for (int j = 0; j < count; j++) {
+        const size_t len = space[j] ? (size_t)h->hp.m : (size_t)h->hp.n;
+        const double *da, *db;
+        if ((rc = st.in(a[j], len, &da)) || (rc = st.in(b[j], len, &db))) return rc;
+        bt.s[j] = dev::SegSpec{da, db, kind[j], space[j], slot[j]};
+    }
+    double *dout;
+    if ((rc = st.out(out, (size_t)nslots * h->hp.nprob, &dout))) return rc;
+    dev::seg_reduce(h->stream, h->plan, bt, dout, h->seg_scr);
+    return st.finish(h->stream);
+}
+
+int32_t chip_debug_bplan_cone_minima(void *handle, int32_t op, const double *dz, const double *ds, const double *z,
+                                     const double *sv, const double *amax, double *out_min, double *out_sum_or_null) {
+    DebugPlan *h = (DebugPlan *)handle;
+    const bool step = op == dev::CONE_STEP;
+    if (!h || op < dev::CONE_STEP || op > dev::CONE_INTERIOR || !z || !out_min || (step && (!dz || !ds || !sv || !amax)) ||
+        (op == dev::CONE_INTERIOR && !sv))
+        return fail(CHIP_ERR_ARG, "chip_debug_bplan_cone_minima: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugStage st;
+    const size_t m = (size_t)h->hp.m, np = (size_t)h->hp.nprob;
+    const double *ddz, *dds, *dzz, *dsv, *dam;
+    double *dmin, *dsum;
+    if ((rc = st.in(dz, m, &ddz)) || (rc = st.in(ds, m, &dds)) || (rc = st.in(z, m, &dzz)) || (rc = st.in(sv, m, &dsv)) ||
+        (rc = st.in(amax, np, &dam)) || (rc = st.out(out_min, np, &dmin)) || (rc = st.out(out_sum_or_null, np, &dsum)))
+        return rc;
+    dev::cone_minima(h->stream, h->plan, op, ddz, dds, dzz, dsv, dam, dmin, dsum, h->cone_scr);
+    return st.finish(h->stream);
+}
+
+int32_t chip_debug_bplan_blin(void *handle, double *w, const double *x, const double *y, const double *sa,
+                              const double *sb, double ca, double cb, int32_t space, const int32_t *mask,
+                              int32_t mask_mode) {
+    DebugPlan *h = (DebugPlan *)handle;
+    if (!h || !w || !x || (space != 0 && space != 1) || mask_mode < dev::MASK_ZERO || mask_mode > dev::MASK_KEEP ||
+        (mask && mask_mode == dev::MASK_Y && !y))
+        return fail(CHIP_ERR_ARG, "chip_debug_bplan_blin: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugStage st;
+    const size_t len = space ? (size_t)h->hp.m : (size_t)h->hp.n, np = (size_t)h->hp.nprob;
+    double *dw;
+    const double *dx, *dy, *dsa, *dsb;
+    const int *dmask;
+    if ((rc = st.out(w, len, &dw)) || (rc = st.in(x, len, &dx)) || (rc = st.in(y, len, &dy)) ||
+        (rc = st.in(sa, np, &dsa)) || (rc = st.in(sb, np, &dsb)) || (rc = st.in((const int *)mask, np, &dmask)))
+        return rc;
+    dev::blin(h->stream, h->plan, dev::BLin{dw, dx, dy, dsa, dsb, ca, cb, space, dmask, mask_mode});
+    return st.finish(h->stream);
+}
+
+int32_t chip_debug_bplan_bresid(void *handle, double *rx, const double *rx_inf, const double *Px, const double *q,
+                                double *rz, const double *rz_inf, const double *b, const double *tau) {
+    DebugPlan *h = (DebugPlan *)handle;
+    if (!h || !rx || !rx_inf || !Px || !q || !rz || !rz_inf || !b || !tau)
+        return fail(CHIP_ERR_ARG, "chip_debug_bplan_bresid: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugStage st;
+    const size_t n = (size_t)h->hp.n, m = (size_t)h->hp.m, np = (size_t)h->hp.nprob;
+    double *drx, *drz;
+    const double *drxi, *dPx, *dq, *drzi, *db, *dtau;
+    if ((rc = st.out(rx, n, &drx)) || (rc = st.in(rx_inf, n, &drxi)) || (rc = st.in(Px, n, &dPx)) ||
+        (rc = st.in(q, n, &dq)) || (rc = st.out(rz, m, &drz)) || (rc = st.in(rz_inf, m, &drzi)) ||
+        (rc = st.in(b, m, &db)) || (rc = st.in(tau, np, &dtau)))
+        return rc;
+    dev::bresid(h->stream, h->plan, drx, drxi, dPx, dq, drz, drzi, db, dtau);
+    return st.finish(h->stream);
+}
+
+int32_t chip_debug_bplan_bunit_shift(void *handle, double *z, const double *alpha, int32_t primal,
+                                     const int32_t *mask) {
+    DebugPlan *h = (DebugPlan *)handle;
+    if (!h || !z || !alpha) return fail(CHIP_ERR_ARG, "chip_debug_bplan_bunit_shift: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugStage st;
+    double *dz;
+    const double *dal;
+    const int *dmask;
+    if ((rc = st.out(z, (size_t)h->hp.m, &dz)) || (rc = st.in(alpha, (size_t)h->hp.nprob, &dal)) ||
+        (rc = st.in((const int *)mask, (size_t)h->hp.nprob, &dmask)))
+        return rc;
+    dev::bunit_shift(h->stream, h->plan, dz, dal, primal, dmask);
+    return st.finish(h->stream);
+}
+
+int32_t chip_debug_bplan_bunit_reset(void *handle, double *x, double *sv, double *z, const int32_t *flag) {
+    DebugPlan *h = (DebugPlan *)handle;
+    if (!h || !x || !sv || !z || !flag) return fail(CHIP_ERR_ARG, "chip_debug_bplan_bunit_reset: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugStage st;
+    double *dx, *dsv, *dz;
+    const int *dflag;
+    if ((rc = st.out(x, (size_t)h->hp.n, &dx)) || (rc = st.out(sv, (size_t)h->hp.m, &dsv)) ||
+        (rc = st.out(z, (size_t)h->hp.m, &dz)) || (rc = st.in((const int *)flag, (size_t)h->hp.nprob, &dflag)))
+        return rc;
+    dev::bunit_reset(h->stream, h->plan, dx, dsv, dz, dflag);
+    return st.finish(h->stream);
+}
+
+int32_t chip_debug_bplan_bunscale(void *handle, double *xo, const double *x, const double *d, double *zo,
+                                  const double *z, const double *e, double *so, const double *sv, const double *einv,
+                                  const double *sx, const double *sz) {
+    DebugPlan *h = (DebugPlan *)handle;
+    if (!h || !xo || !x || !d || !zo || !z || !e || !so || !sv || !einv || !sx || !sz)
+        return fail(CHIP_ERR_ARG, "chip_debug_bplan_bunscale: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugStage st;
+    const size_t n = (size_t)h->hp.n, m = (size_t)h->hp.m, np = (size_t)h->hp.nprob;
+    double *dxo, *dzo, *dso;
+    const double *dx, *dd, *dz, *de, *dsv, *dei, *dsx, *dsz;
+    if ((rc = st.out(xo, n, &dxo)) || (rc = st.in(x, n, &dx)) || (rc = st.in(d, n, &dd)) || (rc = st.out(zo, m, &dzo)) ||
+        (rc = st.in(z, m, &dz)) || (rc = st.in(e, m, &de)) || (rc = st.out(so, m, &dso)) || (rc = st.in(sv, m, &dsv)) ||
+        (rc = st.in(einv, m, &dei)) || (rc = st.in(sx, np, &dsx)) || (rc = st.in(sz, np, &dsz)))
+        return rc;
+    dev::bunscale(h->stream, h->plan, dxo, dx, dd, dzo, dz, de, dso, dsv, dei, dsx, dsz);
+    return st.finish(h->stream);
 }
 #endif

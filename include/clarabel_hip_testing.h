@@ -71,6 +71,37 @@ int32_t chip_debug_ipm_info_update(double *info, const double *sq, double tau, d
  * call). */
 int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration);
 int32_t chip_debug_batch_counter(void *batch, const char *name, double *out);
+/* ---- the batched solver's partition and its device passes (csrc/batch.hpp), each alone ----
+ * chip_debug_bplan_create: the partition chip_batch_create builds for nprob members of n_part[k] columns and m_part[k]
+ * rows with the given cones (Zero / Nonnegative / SecondOrder), by the same code and with the same refusals; host only,
+ * no device is touched.  chip_debug_bplan_get: one int32 array by name; *len <- its length; out (may be NULL) receives
+ * it: "xoff", "zoff", "xmem", "zmem", "ch_beg", "ch_end", "cx_first", "cz_first", "it_beg", "it_end", "it_type",
+ * "it_first", "rtype", and "sizes" = {nprob, n, m, ncx, ncz, nitems}.
+ * The runners (one per launcher of batch.hpp) take HOST arrays of the stack's lengths (n, m, or nprob for the
+ * per-member scalars, masks and outputs): the first one uploads the plan to the current device; each copies its
+ * arrays to device buffers (one buffer per distinct host pointer, so aliased operands stay aliased; arrays written by
+ * the pass are uploaded as well, so entries a pass leaves alone come back unchanged), calls the launcher ONCE on a
+ * private stream, synchronises and copies the written arrays back.  NULL operands the launcher accepts are passed on
+ * as NULL (y, sa, sb, mask, out_sum, b[j] of a sum); a NULL the kernel would read is refused with CHIP_ERR_ARG.
+ * seg_reduce: `count` <= 16 specs (kind / space / slot / a / b per spec) into out[nslots * nprob]. */
+int32_t chip_debug_bplan_create(void **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t ncones,
+                                const int32_t *cone_tags, const int64_t *cone_dims);
+void chip_debug_bplan_destroy(void *h);
+int32_t chip_debug_bplan_get(const void *h, const char *name, int64_t *len, int32_t *out);
+int32_t chip_debug_bplan_seg_reduce(void *h, int32_t count, const int32_t *kind, const int32_t *space,
+                                    const int32_t *slot, const double *const *a, const double *const *b,
+                                    int32_t nslots, double *out);
+int32_t chip_debug_bplan_cone_minima(void *h, int32_t op, const double *dz, const double *ds, const double *z,
+                                     const double *sv, const double *amax, double *out_min, double *out_sum_or_null);
+int32_t chip_debug_bplan_blin(void *h, double *w, const double *x, const double *y, const double *sa, const double *sb,
+                              double ca, double cb, int32_t space, const int32_t *mask, int32_t mask_mode);
+int32_t chip_debug_bplan_bresid(void *h, double *rx, const double *rx_inf, const double *Px, const double *q,
+                                double *rz, const double *rz_inf, const double *b, const double *tau);
+int32_t chip_debug_bplan_bunit_shift(void *h, double *z, const double *alpha, int32_t primal, const int32_t *mask);
+int32_t chip_debug_bplan_bunit_reset(void *h, double *x, double *sv, double *z, const int32_t *flag);
+int32_t chip_debug_bplan_bunscale(void *h, double *xo, const double *x, const double *d, double *zo, const double *z,
+                                  const double *e, double *so, const double *sv, const double *einv, const double *sx,
+                                  const double *sz);
 #ifdef __cplusplus
 }
 #endif
