@@ -1497,6 +1497,109 @@ class BatchPlanDebug:
         return xo, zo, so
 
 
+class PsdConesDebug:
+    """the PSD cone kernels of csrc/cones.hip alone (chip_debug_psd_*; test hooks of include/clarabel_hip_testing.h: a
+    library built with TESTING=1): a bare device view over a vector that holds only the svec ranges of PSD triangle
+    cones of sides `dims`, and one launch of each launcher on host arrays.  Creating it and counter() need no GPU; the
+    first pass uploads the view.  Every pass returns new arrays and leaves its arguments alone."""
+
+    def __init__(self, dims):
+        dims = np.ascontiguousarray(dims, dtype=np.int64)
+        self._h = C.c_void_p()
+        _check(lib().chip_debug_psd_create(C.byref(self._h), C.c_int64(len(dims)), dims.ctypes.data_as(P_I64)),
+               "chip_debug_psd_create")
+        self.dims = [int(d) for d in dims]
+        self.ncones = len(self.dims)
+        self.start = [0]
+        for d in self.dims:
+            self.start.append(self.start[-1] + d * (d + 1) // 2)
+        self.rows = self.start[-1]
+        assert self.rows == int(self.counter("rows"))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().chip_debug_psd_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def counter(self, name):
+        """"gs", "jacobi_lds" (of the last update_scaling / step_length / margins), "maxdim", "rows", "scratch_stride",
+        "state_doubles" """
+        out = C.c_double()
+        _check(lib().chip_debug_psd_counter(self._h, name.encode(), C.byref(out)), "chip_debug_psd_counter")
+        return out.value
+
+    def rows_of(self, c):
+        return slice(self.start[c], self.start[c + 1])
+
+    def _vec(self, a, what):
+        a = np.ascontiguousarray(a, dtype=f64)
+        if a.shape != (self.rows,):
+            raise ValueError("%s must have %d entries" % (what, self.rows))
+        return a
+
+    def update_scaling(self, s, z):
+        """-> True / False (a cone without a Cholesky factor)"""
+        ok = C.c_int32(-1)
+        _check(lib().chip_debug_psd_update_scaling(self._h, _pf(self._vec(s, "s")), _pf(self._vec(z, "z")), C.byref(ok)),
+               "chip_debug_psd_update_scaling")
+        return bool(ok.value)
+
+    def state(self, c):
+        """-> B, lambda, lambda^-1/2, R, Rinv of cone c (matrices as numpy (row, column) arrays)"""
+        n = self.dims[c]
+        buf = np.full(3 * n * n + 2 * n, np.nan)
+        _check(lib().chip_debug_psd_state(self._h, C.c_int64(c), _pf(buf)), "chip_debug_psd_state")
+        mat = lambda o: buf[o:o + n * n].reshape(n, n).T.copy()  # (column major on the device)
+        return mat(0), buf[n * n:n * n + n].copy(), buf[n * n + n:n * n + 2 * n].copy(), mat(n * n + 2 * n), \
+            mat(2 * n * n + 2 * n)
+
+    def mul_hs(self, x):
+        y = np.full(self.rows, np.nan)
+        _check(lib().chip_debug_psd_mul_hs(self._h, _pf(y), _pf(self._vec(x, "x"))), "chip_debug_psd_mul_hs")
+        return y
+
+    def affine_ds(self):
+        ds = np.full(self.rows, np.nan)
+        _check(lib().chip_debug_psd_affine_ds(self._h, _pf(ds)), "chip_debug_psd_affine_ds")
+        return ds
+
+    def combined_ds_shift(self, step_z, step_s, sigma_mu):
+        """-> (shift, W step_z, W^-T step_s)"""
+        shift = np.full(self.rows, np.nan)
+        wz, ws = self._vec(step_z, "step_z").copy(), self._vec(step_s, "step_s").copy()
+        _check(lib().chip_debug_psd_combined_ds_shift(self._h, _pf(shift), _pf(wz), _pf(ws), C.c_double(sigma_mu)),
+               "chip_debug_psd_combined_ds_shift")
+        return shift, wz, ws
+
+    def ds_from_dz_offset(self, ds):
+        out = np.full(self.rows, np.nan)
+        _check(lib().chip_debug_psd_ds_from_dz_offset(self._h, _pf(out), _pf(self._vec(ds, "ds"))),
+               "chip_debug_psd_ds_from_dz_offset")
+        return out
+
+    def step_length(self, dz, ds, amax):
+        """-> the per-cone step lengths"""
+        out = np.full(self.ncones, np.nan)
+        _check(lib().chip_debug_psd_step_length(self._h, _pf(self._vec(dz, "dz")), _pf(self._vec(ds, "ds")),
+                                                C.c_double(amax), _pf(out)), "chip_debug_psd_step_length")
+        return out
+
+    def margins(self, z):
+        """-> per cone (smallest eigenvalue, sum of the positive eigenvalues)"""
+        pmin, psum = np.full(self.ncones, np.nan), np.full(self.ncones, np.nan)
+        _check(lib().chip_debug_psd_margins(self._h, _pf(self._vec(z, "z")), _pf(pmin), _pf(psum)),
+               "chip_debug_psd_margins")
+        return pmin, psum
+
+    def barrier(self, z, s, dz, ds, alpha):
+        """-> the per-cone barrier values at (z, s) + alpha (dz, ds)"""
+        out = np.full(self.ncones, np.nan)
+        _check(lib().chip_debug_psd_barrier(self._h, _pf(self._vec(z, "z")), _pf(self._vec(s, "s")),
+                                            _pf(self._vec(dz, "dz")), _pf(self._vec(ds, "ds")), C.c_double(alpha),
+                                            _pf(out)), "chip_debug_psd_barrier")
+        return out
+
+
 def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
 

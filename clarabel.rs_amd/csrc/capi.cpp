@@ -10,6 +10,7 @@
 #include <memory>
 
 #include "engine.hpp"
+#include "host_util.hpp"
 #include "problem_update.hpp"
 #include "../../include/clarabel_hip_testing.h"
 
@@ -45,6 +46,126 @@ int count_positive(Engine &E, i64 *out) {
     *out = c;
     return CHIP_OK;
 }
+
+// ---- the PSD cones' device view (dev::PsdView, kernels.hpp) -- one function for chip_kkt_create and the test runners
+// (chip_debug_psd_*).  psd_sizing is host arithmetic only: per cone its first row, side, Hs block and the offset of its
+// state (3 n^2 + 2 n doubles: B | lambda | lambda^-1/2 | R | Rinv), the largest side, and the decision that holds for
+// ALL cones of the view: a largest side above 64 puts the kernels' work matrices into a scratch slice per cone in HBM
+// (4 maxdim^2 + 4 maxdim + 16 doubles each) instead of LDS.
+struct PsdSizing {
+    std::vector<int> start, dim, hs, off;
+    i64 state = 0;
+    int maxdim = 0;
+    long long scratch_stride = 0; // 0: work matrices in LDS
+    void add(i64 start_row, i64 side, i64 hs_start) {
+        start.push_back((int)start_row);
+        dim.push_back((int)side);
+        hs.push_back((int)hs_start);
+        off.push_back((int)state);
+        state += 3 * side * side + 2 * side;
+        maxdim = std::max<int>(maxdim, (int)side);
+        scratch_stride = maxdim > 64 ? 4LL * maxdim * maxdim + 4LL * maxdim + 16 : 0;
+    }
+};
+// uploads the sizing through `mem` (Engine or DevPool: alloc(T **, n)) and fills the view; rows_nblk and its arrays
+// (the dense-block analysis of chip_kkt_create) are left as they are
+template <typename Mem>
+int psd_view_build(Mem &mem, dev::PsdView &pv, const PsdSizing &sz, const int *mapHs, int *fail_flag) {
+    int rc;
+    const size_t nc = sz.start.size();
+    int *q[4] = {nullptr, nullptr, nullptr, nullptr};
+    const std::vector<int> *src[4] = {&sz.start, &sz.dim, &sz.hs, &sz.off};
+    for (int k = 0; k < 4; k++) {
+        if ((rc = mem.alloc(&q[k], nc))) return rc;
+        if (nc) CHIP_HIP(hipMemcpy(q[k], src[k]->data(), nc * sizeof(int), hipMemcpyHostToDevice));
+    }
+    double *qs;
+    if ((rc = mem.alloc(&qs, (size_t)(sz.state ? sz.state : 1)))) return rc;
+    pv.ncones = (int)nc;
+    pv.maxdim = sz.maxdim;
+    pv.scratch = nullptr;
+    pv.scratch_stride = sz.scratch_stride;
+    if (sz.scratch_stride) // beyond the LDS budget of three / four n x n matrices: work matrices in HBM
+        if ((rc = mem.alloc(&pv.scratch, (size_t)sz.scratch_stride * nc))) return rc;
+    pv.start = q[0];
+    pv.dim = q[1];
+    pv.hs_start = q[2];
+    pv.state_off = q[3];
+    pv.state = qs;
+    pv.mapHs = mapHs;
+    pv.fail = fail_flag;
+    return CHIP_OK;
+}
+
+#ifdef CHIP_TESTING
+// a bare PsdView over a vector that holds only these cones' svec ranges (chip_debug_psd_*): the sizing is host only, the
+// first runner uploads it to the current device
+struct DebugPsd {
+    PsdSizing sz;
+    i64 m = 0; // rows of the vector (sum of the cones' n (n + 1) / 2)
+    DevPool mem;
+    dev::PsdView pv{};
+    int *fail_flag = nullptr;
+    int gen = 0, last_jacobi_lds = 0;
+    bool uploaded = false;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    ~DebugPsd() {
+        if (stream) {
+            (void)hipStreamSynchronize(stream);
+            (void)hipStreamDestroy(stream);
+        }
+    }
+    int ready() {
+        if (uploaded) {
+            CHIP_HIP(hipSetDevice(device));
+            return CHIP_OK;
+        }
+        if (chip_device_count() < 1) return fail(CHIP_ERR_NO_DEVICE, "chip_debug_psd: no HIP device");
+        CHIP_HIP(hipGetDevice(&device));
+        int rc;
+        if ((rc = mem.alloc(&fail_flag, 1))) return rc;
+        CHIP_HIP(hipMemset(fail_flag, 0, sizeof(int)));
+        if ((rc = psd_view_build(mem, pv, sz, nullptr, fail_flag))) return rc;
+        CHIP_HIP(hipMemset(pv.state, 0, (size_t)(sz.state ? sz.state : 1) * sizeof(double)));
+        CHIP_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        uploaded = true;
+        return CHIP_OK;
+    }
+};
+// the device copies of one runner call; out arrays are uploaded too (entries a pass leaves alone come back unchanged)
+struct DebugPsdStage {
+    DevPool mem;
+    struct Buf {
+        void *host, *dev;
+        size_t bytes;
+    };
+    std::vector<Buf> outs;
+    int in(const double *host, size_t len, const double **devp) {
+        double *d = nullptr;
+        *devp = nullptr;
+        if (!host) return CHIP_OK;
+        int rc = mem.upload(&d, host, len);
+        *devp = d;
+        return rc;
+    }
+    int out(double *host, size_t len, double **devp) {
+        *devp = nullptr;
+        if (!host) return CHIP_OK;
+        int rc = mem.upload(devp, (const double *)host, len);
+        if (rc) return rc;
+        outs.push_back(Buf{host, *devp, len * sizeof(double)});
+        return CHIP_OK;
+    }
+    int finish(hipStream_t s) {
+        CHIP_HIP(hipGetLastError());
+        CHIP_HIP(hipStreamSynchronize(s));
+        for (const Buf &b : outs)
+            if (b.bytes) CHIP_HIP(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
+        return CHIP_OK;
+    }
+};
+#endif
 
 } // namespace
 
@@ -512,11 +633,10 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
 
     // ---- cone work lists ----------------------------------------------------
     std::vector<int> nn_rows, nn_hs, zero_rows, s_start, s_dim, s_hs, s_sidx, s_ptr, mapU, mapV, mapD;
-    std::vector<int> n3_start, n3_hs, n3_tag, pd_start, pd_dim, pd_hs, pd_off;
+    std::vector<int> n3_start, n3_hs, n3_tag;
+    PsdSizing pd;
     std::vector<int> gp_start, gp_d1, gp_d2, gp_hs, gp_off, gp_mapptr, gp_map, gp_mapD;
     i64 gp_state = 0;
-    i64 pd_state = 0;
-    int pd_max = 0;
     std::vector<double> n3_alpha;
     for (const ConeSpec &c : K.cones) {
         if (c.tag == CHIP_CONE_NONNEGATIVE) {
@@ -555,12 +675,7 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
             for (int k = 0; k < 3; k++) gp_mapD.push_back(k2v[(size_t)K.sp_D[3 * sidx + k]]);
             h->gpw_cone_index.push_back((int)(&c - K.cones.data()));
         } else if (c.tag == CHIP_CONE_PSDTRIANGLE) {
-            pd_start.push_back((int)c.start);
-            pd_dim.push_back((int)c.dim);
-            pd_hs.push_back((int)c.block_start);
-            pd_off.push_back((int)pd_state);
-            pd_state += 3 * c.dim * c.dim + 2 * c.dim; // B | lambda | lambda^-1/2 | R | Rinv
-            pd_max = std::max<int>(pd_max, (int)c.dim);
+            pd.add(c.start, c.dim, c.block_start);
         } else {
             h->has_hostHs = true;
         }
@@ -602,43 +717,22 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
     }
     {
         dev::PsdView &pv = h->psd;
-        pv.ncones = (int)pd_start.size();
-        pv.maxdim = pd_max;
-        int *q1, *q2, *q3, *q4;
-        double *qs;
-        if ((rc = E.upload(&q1, pd_start, pd_start.size()))) return rc;
-        if ((rc = E.upload(&q2, pd_dim, pd_dim.size()))) return rc;
-        if ((rc = E.upload(&q3, pd_hs, pd_hs.size()))) return rc;
-        if ((rc = E.upload(&q4, pd_off, pd_off.size()))) return rc;
-        if ((rc = E.alloc(&qs, (size_t)(pd_state ? pd_state : 1)))) return rc;
-        pv.scratch = nullptr;
-        pv.scratch_stride = 0;
-        if (pd_max > 64) { // beyond the LDS budget of three / four n x n matrices: work matrices in HBM
-            pv.scratch_stride = 4LL * pd_max * pd_max + 4LL * pd_max + 16;
-            if ((rc = E.alloc(&pv.scratch, (size_t)pv.scratch_stride * pd_start.size()))) return rc;
-        }
-        pv.start = q1;
-        pv.dim = q2;
-        pv.hs_start = q3;
-        pv.state_off = q4;
-        pv.state = qs;
-        pv.mapHs = h->mapHs;
-        pv.fail = &E.mb_dev->soc_fail;
+        if ((rc = psd_view_build(E, pv, pd, h->mapHs, &E.mb_dev->soc_fail))) return rc;
         // every cone's Hs block one of the dense diagonal blocks of the top?  Then Hs is written row by row of the
         // device's value order (k_psd_write_hs_rows) instead of through mapHs
-        if (pv.ncones > 0 && pd_max <= 64 && E.dblk.nblk > 0) {
+        if (pv.ncones > 0 && pd.maxdim <= 64 && E.dblk.nblk > 0) {
             const int nblk = E.dblk.nblk;
             std::vector<i32> blk_cone((size_t)nblk, -1), row_ij(E.h_dblk_node.size(), 0);
-            std::vector<char> covered(pd_start.size(), 0);
+            std::vector<char> covered(pd.start.size(), 0);
             size_t nc = 0;
             for (int b = 0, o = 0; b < nblk; o += E.h_dblk_m[(size_t)b], b++) {
                 const i32 mb = E.h_dblk_m[(size_t)b];
                 const i64 z0 = (i64)E.h_perm[(size_t)E.h_dblk_node[(size_t)o]] - n;
                 if (z0 < 0) continue;
                 // the cone that holds z0 (cones ascend by start)
-                const size_t c = (size_t)(std::upper_bound(pd_start.begin(), pd_start.end(), (i32)z0) - pd_start.begin());
+                const size_t c = (size_t)(std::upper_bound(pd.start.begin(), pd.start.end(), (i32)z0) - pd.start.begin());
                 if (c == 0) continue;
-                const i32 st = pd_start[c - 1], nd = pd_dim[c - 1], numel = nd * (nd + 1) / 2;
+                const i32 st = pd.start[c - 1], nd = pd.dim[c - 1], numel = nd * (nd + 1) / 2;
                 if (mb != numel || covered[c - 1]) continue;
                 bool ok = true;
                 for (i32 a = 0; a < mb && ok; a++) {
@@ -657,7 +751,7 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
                 covered[c - 1] = 1;
                 nc++;
             }
-            if (nc == pd_start.size()) {
+            if (nc == pd.start.size()) {
                 // (every dense block belongs to a cone: the blocks may be written into L directly, Engine::hs_direct_begin)
                 h->psd_rows_all_blocks = std::all_of(blk_cone.begin(), blk_cone.end(), [](i32 c) { return c >= 0; });
                 int *r1, *r2;
@@ -2139,6 +2233,163 @@ int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out
     }
     else return fail(CHIP_ERR_ARG, "chip_debug_counter: unknown name");
     return CHIP_OK;
+}
+// ---- the PSD cone kernels of cones.hip alone, one launch per call on host arrays (tests/test_psd_passes_gpu.py) ----
+int32_t chip_debug_psd_create(void **out, int64_t ncones, const int64_t *dims) {
+    if (!out) return fail(CHIP_ERR_ARG, "chip_debug_psd_create: bad argument");
+    *out = nullptr;
+    if (ncones < 1 || !dims) return fail(CHIP_ERR_ARG, "chip_debug_psd_create: bad argument");
+    // the cone constructor of chip_kkt_create (build_cone_specs): rows, Hs block starts and refusals are its own
+    std::vector<i32> tags((size_t)ncones, CHIP_CONE_PSDTRIANGLE);
+    std::vector<ConeSpec> specs;
+    i64 m = 0, p = 0, nHs = 0;
+    if (build_cone_specs(ncones, tags.data(), dims, nullptr, specs, m, p, nHs))
+        return fail(CHIP_ERR_ARG, "chip_debug_psd_create: cones refused");
+    for (const ConeSpec &c : specs)
+        if (c.dim < 0 || c.dim > 1024) return fail(CHIP_ERR_ARG, "chip_debug_psd_create: side out of range (0 .. 1024)");
+    std::unique_ptr<DebugPsd> h(new DebugPsd());
+    for (const ConeSpec &c : specs) h->sz.add(c.start, c.dim, c.block_start);
+    h->m = m;
+    *out = h.release();
+    return CHIP_OK;
+}
+void chip_debug_psd_destroy(void *h) { delete (DebugPsd *)h; }
+int32_t chip_debug_psd_counter(const void *handle, const char *name, double *out) {
+    const DebugPsd *h = (const DebugPsd *)handle;
+    if (!h || !name || !out) return fail(CHIP_ERR_ARG, "chip_debug_psd_counter: bad argument");
+    const std::string k(name);
+    if (k == "gs") *out = h->sz.scratch_stride ? 1 : 0;
+    else if (k == "jacobi_lds") *out = h->last_jacobi_lds;
+    else if (k == "maxdim") *out = h->sz.maxdim;
+    else if (k == "rows") *out = (double)h->m;
+    else if (k == "scratch_stride") *out = (double)h->sz.scratch_stride;
+    else if (k == "state_doubles") *out = (double)h->sz.state;
+    else return fail(CHIP_ERR_ARG, "chip_debug_psd_counter: unknown name");
+    return CHIP_OK;
+}
+int32_t chip_debug_psd_update_scaling(void *handle, const double *s, const double *z, int32_t *ok) {
+    DebugPsd *h = (DebugPsd *)handle;
+    if (!h || !s || !z || !ok) return fail(CHIP_ERR_ARG, "chip_debug_psd_update_scaling: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugPsdStage st;
+    const double *ds, *dz;
+    if ((rc = st.in(s, (size_t)h->m, &ds)) || (rc = st.in(z, (size_t)h->m, &dz))) return rc;
+    h->pv.fail_gen = ++h->gen; // (the generation a failing cone leaves in the flag, as chip_kkt_update_scaling does)
+    dev::psd_update_scaling(h->stream, h->pv, ds, dz);
+    h->last_jacobi_lds = dev::psd_last_jacobi_lds();
+    if ((rc = st.finish(h->stream))) return rc;
+    int flag = 0;
+    CHIP_HIP(hipMemcpy(&flag, h->fail_flag, sizeof(int), hipMemcpyDeviceToHost));
+    *ok = flag == h->gen ? 0 : 1;
+    return CHIP_OK;
+}
+int32_t chip_debug_psd_state(void *handle, int64_t cone, double *out) {
+    DebugPsd *h = (DebugPsd *)handle;
+    if (!h || !out || cone < 0 || cone >= (int64_t)h->sz.dim.size())
+        return fail(CHIP_ERR_ARG, "chip_debug_psd_state: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    const size_t n = (size_t)h->sz.dim[(size_t)cone];
+    CHIP_HIP(hipStreamSynchronize(h->stream));
+    CHIP_HIP(hipMemcpy(out, h->pv.state + h->sz.off[(size_t)cone], (3 * n * n + 2 * n) * sizeof(double),
+                       hipMemcpyDeviceToHost));
+    return CHIP_OK;
+}
+int32_t chip_debug_psd_mul_hs(void *handle, double *y, const double *x) {
+    DebugPsd *h = (DebugPsd *)handle;
+    if (!h || !y || !x) return fail(CHIP_ERR_ARG, "chip_debug_psd_mul_hs: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugPsdStage st;
+    double *dy;
+    const double *dx;
+    if ((rc = st.out(y, (size_t)h->m, &dy)) || (rc = st.in(x, (size_t)h->m, &dx))) return rc;
+    dev::psd_mul_hs(h->stream, h->pv, dy, dx);
+    return st.finish(h->stream);
+}
+int32_t chip_debug_psd_affine_ds(void *handle, double *ds) {
+    DebugPsd *h = (DebugPsd *)handle;
+    if (!h || !ds) return fail(CHIP_ERR_ARG, "chip_debug_psd_affine_ds: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugPsdStage st;
+    double *dds;
+    if ((rc = st.out(ds, (size_t)h->m, &dds))) return rc;
+    dev::psd_affine_ds(h->stream, h->pv, dds);
+    return st.finish(h->stream);
+}
+int32_t chip_debug_psd_combined_ds_shift(void *handle, double *shift, double *step_z, double *step_s, double sigma_mu) {
+    DebugPsd *h = (DebugPsd *)handle;
+    if (!h || !shift || !step_z || !step_s || step_z == step_s || shift == step_z || shift == step_s)
+        return fail(CHIP_ERR_ARG, "chip_debug_psd_combined_ds_shift: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugPsdStage st;
+    double *d0, *d1, *d2;
+    if ((rc = st.out(shift, (size_t)h->m, &d0)) || (rc = st.out(step_z, (size_t)h->m, &d1)) ||
+        (rc = st.out(step_s, (size_t)h->m, &d2)))
+        return rc;
+    dev::psd_combined_ds_shift(h->stream, h->pv, d0, d1, d2, sigma_mu);
+    return st.finish(h->stream);
+}
+int32_t chip_debug_psd_ds_from_dz_offset(void *handle, double *out, const double *ds) {
+    DebugPsd *h = (DebugPsd *)handle;
+    if (!h || !out || !ds) return fail(CHIP_ERR_ARG, "chip_debug_psd_ds_from_dz_offset: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugPsdStage st;
+    double *d0;
+    const double *d1;
+    if ((rc = st.out(out, (size_t)h->m, &d0)) || (rc = st.in(ds, (size_t)h->m, &d1))) return rc;
+    dev::psd_ds_from_dz_offset(h->stream, h->pv, d0, d1);
+    return st.finish(h->stream);
+}
+int32_t chip_debug_psd_step_length(void *handle, const double *dz, const double *ds, double amax, double *partial) {
+    DebugPsd *h = (DebugPsd *)handle;
+    if (!h || !dz || !ds || !partial) return fail(CHIP_ERR_ARG, "chip_debug_psd_step_length: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugPsdStage st;
+    const double *d0, *d1;
+    double *dp;
+    if ((rc = st.in(dz, (size_t)h->m, &d0)) || (rc = st.in(ds, (size_t)h->m, &d1)) ||
+        (rc = st.out(partial, h->sz.dim.size(), &dp)))
+        return rc;
+    (void)dev::psd_step_length(h->stream, h->pv, d0, d1, amax, dp);
+    h->last_jacobi_lds = dev::psd_last_jacobi_lds();
+    return st.finish(h->stream);
+}
+int32_t chip_debug_psd_margins(void *handle, const double *z, double *pmin, double *psum) {
+    DebugPsd *h = (DebugPsd *)handle;
+    if (!h || !z || !pmin || !psum) return fail(CHIP_ERR_ARG, "chip_debug_psd_margins: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugPsdStage st;
+    const double *d0;
+    double *dmin, *dsum;
+    if ((rc = st.in(z, (size_t)h->m, &d0)) || (rc = st.out(pmin, h->sz.dim.size(), &dmin)) ||
+        (rc = st.out(psum, h->sz.dim.size(), &dsum)))
+        return rc;
+    (void)dev::psd_margins(h->stream, h->pv, d0, dmin, dsum);
+    h->last_jacobi_lds = dev::psd_last_jacobi_lds();
+    return st.finish(h->stream);
+}
+int32_t chip_debug_psd_barrier(void *handle, const double *z, const double *s, const double *dz, const double *ds,
+                               double alpha, double *partial) {
+    DebugPsd *h = (DebugPsd *)handle;
+    if (!h || !z || !s || !dz || !ds || !partial) return fail(CHIP_ERR_ARG, "chip_debug_psd_barrier: bad argument");
+    int rc;
+    if ((rc = h->ready())) return rc;
+    DebugPsdStage st;
+    const double *d0, *d1, *d2, *d3;
+    double *dp;
+    const size_t m = (size_t)h->m;
+    if ((rc = st.in(z, m, &d0)) || (rc = st.in(s, m, &d1)) || (rc = st.in(dz, m, &d2)) || (rc = st.in(ds, m, &d3)) ||
+        (rc = st.out(partial, h->sz.dim.size(), &dp)))
+        return rc;
+    (void)dev::psd_barrier(h->stream, h->pv, d0, d1, d2, d3, alpha, dp);
+    return st.finish(h->stream);
 }
 #endif
 

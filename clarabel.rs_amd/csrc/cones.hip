@@ -988,7 +988,7 @@ __device__ double psd_eig_tridiag(double *A, int n, double *cs, double *red, dou
 __device__ double psd_eig_min(double *A, int n, double *cs, double *red, int *flag, double *psum) {
     if (n >= 12 && n <= WG && !(g_psd_no_mfma & 2)) return psd_eig_tridiag(A, n, cs, red, psum);
     const int np = (n + 1) & ~1, half = np / 2, tid = threadIdx.x;
-    double *cc = cs, *ss = cs + half;
+    double *cc = cs, *ss = cs + half; // (tau, s) of the round's rotations
     int *pp = (int *)(cs + 2 * half), *qq = pp + half;
     for (int sweep = 0; sweep < 40; ++sweep) {
         if (tid == 0) *flag = 0;
@@ -1008,22 +1008,29 @@ __device__ double psd_eig_min(double *A, int n, double *cs, double *red, int *fl
                     p = q;
                     q = t;
                 }
-                double c = 1.0, sn = 0.0;
+                // the rotation as (s, tau = s / (1 + c)), applied as x - s (y + tau x), y + s (x - tau y): c = 1 - s tau
+                // keeps the t^2 / 2 that 1 / sqrt(1 + t^2) rounds away below t = 1e-8, where (1, t) stretched the pair by
+                // 1 + t^2 at every one of the many tiny rotations of a sweep, always upwards (side 257: the trace, hence the
+                // sum of the eigenvalues, drifted by 8e-12 ||A||).  Only pairs that are not converged yet are rotated -- the
+                // criterion that ends the iteration: rotating rounding noise between equal diagonal entries (t = 1) never
+                // ends on a repeated eigenvalue (40 sweeps) and every needless rotation adds its rounding errors
+                double tau = 0.0, sn = 0.0;
                 if (q < n) {
                     const double apq = A[p + q * n], app = A[p + p * n], aqq = A[q + q * n];
-                    if (fabs(apq) > 1e-17 * sqrt(fabs(app * aqq)) && apq != 0.0) {
+                    if (fabs(apq) > 1e-15 * (fabs(app) + fabs(aqq))) {
                         const double theta = (aqq - app) / (2.0 * apq);
                         const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
-                        c = 1.0 / sqrt(1.0 + t * t);
+                        const double c = 1.0 / sqrt(1.0 + t * t);
                         sn = t * c;
-                        if (fabs(apq) > 1e-15 * (fabs(app) + fabs(aqq))) *flag = 1;
+                        tau = sn / (1.0 + c);
+                        *flag = 1;
                     }
                 } else {
                     q = -1; // (odd n: the player that sits this round out -- no partner, the identity rotation)
                 }
                 pp[pr] = p;
                 qq[pr] = q;
-                cc[pr] = c;
+                cc[pr] = tau;
                 ss[pr] = sn;
             }
             __syncthreads();
@@ -1038,15 +1045,15 @@ __device__ double psd_eig_min(double *A, int n, double *cs, double *red, int *fl
                 for (int w = tid; w < half * half; w += WG) {
                     const int p1 = pp[k1], q1 = qq[k1], p2 = pp[k2], q2 = qq[k2];
                     const bool h1 = q1 >= 0, h2 = q2 >= 0; // (false: the player that sits this round out)
-                    const double c1 = cc[k1], s1 = ss[k1], c2 = cc[k2], s2 = ss[k2];
+                    const double t1 = cc[k1], s1 = ss[k1], t2 = cc[k2], s2 = ss[k2];
                     const double app = A[p1 + p2 * n], apq = h2 ? A[p1 + q2 * n] : 0.0;
                     const double aqp = h1 ? A[q1 + p2 * n] : 0.0, aqq = (h1 && h2) ? A[q1 + q2 * n] : 0.0;
-                    const double bpp = c2 * app - s2 * apq, bpq = s2 * app + c2 * apq;
-                    const double bqp = c2 * aqp - s2 * aqq, bqq = s2 * aqp + c2 * aqq;
-                    A[p1 + p2 * n] = c1 * bpp - s1 * bqp;
-                    if (h1) A[q1 + p2 * n] = s1 * bpp + c1 * bqp;
-                    if (h2) A[p1 + q2 * n] = c1 * bpq - s1 * bqq;
-                    if (h1 && h2) A[q1 + q2 * n] = s1 * bpq + c1 * bqq;
+                    const double bpp = app - s2 * (apq + t2 * app), bpq = apq + s2 * (app - t2 * apq);
+                    const double bqp = aqp - s2 * (aqq + t2 * aqp), bqq = aqq + s2 * (aqp - t2 * aqq);
+                    A[p1 + p2 * n] = bpp - s1 * (bqp + t1 * bpp);
+                    if (h1) A[q1 + p2 * n] = bqp + s1 * (bpp - t1 * bqp);
+                    if (h2) A[p1 + q2 * n] = bpq - s1 * (bqq + t1 * bpq);
+                    if (h1 && h2) A[q1 + q2 * n] = bqq + s1 * (bpq - t1 * bqq);
                     k1 += d1;
                     k2 += d2;
                     if (k1 >= half) {
@@ -2179,6 +2186,10 @@ void sym_write_kkt(hipStream_t s, const SocView &v, const int *nn_rows, const in
 }
 // CHIP_NO_PSD_MFMA -> the device-side flag psd_gemm reads (set when it changes; the launches that follow on `s` see it)
 constexpr size_t PSD_JACOBI_LDS_MAX = 158 * 1024; // dynamic LDS a launch may ask for beside the kernels' small static arrays (160 KiB per CU)
+// doubles of dynamic LDS the calling thread's last psd_update_scaling / psd_step_length / psd_margins launch staged its
+// Jacobi / eigenvalue phase in (PsdView::jacobi_lds of that launch; 0: not staged, or the work matrices are in LDS anyway)
+static thread_local int t_psd_last_jacobi_lds = 0;
+int psd_last_jacobi_lds() { return t_psd_last_jacobi_lds; }
 static void psd_sync_switch(hipStream_t s) {
     // g_psd_no_mfma is a per-DEVICE symbol: the cached state is kept per device (one process may drive several GPUs)
     static std::atomic<int> cur[64];
@@ -2201,11 +2212,13 @@ void psd_update_scaling(hipStream_t s, const PsdView &v, const double *sv, const
         size_t lds = 0;
         if (need <= PSD_JACOBI_LDS_MAX && raise_dynamic_lds((const void *)k_psd_update_scaling<true>, need) == hipSuccess) lds = need;
         vs.jacobi_lds = (int)(lds / sizeof(double));
+        t_psd_last_jacobi_lds = vs.jacobi_lds;
         k_psd_update_scaling<true><<<v.ncones, WG, lds, s>>>(vs, sv, zv);
         return;
     }
     const size_t lds = ((size_t)(4 * v.maxdim * v.maxdim + 3 * v.maxdim) * sizeof(double) + 15) & ~(size_t)15;
     if (lds > 64 * 1024) (void)raise_dynamic_lds((const void *)k_psd_update_scaling<false>, (size_t)lds);
+    t_psd_last_jacobi_lds = 0;
     k_psd_update_scaling<false><<<v.ncones, WG, lds, s>>>(v, sv, zv);
 }
 bool psd_write_hs_rows_active(const PsdView &v) { return v.ncones > 0 && !v.scratch && v.rows_nblk > 0 && !switches().no_psd_rows; }
@@ -2244,9 +2257,11 @@ template <typename K> static void psd_allow_lds(K kernel, size_t lds) {
                 if (need_ <= PSD_JACOBI_LDS_MAX && raise_dynamic_lds((const void *)k_psd_ops<OP, true>, need_) == hipSuccess) jl_ = need_; \
             }                                                                        \
             vs_.jacobi_lds = (int)(jl_ / sizeof(double));                            \
+            if (OP == 4 || OP == 5) t_psd_last_jacobi_lds = vs_.jacobi_lds;          \
             k_psd_ops<OP, true><<<v.ncones, WG, jl_, s>>>(vs_, __VA_ARGS__);         \
         } else {                                                                     \
             const size_t lds_ = psd_ops_lds(v);                                      \
+            if (OP == 4 || OP == 5) t_psd_last_jacobi_lds = 0;                       \
             psd_allow_lds(k_psd_ops<OP, false>, lds_);                               \
             k_psd_ops<OP, false><<<v.ncones, WG, lds_, s>>>(v, __VA_ARGS__);         \
         }                                                                            \

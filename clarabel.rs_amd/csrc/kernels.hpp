@@ -496,6 +496,8 @@ struct PsdView {
     const int *blk_cone = nullptr, *row_ij = nullptr, *blk_m = nullptr, *blk_rowbase = nullptr, *blk_start = nullptr;
 };
 void psd_update_scaling(hipStream_t s, const PsdView &v, const double *sv, const double *zv);
+// PsdView::jacobi_lds of the calling thread's last psd_update_scaling / psd_step_length / psd_margins launch (tests)
+int psd_last_jacobi_lds();
 // (Lx / l0: k_psd_write_hs_rows writes the blocks into L as well -- only when the rows form runs, see psd_write_hs_rows_active)
 void psd_write_hs(hipStream_t s, const PsdView &v, double *Kx, double *Lx = nullptr, const int *l0 = nullptr);
 bool psd_write_hs_rows_active(const PsdView &v);

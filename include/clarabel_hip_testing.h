@@ -102,6 +102,33 @@ int32_t chip_debug_bplan_bunit_reset(void *h, double *x, double *sv, double *z, 
 int32_t chip_debug_bplan_bunscale(void *h, double *xo, const double *x, const double *d, double *zo, const double *z,
                                   const double *e, double *so, const double *sv, const double *einv, const double *sx,
                                   const double *sz);
+/* ---- the PSD cone kernels (csrc/cones.hip: k_psd_update_scaling, k_psd_ops<0..6>) alone ----
+ * chip_debug_psd_create: a bare view over a vector that holds only the svec ranges of `ncones` PSD triangle cones of
+ * sides dims[] (0 .. 1024), in order: rows = sum n (n + 1) / 2.  The sizing is the function chip_kkt_create calls (state
+ * of 3 n^2 + 2 n doubles per cone, maxdim, the maxdim > 64 scratch decision for ALL cones of the view and its stride);
+ * host only, no device is touched until the first runner uploads it to the current device.
+ * chip_debug_psd_counter: "gs" (1: work matrices in an HBM scratch slice, 0: in LDS), "jacobi_lds" (doubles of dynamic
+ * LDS the last update_scaling / step_length / margins launch staged its SVD / eigenvalue iteration in; 0: not staged, or
+ * gs == 0), "maxdim", "rows", "scratch_stride", "state_doubles".
+ * The runners (one per launcher of cones.hip) take HOST arrays of `rows` entries (per-cone outputs: ncones), copy them to
+ * device buffers (arrays the pass writes are uploaded as well), call the launcher ONCE on a private stream, synchronise
+ * and copy the written arrays back.  update_scaling: *ok <- 0 when a cone's S or Z has no Cholesky factor (the flag
+ * chip_kkt_update_scaling reads), 1 otherwise.  state: the state of cone `cone` as the kernels keep it, B (n x n, column
+ * major) | lambda (n) | lambda^-1/2 (n) | R (n x n) | Rinv (n x n).  combined_ds_shift updates step_z (<- W step_z) and
+ * step_s (<- W^-T step_s) in place, like the launcher. */
+int32_t chip_debug_psd_create(void **out, int64_t ncones, const int64_t *dims);
+void chip_debug_psd_destroy(void *h);
+int32_t chip_debug_psd_counter(const void *h, const char *name, double *out);
+int32_t chip_debug_psd_update_scaling(void *h, const double *s, const double *z, int32_t *ok);
+int32_t chip_debug_psd_state(void *h, int64_t cone, double *out);
+int32_t chip_debug_psd_mul_hs(void *h, double *y, const double *x);
+int32_t chip_debug_psd_affine_ds(void *h, double *ds);
+int32_t chip_debug_psd_combined_ds_shift(void *h, double *shift, double *step_z, double *step_s, double sigma_mu);
+int32_t chip_debug_psd_ds_from_dz_offset(void *h, double *out, const double *ds);
+int32_t chip_debug_psd_step_length(void *h, const double *dz, const double *ds, double amax, double *partial);
+int32_t chip_debug_psd_margins(void *h, const double *z, double *pmin, double *psum);
+int32_t chip_debug_psd_barrier(void *h, const double *z, const double *s, const double *dz, const double *ds,
+                               double alpha, double *partial);
 #ifdef __cplusplus
 }
 #endif
