@@ -258,7 +258,7 @@ __device__ __forceinline__ void flat_level_table(const LdlView &v, const BundleV
 }
 template <bool FWDMODE, int TW>
 __device__ __forceinline__ void bundle_sweep_flat(const LdlView &v, const BundleView &bv, int b, double *xs,
-                                                  const double *xt, double *tacc, int k, const int *lev_e) {
+                                                  const double *xt, double *tacc, int k, const int *lev_e, int dl = 0) {
     const int s0 = bv.bundle_ptr[b], nloc = bv.bundle_ptr[b + 1] - s0;
     const int nl = bv.blvl_ptr[b + 1] - bv.blvl_ptr[b] - 1;
     int tid = threadIdx.x;
@@ -297,8 +297,8 @@ __device__ __forceinline__ void bundle_sweep_flat(const LdlView &v, const Bundle
                 for (int u = 0; u < FLAT_U; ++u) {
                     const int t = bs + u * TW + tid;
                     const bool ok = t < ee_;
-                    ii[u] = ok ? (int)v.Li16[t] : -1;
-                    jj[u] = ok ? (int)v.Lj16[t] : 0;
+                    ii[u] = ok ? (int)v.Li16[t + dl] : -1;
+                    jj[u] = ok ? (int)v.Lj16[t + dl] : 0;
                     vv[u] = ok ? v.Lx[t] : 0.0;
                 }
 #pragma unroll
@@ -332,8 +332,8 @@ __device__ __forceinline__ void bundle_sweep_flat(const LdlView &v, const Bundle
         for (int u = 0; u < FLAT_U; ++u) {
             const int t = bs + u * TW + tid;
             const bool ok = t < en;
-            ii[u] = ok ? (int)v.Li16[t] : -1;
-            jj[u] = ok ? (int)v.Lj16[t] : 0;
+            ii[u] = ok ? (int)v.Li16[t + dl] : -1;
+            jj[u] = ok ? (int)v.Lj16[t + dl] : 0;
             vv[u] = ok ? v.Lx[t] : 0.0;
         }
     };
@@ -1134,7 +1134,8 @@ struct RunWalk {
 template <int TW, int NPT, int NLP>
 __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, const int *runs, const double (&c)[NPT],
                                          bool keep_e, double *xs, double *red, double *tacc3, int k, int s0,
-                                         int nloc, int nleaf, const double *xt, double *out_norm, double *out_share) {
+                                         int nloc, int nleaf, const double *xt, double *out_norm, double *out_share,
+                                         int du) {
     double cl[NLP]; // the candidate at the thread's leaf nodes, then (keep_e) their residual
     const int *__restrict__ Up = v.Up;
     const unsigned short *__restrict__ Ucol16 = v.Ucol16, *__restrict__ Urow16 = v.Urow16;
@@ -1194,7 +1195,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
                 for (int q = 0; q < LS; ++q) {
                     const int t = tb[u] + q;
                     const bool ok = t < te[u];
-                    jj[u][q] = ok ? (int)Ucol16[t] : -1;
+                    jj[u][q] = ok ? (int)Ucol16[t + du] : -1;
                     vv[u][q] = ok ? Ux[t] : 0.0;
                 }
             }
@@ -1217,7 +1218,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
 #pragma unroll
                 for (int q = 0; q < LS; ++q)
                     if (jj[u][q] >= 0) apply(jj[u][q], vv[u][q]);
-                for (int t = tb[u] + LS; t < te[u]; ++t) apply((int)Ucol16[t], Ux[t]); // (a leaf with a long row: rare)
+                for (int t = tb[u] + LS; t < te[u]; ++t) apply((int)Ucol16[t + du], Ux[t]); // (a leaf with a long row: rare)
                 if (i < nleaf) {
                     const double val = bi[u] - acc[u];
                     if (keep_e) cl[p * LR + u] = val;
@@ -1239,8 +1240,8 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
             for (int u = 0; u < FLAT_U; ++u) {
                 const int t = bs + u * TW + tid;
                 const bool ok = t < fe;
-                pi[u] = ok ? (int)Urow16[t] : -1;
-                pj[u] = ok ? (int)Ucol16[t] : 0;
+                pi[u] = ok ? (int)Urow16[t + du] : -1;
+                pj[u] = ok ? (int)Ucol16[t + du] : 0;
                 pv[u] = ok ? Ux[t] : 0.0;
             }
         };
@@ -1317,6 +1318,9 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
     __shared__ int lev_e[FLAT_MAXLEV + 1];
     __shared__ double tacc3[8];
     __shared__ IrState st;
+    // the bundle's entry offsets into the index arrays of L / U (IrView::pat_off; 0, 0: its own copy), stored once and
+    // picked up as scalars at every phase's call site (loaded from the table per phase they cost scratch and registers)
+    __shared__ int pat[2];
     const int nb = bv.nb, G = gridDim.x, tid = threadIdx.x, b = blockIdx.x;
     const int k = fold.k;
     const bool folded = k > 0; // a barrier in the middle of every round
@@ -1340,6 +1344,8 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
         st.par = 0;
         st.gen = 0;
         st.pad = 0; // (1: the last verdict accepted its candidate)
+        pat[0] = ir.pat_off ? ir.pat_off[2 * b] : 0;
+        pat[1] = ir.pat_off ? ir.pat_off[2 * b + 1] : 0;
         if (b == 0) {
             ir.res[0] = 0; // "did not finish" until the verdict is written at the very end
             ir.res[2] = 0;
@@ -1544,7 +1550,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
         const int par = round & 1;
         __syncthreads();
         stamp();
-        bundle_sweep_flat<true, TW>(v, bv, b, xs, nullptr, st.tacc, k, lev_e);
+        bundle_sweep_flat<true, TW>(v, bv, b, xs, nullptr, st.tacc, k, lev_e, __builtin_amdgcn_readfirstlane(pat[0]));
         stamp();
         if (tid < k) ir_store(&shf[(size_t)b * k + tid], st.tacc[tid]);
         if (folded) {
@@ -1580,7 +1586,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
         }
         __syncthreads();
         stamp();
-        bundle_sweep_flat<false, TW>(v, bv, b, xs, st.dxt, nullptr, k, lev_e);
+        bundle_sweep_flat<false, TW>(v, bv, b, xs, st.dxt, nullptr, k, lev_e, __builtin_amdgcn_readfirstlane(pat[0]));
         stamp();
         // the candidate: x (round 0) or x + dx (directldlkktsolver.rs:300 axpby(1, x, 1)), into the registers
         const bool more_possible = ir.ir_enable && round < ir.maxiter;
@@ -1658,7 +1664,8 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
         } else {
             stamp();
             irs_symv<TW, NPT, NLP>(v, ir, st.runs, c, more_possible, xs, red, tacc3, k, s0, nloc, nleaf, st.candt,
-                                   &pn[(size_t)par * nb + b], &shs[(size_t)par * nb * k + (size_t)b * k]);
+                                   &pn[(size_t)par * nb + b], &shs[(size_t)par * nb * k + (size_t)b * k],
+                                   __builtin_amdgcn_readfirstlane(pat[1]));
         }
         pending = true;
         if (folded && more_possible) continue; // (the verdict rides on the next round's barrier)

@@ -590,6 +590,24 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
     if (rc) return rc;
     clk("analysis (total)");
     Engine &E = h->E;
+    // pattern classes of the bundles, only for systems whose solves k_bundle_irs can take (an arrow system, every bundle
+    // within that kernel's limits: the host's part of the ir_sf conditions below); host analysis, so the figures are
+    // there on a host-only handle too.  Every other system (a grouped fold, a level-scheduled top) skips all of it.
+    PatternShare pat;
+    {
+        const i32 nbun = S.bundle_ptr.empty() ? 0 : (i32)S.bundle_ptr.size() - 1;
+        bool cand = !S.Li16.empty() && S.gf_ng == 0 && S.nfold >= 1 && nbun > 0;
+        for (i32 b = 0; b < nbun && cand; b++) {
+            const i32 s0 = S.bundle_ptr[(size_t)b], nloc = S.bundle_ptr[(size_t)b + 1] - s0;
+            const i32 nleaf = S.blvl[(size_t)S.blvl_ptr[(size_t)b] + 1] - s0;
+            cand = dev::irs_bundle_ok(nloc, nleaf, S.blvl_ptr[(size_t)b + 1] - S.blvl_ptr[(size_t)b] - 1, 1);
+        }
+        if (cand) {
+            bundle_pattern_classes(S, pat);
+            E.note_patterns(pat);
+            clk("pattern classes");
+        }
+    }
     if (st.device == CHIP_DEVICE_HOST_ONLY) {
         E.init_host_only(S, st);
         *out = h.release();
@@ -878,6 +896,7 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
                 sf = dev::irs_bundle_ok(nloc, nleaf, nlev, rp[(size_t)b + 1] - rp[(size_t)b]);
             }
             h->ir_sf = sf && dev::bundle_irs_capacity_ok(E.bundles);
+            if (h->ir_sf && !switches().no_shared_pattern && (rc = E.upload_patterns(pat))) return rc;
         }
     }
     clk("maps, cone tables");
@@ -1532,6 +1551,19 @@ static int fused_enqueue(chip_kkt *h, double *lhsx_dev, double *lhsz_dev, int *s
         dev::GStepView gsv = E.gstep;
         if (!E.gstep_vals_valid) gsv.gsl = gsv.gsu = nullptr; // (gather L and K through the source positions instead)
         rc = dev::gstep_solve(E.stream, E.view(), E.bundles, ir, E.gfold, gsv);
+    } else if (ir.sf) {
+        // k_bundle_irs: identical bundles read ONE copy of their index pattern through per-bundle entry offsets
+        // (host.hpp: PatternShare); the kernel has no residual spill, the table travels in that slot of the view
+        dev::LdlView lv = E.view();
+        ir.pat_off = nullptr;
+        if (E.pat_off && !switches().no_shared_pattern) {
+            lv.Li16 = E.pat_Li16;
+            lv.Lj16 = E.pat_Lj16;
+            lv.Ucol16 = E.pat_Ucol16;
+            lv.Urow16 = E.pat_Urow16;
+            ir.pat_off = E.pat_off;
+        }
+        rc = dev::bundle_ir(E.stream, lv, E.bundles, E.fold, ir, E.ir_grid, E.ir_tw, E.gfold);
     } else {
         rc = dev::bundle_ir(E.stream, E.view(), E.bundles, E.fold, ir, E.ir_grid, E.ir_tw, E.gfold);
     }
@@ -2231,6 +2263,15 @@ int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out
         for (const auto &r : E.gs_runs) c += r.nlev;
         *out = c;
     }
+    // pattern classes of the bundles (host.hpp: PatternShare): all but the last are host analysis, on host-only handles too
+    else if (k == "pattern_classes") *out = E.pat_classes;
+    else if (k == "pattern_index_bytes") *out = (double)E.pat_index_bytes;
+    else if (k == "pattern_bundles") *out = E.pat_bundles;
+    else if (k == "pattern_full_index_bytes") *out = (double)E.pat_full_bytes;
+    else if (k == "pattern_verified_bundles") *out = E.pat_verified;
+    else if (k == "pattern_mismatches") *out = E.pat_mismatches;
+    else if (k == "pattern_shared_bundles") // bundles whose fused solve launch reads a shared copy
+        *out = (h->ir_sf && E.pat_off && !switches().no_shared_pattern) ? E.bundles.nb : 0;
     else return fail(CHIP_ERR_ARG, "chip_debug_counter: unknown name");
     return CHIP_OK;
 }

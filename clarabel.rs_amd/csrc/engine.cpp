@@ -862,6 +862,17 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
     return CHIP_OK;
 }
 
+// one shared copy of the bundles' index pattern for k_bundle_irs (host.hpp: PatternShare); nothing when P has no arrays
+int Engine::upload_patterns(const PatternShare &P) {
+    if (P.off.empty() || (int)(P.off.size() / 2) != bundles.nb || P.mismatches) return CHIP_OK;
+    int rc;
+    if ((rc = upload(&pat_Li16, P.Li16, P.Li16.size()))) return rc;
+    if ((rc = upload(&pat_Lj16, P.Lj16, P.Lj16.size()))) return rc;
+    if ((rc = upload(&pat_Ucol16, P.Ucol16, P.Ucol16.size()))) return rc;
+    if ((rc = upload(&pat_Urow16, P.Urow16, P.Urow16.size()))) return rc;
+    return upload(&pat_off, P.off, P.off.size()); // (last: pat_off != nullptr says that all five are there)
+}
+
 dev::LdlView Engine::view() const {
     dev::LdlView v{};
     v.N = N;

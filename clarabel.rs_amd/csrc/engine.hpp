@@ -198,6 +198,20 @@ struct Engine {
     unsigned short *sLi16 = nullptr, *sLj16 = nullptr; // dev::LdlView::sLi16
     unsigned short *fu_rec = nullptr, *fu_slot = nullptr;
     int *fu_ptr = nullptr;
+    // pattern classes of the bundles (host.hpp: PatternShare).  The figures are kept on every handle of a system that
+    // k_bundle_irs can take (capi.cpp: chip_kkt_create; all 0 elsewhere), host-only ones included; the shared index
+    // arrays and the offset table are on the device only where k_bundle_irs takes the solves (pat_off == nullptr: that
+    // kernel reads the full arrays with offset 0, like every other kernel)
+    int pat_classes = 0, pat_bundles = 0, pat_verified = 0, pat_mismatches = 0;
+    long long pat_index_bytes = 0, pat_full_bytes = 0;
+    unsigned short *pat_Li16 = nullptr, *pat_Lj16 = nullptr, *pat_Ucol16 = nullptr, *pat_Urow16 = nullptr;
+    int *pat_off = nullptr;
+    void note_patterns(const PatternShare &P) {
+        pat_classes = P.classes, pat_verified = P.verified, pat_mismatches = P.mismatches;
+        pat_index_bytes = (long long)P.index_bytes();
+        pat_bundles = P.bundles, pat_full_bytes = P.full_bytes;
+    }
+    int upload_patterns(const PatternShare &P);
     // grouped fold with small bundles: the step kernels (dev::gstep_solve / gstep_factor); gstep.desc == nullptr: not used
     dev::GStepView gstep{};
     bool gstep_solve_on = false, gstep_factor_on = false;

@@ -239,6 +239,25 @@ int analyse(i64 n, const i64 *Ap, const i64 *Ai, const int8_t *dsigns_or_null,
             const std::vector<i64> &perm0, double amd_dense_scale, Symbolic &S, i32 target_wg = 1024,
             const std::vector<i32> *clique_of = nullptr);
 
+// Pattern classes of the bundles (symbolic.cpp): k_bundle_irs reads the 16-bit index arrays of a bundle (Li16 / Lj16
+// over [Lp[s0], Lp[s1]), Ucol16 / Urow16 over [Up[s0], Up[s1])) six times per launch, and a problem of identical blocks
+// under one coupling row (config 3: 1000 x SOC(1001)) has the SAME bytes in every bundle's slices.  Two bundles are in
+// one class iff their node count, their bundle-relative level table and those four slices are byte-equal; the shared
+// arrays are the slices of the classes' first members one after the other (+ 1 entry of padding, like the originals),
+// and bundle b reads entry t of its own numbering at t + off[2 b] (L) / t + off[2 b + 1] (U) of the shared arrays.
+// Every offset has been checked against the originals byte for byte before it is handed out (verified / mismatches).
+// The arrays stay empty when S has no Li16, when sharing is dropped after a mismatch, or when they would not be
+// smaller than half the originals (classes is still counted).
+struct PatternShare {
+    i32 classes = 0, bundles = 0;
+    i64 full_bytes = 0;               // bytes of S.Li16, Lj16, Ucol16, Urow16 together (what the shared arrays stand in for)
+    i32 verified = 0, mismatches = 0; // bundles whose slices were compared through their offsets / that differed
+    std::vector<uint16_t> Li16, Lj16, Ucol16, Urow16;
+    std::vector<i32> off;             // 2 per bundle
+    size_t index_bytes() const { return (Li16.size() + Lj16.size() + Ucol16.size() + Urow16.size()) * sizeof(uint16_t); }
+};
+void bundle_pattern_classes(const Symbolic &S, PatternShare &P);
+
 // ---------------------------------------------------------------------------
 // KKT assembly (kkt_assembly.cpp)  -- kkt_assembly.rs:20-183, datamaps.rs
 // ---------------------------------------------------------------------------

@@ -187,7 +187,11 @@ struct IrView {
     const int *run_ptr, *runs;
     double *bp;            // N: the permuted right-hand side, kept for the residuals
     double *xa, *xb;       // N each: accepted iterate / candidate (the roles swap)
-    double *ebuf;          // N: residual spill, used only when a workgroup owns several bundles
+    union {                // (one slot, so that the argument layout of k_bundle_ir / k_gstep_solve stays what it was)
+        double *ebuf;      // k_bundle_ir (sf == 0): N, residual spill, used only when a workgroup owns several bundles
+        const int *pat_off; // k_bundle_irs (sf != 0; it has no spill): per bundle the entry offsets {L, U} into the index arrays of the
+                           // LdlView it is launched with (one shared copy per class of identical bundles, host.hpp: PatternShare), or nullptr: 0, 0
+    };
     double *lhsx, *lhsz;   // outputs in the caller's order (either may be nullptr)
     double *part;          // ir_part_doubles(nb, k) doubles of partial results
     int *ctl;              // ir_ctl_ints() ints, zero at launch: the grid barrier's counters (a launch that runs

@@ -46,6 +46,7 @@ const Entry TABLE[] = {
     {"CHIP_NO_BUNDLE_FLAT_SWEEP", Entry::FLAG, SW(no_bundle_flat_sweep), 0},
     {"CHIP_NO_FLAT", Entry::FLAG, SW(no_flat), 0},
     {"CHIP_NO_IR_SF", Entry::FLAG, SW(no_ir_sf), 0},
+    {"CHIP_NO_SHARED_PATTERN", Entry::FLAG, SW(no_shared_pattern), 0},
     {"CHIP_IRS_FLAGS", Entry::INT, SW(irs_flags), 0},
     {"CHIP_IR_TEST_DROP", Entry::FLAG, SW(ir_test_drop), 0},
     {"CHIP_IR_DEBUG", Entry::INT, SW(ir_debug), 0},

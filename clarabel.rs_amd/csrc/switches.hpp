@@ -44,6 +44,7 @@ struct Switches {
     bool no_flat = false;           // CHIP_NO_FLAT: column-per-thread sweeps inside k_bundle_ir
     int irs_flags = -1;             // CHIP_IRS_FLAGS: experiment bits of k_bundle_irs (-1: the defaults; kernels.hpp: IrView::sf)
     bool no_ir_sf = false;          // CHIP_NO_IR_SF: the fused solve stays on k_bundle_ir also where k_bundle_irs (candidate on chip, no permuted copy of b) applies
+    bool no_shared_pattern = false; // CHIP_NO_SHARED_PATTERN: k_bundle_irs reads every bundle's own copy of the 16-bit index arrays, also where identical bundles could share one (host.hpp: PatternShare)
     bool ir_test_drop = false;      // CHIP_IR_TEST_DROP (tests: a fused launch that cannot complete its barrier)
     int ir_debug = 0;               // CHIP_IR_DEBUG: 1 = stamps of two workgroups on stderr, 2 = all workgroups -> file
     std::string ir_debug_file;      // CHIP_IR_DEBUG_FILE

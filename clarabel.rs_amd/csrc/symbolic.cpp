@@ -1719,4 +1719,113 @@ int analyse(i64 n, const i64 *Ap, const i64 *Ai, const int8_t *dsigns, const std
     return 0;
 }
 
+// ---- pattern classes of the bundles (host.hpp: PatternShare) ----------------------------------------
+void bundle_pattern_classes(const Symbolic &S, PatternShare &P) {
+    P = PatternShare();
+    if (S.Li16.empty() || S.bundle_ptr.size() < 2) return;
+    const i32 nb = (i32)S.bundle_ptr.size() - 1;
+    P.bundles = nb;
+    P.full_bytes = (i64)((S.Li16.size() + S.Lj16.size() + S.Ucol16.size() + S.Urow16.size()) * sizeof(uint16_t));
+    struct Slices { // what decides a bundle's class
+        i32 nloc, nlv;
+        const i32 *lv;
+        i32 s0;
+        i64 l0, ln, u0, un; // first entry and length of the L / U slices
+    };
+    auto slices = [&](i32 b) {
+        const i32 s0 = S.bundle_ptr[b], s1 = S.bundle_ptr[b + 1];
+        return Slices{s1 - s0, S.blvl_ptr[b + 1] - S.blvl_ptr[b], S.blvl.data() + S.blvl_ptr[b], s0,
+                      S.Lp[s0], S.Lp[s1] - S.Lp[s0], S.Up[s0], S.Up[s1] - S.Up[s0]};
+    };
+    auto same = [&](const Slices &a, const Slices &c) {
+        if (a.nloc != c.nloc || a.nlv != c.nlv || a.ln != c.ln || a.un != c.un) return false;
+        for (i32 l = 0; l < a.nlv; l++)
+            if (a.lv[l] - a.s0 != c.lv[l] - c.s0) return false;
+        const size_t lb = (size_t)a.ln * sizeof(uint16_t), ub = (size_t)a.un * sizeof(uint16_t);
+        return std::memcmp(&S.Li16[(size_t)a.l0], &S.Li16[(size_t)c.l0], lb) == 0 &&
+               std::memcmp(&S.Lj16[(size_t)a.l0], &S.Lj16[(size_t)c.l0], lb) == 0 &&
+               std::memcmp(&S.Ucol16[(size_t)a.u0], &S.Ucol16[(size_t)c.u0], ub) == 0 &&
+               std::memcmp(&S.Urow16[(size_t)a.u0], &S.Urow16[(size_t)c.u0], ub) == 0;
+    };
+    // candidates by hash (FNV-1a over everything `same` compares), decided by the full comparison
+    std::vector<uint64_t> hash((size_t)nb);
+    run_threads(par_threads((i64)S.Li16.size() + (i64)S.Ucol16.size()), [&](int t, int TT) {
+        for (i32 b = t; b < nb; b += TT) {
+            const Slices a = slices(b);
+            uint64_t h = 1469598103934665603ull;
+            auto mix = [&h](const void *p, size_t bytes) {
+                const unsigned char *c = (const unsigned char *)p;
+                for (size_t i = 0; i < bytes; i++) h = (h ^ c[i]) * 1099511628211ull;
+            };
+            mix(&a.nloc, sizeof a.nloc);
+            for (i32 l = 0; l < a.nlv; l++) {
+                const i32 rel = a.lv[l] - a.s0;
+                mix(&rel, sizeof rel);
+            }
+            mix(&S.Li16[(size_t)a.l0], (size_t)a.ln * sizeof(uint16_t));
+            mix(&S.Lj16[(size_t)a.l0], (size_t)a.ln * sizeof(uint16_t));
+            mix(&S.Ucol16[(size_t)a.u0], (size_t)a.un * sizeof(uint16_t));
+            mix(&S.Urow16[(size_t)a.u0], (size_t)a.un * sizeof(uint16_t));
+            hash[(size_t)b] = h;
+        }
+    });
+    std::vector<i32> order((size_t)nb), cls((size_t)nb, -1), rep; // rep[c]: first member of class c
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](i32 a, i32 c) { return hash[(size_t)a] < hash[(size_t)c]; });
+    for (i32 p = 0, q; p < nb; p = q) { // one run of equal hashes
+        const size_t first = rep.size();
+        for (q = p; q < nb && hash[(size_t)order[(size_t)q]] == hash[(size_t)order[(size_t)p]]; q++) {
+            const i32 b = order[(size_t)q];
+            const Slices a = slices(b);
+            for (size_t c = first; c < rep.size() && cls[(size_t)b] < 0; c++)
+                if (same(a, slices(rep[c]))) cls[(size_t)b] = (i32)c;
+            if (cls[(size_t)b] < 0) {
+                cls[(size_t)b] = (i32)rep.size();
+                rep.push_back(b);
+            }
+        }
+    }
+    P.classes = (i32)rep.size();
+    i64 nl = 0, nu = 0;
+    for (i32 r : rep) nl += slices(r).ln, nu += slices(r).un;
+    if (2 * (nl + nu) >= (i64)S.Lp[S.NF] + S.Up[S.NF]) return; // (not smaller than half the bundles' own entries: nothing to gain)
+    std::vector<i64> cl0(rep.size()), cu0(rep.size());      // where a class starts in the shared arrays
+    P.Li16.assign((size_t)nl + 1, 0);
+    P.Lj16.assign((size_t)nl + 1, 0);
+    P.Ucol16.assign((size_t)nu + 1, 0);
+    P.Urow16.assign((size_t)nu + 1, 0);
+    nl = nu = 0;
+    for (size_t c = 0; c < rep.size(); c++) {
+        const Slices a = slices(rep[c]);
+        cl0[c] = nl, cu0[c] = nu;
+        std::copy_n(&S.Li16[(size_t)a.l0], a.ln, &P.Li16[(size_t)nl]);
+        std::copy_n(&S.Lj16[(size_t)a.l0], a.ln, &P.Lj16[(size_t)nl]);
+        std::copy_n(&S.Ucol16[(size_t)a.u0], a.un, &P.Ucol16[(size_t)nu]);
+        std::copy_n(&S.Urow16[(size_t)a.u0], a.un, &P.Urow16[(size_t)nu]);
+        nl += a.ln, nu += a.un;
+    }
+    P.off.resize(2 * (size_t)nb);
+    for (i32 b = 0; b < nb; b++) {
+        const Slices a = slices(b);
+        P.off[2 * (size_t)b] = (i32)(cl0[(size_t)cls[(size_t)b]] - a.l0);
+        P.off[2 * (size_t)b + 1] = (i32)(cu0[(size_t)cls[(size_t)b]] - a.u0);
+    }
+    // what the kernel will read, against what it read before: every bundle, every byte, through the offsets alone
+    for (i32 b = 0; b < nb; b++) {
+        const Slices a = slices(b);
+        const i64 l = a.l0 + P.off[2 * (size_t)b], u = a.u0 + P.off[2 * (size_t)b + 1];
+        const size_t lb = (size_t)a.ln * sizeof(uint16_t), ub = (size_t)a.un * sizeof(uint16_t);
+        const bool ok = l >= 0 && l + a.ln < (i64)P.Li16.size() && u >= 0 && u + a.un < (i64)P.Ucol16.size() &&
+                        std::memcmp(&P.Li16[(size_t)l], &S.Li16[(size_t)a.l0], lb) == 0 &&
+                        std::memcmp(&P.Lj16[(size_t)l], &S.Lj16[(size_t)a.l0], lb) == 0 &&
+                        std::memcmp(&P.Ucol16[(size_t)u], &S.Ucol16[(size_t)a.u0], ub) == 0 &&
+                        std::memcmp(&P.Urow16[(size_t)u], &S.Urow16[(size_t)a.u0], ub) == 0;
+        P.verified++;
+        if (!ok) P.mismatches++;
+    }
+    if (P.mismatches) { // (never seen; the kernel must not get an offset that was not verified)
+        P.Li16.clear(), P.Lj16.clear(), P.Ucol16.clear(), P.Urow16.clear(), P.off.clear();
+    }
+}
+
 } // namespace chip

@@ -20,7 +20,12 @@ int32_t chip_debug_set_switch(const char *name, const char *value_or_null);
  * mechanism a handle ended up with: "dense_blocks" / "dense_block_rows" (dense diagonal blocks of the top that the
  * residual multiplies from K's values directly), "nnzS" (entries of the full-row copy of the top rows), "psd_hs_row_blocks" (> 0: the PSD cones write Hs row by row
  * of the value store, k_psd_write_hs_rows),
- * "assembled_levels" (unit levels whose ancestor updates can be assembled per target column), "assembled_targets".
+ * "assembled_levels" (unit levels whose ancestor updates can be assembled per target column), "assembled_targets",
+ * "pattern_classes" / "pattern_bundles" / "pattern_index_bytes" / "pattern_full_index_bytes" / "pattern_verified_bundles" /
+ * "pattern_mismatches" (host analysis, on host-only handles too: classes of bundles with byte-equal 16-bit index
+ * slices, the bundles, bytes of the shared index arrays and of the full ones, bundles whose offsets were checked against
+ * the full arrays and how many differed), "pattern_shared_bundles" (bundles whose fused solve launch reads a shared copy:
+ * 0 on a host-only handle or with CHIP_NO_SHARED_PATTERN).
  * Returns CHIP_ERR_ARG for an unknown name. */
 int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out);
 /* a spinner of `blocks` x `threads` for `usec` microseconds on the stream of a communicator (opaque chip_comm *), behind
