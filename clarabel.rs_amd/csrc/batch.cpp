@@ -1,7 +1,7 @@
 // batch.cpp -- the batched L4 solver (chip_batch_*): nprob independent problems of Zero / Nonnegative / SecondOrder
 // cones, stacked block-diagonally, solved by ONE interior-point loop whose scalars are kept per member:
-//   setup: Ruiz equilibration of the stack with one cost scale per member (batch.hip), the members' norms of q and b
-//          and cone degrees, one L2 chip_kkt on the equilibrated stack (its K is block-diagonal: one tree per member);
+//   setup: problem_data.hpp's steps, shared with solver.cpp, on the stack: Ruiz equilibration with one cost scale per
+//          member (batch.hip), one L2 chip_kkt (block-diagonal K: one tree per member); per member norms and degrees;
 //   solve: core/solver.rs:242-464 with tau, kappa, mu, sigma, the step length, DefaultInfo's scalars, the iteration
 //          count and the status of every member on the host, read back from one device-to-host copy per reduction
 //          pass.  Members that terminate are frozen: their step length is 0, selected per entry, and their part of
@@ -24,6 +24,7 @@
 #include "engine.hpp"
 #include "host_util.hpp"
 #include "ipm_info.hpp"
+#include "problem_data.hpp"
 #include "problem_update.hpp"
 
 using namespace chip;
@@ -160,13 +161,13 @@ int host_plan_upload(DevPool &mem, const HostPlan &hp, dev::BatchPlan *pl) {
 } // namespace
 
 struct chip_batch {
-    int nprob = 0, n = 0, m = 0, device = 0;
+    int nprob = 0;
     chip_solver_settings st{};
     DevPool mem;
     std::vector<int> xoff, zoff;
     dev::BatchPlan plan{};
-    dev::EqMats M{};
-    double *q = nullptr, *b = nullptr, *d = nullptr, *e = nullptr, *dinv = nullptr, *einv = nullptr, *negq = nullptr;
+    ProblemData pd; // the whole stack
+    double *negq = nullptr;
     // for the data updates (chip_bdata_*): the unscaled q and b (the members' norms are taken from them, as create
     // takes them from the user's data) and the members' cost scales on the device
     double *uq = nullptr, *ub = nullptr, *dc = nullptr;
@@ -284,7 +285,6 @@ struct chip_batch {
         launches++;
         return kktsystem_spmv(sys, which, y, aux, alpha_, x);
     }
-    int equilibrate(const std::vector<ConeSpec> &cones);
     int default_start();
     int residual_pass();
     void member_info(int k);
@@ -297,7 +297,6 @@ struct chip_batch {
     int end_member(int k, int status, int iterations, bool from_prev);
     int update_work();
     static constexpr const char *UPD_PREFIX = "chip_bdata_update_";
-    int update_len(int which) const { return which == UPD_P ? M.nnzP : which == UPD_A ? M.nnzA : which == UPD_Q ? n : m; }
     static int update_args(chip_batch *h, int which, const void *idx, const double *vals, int64_t k);
     int stage_upload(const uint64_t *idx, const double *vals, size_t k) {
         return stage.upload(stream, idx, vals, k, &upd_launches, &upd_syncs);
@@ -306,53 +305,6 @@ struct chip_batch {
     int backward_work();
     int backward(const double *gx_dev, const double *gz_dev, const double *gs_dev);
 };
-
-int chip_batch::equilibrate(const std::vector<ConeSpec> &cones) {
-    std::vector<double> ones((size_t)std::max(n, m), 1.0);
-    if (n) CHIP_HIP(hipMemcpy(d, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    if (m) CHIP_HIP(hipMemcpy(e, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
-    c.assign((size_t)nprob, 1.0);
-    if (!st.equilibrate_enable) {
-        if (n) CHIP_HIP(hipMemcpy(dinv, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-        if (m) CHIP_HIP(hipMemcpy(einv, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
-        return CHIP_OK;
-    }
-    DevPool work;
-    unsigned long long *bits = nullptr;
-    double *cstate = nullptr, *colsum = nullptr, *delta = nullptr, *scr = nullptr;
-    const size_t nbits = dev::batch_eq_bits_words(n, m, nprob);
-    int rc;
-    if ((rc = work.alloc(&bits, nbits)) || (rc = work.alloc(&cstate, 2 * (size_t)nprob)) ||
-        (rc = work.alloc(&colsum, (size_t)nprob)) || (rc = work.alloc(&delta, (size_t)m)) ||
-        (rc = work.alloc(&scr, dev::seg_scratch_doubles(plan))))
-        return rc;
-    std::vector<double> c0(2 * (size_t)nprob, 1.0);
-    CHIP_HIP(hipMemcpy(cstate, c0.data(), c0.size() * 8, hipMemcpyHostToDevice));
-    hipStream_t s = stream;
-    for (int it = 0; it < st.equilibrate_max_iter; it++) {
-        CHIP_HIP(hipMemsetAsync(bits, 0, nbits * sizeof(unsigned long long), s));
-        dev::batch_eq_ruiz_step(s, plan, M, q, b, d, e, bits, scr, colsum, cstate, st.equilibrate_min_scaling,
-                                st.equilibrate_max_scaling);
-    }
-    // rectification of the second-order cones (compositecone.rs:183-195): per cone, so per member already
-    std::vector<int> sb, se;
-    for (const ConeSpec &cs : cones)
-        if (cs.tag == CHIP_CONE_SECONDORDER && cs.numel > 0) {
-            sb.push_back((int)cs.start);
-            se.push_back((int)(cs.start + cs.numel));
-        }
-    int *dsb = nullptr, *dse = nullptr;
-    if (!sb.empty()) {
-        if ((rc = work.upload(&dsb, sb.data(), sb.size())) || (rc = work.upload(&dse, se.data(), se.size()))) return rc;
-        dev::eq_rectify(s, M, b, e, m, dsb, dse, (int)sb.size(), delta);
-    }
-    dev::eq_invert(s, d, dinv, n, e, einv, m);
-    CHIP_HIP(hipGetLastError());
-    CHIP_HIP(hipMemcpyAsync(c0.data(), cstate, (size_t)nprob * 8, hipMemcpyDeviceToHost, s));
-    CHIP_HIP(hipStreamSynchronize(s));
-    for (int k = 0; k < nprob; k++) c[k] = c0[k];
-    return CHIP_OK;
-}
 
 int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n,
                           int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval, const double *Pnzval,
@@ -371,18 +323,14 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
         return fail(CHIP_ERR_ARG, "chip_batch_create: missing data");
     const double t0 = now_s();
     std::unique_ptr<chip_batch> h(new chip_batch());
-    if (settings) h->st = *settings;
-    else chip_solver_settings_default(&h->st);
     chip_solver_settings &st = h->st;
-    st.linsys.linesearch_backtrack_step = st.linesearch_backtrack_step;
-    st.linsys.min_terminate_step_length = st.min_terminate_step_length;
+    create_settings(settings, st);
     if (st.presolve_enable || st.chordal_decomposition_enable)
         return fail(CHIP_ERR_UNSUPPORTED, "chip_batch_create: presolve and chordal decomposition are not supported");
     if (int rc = batch_cones_supported(ncones, cone_tags)) return rc;
-    if (nprob >= (1ll << 31)) return fail(CHIP_ERR_DIM, "chip_batch_create: sizes out of int32 range");
-    const uint64_t nnzP = Pcolptr[n], nnzA = Acolptr[n];
-    if (n >= (1ll << 31) || m >= (1ll << 31) || nnzP + nnzA + (uint64_t)n + (uint64_t)m >= (1ull << 31) ||
-        n + 2 * m >= (1ll << 31))
+    const ProblemArgs a{n,      m,         Pcolptr,   Prowval,  Pnzval, q, Acolptr, Arowval, Anzval, b,
+                        ncones, cone_tags, cone_dims, cone_dims2};
+    if (nprob >= (1ll << 31) || !a.fits_int32())
         return fail(CHIP_ERR_DIM, "chip_batch_create: sizes out of int32 range");
     // ---- the partition and the checks that every entry and cone stays inside its member
     const int np = (int)nprob;
@@ -390,99 +338,67 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     const int plan_rc = host_plan_build(hp, nprob, n_part, m_part, n, m, ncones, cone_tags, cone_dims, cone_dims2);
     if (plan_rc && !hp.parts_ok) return plan_rc;
     const std::vector<int> &xoff = hp.xoff, &zoff = hp.zoff, &zmem = hp.zmem, &xmem = hp.xmem;
-    std::vector<int> Prow(nnzP), Pcol(nnzP), Arow(nnzA), Acol(nnzA);
+    CooPattern co;
     std::vector<int> lp_init((size_t)np, 1);
-    for (int64_t j = 0; j < n; j++) {
+    int rc = coordinate_form(a, co, [&](char mat, int64_t j, int64_t r) {
         const int k = xmem[j];
-        for (uint64_t p = Pcolptr[j]; p < Pcolptr[j + 1]; p++) {
-            const int64_t r = (int64_t)Prowval[p];
-            if (r > j) return fail(CHIP_ERR_NOT_TRIU, "P is not upper triangular");
+        if (mat == 'P') {
             if (r < xoff[k]) return fail(CHIP_ERR_ARG, "chip_batch_create: an entry of P crosses two members' blocks");
-            Prow[p] = (int)r;
-            Pcol[p] = (int)j;
             lp_init[k] = 0;
+        } else if (zmem[r] != k) {
+            return fail(CHIP_ERR_ARG, "chip_batch_create: an entry of A crosses two members' blocks");
         }
-        for (uint64_t p = Acolptr[j]; p < Acolptr[j + 1]; p++) {
-            const int64_t r = (int64_t)Arowval[p];
-            if (r >= m) return fail(CHIP_ERR_DIM, "A row index out of range");
-            if (zmem[r] != k) return fail(CHIP_ERR_ARG, "chip_batch_create: an entry of A crosses two members' blocks");
-            Arow[p] = (int)r;
-            Acol[p] = (int)j;
-        }
-    }
+        return (int)CHIP_OK;
+    });
+    if (rc) return rc;
     if (plan_rc) return plan_rc; // a refused cone: reported after the entries of P and A, its text still the last error
-    const std::vector<ConeSpec> &cones = hp.cones;
     // ---- the device
     if (st.linsys.device == CHIP_DEVICE_HOST_ONLY || chip_device_count() < 1)
         return fail(CHIP_ERR_NO_DEVICE, "chip_batch_create: no HIP device (the product has no CPU fallback)");
+    ProblemData &pd = h->pd;
     if (st.linsys.device >= 0) CHIP_HIP(hipSetDevice(st.linsys.device));
-    CHIP_HIP(hipGetDevice(&h->device));
+    CHIP_HIP(hipGetDevice(&pd.device));
     h->nprob = np;
-    h->n = (int)n;
-    h->m = (int)m;
     h->xoff = xoff;
     h->zoff = zoff;
     h->degree = hp.degree;
     h->has_soc = hp.has_soc;
     h->lp_init = lp_init;
-    h->anyP = nnzP > 0;
+    h->anyP = a.nnzP() > 0;
     h->anyLP = std::find(lp_init.begin(), lp_init.end(), 1) != lp_init.end();
     DevPool &mem = h->mem;
-    int rc;
     dev::BatchPlan &pl = h->plan;
     if ((rc = host_plan_upload(mem, hp, &pl))) return rc;
-    // ---- the data: b capped at the reference's infinity; per member the norms of the unequilibrated q and b
-    std::vector<double> bcap(b, b + m);
-    for (double &v : bcap) v = std::min(v, 1e20); // problemdata.rs:125-127
-    h->normq.assign((size_t)np, 0.0);
-    h->normb.assign((size_t)np, 0.0);
-    for (int k = 0; k < np; k++) {
-        double nq = 0.0, nb = 0.0;
-        for (int j = xoff[k]; j < xoff[k + 1]; j++) nq = std::isnan(q[j]) ? q[j] : std::max(nq, std::fabs(q[j]));
-        for (int i = zoff[k]; i < zoff[k + 1]; i++) nb = std::isnan(bcap[i]) ? bcap[i] : std::max(nb, std::fabs(bcap[i]));
-        h->normq[k] = nq;
-        h->normb[k] = nb;
-    }
-    dev::EqMats &M = h->M;
-    int *dPr, *dPc, *dAr, *dAc;
-    if ((rc = mem.upload(&dPr, Prow.data(), nnzP)) || (rc = mem.upload(&dPc, Pcol.data(), nnzP)) ||
-        (rc = mem.upload(&M.Px, Pnzval, nnzP)) || (rc = mem.upload(&dAr, Arow.data(), nnzA)) ||
-        (rc = mem.upload(&dAc, Acol.data(), nnzA)) || (rc = mem.upload(&M.Ax, Anzval, nnzA)) ||
-        (rc = mem.upload(&h->q, q, (size_t)n)) || (rc = mem.upload(&h->b, bcap.data(), (size_t)m)) ||
-        (rc = mem.upload(&h->uq, q, (size_t)n)) || (rc = mem.upload(&h->ub, bcap.data(), (size_t)m)))
-        return rc;
-    M.Prow = dPr;
-    M.Pcol = dPc;
-    M.Arow = dAr;
-    M.Acol = dAc;
-    M.nnzP = (int)nnzP;
-    M.nnzA = (int)nnzA;
-    if ((rc = mem.alloc(&h->d, (size_t)n)) || (rc = mem.alloc(&h->e, (size_t)m)) ||
-        (rc = mem.alloc(&h->dinv, (size_t)n)) || (rc = mem.alloc(&h->einv, (size_t)m)) ||
+    // ---- the data, with the unscaled q and (capped) b kept beside it; per member the norms of the two
+    std::vector<double> bcap;
+    if ((rc = pd.upload(mem, a, co, bcap)) || (rc = mem.upload(&h->uq, q, (size_t)n)) ||
+        (rc = mem.upload(&h->ub, bcap.data(), (size_t)m)) || (rc = pd.alloc_scalings(mem)) ||
         (rc = mem.alloc(&h->negq, (size_t)n)))
         return rc;
-    CHIP_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); // replaced by the KKT handle's below
-    hipStream_t s_eq = h->stream;
+    for (int k = 0; k < np; k++) {
+        h->normq.push_back(absmax_nan(q, xoff[k], xoff[k + 1]));
+        h->normb.push_back(absmax_nan(bcap.data(), zoff[k], zoff[k + 1]));
+    }
+    // ---- its equilibration on a stream of its own (the handle's is the KKT handle's, built below)
+    DevPool work;
+    double *colsum = nullptr, *scr = nullptr;
+    if ((rc = work.alloc(&colsum, (size_t)np)) || (rc = work.alloc(&scr, dev::seg_scratch_doubles(pl)))) return rc;
+    hipStream_t s_eq = nullptr;
+    CHIP_HIP(hipStreamCreateWithFlags(&s_eq, hipStreamNonBlocking));
     const double te = now_s();
-    rc = h->equilibrate(cones);
+    h->c.assign((size_t)np, 1.0);
+    auto ruiz_step = [&](unsigned long long *bits, double *cstate) {
+        dev::batch_eq_ruiz_step(s_eq, pl, pd.M, pd.q, pd.b, pd.d, pd.e, bits, scr, colsum, cstate,
+                                st.equilibrate_min_scaling, st.equilibrate_max_scaling);
+    };
+    rc = pd.equilibrate(s_eq, st, hp.cones, np, dev::batch_eq_bits_words(pd.n, pd.m, np), ruiz_step, h->c.data());
     (void)hipStreamDestroy(s_eq);
-    h->stream = nullptr;
     if (rc) return rc;
     h->equilibration_time = now_s() - te;
     if ((rc = mem.upload(&h->dc, h->c.data(), (size_t)np))) return rc;
     // ---- one KKT system of the equilibrated stack (block-diagonal K)
-    std::vector<double> Px(nnzP), Ax(nnzA), qs(n), bs(m);
-    if (nnzP) CHIP_HIP(hipMemcpy(Px.data(), M.Px, nnzP * 8, hipMemcpyDeviceToHost));
-    if (nnzA) CHIP_HIP(hipMemcpy(Ax.data(), M.Ax, nnzA * 8, hipMemcpyDeviceToHost));
-    if (n) CHIP_HIP(hipMemcpy(qs.data(), h->q, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (m) CHIP_HIP(hipMemcpy(bs.data(), h->b, (size_t)m * 8, hipMemcpyDeviceToHost));
-    if ((rc = chip_kkt_create(&h->kkt, n, m, Pcolptr, Prowval, Px.data(), Acolptr, Arowval, Ax.data(), ncones,
-                              cone_tags, cone_dims, cone_dims2, nullptr, &st.linsys, nullptr)))
+    if ((rc = pd.create_kkt(a, nullptr, st.linsys, &h->kkt, &h->sys, &h->stream, [](chip_kkt *) { return 0; })))
         return rc;
-    if ((rc = chip_kktsystem_create(&h->sys, h->kkt, Pcolptr, Prowval, Px.data(), Acolptr, Arowval, Ax.data(),
-                                    qs.data(), bs.data())))
-        return rc;
-    h->stream = (hipStream_t)chip_kkt_stream(h->kkt);
     const size_t N = (size_t)n, Mm = (size_t)m;
     if ((rc = mem.alloc(&h->vx, N)) || (rc = mem.alloc(&h->vs, Mm)) || (rc = mem.alloc(&h->vz, Mm)) ||
         (rc = mem.alloc(&h->px, N)) || (rc = mem.alloc(&h->ps, Mm)) || (rc = mem.alloc(&h->pz, Mm)) ||
@@ -509,7 +425,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     h->hmask_ring.assign((size_t)chip_batch::RING * M_COUNT * np, 0);
     h->dsc = h->dsc_ring;
     h->dmask = h->dmask_ring;
-    dev::waxpby(h->stream, h->negq, -1.0, h->q, 0.0, nullptr, h->n);
+    dev::waxpby(h->stream, h->negq, -1.0, pd.q, 0.0, nullptr, pd.n);
     CHIP_HIP(hipGetLastError());
     CHIP_HIP(hipStreamSynchronize(h->stream));
     h->setup_time = now_s() - t0;
@@ -519,7 +435,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
 
 void chip_batch_destroy(chip_batch *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
+    (void)hipSetDevice(h->pd.device);
     delete h;
 }
 
@@ -529,6 +445,7 @@ void chip_batch_destroy(chip_batch *h) {
 int chip_batch::default_start() {
     int rc;
     hipStream_t s = stream;
+    const int n = pd.n, m = pd.m;
     if ((rc = chip_kkt_unit_initialization_dev(kkt, dz, ds))) return rc;
     if ((rc = chip_kkt_update_scaling_dev(kkt, dz, dz, 1.0, 0)) < 0) return rc;
     if ((rc = chip_kkt_update(kkt, nullptr)) < 0) return rc; // (the reference ignores the bool here)
@@ -538,7 +455,7 @@ int chip_batch::default_start() {
     }
     if ((rc = push_masks())) return rc;
     lin(workx, negq, nullptr, nullptr, nullptr, 1.0, 0.0, 0, mk(M_QP), dev::MASK_ZERO); // QP: -q, LP: 0
-    if ((rc = chip_kkt_setrhs_dev(kkt, workx, b))) return rc;
+    if ((rc = chip_kkt_setrhs_dev(kkt, workx, pd.b))) return rc;
     if ((rc = chip_kkt_solve_dev(kkt, vx, vz)) < 0) return rc;
     dev::waxpby(s, vs, -1.0, vz, 0.0, nullptr, m); // QP: s = -z; LP: s = -(the z part of [0; b])
     if (anyLP) {
@@ -588,29 +505,29 @@ int chip_batch::residual_pass() {
     if ((rc = push_scalars())) return rc;
     if (anyP) {
         if ((rc = spmv(0, Pxv, nullptr, 1.0, vx))) return rc;
-    } else if (n) {
-        CHIP_HIP(hipMemsetAsync(Pxv, 0, (size_t)n * 8, stream));
+    } else if (pd.n) {
+        CHIP_HIP(hipMemsetAsync(Pxv, 0, (size_t)pd.n * 8, stream));
     }
     if ((rc = spmv(2, rx_inf, nullptr, -1.0, vz))) return rc; // rx_inf = -A' z
     if ((rc = spmv(1, rz_inf, vs, 1.0, vx))) return rc;       // rz_inf = A x + s
-    dev::bresid(stream, plan, rx, rx_inf, Pxv, q, rz, rz_inf, b, sc(S_TAU));
+    dev::bresid(stream, plan, rx, rx_inf, Pxv, pd.q, rz, rz_inf, pd.b, sc(S_TAU));
     dev::SegBatch bt{};
     auto add = [&](const double *a, const double *w, int kind, int space, int slot) {
         bt.s[bt.count++] = dev::SegSpec{a, w, kind, space, slot};
     };
-    add(q, vx, dev::SEG_DOT, 0, R_QX);
+    add(pd.q, vx, dev::SEG_DOT, 0, R_QX);
     add(vx, Pxv, dev::SEG_DOT, 0, R_XPX);
-    add(vx, d, dev::SEG_WSQ, 0, R_NX);
-    add(rx_inf, dinv, dev::SEG_WSQ, 0, R_NRXI);
-    add(Pxv, dinv, dev::SEG_WSQ, 0, R_NPX);
-    add(rx, dinv, dev::SEG_WSQ, 0, R_NRX);
+    add(vx, pd.d, dev::SEG_WSQ, 0, R_NX);
+    add(rx_inf, pd.dinv, dev::SEG_WSQ, 0, R_NRXI);
+    add(Pxv, pd.dinv, dev::SEG_WSQ, 0, R_NPX);
+    add(rx, pd.dinv, dev::SEG_WSQ, 0, R_NRX);
     add(vx, nullptr, dev::SEG_NONFINITE, 0, R_BADX);
-    add(b, vz, dev::SEG_DOT, 1, R_BZ);
+    add(pd.b, vz, dev::SEG_DOT, 1, R_BZ);
     add(vs, vz, dev::SEG_DOT, 1, R_SZ);
-    add(vz, e, dev::SEG_WSQ, 1, R_NZ);
-    add(vs, einv, dev::SEG_WSQ, 1, R_NS);
-    add(rz_inf, einv, dev::SEG_WSQ, 1, R_NRZI);
-    add(rz, einv, dev::SEG_WSQ, 1, R_NRZ);
+    add(vz, pd.e, dev::SEG_WSQ, 1, R_NZ);
+    add(vs, pd.einv, dev::SEG_WSQ, 1, R_NS);
+    add(rz_inf, pd.einv, dev::SEG_WSQ, 1, R_NRZI);
+    add(rz, pd.einv, dev::SEG_WSQ, 1, R_NRZ);
     add(vs, vz, dev::SEG_NONFINITE, 1, R_BADSZ);
     dev::seg_reduce(stream, plan, bt, dred, seg_scr);
     dev::cone_minima(stream, plan, dev::CONE_INTERIOR, nullptr, nullptr, vz, vs, nullptr, dred + (size_t)R_COUNT * nprob,
@@ -666,12 +583,12 @@ int chip_batch::solve_direction(const double *conic, const std::vector<double> &
     for (int k = 0; k < nprob; k++) hs_(S_INVTAU, k) = 1.0 / tau[k];
     if ((rc = push_scalars())) return rc;
     dev::SegBatch bt{};
-    bt.s[bt.count++] = dev::SegSpec{q, x1, dev::SEG_DOT, 0, D_QX1};
-    bt.s[bt.count++] = dev::SegSpec{b, z1, dev::SEG_DOT, 1, D_BZ1};
+    bt.s[bt.count++] = dev::SegSpec{pd.q, x1, dev::SEG_DOT, 0, D_QX1};
+    bt.s[bt.count++] = dev::SegSpec{pd.b, z1, dev::SEG_DOT, 1, D_BZ1};
     if (anyP) {
         lin(wn2, vx, nullptr, sc(S_INVTAU), nullptr, 1.0, 0.0, 0, nullptr, 0); // xi = x / tau
         if ((rc = spmv(0, wn, nullptr, 1.0, x1))) return rc;                   // P x1
-        dev::waxpby(s, workx2, -1.0, x2, 1.0, wn2, n);                         // xi - x2
+        dev::waxpby(s, workx2, -1.0, x2, 1.0, wn2, pd.n);                      // xi - x2
         if ((rc = spmv(0, wn3, nullptr, 1.0, workx2))) return rc;
         launches++;
         bt.s[bt.count++] = dev::SegSpec{wn2, wn, dev::SEG_DOT, 0, D_XIPX1};
@@ -707,7 +624,7 @@ int chip_batch::solve_direction(const double *conic, const std::vector<double> &
     lin(lx, x1, x2, nullptr, sc(S_DTAU), 1.0, 0.0, 0, nullptr, 0); // x1 + dtau x2
     lin(lz, z1, z2, nullptr, sc(S_DTAU), 1.0, 0.0, 1, nullptr, 0);
     if ((rc = chip_kkt_mul_Hs_dev(kkt, ls, lz))) return rc; // ds = -(Hs dz + conic)
-    dev::waxpby(s, ls, -1.0, conic, -1.0, ls, m);
+    dev::waxpby(s, ls, -1.0, conic, -1.0, ls, pd.m);
     launches += 2;
     CHIP_HIP(hipGetLastError());
     return CHIP_OK;
@@ -737,15 +654,15 @@ int chip_batch::step_length(const std::vector<double> &lkappa, bool combined) {
 // the constant right-hand side [-q; b] after each KKT update (kktsystem.rs:108-125) and its dots per member
 int chip_batch::constant_rhs(bool *global_ok, int iter) {
     int rc;
-    if ((rc = chip_kkt_setrhs_dev(kkt, negq, b))) return rc;
+    if ((rc = chip_kkt_setrhs_dev(kkt, negq, pd.b))) return rc;
     rc = chip_kkt_solve_dev(kkt, x2, z2);
     syncs++;
     launches++;
     if (rc < 0) return rc;
     *global_ok = rc == 1;
     dev::SegBatch bt{};
-    bt.s[bt.count++] = dev::SegSpec{q, x2, dev::SEG_DOT, 0, 0};
-    bt.s[bt.count++] = dev::SegSpec{b, z2, dev::SEG_DOT, 1, 1};
+    bt.s[bt.count++] = dev::SegSpec{pd.q, x2, dev::SEG_DOT, 0, 0};
+    bt.s[bt.count++] = dev::SegSpec{pd.b, z2, dev::SEG_DOT, 1, 1};
     if (anyP) {
         if ((rc = spmv(0, wn, nullptr, 1.0, x2))) return rc;
         bt.s[bt.count++] = dev::SegSpec{x2, wn, dev::SEG_DOT, 0, 2};
@@ -813,7 +730,7 @@ int chip_batch::post_process() {
     for (int k = 0; k < nprob; k++)
         ipm_post_process(info[k], st, tau[k], kappa[k], c[k], &obj_val[k], &obj_val_dual[k], &hs_(S_SX, k), &hs_(S_SZ, k));
     if ((rc = push_scalars())) return rc;
-    dev::bunscale(stream, plan, xo, vx, d, zo, vz, e, so, vs, einv, sc(S_SX), sc(S_SZ));
+    dev::bunscale(stream, plan, xo, vx, pd.d, zo, vz, pd.e, so, vs, pd.einv, sc(S_SX), sc(S_SZ));
     CHIP_HIP(hipGetLastError());
     CHIP_HIP(hipStreamSynchronize(stream));
     return CHIP_OK;
@@ -822,7 +739,7 @@ int chip_batch::post_process() {
 // IPSolver::solve (core/solver.rs:242-464) with every scalar indexed by member
 int32_t chip_batch_solve(chip_batch *h) {
     if (!h) return fail(CHIP_ERR_ARG, "chip_batch_solve: bad argument");
-    CHIP_HIP(hipSetDevice(h->device));
+    CHIP_HIP(hipSetDevice(h->pd.device));
     const int np = h->nprob;
     const chip_solver_settings &st = h->st;
     auto zeros = [np](std::vector<double> &v) { v.assign((size_t)np, 0.0); };
@@ -950,7 +867,7 @@ int32_t chip_batch_solve(chip_batch *h) {
         if (iter == 1) h->lin(h->lz, h->lz, nullptr, h->sc(S_ALPHA), nullptr, 1.0, 0.0, 1, nullptr, 0);
         if ((rc = chip_kkt_combined_ds_shift_dev(h->kkt, h->dz, h->lz, h->ls, 0.0))) return rc; // dz is work
         dev::bunit_shift(h->stream, h->plan, h->dz, h->sc(S_NEGSM), 0, nullptr);                 // - sigma_mu e
-        dev::waxpby(h->stream, h->ds, 1.0, h->ds, 1.0, h->dz, h->m);
+        dev::waxpby(h->stream, h->ds, 1.0, h->ds, 1.0, h->dz, h->pd.m);
         h->lin(h->dz, h->rz, nullptr, h->sc(S_OMS), nullptr, 1.0, 0.0, 1, nullptr, 0);
         if ((rc = chip_kkt_ds_from_dz_offset_dev(h->kkt, h->conicw, h->ds, h->vz))) return rc;
         h->launches += 4;
@@ -1011,17 +928,10 @@ int32_t chip_batch_solve(chip_batch *h) {
 }
 
 static void fill_info(const chip_batch *h, int k, chip_solution_info *out) {
-    std::memset(out, 0, sizeof(*out));
-    out->status = h->solved_once ? h->info[k].status : CHIP_SOLVER_UNSOLVED;
-    out->iterations = h->solved_once ? h->info[k].iterations : 0;
-    out->obj_val = h->solved_once ? h->obj_val[k] : 0.0;
-    out->obj_val_dual = h->solved_once ? h->obj_val_dual[k] : 0.0;
-    out->r_prim = h->solved_once ? h->info[k].res_primal : 0.0;
-    out->r_dual = h->solved_once ? h->info[k].res_dual : 0.0;
-    out->solve_time = h->solve_time;
-    out->setup_time = h->setup_time;
-    out->equilibration_time = h->equilibration_time;
-    out->iteration_time = h->iteration_time;
+    const bool done = h->solved_once; // (the per-member vectors are empty before the first solve)
+    fill_solution_info(out, done, done ? h->info[k] : IpmInfo(), done ? h->obj_val[k] : 0.0,
+                       done ? h->obj_val_dual[k] : 0.0, h->solve_time, h->setup_time, h->equilibration_time,
+                       h->iteration_time);
 }
 
 int32_t chip_batch_get_info(chip_batch *h, chip_solution_info *infos) {
@@ -1032,7 +942,7 @@ int32_t chip_batch_get_info(chip_batch *h, chip_solution_info *infos) {
 
 int32_t chip_batch_get_solution(chip_batch *h, int64_t k, double *x, double *s, double *z, chip_solution_info *info) {
     if (!h || k < 0 || k >= h->nprob) return fail(CHIP_ERR_ARG, "chip_batch_get_solution: bad argument");
-    CHIP_HIP(hipSetDevice(h->device));
+    CHIP_HIP(hipSetDevice(h->pd.device));
     const int x0 = h->xoff[k], nk = h->xoff[k + 1] - x0, z0 = h->zoff[k], mk_ = h->zoff[k + 1] - z0;
     if (h->solved_once) {
         if (x && nk) CHIP_HIP(hipMemcpy(x, h->xo + x0, (size_t)nk * 8, hipMemcpyDeviceToHost));
@@ -1057,10 +967,10 @@ int32_t chip_batch_get_solution_dev(chip_batch *h, double **x_dev, double **s_de
 
 int32_t chip_batch_get_equilibration(chip_batch *h, int64_t k, double *d, double *e, double *c) {
     if (!h || k < 0 || k >= h->nprob) return fail(CHIP_ERR_ARG, "chip_batch_get_equilibration: bad argument");
-    CHIP_HIP(hipSetDevice(h->device));
+    CHIP_HIP(hipSetDevice(h->pd.device));
     const int x0 = h->xoff[k], nk = h->xoff[k + 1] - x0, z0 = h->zoff[k], mk_ = h->zoff[k + 1] - z0;
-    if (d && nk) CHIP_HIP(hipMemcpy(d, h->d + x0, (size_t)nk * 8, hipMemcpyDeviceToHost));
-    if (e && mk_) CHIP_HIP(hipMemcpy(e, h->e + z0, (size_t)mk_ * 8, hipMemcpyDeviceToHost));
+    if (d && nk) CHIP_HIP(hipMemcpy(d, h->pd.d + x0, (size_t)nk * 8, hipMemcpyDeviceToHost));
+    if (e && mk_) CHIP_HIP(hipMemcpy(e, h->pd.e + z0, (size_t)mk_ * 8, hipMemcpyDeviceToHost));
     if (c) *c = h->c[k];
     return CHIP_OK;
 }
@@ -1076,7 +986,7 @@ int32_t chip_batch_get_equilibration(chip_batch *h, int64_t k, double *d, double
 // ---------------------------------------------------------------------------------------------------------------
 int chip_batch::update_work() {
     if (uflag) return CHIP_OK;
-    const size_t len = (size_t)std::max({M.nnzP, M.nnzA, n, m, 1});
+    const size_t len = (size_t)std::max({pd.M.nnzP, pd.M.nnzA, pd.n, pd.m, 1});
     int rc;
     if ((rc = mem.alloc(&upos, len)) || (rc = mem.alloc(&unpart, (size_t)dev::pu_norm_partials())) ||
         (rc = mem.alloc(&unout, 3)) || (rc = mem.alloc(&ubpart, (size_t)(plan.ncx + plan.ncz))) ||
@@ -1097,7 +1007,8 @@ int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev
     // (chip_bgrad_*).  Only the refusal that has changed nothing puts the flag back; a call that fails on the way does not
     const bool was_current = solve_current;
     solve_current = false;
-    const int len = update_len(which);
+    const int len = (int)pd.update_len(which);
+    const dev::EqMats &M = pd.M;
     hipStream_t s = stream;
     if (idx_dev) { // the whole index list is checked on the device before any pass writes
         if ((rc = grow_dev(&clean, &clean_cap, (size_t)k, s, &upd_syncs))) return rc;
@@ -1107,10 +1018,10 @@ int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev
     }
     dev::BuTarget t{};
     switch (which) {
-    case UPD_P: t = {M.Px, nullptr, nullptr, len, M.Prow, M.Pcol, d, d, dc, plan.xmem}; break;
-    case UPD_A: t = {M.Ax, nullptr, nullptr, len, M.Arow, M.Acol, e, d, nullptr, plan.xmem}; break;
-    case UPD_Q: t = {q, uq, negq, len, nullptr, nullptr, d, nullptr, dc, plan.xmem}; break;
-    default: t = {b, ub, nullptr, len, nullptr, nullptr, e, nullptr, nullptr, plan.zmem}; break;
+    case UPD_P: t = {M.Px, nullptr, nullptr, len, M.Prow, M.Pcol, pd.d, pd.d, dc, plan.xmem}; break;
+    case UPD_A: t = {M.Ax, nullptr, nullptr, len, M.Arow, M.Acol, pd.e, pd.d, nullptr, plan.xmem}; break;
+    case UPD_Q: t = {pd.q, uq, negq, len, nullptr, nullptr, pd.d, nullptr, dc, plan.xmem}; break;
+    default: t = {pd.b, ub, nullptr, len, nullptr, nullptr, pd.e, nullptr, nullptr, plan.zmem}; break;
     }
     if (idx_dev) {
         dev::bu_write_partial(s, t, idx_dev, vals_dev, k, upos, uflag, clean);
@@ -1128,7 +1039,7 @@ int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev
         upd_launches++;
     }
     if ((rc = kktsystem_update_data_dev(sys, which == UPD_P ? M.Px : nullptr, which == UPD_A ? M.Ax : nullptr,
-                                        which == UPD_Q ? q : nullptr, which == UPD_B ? b : nullptr)))
+                                        which == UPD_Q ? pd.q : nullptr, which == UPD_B ? pd.b : nullptr)))
         return rc;
     upd_launches += (which == UPD_A || which == UPD_Q) ? 2 : 1; // A: two mirrors; q: the copy and its negation
     // the scalars create derived from the values: the members' norms of the unscaled q / b, max |P_ii| of the stack
@@ -1163,7 +1074,7 @@ int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev
 
 int chip_batch::update_args(chip_batch *h, int which, const void *idx, const double *vals, int64_t k) {
     const std::string fn = update_fn(UPD_PREFIX, which);
-    const int64_t len = h ? h->update_len(which) : 0;
+    const int64_t len = h ? h->pd.update_len(which) : 0;
     const int rc = chip::update_args(fn, h, idx, vals, k, len, [&] {
         h->upd_syncs = h->upd_launches = 0;
         return 0;
@@ -1187,12 +1098,8 @@ int32_t chip_bdata_update_settings(chip_batch *h, const chip_solver_settings *se
 int32_t chip_bdata_get_scaled(chip_batch *h, double *Px, double *Ax, double *q, double *b, double *normq,
                               double *normb) {
     if (!h) return fail(CHIP_ERR_ARG, "chip_bdata_get_scaled: bad argument");
-    CHIP_HIP(hipSetDevice(h->device));
-    CHIP_HIP(hipStreamSynchronize(h->stream));
-    if (Px && h->M.nnzP) CHIP_HIP(hipMemcpy(Px, h->M.Px, (size_t)h->M.nnzP * 8, hipMemcpyDeviceToHost));
-    if (Ax && h->M.nnzA) CHIP_HIP(hipMemcpy(Ax, h->M.Ax, (size_t)h->M.nnzA * 8, hipMemcpyDeviceToHost));
-    if (q && h->n) CHIP_HIP(hipMemcpy(q, h->q, (size_t)h->n * 8, hipMemcpyDeviceToHost));
-    if (b && h->m) CHIP_HIP(hipMemcpy(b, h->b, (size_t)h->m * 8, hipMemcpyDeviceToHost));
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    if (int rc = h->pd.get_scaled(h->stream, Px, Ax, q, b)) return rc;
     if (normq) std::copy(h->normq.begin(), h->normq.end(), normq);
     if (normb) std::copy(h->normb.begin(), h->normb.end(), normb);
     return CHIP_OK;
@@ -1215,10 +1122,10 @@ int32_t chip_bdata_get_scaled(chip_batch *h, double *Px, double *Ax, double *q, 
 int chip_batch::backward_work() {
     if (g_valid) return CHIP_OK;
     int rc;
-    if ((rc = mem.alloc(&g_dq, (size_t)n)) || (rc = mem.alloc(&g_db, (size_t)m)) ||
-        (rc = mem.alloc(&g_dP, (size_t)M.nnzP)) || (rc = mem.alloc(&g_dA, (size_t)M.nnzA)) ||
-        (rc = mem.alloc(&g_in[0], (size_t)n)) || (rc = mem.alloc(&g_in[1], (size_t)m)) ||
-        (rc = mem.alloc(&g_in[2], (size_t)m)) || (rc = mem.alloc(&g_valid, (size_t)nprob)))
+    const size_t n = (size_t)pd.n, m = (size_t)pd.m;
+    if ((rc = mem.alloc(&g_dq, n)) || (rc = mem.alloc(&g_db, m)) || (rc = mem.alloc(&g_dP, (size_t)pd.M.nnzP)) ||
+        (rc = mem.alloc(&g_dA, (size_t)pd.M.nnzA)) || (rc = mem.alloc(&g_in[0], n)) || (rc = mem.alloc(&g_in[1], m)) ||
+        (rc = mem.alloc(&g_in[2], m)) || (rc = mem.alloc(&g_valid, (size_t)nprob)))
         return rc;
     gvalid.assign((size_t)nprob, 0);
     return CHIP_OK;
@@ -1233,7 +1140,7 @@ int chip_batch::backward(const double *gx, const double *gz, const double *gs) {
     // right-hand side: its block of K stays well posed and its part of the solution is 0
     for (int k = 0; k < nprob; k++) gvalid[k] = info[k].status == CHIP_SOLVER_SOLVED && !has_soc[k];
     CHIP_HIP(hipMemcpyAsync(g_valid, gvalid.data(), (size_t)nprob * sizeof(int), hipMemcpyHostToDevice, s));
-    dev::ba_rhs(s, plan, dev::BaRhs{g_valid, gx, gz, gs, d, e, dc, vs, vz, wn, conicw, workz, ds, dz});
+    dev::ba_rhs(s, plan, dev::BaRhs{g_valid, gx, gz, gs, pd.d, pd.e, dc, vs, vz, wn, conicw, workz, ds, dz});
     grad_launches += 2;
     if ((rc = kktsystem_spmv(sys, 2, workx, wn, -1.0, conicw))) return rc; // D gx - A^' (gs / e)
     grad_launches++;
@@ -1249,9 +1156,9 @@ int chip_batch::backward(const double *gx, const double *gz, const double *gs) {
     grad_launches++;
     if (rc < 0) return rc;
     if (rc != 1) return fail(CHIP_ERR_ZERO_PIVOT, "chip_bgrad_backward: the solve at the final iterate failed");
-    const dev::BaGrad g{g_valid, x1, z1, gs, d, e, dc, xo, zo, x2, z2, g_dq, g_db, g_dP, g_dA};
+    const dev::BaGrad g{g_valid, x1, z1, gs, pd.d, pd.e, dc, xo, zo, x2, z2, g_dq, g_db, g_dP, g_dA};
     dev::ba_grad_vectors(s, plan, g);
-    dev::ba_grad_matrices(s, plan, M, g);
+    dev::ba_grad_matrices(s, plan, pd.M, g);
     grad_launches += 2;
     CHIP_HIP(hipGetLastError());
     CHIP_HIP(hipStreamSynchronize(s));
@@ -1272,13 +1179,13 @@ int bg_ready(chip_batch *h, const char *fn) {
 int32_t chip_bgrad_backward(chip_batch *h, const double *gx, const double *gz, const double *gs) {
     int rc = bg_ready(h, "chip_bgrad_backward");
     if (rc) return rc;
-    CHIP_HIP(hipSetDevice(h->device));
+    CHIP_HIP(hipSetDevice(h->pd.device));
     h->grad_syncs = h->grad_launches = 0;
     if ((rc = h->backward_work())) return rc;
     const double *src[3] = {gx, gz, gs};
     const double *in[3] = {nullptr, nullptr, nullptr};
     for (int i = 0; i < 3; i++) {
-        const size_t len = (size_t)(i == 0 ? h->n : h->m);
+        const size_t len = (size_t)(i == 0 ? h->pd.n : h->pd.m);
         if (!src[i]) continue;
         in[i] = h->g_in[i];
         if (!len) continue;
@@ -1291,7 +1198,7 @@ int32_t chip_bgrad_backward(chip_batch *h, const double *gx, const double *gz, c
 int32_t chip_bgrad_backward_dev(chip_batch *h, const double *gx_dev, const double *gz_dev, const double *gs_dev) {
     int rc = bg_ready(h, "chip_bgrad_backward_dev");
     if (rc) return rc;
-    CHIP_HIP(hipSetDevice(h->device));
+    CHIP_HIP(hipSetDevice(h->pd.device));
     h->grad_syncs = h->grad_launches = 0;
     if ((rc = h->backward_work())) return rc;
     return h->backward(gx_dev, gz_dev, gs_dev);
@@ -1300,11 +1207,12 @@ int32_t chip_bgrad_backward_dev(chip_batch *h, const double *gx_dev, const doubl
 int32_t chip_bgrad_get(chip_batch *h, double *dq, double *db, double *dPx, double *dAx, int32_t *valid) {
     if (!h) return fail(CHIP_ERR_ARG, "chip_bgrad_get: bad argument");
     if (!h->grad_done) return fail(CHIP_ERR_ARG, "chip_bgrad_get: no chip_bgrad_backward since the last solve");
-    CHIP_HIP(hipSetDevice(h->device));
-    if (dq && h->n) CHIP_HIP(hipMemcpy(dq, h->g_dq, (size_t)h->n * 8, hipMemcpyDeviceToHost));
-    if (db && h->m) CHIP_HIP(hipMemcpy(db, h->g_db, (size_t)h->m * 8, hipMemcpyDeviceToHost));
-    if (dPx && h->M.nnzP) CHIP_HIP(hipMemcpy(dPx, h->g_dP, (size_t)h->M.nnzP * 8, hipMemcpyDeviceToHost));
-    if (dAx && h->M.nnzA) CHIP_HIP(hipMemcpy(dAx, h->g_dA, (size_t)h->M.nnzA * 8, hipMemcpyDeviceToHost));
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    const dev::EqMats &M = h->pd.M;
+    if (dq && h->pd.n) CHIP_HIP(hipMemcpy(dq, h->g_dq, (size_t)h->pd.n * 8, hipMemcpyDeviceToHost));
+    if (db && h->pd.m) CHIP_HIP(hipMemcpy(db, h->g_db, (size_t)h->pd.m * 8, hipMemcpyDeviceToHost));
+    if (dPx && M.nnzP) CHIP_HIP(hipMemcpy(dPx, h->g_dP, (size_t)M.nnzP * 8, hipMemcpyDeviceToHost));
+    if (dAx && M.nnzA) CHIP_HIP(hipMemcpy(dAx, h->g_dA, (size_t)M.nnzA * 8, hipMemcpyDeviceToHost));
     if (valid) std::copy(h->gvalid.begin(), h->gvalid.end(), valid);
     return CHIP_OK;
 }

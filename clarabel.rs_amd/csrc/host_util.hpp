@@ -1,6 +1,7 @@
 // host_util.hpp -- host-side helpers the L3 / L4 handles share (kktsystem.cpp, solver.cpp, batch.cpp): the owning pool
 // of device allocations, and the front end of the data updates (chip_problem_update_* of chip_solver, chip_bdata_update_*
-// of chip_batch): argument check, staging of the host forms, the ABI wrappers, the settings validator.
+// of chip_batch): argument check, staging of the host forms, the ABI wrappers, the settings validator.  The problem data
+// the two L4 handles are set up with, and whose length an update is checked against, is problem_data.hpp's.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -98,19 +99,19 @@ int update_args(const std::string &fn, const void *h, const void *idx, const dou
 }
 
 // the two forms of one update of handle type H, which provides: static update_args(h, which, idx, vals, k) (the check
-// above with the handle's own refusals), device, stage_upload(idx, vals, k) (UpdateStage::upload on its stream with
-// its counters), stage and update(which, idx_dev, vals_dev, k)
+// above with the handle's own refusals), pd (its ProblemData, for the device), stage_upload(idx, vals, k)
+// (UpdateStage::upload on its stream with its counters), stage and update(which, idx_dev, vals_dev, k)
 template <typename H> int update_host(H *h, int which, const uint64_t *idx, const double *vals, int64_t k) {
     int rc = H::update_args(h, which, idx, vals, k);
     if (rc) return rc < 0 ? rc : CHIP_OK;
-    CHIP_HIP(hipSetDevice(h->device));
+    CHIP_HIP(hipSetDevice(h->pd.device));
     if ((rc = h->stage_upload(idx, vals, (size_t)k))) return rc;
     return h->update(which, idx ? h->stage.i : nullptr, h->stage.v, (int)k);
 }
 template <typename H> int update_dev(H *h, int which, const int64_t *idx, const double *vals, int64_t k) {
     int rc = H::update_args(h, which, idx, vals, k);
     if (rc) return rc < 0 ? rc : CHIP_OK;
-    CHIP_HIP(hipSetDevice(h->device));
+    CHIP_HIP(hipSetDevice(h->pd.device));
     return h->update(which, idx, vals, (int)k);
 }
 
@@ -129,8 +130,8 @@ template <typename H> int update_dev(H *h, int which, const int64_t *idx, const 
     CHIP_UPDATE_ENTRY(prefix, H, b, chip::UPD_B)
 
 // validate_as_update (settings.rs:307) for chip_problem_update_settings / chip_bdata_update_settings (fn: the caller's
-// name in the error text): copies the two line-search fields into nw.linsys as create does, then CHIP_ERR_ARG if a
-// field that setup consumed differs from old.  Defined in solver.cpp
+// name in the error text): copies the two line-search fields into nw.linsys as create does (create_settings,
+// problem_data.hpp), then CHIP_ERR_ARG if a field that setup consumed differs from old.  Defined in solver.cpp
 int validate_settings_update(const chip_solver_settings &old, chip_solver_settings &nw, const char *fn);
 
 } // namespace chip

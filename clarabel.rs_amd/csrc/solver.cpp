@@ -1,6 +1,6 @@
 // solver.cpp -- L4 of the C ABI: DefaultSolver::new(P, q, A, b, cones, settings).solve() on one GPU.
-//   setup: DefaultProblemData::new + equilibrate (default/problemdata.rs:86-312) with the data on the device
-//          (equilibrate.hip), then the L2 / L3 handles built from the equilibrated values;
+//   setup: problem_data.hpp's steps, shared with batch.cpp: DefaultProblemData::new + equilibrate (default/
+//          problemdata.rs:59-312) with the data on the device, then the L2 / L3 handles of the equilibrated values;
 //   solve: the interior-point loop of core/solver.rs:242-464 over the L3 entry points, with DefaultInfo's update /
 //          check_termination / post_process (default/info.rs:80-389) and DefaultSolution::post_process
 //          (default/solution.rs:68-111) on the host: only scalars cross the boundary per iteration.
@@ -15,6 +15,7 @@
 #include "equilibrate.hpp"
 #include "host_util.hpp"
 #include "ipm_info.hpp"
+#include "problem_data.hpp"
 #include "problem_transform.hpp"
 #include "problem_update.hpp"
 
@@ -25,12 +26,9 @@ enum { PRIMAL_DUAL = 0, DUAL = 1 }; // ScalingStrategy (core/solver.rs:77-80)
 } // namespace
 
 struct chip_solver {
-    int n = 0, m = 0, device = 0;
     chip_solver_settings st{};
     DevPool mem;
-    // the problem data: patterns in coordinate form, equilibrated values, scalings
-    dev::EqMats M{};
-    double *q = nullptr, *b = nullptr, *d = nullptr, *e = nullptr, *dinv = nullptr, *einv = nullptr;
+    ProblemData pd;
     double c = 1.0, normq = 0.0, normb = 0.0;
     chip_kkt *kkt = nullptr;
     chip_kktsystem *sys = nullptr;
@@ -41,7 +39,7 @@ struct chip_solver {
     double *rx = nullptr, *rz = nullptr, *rx_inf = nullptr, *rz_inf = nullptr, *Pxv = nullptr;
     double *xo = nullptr, *so = nullptr, *zo = nullptr; // the unscaled solution (original sizes n_out, m_out)
     // presolve / chordal decomposition (problem_transform.cpp): tf is null unless one of them changed the problem; then
-    // n, m above are the internal sizes and the reverse maps live on the device
+    // pd.n, pd.m are the internal sizes and the reverse maps live on the device
     std::unique_ptr<ProblemTransform> tf;
     int n_out = 0, m_out = 0;
     int32_t *rv_mode = nullptr;
@@ -66,27 +64,26 @@ struct chip_solver {
     }
     int alloc_vars(chip_vars &v) {
         int rc;
-        if ((rc = mem.alloc(&v.x, (size_t)n)) || (rc = mem.alloc(&v.z, (size_t)m)) || (rc = mem.alloc(&v.s, (size_t)m)))
+        if ((rc = mem.alloc(&v.x, (size_t)pd.n)) || (rc = mem.alloc(&v.z, (size_t)pd.m)) ||
+            (rc = mem.alloc(&v.s, (size_t)pd.m)))
             return rc;
         v.tau = v.kappa = 1.0;
         return CHIP_OK;
     }
     int copy_vars(chip_vars &dst, const chip_vars &src) {
-        if (n) CHIP_HIP(hipMemcpyAsync(dst.x, src.x, (size_t)n * 8, hipMemcpyDeviceToDevice, stream));
-        if (m) CHIP_HIP(hipMemcpyAsync(dst.z, src.z, (size_t)m * 8, hipMemcpyDeviceToDevice, stream));
-        if (m) CHIP_HIP(hipMemcpyAsync(dst.s, src.s, (size_t)m * 8, hipMemcpyDeviceToDevice, stream));
+        if (pd.n) CHIP_HIP(hipMemcpyAsync(dst.x, src.x, (size_t)pd.n * 8, hipMemcpyDeviceToDevice, stream));
+        if (pd.m) CHIP_HIP(hipMemcpyAsync(dst.z, src.z, (size_t)pd.m * 8, hipMemcpyDeviceToDevice, stream));
+        if (pd.m) CHIP_HIP(hipMemcpyAsync(dst.s, src.s, (size_t)pd.m * 8, hipMemcpyDeviceToDevice, stream));
         dst.tau = src.tau;
         dst.kappa = src.kappa;
         return CHIP_OK;
     }
-    int equilibrate(const std::vector<ConeSpec> &cones);
     int default_start();
     int residuals_and_info();
     int backtrack_step_to_barrier(double alpha_init, double *alpha_out);
     int post_process();
     int update_work();
     static constexpr const char *UPD_PREFIX = "chip_problem_update_";
-    int64_t update_len(int which) const { return which == UPD_P ? M.nnzP : which == UPD_A ? M.nnzA : which == UPD_Q ? n : m; }
     static int update_args(chip_solver *h, int which, const void *idx, const double *vals, int64_t k);
     int stage_upload(const uint64_t *idx, const double *vals, size_t k) { return stage.upload(stream, idx, vals, k); }
     int update(int which, const int64_t *idx_dev, const double *vals_dev, int k);
@@ -127,62 +124,6 @@ void chip_solver_settings_default(chip_solver_settings *s) {
     s->chordal_decomposition_complete_dual = 1;
 }
 
-// DefaultProblemData::equilibrate (problemdata.rs:231-312): every Ruiz step enqueued without a host synchronisation,
-// c on the device until the end
-int chip_solver::equilibrate(const std::vector<ConeSpec> &cones) {
-    std::vector<double> ones((size_t)std::max(n, m), 1.0);
-    if (n) CHIP_HIP(hipMemcpy(d, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    if (m) CHIP_HIP(hipMemcpy(e, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
-    c = 1.0;
-    if (!st.equilibrate_enable) {
-        if (n) CHIP_HIP(hipMemcpy(dinv, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-        if (m) CHIP_HIP(hipMemcpy(einv, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
-        return CHIP_OK;
-    }
-    DevPool work;
-    unsigned long long *bits = nullptr;
-    double *partials = nullptr, *cstate = nullptr, *delta = nullptr;
-    const size_t nbits = dev::eq_bits_words(n, m);
-    int rc;
-    if ((rc = work.alloc(&bits, nbits)) || (rc = work.alloc(&partials, (size_t)dev::eq_cost_partials())) ||
-        (rc = work.alloc(&cstate, 2)) || (rc = work.alloc(&delta, (size_t)m)))
-        return rc;
-    hipStream_t s = nullptr;
-    CHIP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    const double c0[2] = {1.0, 1.0};
-    hipError_t err = hipMemcpyAsync(cstate, c0, sizeof(c0), hipMemcpyHostToDevice, s);
-    for (int it = 0; err == hipSuccess && it < st.equilibrate_max_iter; it++) {
-        err = hipMemsetAsync(bits, 0, nbits * sizeof(unsigned long long), s);
-        if (err == hipSuccess)
-            dev::eq_ruiz_step(s, M, q, b, d, e, n, m, bits, partials, cstate, st.equilibrate_min_scaling,
-                              st.equilibrate_max_scaling);
-    }
-    // rectification (compositecone.rs:183-195): SOC, PSDTriangle, Exp, Pow, GenPow take mean(e) / e over their range
-    std::vector<int> sb, se;
-    for (const ConeSpec &cs : cones)
-        if (cs.tag >= CHIP_CONE_SECONDORDER && cs.numel > 0) {
-            sb.push_back((int)cs.start);
-            se.push_back((int)(cs.start + cs.numel));
-        }
-    int *dsb = nullptr, *dse = nullptr;
-    if (err == hipSuccess && !sb.empty()) {
-        if ((rc = work.upload(&dsb, sb.data(), sb.size())) || (rc = work.upload(&dse, se.data(), se.size()))) {
-            (void)hipStreamDestroy(s);
-            return rc;
-        }
-        dev::eq_rectify(s, M, b, e, m, dsb, dse, (int)sb.size(), delta);
-    }
-    if (err == hipSuccess) dev::eq_invert(s, d, dinv, n, e, einv, m);
-    double hc[2] = {1.0, 1.0};
-    if (err == hipSuccess) err = hipMemcpyAsync(hc, cstate, sizeof(hc), hipMemcpyDeviceToHost, s);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err == hipSuccess) err = hipStreamSynchronize(s);
-    (void)hipStreamDestroy(s);
-    if (err != hipSuccess) return fail(CHIP_ERR_HIP, hip_err(err, "equilibrate"));
-    c = hc[0];
-    return CHIP_OK;
-}
-
 int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval,
                            const double *Pnzval, const double *q, const uint64_t *Acolptr, const uint64_t *Arowval,
                            const double *Anzval, const double *b, int64_t ncones, const int32_t *cone_tags,
@@ -193,11 +134,8 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
     *out = nullptr;
     const double t0 = now_s();
     std::unique_ptr<chip_solver> h(new chip_solver());
-    if (settings) h->st = *settings;
-    else chip_solver_settings_default(&h->st);
     chip_solver_settings &st = h->st;
-    st.linsys.linesearch_backtrack_step = st.linesearch_backtrack_step;
-    st.linsys.min_terminate_step_length = st.min_terminate_step_length;
+    create_settings(settings, st);
     if (st.linsys.device == CHIP_DEVICE_HOST_ONLY || chip_device_count() < 1)
         return fail(CHIP_ERR_NO_DEVICE, "chip_solver_create: no HIP device (the product has no CPU fallback)");
     if ((Pcolptr[n] && (!Prowval || !Pnzval)) || (Acolptr[n] && (!Arowval || !Anzval)) || (n && !q) || (m && !b))
@@ -205,6 +143,8 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
     h->n_out = (int)std::min<int64_t>(n, INT32_MAX);
     h->m_out = (int)std::min<int64_t>(m, INT32_MAX);
     // ---- presolve and chordal decomposition (problemdata.rs:59-165): everything below sees the transformed problem
+    ProblemArgs a{n,      m,         Pcolptr,   Prowval,  Pnzval, q, Acolptr, Arowval, Anzval, b,
+                  ncones, cone_tags, cone_dims, cone_dims2};
     if (st.presolve_enable || st.chordal_decomposition_enable) {
         if (n >= (1ll << 31) || m >= (1ll << 31)) return fail(CHIP_ERR_DIM, "chip_solver_create: sizes out of int32 range");
         for (uint64_t k = 0; k < Acolptr[n]; k++)
@@ -216,111 +156,69 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
         h->transform_time = tf->transform_time;
         if (tf->active()) {
             const ProblemTransform &t = *tf;
-            n = t.n2;
-            m = t.m2;
-            Pcolptr = t.Pp.data();
-            Prowval = t.Pi.data();
-            Pnzval = t.Px.data();
-            q = t.q.data();
-            Acolptr = t.Ap.data();
-            Arowval = t.Ai.data();
-            Anzval = t.Ax.data();
-            b = t.b.data();
-            ncones = (int64_t)t.tags.size();
-            cone_tags = t.tags.data();
-            cone_dims = t.dims.data();
-            cone_dims2 = t.dims2.data();
+            a = {t.n2,        t.m2,        t.Pp.data(), t.Pi.data(), t.Px.data(), t.q.data(), t.Ap.data(),
+                 t.Ai.data(), t.Ax.data(), t.b.data(),  (int64_t)t.tags.size(), t.tags.data(), t.dims.data(),
+                 t.dims2.data()};
             cone_alphas_or_null = t.alphas.data();
             h->tf = std::move(tf);
         }
     }
-    const uint64_t nnzP = Pcolptr[n], nnzA = Acolptr[n];
-    // the entry-parallel passes of equilibrate.hip index P and A together, and A with b / e, in int32
-    if (nnzP + nnzA + (uint64_t)n + (uint64_t)m >= (1ull << 31) || n + 2 * m >= (1ll << 31))
-        return fail(CHIP_ERR_DIM, "chip_solver_create: sizes out of int32 range");
+    if (!a.fits_int32()) return fail(CHIP_ERR_DIM, "chip_solver_create: sizes out of int32 range");
     std::vector<ConeSpec> cones;
     int64_t mm = 0, p = 0, nHs = 0;
-    if (build_cone_specs(ncones, cone_tags, cone_dims, cone_dims2, cones, mm, p, nHs))
+    if (build_cone_specs(a.ncones, a.cone_tags, a.cone_dims, a.cone_dims2, cones, mm, p, nHs))
         return fail(CHIP_ERR_ARG, "chip_solver_create: bad cone");
-    if (mm != m) return fail(CHIP_ERR_DIM, "chip_solver_create: cone dimensions do not add up to m");
-    h->n = (int)n;
-    h->m = (int)m;
+    if (mm != a.m) return fail(CHIP_ERR_DIM, "chip_solver_create: cone dimensions do not add up to m");
+    ProblemData &pd = h->pd;
     if (st.linsys.device >= 0) CHIP_HIP(hipSetDevice(st.linsys.device));
-    CHIP_HIP(hipGetDevice(&h->device));
-    // ---- the data (problemdata.rs:86-160): b capped at the reference's infinity, norms of the unequilibrated q, b
-    std::vector<int> Prow(nnzP), Pcol(nnzP), Arow(nnzA), Acol(nnzA);
-    for (int64_t j = 0; j < n; j++) {
-        for (uint64_t k = Pcolptr[j]; k < Pcolptr[j + 1]; k++) {
-            if ((int64_t)Prowval[k] > j) return fail(CHIP_ERR_NOT_TRIU, "P is not upper triangular");
-            Prow[k] = (int)Prowval[k];
-            Pcol[k] = (int)j;
-        }
-        for (uint64_t k = Acolptr[j]; k < Acolptr[j + 1]; k++) {
-            if ((int64_t)Arowval[k] >= m) return fail(CHIP_ERR_DIM, "A row index out of range");
-            Arow[k] = (int)Arowval[k];
-            Acol[k] = (int)j;
-        }
-    }
-    std::vector<double> bcap(b, b + m);
-    for (double &v : bcap) v = std::min(v, 1e20); // problemdata.rs:125-127 (get_infinity)
-    double nq = 0.0, nb = 0.0;
-    for (int64_t j = 0; j < n; j++) nq = std::isnan(q[j]) ? q[j] : std::max(nq, std::fabs(q[j]));
-    for (double v : bcap) nb = std::isnan(v) ? v : std::max(nb, std::fabs(v));
-    h->normq = nq;
-    h->normb = nb;
+    CHIP_HIP(hipGetDevice(&pd.device));
+    // ---- the data (problemdata.rs:86-160), the norms of the unequilibrated q and b, the equilibration (own stream)
+    CooPattern co;
+    std::vector<double> bcap;
     DevPool &mem = h->mem;
     int rc;
-    dev::EqMats &M = h->M;
-    int *dPr, *dPc, *dAr, *dAc;
-    if ((rc = mem.upload(&dPr, Prow.data(), nnzP)) || (rc = mem.upload(&dPc, Pcol.data(), nnzP)) ||
-        (rc = mem.upload(&M.Px, Pnzval, nnzP)) || (rc = mem.upload(&dAr, Arow.data(), nnzA)) ||
-        (rc = mem.upload(&dAc, Acol.data(), nnzA)) || (rc = mem.upload(&M.Ax, Anzval, nnzA)) ||
-        (rc = mem.upload(&h->q, q, (size_t)n)) || (rc = mem.upload(&h->b, bcap.data(), (size_t)m)))
+    if ((rc = coordinate_form(a, co, [](char, int64_t, int64_t) { return 0; })) || (rc = pd.upload(mem, a, co, bcap)) ||
+        (rc = pd.alloc_scalings(mem)))
         return rc;
-    M.Prow = dPr;
-    M.Pcol = dPc;
-    M.Arow = dAr;
-    M.Acol = dAc;
-    M.nnzP = (int)nnzP;
-    M.nnzA = (int)nnzA;
-    if ((rc = mem.alloc(&h->d, (size_t)n)) || (rc = mem.alloc(&h->e, (size_t)m)) || (rc = mem.alloc(&h->dinv, (size_t)n)) ||
-        (rc = mem.alloc(&h->einv, (size_t)m)))
-        return rc;
+    h->normq = absmax_nan(a.q, 0, pd.n);
+    h->normb = absmax_nan(bcap.data(), 0, pd.m);
     const double te = now_s();
-    if ((rc = h->equilibrate(cones))) return rc;
+    DevPool work;
+    double *partials = nullptr;
+    if ((rc = work.alloc(&partials, (size_t)dev::eq_cost_partials()))) return rc;
+    hipStream_t s_eq = nullptr;
+    CHIP_HIP(hipStreamCreateWithFlags(&s_eq, hipStreamNonBlocking));
+    auto ruiz_step = [&](unsigned long long *bits, double *cstate) {
+        dev::eq_ruiz_step(s_eq, pd.M, pd.q, pd.b, pd.d, pd.e, pd.n, pd.m, bits, partials, cstate,
+                          st.equilibrate_min_scaling, st.equilibrate_max_scaling);
+    };
+    rc = pd.equilibrate(s_eq, st, cones, 1, dev::eq_bits_words(pd.n, pd.m), ruiz_step, &h->c);
+    (void)hipStreamDestroy(s_eq);
+    if (rc) return rc;
     h->equilibration_time = now_s() - te;
-    // ---- the KKT system of the equilibrated data: one copy of the scaled values to the host, then L2 / L3 as built
-    // from host arrays (the patterns do not change)
-    std::vector<double> Px(nnzP), Ax(nnzA), qs(n), bs(m);
-    if (nnzP) CHIP_HIP(hipMemcpy(Px.data(), M.Px, nnzP * 8, hipMemcpyDeviceToHost));
-    if (nnzA) CHIP_HIP(hipMemcpy(Ax.data(), M.Ax, nnzA * 8, hipMemcpyDeviceToHost));
-    if (n) CHIP_HIP(hipMemcpy(qs.data(), h->q, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (m) CHIP_HIP(hipMemcpy(bs.data(), h->b, (size_t)m * 8, hipMemcpyDeviceToHost));
-    if ((rc = chip_kkt_create(&h->kkt, n, m, Pcolptr, Prowval, Px.data(), Acolptr, Arowval, Ax.data(), ncones,
-                              cone_tags, cone_dims, cone_dims2, cone_alphas_or_null, &st.linsys, nullptr)))
-        return rc;
-    const double *ga = genpow_alphas_or_null;
-    for (int64_t i = 0; i < ncones; i++) {
-        if (cone_tags[i] == CHIP_CONE_GENPOWER) {
-            if (!ga) return fail(CHIP_ERR_ARG, "chip_solver_create: GenPow cone without its powers");
-            if ((rc = chip_kkt_set_genpow_alpha(h->kkt, i, ga))) return rc;
-            ga += cone_dims[i];
+    // ---- the KKT system of the equilibrated data; the L2 handle takes the GenPow cones' powers before L3 reads it
+    rc = pd.create_kkt(a, cone_alphas_or_null, st.linsys, &h->kkt, &h->sys, &h->stream, [&](chip_kkt *kkt) {
+        const double *ga = genpow_alphas_or_null;
+        for (int64_t i = 0; i < a.ncones; i++) {
+            const int32_t tag = a.cone_tags[i];
+            if (tag == CHIP_CONE_GENPOWER) {
+                if (!ga) return fail(CHIP_ERR_ARG, "chip_solver_create: GenPow cone without its powers");
+                if (int rc1 = chip_kkt_set_genpow_alpha(kkt, i, ga)) return rc1;
+                ga += a.cone_dims[i];
+            }
+            if (tag == CHIP_CONE_EXPONENTIAL || tag == CHIP_CONE_POWER || tag == CHIP_CONE_GENPOWER)
+                h->symmetric = false;
+            if (tag == CHIP_CONE_GENPOWER) h->allows_primal_dual = false; // genpowcone.rs:96-98
         }
-        if (cone_tags[i] == CHIP_CONE_EXPONENTIAL || cone_tags[i] == CHIP_CONE_POWER || cone_tags[i] == CHIP_CONE_GENPOWER)
-            h->symmetric = false;
-        if (cone_tags[i] == CHIP_CONE_GENPOWER) h->allows_primal_dual = false; // genpowcone.rs:96-98
-    }
-    if ((rc = chip_kktsystem_create(&h->sys, h->kkt, Pcolptr, Prowval, Px.data(), Acolptr, Arowval, Ax.data(),
-                                    qs.data(), bs.data())))
-        return rc;
-    h->stream = (hipStream_t)chip_kkt_stream(h->kkt);
-    if ((rc = chip_kkt_degree(h->kkt, &h->degree))) return rc;
+        return (int)CHIP_OK;
+    });
+    if (rc || (rc = chip_kkt_degree(h->kkt, &h->degree))) return rc;
     if ((rc = h->alloc_vars(h->vars)) || (rc = h->alloc_vars(h->lhs)) || (rc = h->alloc_vars(h->rhs)) ||
         (rc = h->alloc_vars(h->prev)))
         return rc;
-    if ((rc = mem.alloc(&h->rx, (size_t)n)) || (rc = mem.alloc(&h->rz, (size_t)m)) ||
-        (rc = mem.alloc(&h->rx_inf, (size_t)n)) || (rc = mem.alloc(&h->rz_inf, (size_t)m)) ||
-        (rc = mem.alloc(&h->Pxv, (size_t)n)) || (rc = mem.alloc(&h->xo, (size_t)h->n_out)) ||
+    if ((rc = mem.alloc(&h->rx, (size_t)pd.n)) || (rc = mem.alloc(&h->rz, (size_t)pd.m)) ||
+        (rc = mem.alloc(&h->rx_inf, (size_t)pd.n)) || (rc = mem.alloc(&h->rz_inf, (size_t)pd.m)) ||
+        (rc = mem.alloc(&h->Pxv, (size_t)pd.n)) || (rc = mem.alloc(&h->xo, (size_t)h->n_out)) ||
         (rc = mem.alloc(&h->so, (size_t)h->m_out)) || (rc = mem.alloc(&h->zo, (size_t)h->m_out)))
         return rc;
     if (h->tf) {
@@ -337,7 +235,7 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
 
 void chip_solver_destroy(chip_solver *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
+    (void)hipSetDevice(h->pd.device);
     delete h;
 }
 
@@ -358,9 +256,10 @@ int chip_solver::default_start() {
 // Residuals::update + calc_mu's dot + DefaultInfo::update (info.rs:113-178) with ONE device-to-host copy
 int chip_solver::residuals_and_info() {
     dev::WNormBatch wn{};
-    const dev::WNormSpec specs[8] = {{vars.x, d, n, 0},     {vars.z, e, m, 1},   {vars.s, einv, m, 2},
-                                     {rx_inf, dinv, n, 3}, {Pxv, dinv, n, 4},   {rz_inf, einv, m, 5},
-                                     {rz, einv, m, 6},     {rx, dinv, n, 7}};
+    const int n = pd.n, m = pd.m;
+    const dev::WNormSpec specs[8] = {{vars.x, pd.d, n, 0},    {vars.z, pd.e, m, 1},  {vars.s, pd.einv, m, 2},
+                                     {rx_inf, pd.dinv, n, 3}, {Pxv, pd.dinv, n, 4},  {rz_inf, pd.einv, m, 5},
+                                     {rz, pd.einv, m, 6},     {rx, pd.dinv, n, 7}};
     for (int k = 0; k < 8; k++) wn.s[k] = specs[k];
     wn.count = 8;
     double sq[8];
@@ -390,11 +289,12 @@ int chip_solver::post_process() {
     double scaleinv, scale_z;
     ipm_post_process(info, st, vars.tau, vars.kappa, c, &obj_val, &obj_val_dual, &scaleinv, &scale_z);
     if (!tf) {
-        dev::unscale(stream, xo, vars.x, d, scaleinv, n, zo, vars.z, e, scale_z, so, vars.s, einv, scaleinv, m);
+        dev::unscale(stream, xo, vars.x, pd.d, scaleinv, pd.n, zo, vars.z, pd.e, scale_z, so, vars.s, pd.einv, scaleinv,
+                     pd.m);
     } else { // decomp_reverse + reverse_presolve (solution.rs:94-110) in one gather, straight from the scaled variables
         const dev::RvMaps mp{rv_mode, rv_ptr, rv_src};
-        dev::transform_reverse(stream, mp, n_out, m_out, xo, vars.x, d, scaleinv, so, vars.s, einv, scaleinv, zo, vars.z,
-                               e, scale_z);
+        dev::transform_reverse(stream, mp, n_out, m_out, xo, vars.x, pd.d, scaleinv, so, vars.s, pd.einv, scaleinv, zo,
+                               vars.z, pd.e, scale_z);
     }
     CHIP_HIP(hipGetLastError());
     CHIP_HIP(hipStreamSynchronize(stream));
@@ -413,7 +313,7 @@ int chip_solver::post_process() {
 // IPSolver::solve (core/solver.rs:242-464)
 int32_t chip_solver_solve(chip_solver *h) {
     if (!h) return CHIP_ERR_ARG;
-    CHIP_HIP(hipSetDevice(h->device));
+    CHIP_HIP(hipSetDevice(h->pd.device));
     IpmInfo &info = h->info;
     info = IpmInfo(); // info.reset; the previous-iterate scalars start from the same values on every solve
     h->solve_time = 0;
@@ -506,9 +406,9 @@ int32_t chip_solver_solve(chip_solver *h) {
         // previous iterate costs no copy
         ipm_save_prev(info);
         chip_vars &nv = h->prev, &v = h->vars, &st_ = h->lhs;
-        dev::waxpby(h->stream, nv.x, alpha, st_.x, 1.0, v.x, h->n);
-        dev::waxpby(h->stream, nv.s, alpha, st_.s, 1.0, v.s, h->m);
-        dev::waxpby(h->stream, nv.z, alpha, st_.z, 1.0, v.z, h->m);
+        dev::waxpby(h->stream, nv.x, alpha, st_.x, 1.0, v.x, h->pd.n);
+        dev::waxpby(h->stream, nv.s, alpha, st_.s, 1.0, v.s, h->pd.m);
+        dev::waxpby(h->stream, nv.z, alpha, st_.z, 1.0, v.z, h->pd.m);
         CHIP_HIP(hipGetLastError());
         nv.tau = v.tau;
         nv.tau += alpha * st_.tau;
@@ -525,7 +425,7 @@ int32_t chip_solver_solve(chip_solver *h) {
 
 int32_t chip_solver_get_solution(chip_solver *h, double *x, double *s, double *z, chip_solution_info *out) {
     if (!h) return CHIP_ERR_ARG;
-    CHIP_HIP(hipSetDevice(h->device));
+    CHIP_HIP(hipSetDevice(h->pd.device));
     if (h->solved_once) {
         if (x && h->n_out) CHIP_HIP(hipMemcpy(x, h->xo, (size_t)h->n_out * 8, hipMemcpyDeviceToHost));
         if (s && h->m_out) CHIP_HIP(hipMemcpy(s, h->so, (size_t)h->m_out * 8, hipMemcpyDeviceToHost));
@@ -535,19 +435,9 @@ int32_t chip_solver_get_solution(chip_solver *h, double *x, double *s, double *z
         if (s) std::fill(s, s + h->m_out, 0.0);
         if (z) std::fill(z, z + h->m_out, 0.0);
     }
-    if (out) {
-        std::memset(out, 0, sizeof(*out));
-        out->status = h->solved_once ? h->info.status : CHIP_SOLVER_UNSOLVED;
-        out->iterations = h->info.iterations;
-        out->obj_val = h->obj_val;
-        out->obj_val_dual = h->obj_val_dual;
-        out->r_prim = h->info.res_primal;
-        out->r_dual = h->info.res_dual;
-        out->solve_time = h->solve_time;
-        out->setup_time = h->setup_time;
-        out->equilibration_time = h->equilibration_time;
-        out->iteration_time = h->iteration_time;
-    }
+    if (out)
+        fill_solution_info(out, h->solved_once, h->info, h->obj_val, h->obj_val_dual, h->solve_time, h->setup_time,
+                           h->equilibration_time, h->iteration_time);
     return CHIP_OK;
 }
 
@@ -561,9 +451,9 @@ int32_t chip_solver_get_solution_dev(chip_solver *h, double **x_dev, double **s_
 
 int32_t chip_solver_get_equilibration(chip_solver *h, double *d, double *e, double *c) {
     if (!h) return CHIP_ERR_ARG;
-    CHIP_HIP(hipSetDevice(h->device));
-    if (d && h->n) CHIP_HIP(hipMemcpy(d, h->d, (size_t)h->n * 8, hipMemcpyDeviceToHost));
-    if (e && h->m) CHIP_HIP(hipMemcpy(e, h->e, (size_t)h->m * 8, hipMemcpyDeviceToHost));
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    if (d && h->pd.n) CHIP_HIP(hipMemcpy(d, h->pd.d, (size_t)h->pd.n * 8, hipMemcpyDeviceToHost));
+    if (e && h->pd.m) CHIP_HIP(hipMemcpy(e, h->pd.e, (size_t)h->pd.m * 8, hipMemcpyDeviceToHost));
     if (c) *c = h->c;
     return CHIP_OK;
 }
@@ -576,7 +466,7 @@ int32_t chip_solver_get_equilibration(chip_solver *h, double *d, double *e, doub
 // ---------------------------------------------------------------------------------------------------------------
 int chip_solver::update_work() {
     if (flag) return CHIP_OK;
-    const size_t len = (size_t)std::max({M.nnzP, M.nnzA, n, m});
+    const size_t len = (size_t)std::max({pd.M.nnzP, pd.M.nnzA, pd.n, pd.m});
     int rc;
     if ((rc = mem.alloc(&pos, len)) || (rc = mem.alloc(&npart, (size_t)dev::pu_norm_partials())) ||
         (rc = mem.alloc(&nout, 3)) || (rc = mem.alloc(&flag, 1)))
@@ -589,7 +479,8 @@ int chip_solver::update_work() {
 int chip_solver::update(int which, const int64_t *idx_dev, const double *vals_dev, int k) {
     int rc;
     if ((rc = update_work())) return rc;
-    const int64_t len = update_len(which);
+    const int64_t len = pd.update_len(which);
+    const dev::EqMats &M = pd.M;
     hipStream_t s = stream;
     if (idx_dev) { // the whole index list is checked before anything is written
         int bad = 0;
@@ -602,10 +493,10 @@ int chip_solver::update(int which, const int64_t *idx_dev, const double *vals_de
     }
     dev::PuTarget t{};
     switch (which) { // update_P / _A / _q / _b (data_updating.rs:96-170)
-    case UPD_P: t = {M.Px, (int)len, M.Prow, M.Pcol, d, d, c, true}; break;
-    case UPD_A: t = {M.Ax, (int)len, M.Arow, M.Acol, e, d, 1.0, false}; break;
-    case UPD_Q: t = {q, (int)len, nullptr, nullptr, d, nullptr, c, true}; break;
-    default: t = {b, (int)len, nullptr, nullptr, e, nullptr, 1.0, false}; break;
+    case UPD_P: t = {M.Px, (int)len, M.Prow, M.Pcol, pd.d, pd.d, c, true}; break;
+    case UPD_A: t = {M.Ax, (int)len, M.Arow, M.Acol, pd.e, pd.d, 1.0, false}; break;
+    case UPD_Q: t = {pd.q, (int)len, nullptr, nullptr, pd.d, nullptr, c, true}; break;
+    default: t = {pd.b, (int)len, nullptr, nullptr, pd.e, nullptr, 1.0, false}; break;
     }
     if (idx_dev) dev::pu_write_partial(s, t, idx_dev, vals_dev, k, pos);
     else dev::pu_write_full(s, t, vals_dev);
@@ -616,14 +507,14 @@ int chip_solver::update(int which, const int64_t *idx_dev, const double *vals_de
         if ((rc = kkt_update_values_dev(kkt, which, src, idx_dev, idx_dev ? k : (int)len))) return rc;
     }
     if ((rc = kktsystem_update_data_dev(sys, which == UPD_P ? M.Px : nullptr, which == UPD_A ? M.Ax : nullptr,
-                                        which == UPD_Q ? q : nullptr, which == UPD_B ? b : nullptr)))
+                                        which == UPD_Q ? pd.q : nullptr, which == UPD_B ? pd.b : nullptr)))
         return rc;
     // the scalars setup derived from the values: normq / normb as the lazy getters recompute them (problemdata.rs:
     // 168-189) and max |P_ii| of the static regulariser; read back in the call's one synchronisation
     const int mask = which == UPD_Q ? 1 : which == UPD_B ? 2 : which == UPD_P ? 4 : 0;
     double hn[3] = {0, 0, 0};
     if (mask) {
-        dev::pu_norms(s, mask, q, dinv, n, b, einv, m, M.Prow, M.Pcol, M.Px, M.nnzP, npart, nout);
+        dev::pu_norms(s, mask, pd.q, pd.dinv, pd.n, pd.b, pd.einv, pd.m, M.Prow, M.Pcol, M.Px, M.nnzP, npart, nout);
         CHIP_HIP(hipGetLastError());
         CHIP_HIP(hipMemcpyAsync(hn, nout, sizeof(hn), hipMemcpyDeviceToHost, s));
     }
@@ -636,7 +527,7 @@ int chip_solver::update(int which, const int64_t *idx_dev, const double *vals_de
 
 int chip_solver::update_args(chip_solver *h, int which, const void *idx, const double *vals, int64_t k) {
     const std::string fn = update_fn(UPD_PREFIX, which);
-    return chip::update_args(fn, h, idx, vals, k, h ? h->update_len(which) : 0, [&] {
+    return chip::update_args(fn, h, idx, vals, k, h ? h->pd.update_len(which) : 0, [&] {
         if (h->tf) // data_updating.rs: PresolveIsActive / ChordalDecompositionIsActive
             return fail(CHIP_ERR_UPDATE_NOT_ALLOWED, fn + ": presolve or chordal decomposition is active (nothing changed)");
         return 0;
@@ -649,8 +540,7 @@ CHIP_UPDATE_ENTRIES(chip_problem_update_, chip_solver)
 // fields as in the reference, and every field chip_kkt keeps its own copy of (all of linsys, with the two line-search
 // fields create copies into it)
 int chip::validate_settings_update(const chip_solver_settings &o, chip_solver_settings &nw, const char *fn) {
-    nw.linsys.linesearch_backtrack_step = nw.linesearch_backtrack_step;
-    nw.linsys.min_terminate_step_length = nw.min_terminate_step_length;
+    create_settings(&nw, nw); // (linsys' copies of the two line-search fields)
     const chip_settings &a = nw.linsys, &l = o.linsys;
 #define IMMUTABLE(cond, name) \
     if (cond) return fail(CHIP_ERR_ARG, std::string(fn) + ": " name " cannot change after setup")
@@ -703,13 +593,8 @@ int32_t chip_problem_update_allowed(const chip_solver *h, int32_t *allowed) {
 
 int32_t chip_problem_get_scaled(chip_solver *h, double *Px, double *Ax, double *q, double *b) {
     if (!h) return fail(CHIP_ERR_ARG, "chip_problem_get_scaled: bad argument");
-    CHIP_HIP(hipSetDevice(h->device));
-    CHIP_HIP(hipStreamSynchronize(h->stream));
-    if (Px && h->M.nnzP) CHIP_HIP(hipMemcpy(Px, h->M.Px, (size_t)h->M.nnzP * 8, hipMemcpyDeviceToHost));
-    if (Ax && h->M.nnzA) CHIP_HIP(hipMemcpy(Ax, h->M.Ax, (size_t)h->M.nnzA * 8, hipMemcpyDeviceToHost));
-    if (q && h->n) CHIP_HIP(hipMemcpy(q, h->q, (size_t)h->n * 8, hipMemcpyDeviceToHost));
-    if (b && h->m) CHIP_HIP(hipMemcpy(b, h->b, (size_t)h->m * 8, hipMemcpyDeviceToHost));
-    return CHIP_OK;
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    return h->pd.get_scaled(h->stream, Px, Ax, q, b);
 }
 
 int32_t chip_transform_get_info(const chip_solver *h, chip_transform_info *out) {
@@ -718,9 +603,9 @@ int32_t chip_transform_get_info(const chip_solver *h, chip_transform_info *out) 
     const ProblemTransform *t = h->tf.get();
     out->m_full = h->m_out;
     out->m_reduced = t ? t->m_reduced : h->m_out;
-    out->n_internal = h->n;
-    out->m_internal = h->m;
-    out->nnzA_internal = h->M.nnzA;
+    out->n_internal = h->pd.n;
+    out->m_internal = h->pd.m;
+    out->nnzA_internal = h->pd.M.nnzA;
     out->psd_cones_decomposed = t ? (int64_t)t->patterns.size() : 0;
     out->psd_cones_added = t ? t->final_added : 0;
     out->psd_cones_added_premerge = t ? t->premerge_added : 0;
@@ -735,8 +620,9 @@ int32_t chip_transform_get_info(const chip_solver *h, chip_transform_info *out) 
 int32_t chip_debug_solver_internal_solution(void *solver, double *x2, double *s2, double *z2) {
     chip_solver *h = (chip_solver *)solver;
     if (!h) return fail(CHIP_ERR_ARG, "chip_debug_solver_internal_solution: bad argument");
-    CHIP_HIP(hipSetDevice(h->device));
-    const int n = h->n, m = h->m;
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    const ProblemData &pd = h->pd;
+    const int n = pd.n, m = pd.m;
     const bool inf = ipm_is_infeasible(h->info.status);
     const chip_vars &v = h->vars;
     const double scaleinv = inf ? 1.0 / v.kappa : 1.0 / v.tau, cinv = 1.0 / h->c;
@@ -745,7 +631,7 @@ int32_t chip_debug_solver_internal_solution(void *solver, double *x2, double *s2
     int rc;
     if ((rc = tmp.alloc(&xo, (size_t)n)) || (rc = tmp.alloc(&so, (size_t)m)) || (rc = tmp.alloc(&zo, (size_t)m)))
         return rc;
-    dev::unscale(h->stream, xo, v.x, h->d, scaleinv, n, zo, v.z, h->e, scaleinv * cinv, so, v.s, h->einv, scaleinv, m);
+    dev::unscale(h->stream, xo, v.x, pd.d, scaleinv, n, zo, v.z, pd.e, scaleinv * cinv, so, v.s, pd.einv, scaleinv, m);
     CHIP_HIP(hipGetLastError());
     CHIP_HIP(hipStreamSynchronize(h->stream));
     if (x2 && n) CHIP_HIP(hipMemcpy(x2, xo, (size_t)n * 8, hipMemcpyDeviceToHost));

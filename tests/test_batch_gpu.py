@@ -7,6 +7,7 @@ import pytest
 import scipy.sparse as sp
 
 from tests import e2e_problems as E
+from tests.test_create_refusals_host import raw_batch_create as _raw_create
 
 pytestmark = pytest.mark.gpu
 
@@ -150,26 +151,6 @@ def test_refuses_transforms(hipdev, field):
     with pytest.raises(hipdev.ChipError) as e:
         batch(hipdev, [E.basic_qp(), E.basic_lp()], **{field: 1})
     assert e.value.code == hipdev.ERR_UNSUPPORTED
-
-
-def _raw_create(hip, st, n_part, m_part, cones=None):
-    import ctypes as C
-    Pp, Pi, Px = st["P"]
-    Ap, Ai, Ax = st["A"]
-    tags, dims, dims2, alphas = hip._cone_arrays(cones if cones is not None else st["cones"])
-    n_part = np.asarray(n_part, dtype=np.int64)
-    m_part = np.asarray(m_part, dtype=np.int64)
-    h = C.c_void_p()
-    s = hip.SolverSettings.default()
-    rc = hip.lib().chip_batch_create(C.byref(h), C.c_int64(len(n_part)), n_part.ctypes.data_as(hip.P_I64),
-                                     m_part.ctypes.data_as(hip.P_I64), C.c_int64(st["n"]), C.c_int64(st["m"]),
-                                     hip._pu(Pp), hip._pu(Pi), hip._pf(Px), hip._pf(st["q"]), hip._pu(Ap), hip._pu(Ai),
-                                     hip._pf(Ax), hip._pf(st["b"]), C.c_int64(len(tags)), tags.ctypes.data_as(hip.P_I32),
-                                     dims.ctypes.data_as(hip.P_I64), dims2.ctypes.data_as(hip.P_I64), hip._pf(alphas),
-                                     None, C.byref(s))
-    if rc == 0:
-        hip.lib().chip_batch_destroy(h)
-    return rc
 
 
 def test_refuses_entries_and_cones_across_members(hipdev):
