@@ -214,12 +214,14 @@ struct chip_kkt {
     bool has_hostHs = false; // cones whose Hs must come from the host (none of the SupportedConeT kinds any more)
     double *d_s = nullptr, *d_z = nullptr, *d_w = nullptr, *d_lam = nullptr;
     double *d_rhs = nullptr, *d_lhs = nullptr; // n+m staging
-    double *bp = nullptr, *x = nullptr, *e = nullptr, *dx = nullptr; // N, permuted numbering
-    double *bp2 = nullptr, *x2 = nullptr, *e2 = nullptr, *dx2 = nullptr; // ... of the second solve of a pair (chip_kkt_solve2_dev_enqueue)
-    int last_ir2 = 0;
+    // the work vectors of a solve (N, permuted numbering): wk[k] goes with the engine's solve context k; wk[1] is
+    // allocated by the first pair of solves (chip_kkt_solve2_dev_enqueue)
+    struct SolveVecs {
+        double *bp = nullptr, *x = nullptr, *e = nullptr, *dx = nullptr;
+        int last_ir = 0;
+    } wk[2];
     double *d_tmp = nullptr;                                         // max(N, nHs, nnzP, nnzA) staging
     size_t tmp_len = 0;
-    int last_ir = 0;
     double last_eps = 0;
     bool scaling_pending_check = false;
     bool psd_rows_all_blocks = false; // every dense diagonal block of the top is a PSD cone's Hs block (k_psd_write_hs_rows)
@@ -478,7 +480,7 @@ int32_t chip_ldl_solve_dev(chip_ldl *h, double *x_dev, const double *b_dev) {
     if (!E.factored) return fail(CHIP_ERR_NOT_FACTORED, "solve() before the first refactor()");
     CHIP_HIP(hipSetDevice(E.device));
     dev::permute_in(E.stream, h->d_y, b_dev, E.perm, E.N);
-    E.enqueue_solve_inplace(h->d_y);
+    E.enqueue_solve_inplace(E.ctx[0], h->d_y);
     dev::permute_out(E.stream, x_dev, h->d_y, E.perm, E.N);
     CHIP_HIP(hipGetLastError());
     return CHIP_OK;
@@ -855,13 +857,13 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
     // ---- vectors -------------------------------------------------------------
     if ((rc = E.alloc(&h->d_rhs, (size_t)(n + m)))) return rc;
     if ((rc = E.alloc(&h->d_lhs, (size_t)(n + m)))) return rc;
-    if ((rc = E.alloc(&h->bp, (size_t)K.N))) return rc;
-    if ((rc = E.alloc(&h->x, (size_t)K.N))) return rc;
-    if ((rc = E.alloc(&h->e, (size_t)K.N))) return rc;
-    if ((rc = E.alloc(&h->dx, (size_t)K.N))) return rc;
+    if ((rc = E.alloc(&h->wk[0].bp, (size_t)K.N))) return rc;
+    if ((rc = E.alloc(&h->wk[0].x, (size_t)K.N))) return rc;
+    if ((rc = E.alloc(&h->wk[0].e, (size_t)K.N))) return rc;
+    if ((rc = E.alloc(&h->wk[0].dx, (size_t)K.N))) return rc;
     h->tmp_len = std::max<size_t>({(size_t)K.N, (size_t)K.nHs, nnzP, nnzA, 1});
     if ((rc = E.alloc(&h->d_tmp, h->tmp_len))) return rc;
-    CHIP_HIP(hipMemset(h->bp, 0, (size_t)(K.N ? K.N : 1) * sizeof(double)));
+    CHIP_HIP(hipMemset(h->wk[0].bp, 0, (size_t)(K.N ? K.N : 1) * sizeof(double)));
     if (E.ir_fused) {
         // the permutation inside every bundle as maximal ascending runs that stay inside one of the ranges
         // [0, n) (rhsx), [n, n + m) (rhsz), [n + m, N) (zeros); used when they are long on average
@@ -1117,6 +1119,17 @@ int32_t chip_kkt_update_scaled_enqueue(chip_kkt *h, const double *s_dev, const d
     return CHIP_OK;
 }
 
+// one pass writes the permuted rhs twice into work vectors k: bp (kept for the residuals) and x (solved in place), and
+// folds ||b||inf into norm set 0 of context k -- no separate copy / norm launches
+static int stage_rhs(chip_kkt *h, int k, const double *rhsx_dev, const double *rhsz_dev) {
+    Engine &E = h->E;
+    SolveCtx &c = E.ctx[k];
+    int rc = E.zero_norm_sets(c);
+    if (rc) return rc;
+    dev::setrhs_perm(c.stream, h->wk[k].bp, h->wk[k].x, rhsx_dev, rhsz_dev, E.perm, (int)h->K.n, (int)h->K.m, E.N, c.norm_set(0),
+                     c.norm_nan(0));
+    return CHIP_OK;
+}
 int32_t chip_kkt_setrhs_dev(chip_kkt *h, const double *rhsx_dev, const double *rhsz_dev) {
     if (!h) return CHIP_ERR_ARG;
     Engine &E = h->E;
@@ -1129,12 +1142,8 @@ int32_t chip_kkt_setrhs_dev(chip_kkt *h, const double *rhsx_dev, const double *r
         h->x_holds_b = true;
         return CHIP_OK;
     }
-    int rc = E.zero_norm_sets();
+    int rc = stage_rhs(h, 0, rhsx_dev, rhsz_dev);
     if (rc) return rc;
-    // one pass writes the permuted rhs twice: bp (kept for the residuals) and x (solved in
-    // place), and folds ||b||inf into norm set 0 -- no separate copy / norm launches
-    dev::setrhs_perm(E.stream, h->bp, h->x, rhsx_dev, rhsz_dev, E.perm, (int)h->K.n, (int)h->K.m, E.N,
-                     E.norm_set(0), E.norm_nan(0));
     h->x_holds_b = true;
     CHIP_HIP(hipGetLastError());
     return CHIP_OK;
@@ -1162,30 +1171,44 @@ int32_t chip_kkt_setrhs(chip_kkt *h, const double *rhsx, const double *rhsz) {
 // (the refinement loop itself, shared by the L2 handle and by chip_ldl_solve_refined: xio / eio / wio are the three work
 // vectors and come back renamed; x holds K^-1 bp's first approximation on entry)
 // (in two halves, so that two independent solves can be enqueued on two streams before either is waited for)
-static void refine_begin(Engine &E, const double *bp, double *x, double *e, double *w) {
+static void refine_begin(Engine &E, SolveCtx &c, const double *bp, double *x, double *e, double *w) {
     const chip_settings &st = E.st;
     if (!st.iterative_refinement_enable) {
-        dev::norm_inf(E.stream, x, E.N, E.norm_set(1), E.norm_nan(1));
+        dev::norm_inf(c.stream, x, E.N, c.norm_set(1), c.norm_nan(1));
         return;
     }
     // The first refinement round is enqueued SPECULATIVELY together with the initial residual,
     // so that one host synchronisation (one D2H copy of norm sets 0..2) serves both decisions of
     // directldlkktsolver.rs:288-318; if ||e0|| already meets the tolerance the speculative
     // candidate is simply never looked at.  Decisions are exactly the reference's.
-    E.enqueue_residual(e, bp, x, 1);
+    E.enqueue_residual(c, e, bp, x, 1);
     if (st.iterative_refinement_max_iter >= 1) {
         // w <- e0 is needed if the round is rejected?  No: a rejected round leaves x untouched and e
         // is dead afterwards, so e is solved in place.
-        E.enqueue_solve_inplace(e, x); // e <- x + K^-1 e0   (the candidate; "+ x" fused into the sweep)
-        E.enqueue_residual(w, bp, e, 2);
+        E.enqueue_solve_inplace(c, e, x); // e <- x + K^-1 e0   (the candidate; "+ x" fused into the sweep)
+        E.enqueue_residual(c, w, bp, e, 2);
     }
 }
-static int refine_finish(Engine &E, const double *bp, double *&xio, double *&eio, double *&wio, int &last_ir) {
+// the pair form, for two solves that walk the levels together (Engine::pair_lockstep_ok): a in context 0, b in context 1
+static void refine_begin_pair(Engine &E, const chip_kkt::SolveVecs &a, const chip_kkt::SolveVecs &b) {
+    const chip_settings &st = E.st;
+    if (!st.iterative_refinement_enable) {
+        refine_begin(E, E.ctx[0], a.bp, a.x, a.e, a.dx);
+        refine_begin(E, E.ctx[1], b.bp, b.x, b.e, b.dx);
+        return;
+    }
+    E.enqueue_residual_pair(a.e, a.bp, a.x, b.e, b.bp, b.x, 1);
+    if (st.iterative_refinement_max_iter >= 1) {
+        E.enqueue_solve_pair(a.e, a.x, b.e, b.x);
+        E.enqueue_residual_pair(a.dx, a.bp, a.e, b.dx, b.bp, b.e, 2);
+    }
+}
+static int refine_finish(Engine &E, SolveCtx &c, const double *bp, double *&xio, double *&eio, double *&wio, int &last_ir) {
     const chip_settings &st = E.st;
     int rc;
     if (!st.iterative_refinement_enable) {
         double nx;
-        if ((rc = E.read_norm(1, &nx))) return rc;
+        if ((rc = E.read_norm(c, 1, &nx))) return rc;
         return std::isfinite(nx) ? 1 : 0; // x.is_finite(), directldlkktsolver.rs:180
     }
     double *x = xio, *e = eio, *w = wio;
@@ -1193,7 +1216,7 @@ static int refine_finish(Engine &E, const double *bp, double *&xio, double *&eio
     const double stopratio = st.iterative_refinement_stop_ratio;
     const int maxiter = st.iterative_refinement_max_iter;
     double nn[3] = {0, 0, 0};
-    if ((rc = E.read_norms(0, maxiter >= 1 ? 3 : 2, nn))) return rc;
+    if ((rc = E.read_norms(c, 0, maxiter >= 1 ? 3 : 2, nn))) return rc;
     const double normb = nn[0];
     double norme = nn[1];
     if (!std::isfinite(norme)) return 0;
@@ -1204,13 +1227,13 @@ static int refine_finish(Engine &E, const double *bp, double *&xio, double *&eio
         if (it == 0) {
             norme = nn[2]; // already computed above
         } else {
-            E.enqueue_solve_inplace(e, x);
+            E.enqueue_solve_inplace(c, e, x);
             set += 1;
             if (set >= NRM_SETS) set = 3;
             if (it + 2 >= NRM_SETS) // the set is being reused: clear it first
-                CHIP_HIP(hipMemsetAsync(E.norm_set(set), 0, NRM_SET_WORDS * sizeof(unsigned long long), E.stream));
-            E.enqueue_residual(w, bp, e, set);
-            if ((rc = E.read_norm(set, &norme))) return rc;
+                CHIP_HIP(hipMemsetAsync(c.norm_set(set), 0, NRM_SET_WORDS * sizeof(unsigned long long), c.stream));
+            E.enqueue_residual(c, w, bp, e, set);
+            if ((rc = E.read_norm(c, set, &norme))) return rc;
         }
         last_ir += 1;
         if (!std::isfinite(norme)) return 0;
@@ -1229,42 +1252,39 @@ static int refine_finish(Engine &E, const double *bp, double *&xio, double *&eio
     wio = w;
     return 1;
 }
-static int refine_core(Engine &E, const double *bp, double *&xio, double *&eio, double *&wio, int &last_ir) {
-    refine_begin(E, bp, xio, eio, wio);
-    return refine_finish(E, bp, xio, eio, wio, last_ir);
+static int refine_core(Engine &E, SolveCtx &c, const double *bp, double *&xio, double *&eio, double *&wio, int &last_ir) {
+    refine_begin(E, c, bp, xio, eio, wio);
+    return refine_finish(E, c, bp, xio, eio, wio, last_ir);
 }
-static int solve_core(chip_kkt *h) {
+// the solve of the right-hand side that work vectors k hold (or that setrhs noted), in solve context k
+static int solve_core(chip_kkt *h, int k) {
     Engine &E = h->E;
+    SolveCtx &c = E.ctx[k];
+    chip_kkt::SolveVecs &w = h->wk[k];
     const int N = E.N;
     if (!E.factored) return fail(CHIP_ERR_NOT_FACTORED, "solve() before the first update()");
-    h->last_ir = 0;
     int rc;
     if (h->bp_stale && !h->rhs_deferred) h->rhs_deferred = true; // (the last fused solve left no permuted copy of b)
     if (h->rhs_deferred) { // (fused path not taken for this solve: stage the noted right-hand side now)
         h->rhs_deferred = false;
         h->bp_stale = false;
-        if ((rc = E.zero_norm_sets())) return rc;
-        dev::setrhs_perm(E.stream, h->bp, h->x, h->rhs_x, h->rhs_z, E.perm, (int)h->K.n, (int)h->K.m, E.N,
-                         E.norm_set(0), E.norm_nan(0));
+        if ((rc = stage_rhs(h, k, h->rhs_x, h->rhs_z))) return rc;
         h->x_holds_b = true;
     }
-    if (!h->x_holds_b) { // solve() again on the same right-hand side, or a full-N rhs in bp
-        if ((rc = E.zero_norm_sets())) return rc;
-        CHIP_HIP(hipMemcpyAsync(h->x, h->bp, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, E.stream));
-        dev::norm_inf(E.stream, h->bp, N, E.norm_set(0), E.norm_nan(0));
-    }
-    h->x_holds_b = false;
-    E.enqueue_solve_inplace(h->x);
-    int ok = refine_core(E, h->bp, h->x, h->e, h->dx, h->last_ir);
-    if (ok == 0 && E.sweeps_after_failure()) {
+    int ok = 0;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        w.last_ir = 0;
+        if (!h->x_holds_b) { // solve() again on the same right-hand side, a full-N rhs in bp, or the second attempt
+            if ((rc = E.zero_norm_sets(c))) return rc;
+            CHIP_HIP(hipMemcpyAsync(w.x, w.bp, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
+            dev::norm_inf(c.stream, w.bp, N, c.norm_set(0), c.norm_nan(0));
+        }
+        h->x_holds_b = false;
+        E.enqueue_solve_inplace(c, w.x);
+        ok = refine_core(E, c, w.bp, w.x, w.e, w.dx, w.last_ir);
         // non-finite with persistent sweeps in use: possibly a level barrier that timed out -- once more on the per-level
         // launches (a genuinely non-finite system fails again, at the price of one more solve)
-        h->last_ir = 0;
-        if ((rc = E.zero_norm_sets())) return rc;
-        CHIP_HIP(hipMemcpyAsync(h->x, h->bp, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, E.stream));
-        dev::norm_inf(E.stream, h->bp, N, E.norm_set(0), E.norm_nan(0));
-        E.enqueue_solve_inplace(h->x);
-        ok = refine_core(E, h->bp, h->x, h->e, h->dx, h->last_ir);
+        if (ok != 0 || attempt == 1 || !E.sweeps_after_failure()) break;
     }
     return ok;
 }
@@ -1449,13 +1469,14 @@ int32_t chip_ldl_solve_refined(chip_ldl *h, double *x, const double *b, const ch
         E.st.iterative_refinement_stop_ratio = ir_settings->iterative_refinement_stop_ratio;
     }
     if (N) CHIP_HIP(hipMemcpyAsync(h->d_b, b, N * sizeof(double), hipMemcpyHostToDevice, E.stream));
-    if ((rc = E.zero_norm_sets())) return rc;
+    SolveCtx &c = E.ctx[0];
+    if ((rc = E.zero_norm_sets(c))) return rc;
     dev::permute_in(E.stream, h->r_bp, h->d_b, E.perm, E.N);
     if (N) CHIP_HIP(hipMemcpyAsync(h->r_x, h->r_bp, N * sizeof(double), hipMemcpyDeviceToDevice, E.stream));
-    dev::norm_inf(E.stream, h->r_bp, E.N, E.norm_set(0), E.norm_nan(0));
-    E.enqueue_solve_inplace(h->r_x);
+    dev::norm_inf(E.stream, h->r_bp, E.N, c.norm_set(0), c.norm_nan(0));
+    E.enqueue_solve_inplace(c, h->r_x);
     int its = 0;
-    const int ok = refine_core(E, h->r_bp, h->r_x, h->r_e, h->r_w, its);
+    const int ok = refine_core(E, c, h->r_bp, h->r_x, h->r_e, h->r_w, its);
     if (ok == 0) (void)E.sweeps_after_failure(); // (stale barrier words must not outlive a failed solve)
     if (iterations) *iterations = its;
     if (ok != 1) return ok;
@@ -1483,10 +1504,10 @@ static int fused_enqueue(chip_kkt *h, double *lhsx_dev, double *lhsz_dev, int *s
     ir.perm = E.perm;
     ir.run_ptr = h->ir_run_ptr;
     ir.runs = h->ir_runs;
-    ir.bp = h->bp;
-    ir.xa = h->x;
-    ir.xb = h->e;
-    ir.ebuf = h->dx;
+    ir.bp = h->wk[0].bp;
+    ir.xa = h->wk[0].x;
+    ir.xb = h->wk[0].e;
+    ir.ebuf = h->wk[0].dx;
     ir.lhsx = lhsx_dev;
     ir.lhsz = lhsz_dev;
     ir.part = E.ir_part;
@@ -1602,10 +1623,9 @@ static int fused_verdict(chip_kkt *h, int slot) {
         (void)hipMemsetAsync(E.ir_ctl, 0, E.ir_ctl_len * sizeof(int), E.stream);
         return FUSED_TIMEOUT;
     }
-    h->last_ir = r[1];
+    h->wk[0].last_ir = r[1];
     return r[0] > 0 ? 1 : 0;
 }
-static int solve_core(chip_kkt *h);
 // the solve of ring slot `slot` once more, one kernel per phase with the refinement decisions on the host
 // (same results up to rounding); the slot's right-hand side buffers must still hold what was enqueued
 static int fused_retry_unfused(chip_kkt *h, int slot) {
@@ -1616,9 +1636,9 @@ static int fused_retry_unfused(chip_kkt *h, int slot) {
     h->rhs_z = a.rz;
     h->rhs_deferred = true;
     h->x_holds_b = true;
-    const int ok = solve_core(h);
+    const int ok = solve_core(h, 0);
     if (ok != 1) return ok;
-    dev::getlhs_perm(E.stream, a.lx, a.lz, h->x, E.iperm, (int)h->K.n, (int)h->K.m);
+    dev::getlhs_perm(E.stream, a.lx, a.lz, h->wk[0].x, E.iperm, (int)h->K.n, (int)h->K.m);
     CHIP_HIP(hipGetLastError());
     CHIP_HIP(hipStreamSynchronize(E.stream));
     return 1;
@@ -1642,9 +1662,9 @@ int32_t chip_kkt_solve_dev(chip_kkt *h, double *lhsx_dev, double *lhsz_dev) {
         rc = fused_verdict(h, slot);
         return rc == FUSED_TIMEOUT ? fused_retry_unfused(h, slot) : rc;
     }
-    int ok = solve_core(h);
+    int ok = solve_core(h, 0);
     if (ok != 1) return ok;
-    dev::getlhs_perm(E.stream, lhsx_dev, lhsz_dev, h->x, E.iperm, (int)h->K.n, (int)h->K.m);
+    dev::getlhs_perm(E.stream, lhsx_dev, lhsz_dev, h->wk[0].x, E.iperm, (int)h->K.n, (int)h->K.m);
     CHIP_HIP(hipGetLastError());
     return 1;
 }
@@ -1712,72 +1732,50 @@ int32_t chip_kkt_solve2_dev_enqueue(chip_kkt *h, const double *rhsx_a, const dou
     }
     if (!E.factored) return fail(CHIP_ERR_NOT_FACTORED, "solve() before the first update()");
     const size_t N = (size_t)E.N;
-    if (!h->bp2) {
-        if ((rc = E.alloc(&h->bp2, N))) return rc;
-        if ((rc = E.alloc(&h->x2, N))) return rc;
-        if ((rc = E.alloc(&h->e2, N))) return rc;
-        if ((rc = E.alloc(&h->dx2, N))) return rc;
+    chip_kkt::SolveVecs &wb = h->wk[1];
+    if (!wb.bp) {
+        if ((rc = E.alloc(&wb.bp, N))) return rc;
+        if ((rc = E.alloc(&wb.x, N))) return rc;
+        if ((rc = E.alloc(&wb.e, N))) return rc;
+        if ((rc = E.alloc(&wb.dx, N))) return rc;
     }
     if ((rc = E.pair_begin())) return rc;
     const int n = (int)h->K.n, m = (int)h->K.m;
-    h->last_ir = h->last_ir2 = 0;
     h->rhs_deferred = false;
     h->x_holds_b = false;
     h->bp_stale = false;
-    // ---- both chains enqueued: A on the engine's stream, B on the second one
-    if (E.pair_lockstep_ok()) {
-        // (wide chain supernodes with a form for two right-hand sides: the two chains walk the levels together, the wide
-        // levels as ONE launch that streams the panels for both vectors -- Engine::enqueue_solve_pair)
-        if ((rc = E.zero_norm_sets())) return rc;
-        dev::setrhs_perm(E.stream, h->bp, h->x, rhsx_a, rhsz_a, E.perm, n, m, E.N, E.norm_set(0), E.norm_nan(0));
-        E.swap_ctx();
-        rc = E.zero_norm_sets();
-        if (!rc) dev::setrhs_perm(E.stream, h->bp2, h->x2, rhsx_b, rhsz_b, E.perm, n, m, E.N, E.norm_set(0), E.norm_nan(0));
-        E.swap_ctx();
-        if (rc) return rc;
-        E.enqueue_solve_pair(h->x, nullptr, h->x2, nullptr);
-        const chip_settings &st = E.st;
-        if (!st.iterative_refinement_enable) {
-            dev::norm_inf(E.stream, h->x, E.N, E.norm_set(1), E.norm_nan(1));
-            E.swap_ctx();
-            dev::norm_inf(E.stream, h->x2, E.N, E.norm_set(1), E.norm_nan(1));
-            E.swap_ctx();
-        } else { // (refine_begin for both: the residuals, then the first round enqueued ahead of its decision)
-            E.enqueue_residual_pair(h->e, h->bp, h->x, h->e2, h->bp2, h->x2, 1);
-            if (st.iterative_refinement_max_iter >= 1) {
-                E.enqueue_solve_pair(h->e, h->x, h->e2, h->x2);
-                E.enqueue_residual_pair(h->dx, h->bp, h->e, h->dx2, h->bp2, h->e2, 2);
-            }
-        }
-    } else {
-    if ((rc = E.zero_norm_sets())) return rc;
-    dev::setrhs_perm(E.stream, h->bp, h->x, rhsx_a, rhsz_a, E.perm, n, m, E.N, E.norm_set(0), E.norm_nan(0));
-    E.enqueue_solve_inplace(h->x);
-    refine_begin(E, h->bp, h->x, h->e, h->dx);
-    E.swap_ctx();
-    rc = E.zero_norm_sets();
-    if (!rc) {
-        dev::setrhs_perm(E.stream, h->bp2, h->x2, rhsx_b, rhsz_b, E.perm, n, m, E.N, E.norm_set(0), E.norm_nan(0));
-        E.enqueue_solve_inplace(h->x2);
-        refine_begin(E, h->bp2, h->x2, h->e2, h->dx2);
+    const double *const rhsx[2] = {rhsx_a, rhsx_b}, *const rhsz[2] = {rhsz_a, rhsz_b};
+    double *const lhsx[2] = {lhsx_a, lhsx_b}, *const lhsz[2] = {lhsz_a, lhsz_b};
+    // ---- both chains enqueued before either is waited for: A in context 0 (the main stream), B in context 1.  Wide chain
+    // supernodes with a form for two right-hand sides: the two chains walk the levels together (Engine::enqueue_solve_pair)
+    const bool lockstep = E.pair_lockstep_ok();
+    for (int k = 0; k < 2; k++) {
+        chip_kkt::SolveVecs &w = h->wk[k];
+        w.last_ir = 0;
+        if ((rc = stage_rhs(h, k, rhsx[k], rhsz[k]))) return rc;
+        if (lockstep) continue;
+        E.enqueue_solve_inplace(E.ctx[k], w.x);
+        refine_begin(E, E.ctx[k], w.bp, w.x, w.e, w.dx);
     }
-    E.swap_ctx();
-    if (rc) return rc;
+    if (lockstep) {
+        E.enqueue_solve_pair(h->wk[0].x, nullptr, wb.x, nullptr);
+        refine_begin_pair(E, h->wk[0], wb);
     }
     // ---- decisions (and any further rounds) of A, then of B
-    const int oka = refine_finish(E, h->bp, h->x, h->e, h->dx, h->last_ir);
-    if (oka == 1) dev::getlhs_perm(E.stream, lhsx_a, lhsz_a, h->x, E.iperm, n, m);
-    E.swap_ctx();
-    const int okb = refine_finish(E, h->bp2, h->x2, h->e2, h->dx2, h->last_ir2);
-    if (oka == 0 || okb == 0) (void)E.sweeps_after_failure(); // (stale barrier words must not outlive a failed solve)
-    if (okb == 1) dev::getlhs_perm(E.stream, lhsx_b, lhsz_b, h->x2, E.iperm, n, m);
-    const hipError_t se = hipStreamSynchronize(E.stream); // (the second stream: its results are complete when this call returns)
-    E.swap_ctx();
+    int ok[2] = {0, 0};
+    for (int k = 0; k < 2; k++) {
+        chip_kkt::SolveVecs &w = h->wk[k];
+        ok[k] = refine_finish(E, E.ctx[k], w.bp, w.x, w.e, w.dx, w.last_ir);
+        if (ok[k] == 1) dev::getlhs_perm(E.ctx[k].stream, lhsx[k], lhsz[k], w.x, E.iperm, n, m);
+    }
+    if (ok[0] == 0 || ok[1] == 0) (void)E.sweeps_after_failure(); // (stale barrier words must not outlive a failed solve)
+    // (the second stream: its results are complete when this call returns)
+    const hipError_t se = hipStreamSynchronize(E.ctx[1].stream);
     if (se != hipSuccess) return fail(CHIP_ERR_HIP, hip_err(se, "second solve stream"));
-    if (oka < 0) return oka;
-    if (okb < 0) return okb;
-    h->pend_slots.push_back(-1 - oka);
-    h->pend_slots.push_back(-1 - okb);
+    for (int k = 0; k < 2; k++)
+        if (ok[k] < 0) return ok[k];
+    h->pend_slots.push_back(-1 - ok[0]);
+    h->pend_slots.push_back(-1 - ok[1]);
     return CHIP_OK;
 }
 int32_t chip_kkt_collect(chip_kkt *h, int32_t *update_ok, int32_t *nsolves, int32_t solves_ok[16]) {
@@ -1870,15 +1868,15 @@ int32_t chip_kkt_solve_full(chip_kkt *h, double *x, const double *b) {
     CHIP_HIP(hipSetDevice(E.device));
     const size_t bytes = (size_t)E.N * sizeof(double);
     CHIP_HIP(hipMemcpyAsync(h->d_tmp, b, bytes, hipMemcpyHostToDevice, E.stream));
-    dev::permute_in(E.stream, h->bp, h->d_tmp, E.perm, E.N);
+    dev::permute_in(E.stream, h->wk[0].bp, h->d_tmp, E.perm, E.N);
     h->x_holds_b = false;
     // bp was written directly: a right-hand side noted by an earlier setrhs() (borrowed pointers) is void
     h->rhs_deferred = false;
     h->bp_stale = false;
     h->rhs_x = h->rhs_z = nullptr;
-    int ok = solve_core(h);
+    int ok = solve_core(h, 0);
     if (ok != 1) return ok;
-    dev::permute_out(E.stream, h->d_tmp, h->x, E.perm, E.N);
+    dev::permute_out(E.stream, h->d_tmp, h->wk[0].x, E.perm, E.N);
     CHIP_HIP(hipMemcpyAsync(x, h->d_tmp, bytes, hipMemcpyDeviceToHost, E.stream));
     CHIP_HIP(hipStreamSynchronize(E.stream));
     return 1;
@@ -2123,7 +2121,7 @@ int32_t chip_kkt_info(const chip_kkt *h, chip_info *info) {
     if (!h || !info) return CHIP_ERR_ARG;
     fill_info(h->E, info);
     info->threads = h->world;
-    info->last_ir_iterations = h->last_ir;
+    info->last_ir_iterations = h->wk[0].last_ir;
     info->last_regularizer = h->last_eps;
     if (h->E.factored && !h->E.host_only) {
         i64 c = 0;

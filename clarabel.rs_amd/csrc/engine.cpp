@@ -22,10 +22,9 @@ Engine::~Engine() {
     for (SolveGraph &g : graphs) (void)hipGraphExecDestroy(g.exec);
     for (void *p : allocs) (void)hipFree(p);
     if (mb_host) (void)hipHostFree(mb_host);
-    if (alt_active) swap_ctx();
-    if (nrm_host) (void)hipHostFree(nrm_host);
-    if (alt.nrm_host) (void)hipHostFree(alt.nrm_host);
-    if (alt.stream) (void)hipStreamDestroy(alt.stream);
+    for (SolveCtx &c : ctx)
+        if (c.nrm_host) (void)hipHostFree(c.nrm_host);
+    if (ctx[1].stream) (void)hipStreamDestroy(ctx[1].stream);
     if (pair_event) (void)hipEventDestroy(pair_event);
     if (pair_ev_a) (void)hipEventDestroy(pair_ev_a);
     if (pair_ev_b) (void)hipEventDestroy(pair_ev_b);
@@ -153,6 +152,7 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
         CHIP_HIP(hipGetDevice(&device));
     }
     CHIP_HIP(hipStreamCreate(&stream));
+    ctx[0].stream = stream;
     dev::solve_kernel_attributes();
     N = S.N;
     nlevels = S.nlevels;
@@ -188,7 +188,7 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
     if ((rc = upload(&Scol, S.Scol, (size_t)nnzS))) return rc;
     if (!S.xperm.empty()) { // (the residual over the top rows reads x through a supernode-contiguous copy)
         if ((rc = upload(&xperm, S.xperm, S.xperm.size()))) return rc;
-        if ((rc = alloc(&xs_view, n))) return rc;
+        if ((rc = alloc(&ctx[0].xs_view, n))) return rc;
     }
     if ((rc = upload(&Smap, S.Smap, (size_t)nnzS))) return rc;
     if (!S.dblk_p0.empty()) {
@@ -218,8 +218,8 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
         dblk.rowbase = drb;
         dblk.start = dst;
         dblk.rownode = drn;
-        if ((rc = alloc(&dblk.P, (size_t)dblk.nrows * dblk.split))) return rc;
-        if ((rc = alloc(&bt_view, n))) return rc;
+        if ((rc = alloc(&ctx[0].dblk_P, (size_t)dblk.nrows * dblk.split))) return rc;
+        if ((rc = alloc(&ctx[0].bt_view, n))) return rc;
         { // rows of the blocks that are contiguous in L too -> dblk_l0, and the rest of K's top entries -> rest_idx
             const size_t nrows = rownode.size();
             const i64 ntop = (i64)nnzK - (i64)nnzU;
@@ -389,8 +389,8 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
             for (int sn = 0; sn < nsn; sn++) bp[sn + 1] = bp[sn] + (S.sn_ptr[sn + 1] - S.sn_ptr[sn] + 63) / 64;
             if ((rc = upload(&sn_blk_ptr, bp, bp.size()))) return rc;
             // message slots of the pipelined substitution (k_snode_tri): 64 x 16 bytes per block, epoch 0 = never written
-            if ((rc = alloc(&sn_flags, ((size_t)bp[nsn] + 1) * 256))) return rc;
-            CHIP_HIP(hipMemset(sn_flags, 0, ((size_t)bp[nsn] + 1) * 256 * sizeof(int)));
+            if ((rc = alloc(&ctx[0].sn_flags, ((size_t)bp[nsn] + 1) * 256))) return rc;
+            CHIP_HIP(hipMemset(ctx[0].sn_flags, 0, ((size_t)bp[nsn] + 1) * 256 * sizeof(int)));
         }
         for (int sn = 0; sn < nsn; sn++) {
             const i32 e = S.sn_col[S.sn_ptr[sn + 1] - 1];
@@ -509,10 +509,10 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
                 }
                 if (total > 0) {
                 CHIP_HIP(hipMemset(sn_Gx, 0, ((size_t)total + 8) * sizeof(double))); // (entries above a row's diagonal block are never written)
-                if ((rc = alloc(&sn_yt, n))) return rc;
-                CHIP_HIP(hipMemset(sn_yt, 0, n * sizeof(double)));
-                if ((rc = alloc(&gs_ctl, (size_t)dev::ir_ctl_ints()))) return rc;
-                CHIP_HIP(hipMemset(gs_ctl, 0, (size_t)dev::ir_ctl_ints() * sizeof(int)));
+                if ((rc = alloc(&ctx[0].sn_yt, n))) return rc;
+                CHIP_HIP(hipMemset(ctx[0].sn_yt, 0, n * sizeof(double)));
+                if ((rc = alloc(&ctx[0].gs_ctl, (size_t)dev::ir_ctl_ints()))) return rc;
+                CHIP_HIP(hipMemset(ctx[0].gs_ctl, 0, (size_t)dev::ir_ctl_ints() * sizeof(int)));
                 sn_g_entries = (double)total;
                 if (dev::snode_g_attributes(ghmax) != 0) {
                     set_error("k_snode_ginv: dynamic LDS size rejected");
@@ -856,9 +856,9 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
         if ((rc = alloc(&fold_cnt, (size_t)32))) return rc;
         CHIP_HIP(hipMemset(fold_cnt, 0, 32 * sizeof(int)));
     }
-    if ((rc = alloc(&nrm_dev, (size_t)NRM_SETS * NRM_SET_WORDS))) return rc;
-    CHIP_HIP(hipMemset(nrm_dev, 0, (size_t)NRM_SETS * NRM_SET_WORDS * sizeof(unsigned long long)));
-    CHIP_HIP(hipHostMalloc((void **)&nrm_host, 3 * NRM_SET_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+    if ((rc = alloc(&ctx[0].nrm_dev, (size_t)NRM_SETS * NRM_SET_WORDS))) return rc;
+    CHIP_HIP(hipMemset(ctx[0].nrm_dev, 0, (size_t)NRM_SETS * NRM_SET_WORDS * sizeof(unsigned long long)));
+    CHIP_HIP(hipHostMalloc((void **)&ctx[0].nrm_host, 3 * NRM_SET_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
     return CHIP_OK;
 }
 
@@ -962,22 +962,32 @@ void Engine::prof_collect() {
 }
 
 bool Engine::sweeps_after_failure() {
-    if (!gs_ctl || gs_off || gs_launches == 0) return false;
+    if (!ctx[0].gs_ctl || gs_off || gs_launches == 0) return false;
     (void)hipDeviceSynchronize();
-    (void)hipMemset(gs_ctl, 0, (size_t)dev::ir_ctl_ints() * sizeof(int));
-    if (alt.gs_ctl) (void)hipMemset(alt.gs_ctl, 0, (size_t)dev::ir_ctl_ints() * sizeof(int));
+    for (SolveCtx &c : ctx)
+        if (c.gs_ctl) (void)hipMemset(c.gs_ctl, 0, (size_t)dev::ir_ctl_ints() * sizeof(int));
     (void)hipGetLastError();
     gs_off = true;
     gs_recoveries += 1;
     return true;
 }
-// a device-side wait that cannot be enqueued becomes a host-side one: the chain of block columns must not read member
-// columns while the second stream still adds into them
-static void wait_event_or_sync(hipStream_t s, hipEvent_t ev) {
-    if (hipStreamWaitEvent(s, ev, 0) != hipSuccess) {
+// stream `to` waits for event `ev`, which has been recorded; a device-side wait that cannot be enqueued becomes a
+// host-side one
+static void wait_event_or_sync(hipStream_t to, hipEvent_t ev) {
+    if (hipStreamWaitEvent(to, ev, 0) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipEventSynchronize(ev);
     }
+}
+// the hand-over between two streams: `to` waits for everything stream `from` has enqueued so far.  A record that
+// fails must not let `to` run ahead either: the host waits for `from` instead
+static void wait_event_or_sync(hipStream_t to, hipStream_t from, hipEvent_t ev) {
+    if (hipEventRecord(ev, from) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(from);
+        return;
+    }
+    wait_event_or_sync(to, ev);
 }
 int Engine::wait_for_exchange() {
     if (!exch_pending) return CHIP_OK;
@@ -999,45 +1009,35 @@ int Engine::ensure_alt() {
 }
 int Engine::ensure_alt_once() {
     int rc;
-    if (!alt.stream) CHIP_HIP(hipStreamCreateWithFlags(&alt.stream, hipStreamNonBlocking));
+    const SolveCtx &c0 = ctx[0];
+    SolveCtx &c = ctx[1];
+    if (!c.stream) CHIP_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
     if (!pair_event) CHIP_HIP(hipEventCreateWithFlags(&pair_event, hipEventDisableTiming));
     if (!pair_ev_a) CHIP_HIP(hipEventCreateWithFlags(&pair_ev_a, hipEventDisableTiming));
     if (!pair_ev_b) CHIP_HIP(hipEventCreateWithFlags(&pair_ev_b, hipEventDisableTiming));
     const size_t n = (size_t)N;
-    if (sn_yt) {
-        if ((rc = alloc(&alt.sn_yt, n))) return rc;
-        CHIP_HIP(hipMemset(alt.sn_yt, 0, n * sizeof(double)));
+    if (c0.sn_yt) {
+        if ((rc = alloc(&c.sn_yt, n))) return rc;
+        CHIP_HIP(hipMemset(c.sn_yt, 0, n * sizeof(double)));
     }
-    if (gs_ctl) {
-        if ((rc = alloc(&alt.gs_ctl, (size_t)dev::ir_ctl_ints()))) return rc;
-        CHIP_HIP(hipMemset(alt.gs_ctl, 0, (size_t)dev::ir_ctl_ints() * sizeof(int)));
+    if (c0.gs_ctl) {
+        if ((rc = alloc(&c.gs_ctl, (size_t)dev::ir_ctl_ints()))) return rc;
+        CHIP_HIP(hipMemset(c.gs_ctl, 0, (size_t)dev::ir_ctl_ints() * sizeof(int)));
     }
-    if (xs_view && (rc = alloc(&alt.xs_view, n))) return rc;
-    if (bt_view && (rc = alloc(&alt.bt_view, n))) return rc;
-    if (dblk.P && (rc = alloc(&alt.dblk_P, (size_t)dblk.nrows * dblk.split))) return rc;
-    if ((rc = alloc(&alt.nrm_dev, (size_t)NRM_SETS * NRM_SET_WORDS))) return rc;
-    CHIP_HIP(hipMemset(alt.nrm_dev, 0, (size_t)NRM_SETS * NRM_SET_WORDS * sizeof(unsigned long long)));
-    CHIP_HIP(hipHostMalloc((void **)&alt.nrm_host, 3 * NRM_SET_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
-    if (sn_flags && nsn > 0) {
+    if (c0.xs_view && (rc = alloc(&c.xs_view, n))) return rc;
+    if (c0.bt_view && (rc = alloc(&c.bt_view, n))) return rc;
+    if (c0.dblk_P && (rc = alloc(&c.dblk_P, (size_t)dblk.nrows * dblk.split))) return rc;
+    if ((rc = alloc(&c.nrm_dev, (size_t)NRM_SETS * NRM_SET_WORDS))) return rc;
+    CHIP_HIP(hipMemset(c.nrm_dev, 0, (size_t)NRM_SETS * NRM_SET_WORDS * sizeof(unsigned long long)));
+    CHIP_HIP(hipHostMalloc((void **)&c.nrm_host, 3 * NRM_SET_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+    if (c0.sn_flags && nsn > 0) {
         size_t blocks = 0;
         for (int sn = 0; sn < nsn; sn++) blocks += (size_t)(h_sn_ptr[sn + 1] - h_sn_ptr[sn] + 63) / 64;
-        if ((rc = alloc(&alt.sn_flags, (blocks + 1) * 256))) return rc;
-        CHIP_HIP(hipMemset(alt.sn_flags, 0, (blocks + 1) * 256 * sizeof(int)));
+        if ((rc = alloc(&c.sn_flags, (blocks + 1) * 256))) return rc;
+        CHIP_HIP(hipMemset(c.sn_flags, 0, (blocks + 1) * 256 * sizeof(int)));
     }
     alt_ready = true;
     return CHIP_OK;
-}
-void Engine::swap_ctx() {
-    std::swap(stream, alt.stream);
-    std::swap(sn_yt, alt.sn_yt);
-    std::swap(xs_view, alt.xs_view);
-    std::swap(bt_view, alt.bt_view);
-    std::swap(dblk.P, alt.dblk_P);
-    std::swap(nrm_dev, alt.nrm_dev);
-    std::swap(nrm_host, alt.nrm_host);
-    std::swap(sn_flags, alt.sn_flags);
-    std::swap(gs_ctl, alt.gs_ctl);
-    alt_active = !alt_active;
 }
 int Engine::pair_begin() {
     int rc = ensure_alt();
@@ -1050,8 +1050,7 @@ int Engine::pair_begin() {
         dev::gather_values(stream, Sx, Kx, Smap, (int)nnzS);
         sx_valid = true;
     }
-    CHIP_HIP(hipEventRecord(pair_event, stream));
-    CHIP_HIP(hipStreamWaitEvent(alt.stream, pair_event, 0));
+    wait_event_or_sync(ctx[1].stream, stream, pair_event);
     return CHIP_OK;
 }
 
@@ -1066,7 +1065,7 @@ int Engine::build_gsweeps() {
     gs_runs.clear();
     gs_run_f.assign((size_t)nfaclevels, -1);
     gs_run_b.assign((size_t)nfaclevels, -1);
-    if (sn_g_ntasks <= 0 || !gs_ctl || switches().no_sweep_merge || switches().no_sweep_persist) return CHIP_OK;
+    if (sn_g_ntasks <= 0 || !ctx[0].gs_ctl || switches().no_sweep_merge || switches().no_sweep_persist) return CHIP_OK;
     std::vector<dev::GSweepLevel> tab;
     int ncu = 0, devid = 0;
     {
@@ -1165,7 +1164,7 @@ dev::SnodeView Engine::snode_view() const {
 
 void Engine::hs_direct_prefill_async() {
     if (!hs_direct_ok || fill_from < 0 || switches().no_hs_direct || switches().no_hs_prefill_async || (long long)nnzL <= fill_from ||
-        hs_prefill_pending || alt_active || prof_family != PF_NONE)
+        hs_prefill_pending || prof_family != PF_NONE)
         return;
     if (ensure_alt() != CHIP_OK) return;
     for (hipEvent_t &e : hs_ev)
@@ -1175,11 +1174,12 @@ void Engine::hs_direct_prefill_async() {
             return;
         }
     // (L's last readers -- the previous step's solves -- are on the main stream: the clear waits for them)
-    if (hipEventRecord(hs_ev[0], stream) != hipSuccess || hipStreamWaitEvent(alt.stream, hs_ev[0], 0) != hipSuccess ||
-        hipMemsetAsync(Lx + fill_from, 0, (size_t)((long long)nnzL - fill_from) * sizeof(double), alt.stream) != hipSuccess ||
-        hipEventRecord(hs_ev[1], alt.stream) != hipSuccess) {
+    const hipStream_t side = ctx[1].stream;
+    wait_event_or_sync(side, stream, hs_ev[0]);
+    if (hipMemsetAsync(Lx + fill_from, 0, (size_t)((long long)nnzL - fill_from) * sizeof(double), side) != hipSuccess ||
+        hipEventRecord(hs_ev[1], side) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipStreamSynchronize(alt.stream); // (whatever was enqueued there is done before the main stream goes on)
+        (void)hipStreamSynchronize(side); // (whatever was enqueued there is done before the main stream goes on)
         return;
     }
     hs_prefill_pending = true;
@@ -1375,7 +1375,7 @@ int Engine::refactor_enqueue(bool static_reg, const int *diag_idx_dev, double st
     // not with assembled updates / CHIP_DETERMINISTIC (plain read-modify-writes), not while launches are being timed.
     const int nsl = (int)snb.b_ptr.size() - 1;
     bool beside = nsn > 0 && !top_folded && snb_groups.size() > 1 && !switches().no_factor_overlap && asm_min == (1 << 30) &&
-                  prof_family == PF_NONE && !alt_active;
+                  prof_family == PF_NONE;
     if (beside && ensure_alt() != CHIP_OK) beside = false;
     if (beside) {
         if (!snb_ready) CHIP_HIP(hipEventCreateWithFlags(&snb_ready, hipEventDisableTiming));
@@ -1385,11 +1385,11 @@ int Engine::refactor_enqueue(bool static_reg, const int *diag_idx_dev, double st
             snb_events.push_back(ev);
         }
         dev::factor_B(stream, vf, snb.Brange(snb_groups[0].first, snb_groups[0].second));
-        CHIP_HIP(hipEventRecord(snb_ready, stream));
-        CHIP_HIP(hipStreamWaitEvent(alt.stream, snb_ready, 0));
+        const hipStream_t side = ctx[1].stream;
+        wait_event_or_sync(side, stream, snb_ready);
         for (size_t g = 1; g < snb_groups.size(); g++) {
-            dev::factor_B(alt.stream, vf, snb.Brange(snb_groups[g].first, snb_groups[g].second));
-            CHIP_HIP(hipEventRecord(snb_events[g], alt.stream));
+            dev::factor_B(side, vf, snb.Brange(snb_groups[g].first, snb_groups[g].second));
+            CHIP_HIP(hipEventRecord(snb_events[g], side));
         }
     } else if (nsn > 0 && !top_folded && nsl >= 1) {
         dev::factor_B(stream, vf, snb.Brange(0, nsl));
@@ -1456,30 +1456,30 @@ int Engine::refactor_collect() {
 }
 
 // qdldl.rs:755-768 in the permuted numbering, in place
-void Engine::enqueue_solve_inplace(double *xp, const double *addv) {
+void Engine::enqueue_solve_inplace(SolveCtx &c, double *xp, const double *addv) {
     if (!gs_built && nsn > 0) (void)build_gsweeps(); // (outside any capture: allocates)
     // (a fused handle taking the one-kernel-per-phase path: these kernels stream L by rows.  Refreshed here,
     // ahead of the graph lookup and outside any capture: a replayed graph contains no gather)
     if (!rx_valid && rx_needed()) {
-        dev::gather_values(stream, Rx, Lx, Rpos, (int)nnzR);
+        dev::gather_values(c.stream, Rx, Lx, Rpos, (int)nnzR);
         rx_valid = true;
     }
     if (st.use_graph && prof_family == PF_NONE) {
         for (const SolveGraph &g : graphs)
-            if (g.xp == xp && g.addv == addv) {
-                if (hipGraphLaunch(g.exec, stream) == hipSuccess) return;
+            if (g.ctx == &c && g.xp == xp && g.addv == addv) {
+                if (hipGraphLaunch(g.exec, c.stream) == hipSuccess) return;
                 break;
             }
-        if (graphs.size() < 16) { // the refinement rotates three vectors: a handful of pairs at most
+        if (graphs.size() < 16) { // the refinement rotates three vectors: a handful of triples at most
             hipGraph_t gr = nullptr;
             hipGraphExec_t ex = nullptr;
-            if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                enqueue_solve_direct(xp, addv);
-                const bool ok = hipStreamEndCapture(stream, &gr) == hipSuccess && gr &&
+            if (hipStreamBeginCapture(c.stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+                enqueue_solve_direct(c, xp, addv);
+                const bool ok = hipStreamEndCapture(c.stream, &gr) == hipSuccess && gr &&
                                 hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0) == hipSuccess;
                 if (gr) (void)hipGraphDestroy(gr);
-                if (ok && hipGraphLaunch(ex, stream) == hipSuccess) {
-                    graphs.push_back({xp, addv, ex});
+                if (ok && hipGraphLaunch(ex, c.stream) == hipSuccess) {
+                    graphs.push_back({&c, xp, addv, ex});
                     return;
                 }
                 if (ex) (void)hipGraphExecDestroy(ex);
@@ -1487,11 +1487,11 @@ void Engine::enqueue_solve_inplace(double *xp, const double *addv) {
             }
         }
     }
-    enqueue_solve_direct(xp, addv);
+    enqueue_solve_direct(c, xp, addv);
 }
 bool Engine::pair_lockstep_ok() {
     if (nsn <= 0 || fold.k || st.use_graph || switches().no_snode_tri || switches().no_pair_lockstep || prof_family != PF_NONE ||
-        !sn_flags || !alt.sn_flags)
+        !ctx[0].sn_flags || !ctx[1].sn_flags)
         return false;
     for (int l = 0; l < nfaclevels; l++) {
         const bool g = sn_g_ntasks > 0 && sn_lvl_g[l];
@@ -1500,11 +1500,11 @@ bool Engine::pair_lockstep_ok() {
     return false;
 }
 void Engine::enqueue_solve_pair(double *xa, const double *addva, double *xb, const double *addvb) {
+    SolveCtx *const cs[2] = {&ctx[0], &ctx[1]};
+    double *const xs[2] = {xa, xb};
+    const double *const addvs[2] = {addva, addvb};
     if (!pair_lockstep_ok()) {
-        enqueue_solve_inplace(xa, addva);
-        swap_ctx();
-        enqueue_solve_inplace(xb, addvb);
-        swap_ctx();
+        for (int k = 0; k < 2; k++) enqueue_solve_inplace(*cs[k], xs[k], addvs[k]);
         return;
     }
     if (!gs_built && nsn > 0) (void)build_gsweeps();
@@ -1512,351 +1512,248 @@ void Engine::enqueue_solve_pair(double *xa, const double *addva, double *xb, con
         dev::gather_values(stream, Rx, Lx, Rpos, (int)nnzR);
         rx_valid = true;
     }
-    // The level loop of enqueue_solve_direct's supernode branch, once, for both contexts: `each` runs a stage for A on
-    // A's stream, swaps the contexts (stream, scratch vectors, barrier words, message buffers), runs it for B, swaps back.
-    double *xs[2] = {xa, xb};
-    const double *addvs[2] = {addva, addvb};
-    int ctx = 0;
-    auto each = [&](auto &&fn) {
-        ctx = 0;
-        fn(xs[0], addvs[0]);
-        swap_ctx();
-        ctx = 1;
-        fn(xs[1], addvs[1]);
-        swap_ctx();
-        ctx = 0;
-    };
-    hipStream_t sA = stream, sB = alt.stream;
+    const dev::LdlView v = view();
+    for (int k = 0; k < 2; k++) dev::bundle_fwd(cs[k]->stream, v, bundles, xs[k], fold);
+    enqueue_snode_sweeps(2, cs, xs);
+    for (int k = 0; k < 2; k++) {
+        dev::bundle_bwd(cs[k]->stream, v, bundles, xs[k], addvs[k]);
+        if (addvs[k] && N > NF) dev::add_vec(cs[k]->stream, xs[k] + NF, addvs[k] + NF, N - NF);
+    }
+}
+// Chain supernodes: units by unit level.  Forward: every top row first gathers from the columns that are not supernode
+// members, then the level's supernodes solve their dense triangles and push L_BS x_S to their ancestors' entries;
+// backward: the reverse, column oriented.  A stage is a launch per context, A's on A's stream, then B's on B's.
+void Engine::enqueue_snode_sweeps(int nc, SolveCtx *const cs[], double *const xs[]) {
     const dev::LdlView v = view();
     const dev::SnodeView sview = snode_view();
-    each([&](double *x, const double *) { dev::bundle_fwd(stream, v, bundles, x, fold); });
+    auto each = [&](auto &&fn) {
+        for (int k = 0; k < nc; k++) fn(*cs[k], xs[k]);
+    };
+    // wide supernodes: several workgroups per supernode, pipelined through per-block flags that carry this
+    // sweep's epoch (not inside a captured graph: a replay would meet its own flags); one epoch serves every context
+    const bool use_tri = !switches().no_snode_tri && !st.use_graph;
+    int epoch = ++sn_epoch;
+    const dev::LaunchProf lprof = launch_prof();
+    const dev::LaunchProf *lp = prof_family >= PF_SN_UPDATE ? &lprof : nullptr;
+    // levels on the one-pass matrices take the NEXT level's row gathers (forward) / their own ordinary columns (backward)
+    // into the supernodes' launch (snode_g.hip: SweepGather); CHIP_NO_SWEEP_MERGE keeps the two launches per level
     const bool merge = sn_g_ntasks > 0 && !switches().no_sweep_merge;
     auto is_g = [&](int l) { return sn_g_ntasks > 0 && sn_lvl_g[l] && sn_lvl_ptr[l + 1] > sn_lvl_ptr[l]; };
-    const bool persist = merge && gs_lv && !switches().no_sweep_persist && !gs_off;
-    if (persist && exch_pending) (void)wait_for_exchange();
-    int epoch = ++sn_epoch;
-    // the wide levels: B's stream hands its vector over (event), A's stream runs the launch for both, B's stream waits for it
-    auto tri_level = [&](dev::GatherMode m, int l) {
-        dev::SnodeTriView ta{sn_blk_ptr, sn_flags, epoch, norm_nan(1)};
-        swap_ctx();
-        dev::SnodeTriView tb{sn_blk_ptr, sn_flags, epoch, norm_nan(1)};
-        swap_ctx();
-        (void)hipEventRecord(pair_ev_b, sB);
-        if (hipStreamWaitEvent(sA, pair_ev_b, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipEventSynchronize(pair_ev_b);
+    const bool persist = merge && gs_lv && !switches().no_sweep_persist && !gs_off; // runs of such levels: one persistent launch each
+    if (persist && exch_pending) (void)wait_for_exchange(); // (a persistent sweep beside the collective's kernels may not be co-resident)
+    // a level off the one-pass matrices (k_snode_tri and the narrow forms).  Two contexts take a wide level as ONE launch
+    // for both vectors: B's stream hands its vector over, A's stream runs the launch, B's stream waits for it
+    auto hop_level = [&](dev::GatherMode m, int l) {
+        const int *ord = sn_order + 8 * sn_lvl_ptr[l];
+        const int count = sn_lvl_ptr[l + 1] - sn_lvl_ptr[l], width = sn_lvl_nblk[l] * 64;
+        if (nc == 2 && count > 0 && width > 2 * 64) {
+            const dev::SnodeTriView ta{sn_blk_ptr, cs[0]->sn_flags, epoch, cs[0]->norm_nan(1)};
+            const dev::SnodeTriView tb{sn_blk_ptr, cs[1]->sn_flags, epoch, cs[1]->norm_nan(1)};
+            wait_event_or_sync(cs[0]->stream, cs[1]->stream, pair_ev_b);
+            dev::solve_snodes(cs[0]->stream, m, v, sview, ord, count, sn_wmax, sn_nbmax, width, sn_lvl_nbmax[l], xs[0], &ta, nullptr,
+                              xs[1], &tb);
+            tri2_launches++;
+            wait_event_or_sync(cs[1]->stream, cs[0]->stream, pair_ev_a);
+            return;
         }
-        dev::solve_snodes(sA, m, v, sview, sn_order + 8 * sn_lvl_ptr[l], sn_lvl_ptr[l + 1] - sn_lvl_ptr[l], sn_wmax, sn_nbmax,
-                          sn_lvl_nblk[l] * 64, sn_lvl_nbmax[l], xs[0], &ta, nullptr, xs[1], &tb);
-        tri2_launches++;
-        (void)hipEventRecord(pair_ev_a, sA);
-        if (hipStreamWaitEvent(sB, pair_ev_a, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipEventSynchronize(pair_ev_a);
-        }
+        each([&](SolveCtx &c, double *x) {
+            const dev::SnodeTriView t{sn_blk_ptr, c.sn_flags, epoch, c.norm_nan(1)};
+            dev::solve_snodes(c.stream, m, v, sview, ord, count, sn_wmax, sn_nbmax, width, sn_lvl_nbmax[l], x, use_tri ? &t : nullptr, lp);
+        });
     };
-    bool gathered = false;
+    auto fwd_args = [&](double *x) { return dev::GatherArgs{Rf_p, Rf_col, Rfx, x, x, nullptr, nullptr, nullptr}; };
+    auto bwd_args = [&](double *x) { return dev::GatherArgs{Lp, Li, Lx, x, x, Dinv, nullptr, nullptr}; };
+    bool gathered = false; // level l's gathers already ran inside the previous level's launch
     for (int l = 0; l < nfaclevels; l++) {
         if (!gathered)
-            each([&](double *x, const double *) {
-                dev::GatherArgs f{Rf_p, Rf_col, Rfx, x, x, nullptr, nullptr, nullptr};
-                dev::gather_merged(stream, dev::FWD, f, fwu.T(l), fwu.W(l), fwu.B(l));
+            each([&](SolveCtx &c, double *x) {
+                prof_begin(PF_SN_GATHER);
+                dev::gather_merged(c.stream, dev::FWD, fwd_args(x), fwu.T(l), fwu.W(l), fwu.B(l));
+                prof_end(PF_SN_GATHER);
             });
         gathered = false;
-        if (persist && gs_run_f[(size_t)l] >= 0) {
+        if (persist && gs_run_f[(size_t)l] >= 0) { // a run of such levels: one persistent launch
             const GRun &r = gs_runs[(size_t)gs_run_f[(size_t)l]];
-            each([&](double *x, const double *) {
-                dev::GatherArgs f{Rf_p, Rf_col, Rfx, x, x, nullptr, nullptr, nullptr};
-                dev::solve_snodes_gsweep(stream, dev::FWD, v, sview, sn_order, x, sn_yt, gs_lv + r.off, r.nlev, r.grid, r.lds, f, gs_ctl,
-                                         norm_nan(1), nullptr);
+            each([&](SolveCtx &c, double *x) {
+                dev::solve_snodes_gsweep(c.stream, dev::FWD, v, sview, sn_order, x, c.sn_yt, gs_lv + r.off, r.nlev, r.grid, r.lds,
+                                         fwd_args(x), c.gs_ctl, c.norm_nan(1), lp);
                 gs_launches++;
             });
             l += r.nlev - 1;
-            gathered = l + 1 < nfaclevels;
+            gathered = l + 1 < nfaclevels; // (the run's last level carried them)
             continue;
         }
-        if (is_g(l)) {
+        if (is_g(l)) { // one pass over G, no hops (x_S(new) -> sn_yt, the rows of B subtracted in place)
             const bool ride = merge && l + 1 < nfaclevels;
-            each([&](double *x, const double *) {
-                dev::GatherArgs f{Rf_p, Rf_col, Rfx, x, x, nullptr, nullptr, nullptr};
-                dev::solve_snodes_g(stream, dev::FWD, v, sview, sn_order + 8 * sn_lvl_ptr[l], sn_lvl_ptr[l + 1] - sn_lvl_ptr[l],
-                                    sn_lvl_wmax[l], sn_lvl_hmax[l], x, sn_yt, nullptr, ride ? &f : nullptr,
+            each([&](SolveCtx &c, double *x) {
+                const dev::GatherArgs f = fwd_args(x);
+                dev::solve_snodes_g(c.stream, dev::FWD, v, sview, sn_order + 8 * sn_lvl_ptr[l], sn_lvl_ptr[l + 1] - sn_lvl_ptr[l],
+                                    sn_lvl_wmax[l], sn_lvl_hmax[l], x, c.sn_yt, lp, ride ? &f : nullptr,
                                     ride ? fwu.T(l + 1) : dev::ListView{nullptr, 0}, ride ? fwu.W(l + 1) : dev::ListView{nullptr, 0},
                                     ride ? fwu.B(l + 1) : dev::ChunkView{nullptr, nullptr, nullptr, 0});
             });
             gathered = ride;
-        } else if (sn_lvl_ptr[l + 1] > sn_lvl_ptr[l] && sn_lvl_nblk[l] * 64 > 2 * 64) {
-            tri_level(dev::FWD, l);
         } else {
-            each([&](double *x, const double *) {
-                dev::SnodeTriView t{sn_blk_ptr, sn_flags, epoch, norm_nan(1)};
-                dev::solve_snodes(stream, dev::FWD, v, sview, sn_order + 8 * sn_lvl_ptr[l], sn_lvl_ptr[l + 1] - sn_lvl_ptr[l], sn_wmax,
-                                  sn_nbmax, sn_lvl_nblk[l] * 64, sn_lvl_nbmax[l], x, &t, nullptr);
-            });
+            hop_level(dev::FWD, l);
         }
     }
     epoch = ++sn_epoch;
     for (int l = nfaclevels - 1; l >= 0; l--) {
         if (persist && gs_run_b[(size_t)l] >= 0) {
             const GRun &r = gs_runs[(size_t)gs_run_b[(size_t)l]];
-            each([&](double *x, const double *) {
-                dev::GatherArgs g{Lp, Li, Lx, x, x, Dinv, nullptr, nullptr};
-                dev::solve_snodes_gsweep(stream, dev::BWD, v, sview, sn_order, x, sn_yt, gs_lv + r.off, r.nlev, r.grid, r.lds, g, gs_ctl,
-                                         norm_nan(1), nullptr);
+            each([&](SolveCtx &c, double *x) {
+                dev::solve_snodes_gsweep(c.stream, dev::BWD, v, sview, sn_order, x, c.sn_yt, gs_lv + r.off, r.nlev, r.grid, r.lds,
+                                         bwd_args(x), c.gs_ctl, c.norm_nan(1), lp);
                 gs_launches++;
             });
             l -= r.nlev - 1;
             continue;
         }
         const dev::ChunkView b = bwu.B(l);
-        bool rode = false;
         if (is_g(l)) {
-            const bool ride = merge && b.count == 0;
-            each([&](double *x, const double *) {
-                dev::GatherArgs g{Lp, Li, Lx, x, x, Dinv, nullptr, nullptr};
-                dev::solve_snodes_g(stream, dev::BWD, v, sview, sn_order + 8 * sn_lvl_ptr[l], sn_lvl_ptr[l + 1] - sn_lvl_ptr[l],
-                                    sn_lvl_wmax[l], sn_lvl_hmax[l], x, sn_yt, nullptr, ride ? &g : nullptr,
+            const bool ride = merge && b.count == 0; // (chunked columns need their preparation pass first)
+            each([&](SolveCtx &c, double *x) {
+                const dev::GatherArgs g = bwd_args(x);
+                dev::solve_snodes_g(c.stream, dev::BWD, v, sview, sn_order + 8 * sn_lvl_ptr[l], sn_lvl_ptr[l + 1] - sn_lvl_ptr[l],
+                                    sn_lvl_wmax[l], sn_lvl_hmax[l], x, c.sn_yt, lp, ride ? &g : nullptr,
                                     ride ? bwu.T(l) : dev::ListView{nullptr, 0}, ride ? bwu.W(l) : dev::ListView{nullptr, 0});
             });
-            rode = ride;
-        } else if (sn_lvl_ptr[l + 1] > sn_lvl_ptr[l] && sn_lvl_nblk[l] * 64 > 2 * 64) {
-            tri_level(dev::BWD, l);
+            if (ride) continue;
         } else {
-            each([&](double *x, const double *) {
-                dev::SnodeTriView t{sn_blk_ptr, sn_flags, epoch, norm_nan(1)};
-                dev::solve_snodes(stream, dev::BWD, v, sview, sn_order + 8 * sn_lvl_ptr[l], sn_lvl_ptr[l + 1] - sn_lvl_ptr[l], sn_wmax,
-                                  sn_nbmax, sn_lvl_nblk[l] * 64, sn_lvl_nbmax[l], x, &t, nullptr);
-            });
+            hop_level(dev::BWD, l);
         }
-        if (rode) continue;
-        each([&](double *x, const double *) {
-            dev::GatherArgs g{Lp, Li, Lx, x, x, Dinv, nullptr, nullptr};
-            if (b.count) dev::gather_Bprep(stream, dev::BWD, g, bwu.BR(l));
-            dev::gather_merged(stream, dev::BWD, g, bwu.T(l), bwu.W(l), b);
+        each([&](SolveCtx &c, double *x) {
+            const dev::GatherArgs g = bwd_args(x);
+            if (b.count) dev::gather_Bprep(c.stream, dev::BWD, g, bwu.BR(l));
+            prof_begin(PF_SN_GATHER);
+            dev::gather_merged(c.stream, dev::BWD, g, bwu.T(l), bwu.W(l), b);
+            prof_end(PF_SN_GATHER);
         });
     }
-    each([&](double *x, const double *addv) {
-        dev::bundle_bwd(stream, v, bundles, x, addv);
-        if (addv && N > NF) dev::add_vec(stream, x + NF, addv + NF, N - NF);
-    });
 }
-void Engine::enqueue_solve_direct(double *xp, const double *addv) {
+void Engine::enqueue_solve_direct(SolveCtx &c, double *xp, const double *addv) {
+    const hipStream_t s = c.stream;
     const dev::LdlView v = view();
-    dev::bundle_fwd(stream, v, bundles, xp, fold);
+    dev::bundle_fwd(s, v, bundles, xp, fold);
     if (fold.k) { // an "arrow": the bundles have already folded the top rows; finish the k x k part
-        dev::fold_top_solve(stream, v, fold, xp);
-        dev::bundle_bwd(stream, v, bundles, xp, addv);
-        if (addv && N > NF) dev::add_vec(stream, xp + NF, addv + NF, N - NF);
-        return;
-    }
-    if (nsn > 0) {
-        // chain supernodes: units by unit level.  Forward: every top row first gathers from the columns
-        // that are not supernode members, then the level's supernodes solve their dense triangles and
-        // push L_BS x_S to their ancestors' entries; backward: the reverse, column oriented.
-        const dev::SnodeView sview = snode_view();
-        // wide supernodes: several workgroups per supernode, pipelined through per-block flags that carry this
-        // sweep's epoch (not inside a captured graph: a replay would meet its own flags)
-        const bool use_tri = !switches().no_snode_tri && !st.use_graph;
-        dev::SnodeTriView tri{sn_blk_ptr, sn_flags, 0, norm_nan(1)};
-        dev::GatherArgs f{Rf_p, Rf_col, Rfx, xp, xp, nullptr, nullptr, nullptr};
-        tri.epoch = ++sn_epoch;
-        const dev::LaunchProf lprof = launch_prof();
-        const dev::LaunchProf *lp = prof_family >= PF_SN_UPDATE ? &lprof : nullptr;
-        // levels on the one-pass matrices take the NEXT level's row gathers (forward) / their own ordinary columns (backward)
-        // into the supernodes' launch (snode_g.hip: SweepGather); CHIP_NO_SWEEP_MERGE keeps the two launches per level
-        const bool merge = sn_g_ntasks > 0 && !switches().no_sweep_merge;
-        auto is_g = [&](int l) { return sn_g_ntasks > 0 && sn_lvl_g[l] && sn_lvl_ptr[l + 1] > sn_lvl_ptr[l]; };
-        const bool persist = merge && gs_lv && !switches().no_sweep_persist && !gs_off; // runs of such levels: one persistent launch each
-        if (persist && exch_pending) (void)wait_for_exchange(); // (a persistent sweep beside the collective's kernels may not be co-resident)
-        bool gathered = false; // level l's gathers already ran inside the previous level's launch
-        for (int l = 0; l < nfaclevels; l++) {
-            if (!gathered) {
-                prof_begin(PF_SN_GATHER);
-                dev::gather_merged(stream, dev::FWD, f, fwu.T(l), fwu.W(l), fwu.B(l));
-                prof_end(PF_SN_GATHER);
-            }
-            gathered = false;
-            if (persist && gs_run_f[(size_t)l] >= 0) { // a run of such levels: one persistent launch
-                const GRun &r = gs_runs[(size_t)gs_run_f[(size_t)l]];
-                dev::solve_snodes_gsweep(stream, dev::FWD, v, sview, sn_order, xp, sn_yt, gs_lv + r.off, r.nlev, r.grid, r.lds, f,
-                                         gs_ctl, norm_nan(1), lp);
-                gs_launches++;
-                l += r.nlev - 1;
-                gathered = l + 1 < nfaclevels; // (the run's last level carried them)
+        dev::fold_top_solve(s, v, fold, xp);
+    } else if (nsn > 0) {
+        SolveCtx *const cs[1] = {&c};
+        double *const xs[1] = {xp};
+        enqueue_snode_sweeps(1, cs, xs);
+    } else if (topblk.nblocks) { // tall top: one dependent step per block of rows instead of per level
+        dev::topblk_solve(s, dev::FWD, v, topblk, xp);
+        dev::topblk_solve(s, dev::BWD, v, topblk, xp);
+    } else {
+        dev::GatherArgs f{Rp, Rcol, Rx, xp, xp, nullptr, nullptr, nullptr};
+        for (int l = 0; l < nlevels;) {
+            const int e = fwd.chain_end[l];
+            if (e > l + 1) { // a chain-like stretch: one single-workgroup launch for levels [l, e)
+                dev::gather_chain(s, dev::FWD, f, fwd.t_idx, fwd.d_t_ptr, fwd.w_idx, fwd.d_w_ptr, l, e);
+                l = e;
                 continue;
             }
-            if (is_g(l)) { // one pass over G, no hops (x_S(new) -> sn_yt, the rows of B subtracted in place)
-                const bool ride = merge && l + 1 < nfaclevels;
-                dev::solve_snodes_g(stream, dev::FWD, v, sview, sn_order + 8 * sn_lvl_ptr[l], sn_lvl_ptr[l + 1] - sn_lvl_ptr[l],
-                                    sn_lvl_wmax[l], sn_lvl_hmax[l], xp, sn_yt, lp, ride ? &f : nullptr,
-                                    ride ? fwu.T(l + 1) : dev::ListView{nullptr, 0}, ride ? fwu.W(l + 1) : dev::ListView{nullptr, 0},
-                                    ride ? fwu.B(l + 1) : dev::ChunkView{nullptr, nullptr, nullptr, 0});
-                gathered = ride;
-            } else {
-                dev::solve_snodes(stream, dev::FWD, v, sview, sn_order + 8 * sn_lvl_ptr[l], sn_lvl_ptr[l + 1] - sn_lvl_ptr[l],
-                                  sn_wmax, sn_nbmax, sn_lvl_nblk[l] * 64, sn_lvl_nbmax[l], xp, use_tri ? &tri : nullptr, lp);
-            }
+            prof_begin(PF_FWD_T);
+            dev::gather_merged(s, dev::FWD, f, fwd.T(l), fwd.W(l), fwd.B(l));
+            prof_end(PF_FWD_T);
+            l++;
         }
-        tri.epoch = ++sn_epoch;
         dev::GatherArgs g{Lp, Li, Lx, xp, xp, Dinv, nullptr, nullptr};
-        for (int l = nfaclevels - 1; l >= 0; l--) {
-            if (persist && gs_run_b[(size_t)l] >= 0) {
-                const GRun &r = gs_runs[(size_t)gs_run_b[(size_t)l]];
-                dev::solve_snodes_gsweep(stream, dev::BWD, v, sview, sn_order, xp, sn_yt, gs_lv + r.off, r.nlev, r.grid, r.lds, g,
-                                         gs_ctl, norm_nan(1), lp);
-                gs_launches++;
-                l -= r.nlev - 1;
+        for (int l = nlevels - 1; l >= 0;) {
+            const int b0 = bwd.chain_begin[l]; // first level of the run of narrow levels that ends at l
+            if (bwd.chain_end[l] == l + 1 && l + 1 - b0 >= 2) {
+                dev::gather_chain(s, dev::BWD, g, bwd.t_idx, bwd.d_t_ptr, bwd.w_idx, bwd.d_w_ptr, b0, l + 1);
+                l = b0 - 1;
                 continue;
             }
-            const dev::ChunkView b = bwu.B(l);
-            if (is_g(l)) {
-                const bool ride = merge && b.count == 0; // (chunked columns need their preparation pass first)
-                dev::solve_snodes_g(stream, dev::BWD, v, sview, sn_order + 8 * sn_lvl_ptr[l], sn_lvl_ptr[l + 1] - sn_lvl_ptr[l],
-                                    sn_lvl_wmax[l], sn_lvl_hmax[l], xp, sn_yt, lp, ride ? &g : nullptr,
-                                    ride ? bwu.T(l) : dev::ListView{nullptr, 0}, ride ? bwu.W(l) : dev::ListView{nullptr, 0});
-                if (ride) continue;
-            } else {
-                dev::solve_snodes(stream, dev::BWD, v, sview, sn_order + 8 * sn_lvl_ptr[l], sn_lvl_ptr[l + 1] - sn_lvl_ptr[l],
-                                  sn_wmax, sn_nbmax, sn_lvl_nblk[l] * 64, sn_lvl_nbmax[l], xp, use_tri ? &tri : nullptr, lp);
-            }
-            if (b.count) dev::gather_Bprep(stream, dev::BWD, g, bwu.BR(l));
-            prof_begin(PF_SN_GATHER);
-            dev::gather_merged(stream, dev::BWD, g, bwu.T(l), bwu.W(l), b);
-            prof_end(PF_SN_GATHER);
+            const dev::ChunkView b = bwd.B(l);
+            if (b.count) dev::gather_Bprep(s, dev::BWD, g, bwd.BR(l));
+            prof_begin(PF_BWD_T);
+            dev::gather_merged(s, dev::BWD, g, bwd.T(l), bwd.W(l), b);
+            prof_end(PF_BWD_T);
+            l--;
         }
-        dev::bundle_bwd(stream, v, bundles, xp, addv);
-        if (addv && N > NF) dev::add_vec(stream, xp + NF, addv + NF, N - NF);
-        return;
     }
-    if (topblk.nblocks) { // tall top: one dependent step per block of rows instead of per level
-        dev::topblk_solve(stream, dev::FWD, v, topblk, xp);
-        dev::topblk_solve(stream, dev::BWD, v, topblk, xp);
-        dev::bundle_bwd(stream, v, bundles, xp, addv);
-        if (addv && N > NF) dev::add_vec(stream, xp + NF, addv + NF, N - NF);
-        return;
-    }
-    dev::GatherArgs f{Rp, Rcol, Rx, xp, xp, nullptr, nullptr, nullptr};
-    for (int l = 0; l < nlevels;) {
-        const int e = fwd.chain_end[l];
-        if (e > l + 1) { // a chain-like stretch: one single-workgroup launch for levels [l, e)
-            dev::gather_chain(stream, dev::FWD, f, fwd.t_idx, fwd.d_t_ptr, fwd.w_idx, fwd.d_w_ptr, l, e);
-            l = e;
-            continue;
-        }
-        prof_begin(PF_FWD_T);
-        dev::gather_merged(stream, dev::FWD, f, fwd.T(l), fwd.W(l), fwd.B(l));
-        prof_end(PF_FWD_T);
-        l++;
-    }
-    dev::GatherArgs g{Lp, Li, Lx, xp, xp, Dinv, nullptr, nullptr};
-    for (int l = nlevels - 1; l >= 0;) {
-        const int b0 = bwd.chain_begin[l]; // first level of the run of narrow levels that ends at l
-        if (bwd.chain_end[l] == l + 1 && l + 1 - b0 >= 2) {
-            dev::gather_chain(stream, dev::BWD, g, bwd.t_idx, bwd.d_t_ptr, bwd.w_idx, bwd.d_w_ptr, b0, l + 1);
-            l = b0 - 1;
-            continue;
-        }
-        const dev::ChunkView b = bwd.B(l);
-        if (b.count) dev::gather_Bprep(stream, dev::BWD, g, bwd.BR(l));
-        prof_begin(PF_BWD_T);
-        dev::gather_merged(stream, dev::BWD, g, bwd.T(l), bwd.W(l), b);
-        prof_end(PF_BWD_T);
-        l--;
-    }
-    dev::bundle_bwd(stream, v, bundles, xp, addv);
+    dev::bundle_bwd(s, v, bundles, xp, addv);
     // the top rows feed the bundles' backward sweeps, so their share of "+ addv" comes last
-    if (addv && N > NF) dev::add_vec(stream, xp + NF, addv + NF, N - NF);
+    if (addv && N > NF) dev::add_vec(s, xp + NF, addv + NF, N - NF);
 }
 
 // e = b - K x with the UNregularised K (directldlkktsolver.rs:334-347)
 // phases (enqueue_residual_pair runs them separately): 1 = what precedes the dense diagonal blocks' products, 2 = those
 // products for this vector alone, 4 = everything after them
-void Engine::enqueue_residual(double *e, const double *b, const double *x, int set, int phases) {
+void Engine::enqueue_residual(SolveCtx &c, double *e, const double *b, const double *x, int set, int phases) {
+    const hipStream_t s = c.stream;
     dev::GatherArgs a{Sp, Scol, Sx, x, e, b, nullptr, nullptr};
     if (set >= 0) {
-        a.nrm = norm_set(set);
-        a.nan = norm_nan(set);
+        a.nrm = c.norm_set(set);
+        a.nan = c.norm_nan(set);
     }
     if (fold.k) { // top rows: bundle shares accumulated by the bundle kernel, finished by one tiny launch
         if (!(phases & 4)) return;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         prof_pair(PF_SYMV_T, &ev0, &ev1);
-        dev::bundle_symv(stream, bundles, Up, Ucol, Ux, x, b, e, a.nrm, a.nan, fold, ev0, ev1);
-        dev::fold_top_residual(stream, fold, Kx, x, b, e, a.nrm, a.nan); // (top-top entries by their position in Kx)
+        dev::bundle_symv(s, bundles, Up, Ucol, Ux, x, b, e, a.nrm, a.nan, fold, ev0, ev1);
+        dev::fold_top_residual(s, fold, Kx, x, b, e, a.nrm, a.nan); // (top-top entries by their position in Kx)
         return;
     }
     if (phases & 1) {
         if (!sx_valid) { // (K's values have not changed since the refactor: every write to them is followed by one)
-            dev::gather_values(stream, Sx, Kx, Smap, (int)nnzS);
+            dev::gather_values(s, Sx, Kx, Smap, (int)nnzS);
             sx_valid = true;
         }
-        if (xperm) dev::gather_values(stream, xs_view, x, xperm, N);
+        if (xperm) dev::gather_values(s, c.xs_view, x, xperm, N);
         // dense diagonal blocks of the top: multiplied from K's values directly, taken off b beforehand
-        if (dblk.nblk) (void)hipMemcpyAsync(bt_view, b, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, stream);
+        if (dblk.nblk) (void)hipMemcpyAsync(c.bt_view, b, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s);
     }
-    if (xperm) a.xin = xs_view;
+    if (xperm) a.xin = c.xs_view;
     if (dblk.nblk) {
-        if (phases & 2) dev::dblk_symv(stream, dblk, Kx, x, bt_view);
-        a.aux = bt_view;
+        if (phases & 2) dev::dblk_symv(s, dblk_of(c), Kx, x, c.bt_view);
+        a.aux = c.bt_view;
     }
     if (!(phases & 4)) return;
     const dev::ChunkView bc = smv.B(0);
-    if (bc.count) dev::gather_Bprep(stream, dev::SYMV, a, smv.BR(0));
-    dev::gather_merged(stream, dev::SYMV, a, smv.T(0), smv.W(0), bc); // the top rows (full rows)
+    if (bc.count) dev::gather_Bprep(s, dev::SYMV, a, smv.BR(0));
+    dev::gather_merged(s, dev::SYMV, a, smv.T(0), smv.W(0), bc); // the top rows (full rows)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     prof_pair(PF_SYMV_T, &ev0, &ev1);
-    dev::bundle_symv(stream, bundles, Up, Ucol, Ux, x, b, e, a.nrm, a.nan, dev::FoldView{}, ev0, ev1); // everything else
-    if (bc.count && set >= 0) dev::norm_rows(stream, e, smv.BR(0), a.nrm, a.nan);
+    dev::bundle_symv(s, bundles, Up, Ucol, Ux, x, b, e, a.nrm, a.nan, dev::FoldView{}, ev0, ev1); // everything else
+    if (bc.count && set >= 0) dev::norm_rows(s, e, smv.BR(0), a.nrm, a.nan);
 }
-// The residuals of the two solves of a pair (A: this context, B: the second one).  With dense diagonal blocks in the top
-// their products are ONE launch for both vectors (k_dblk_symv<2>: every entry of the blocks read once) on A's stream:
-// B's stream hands its vector over (event), waits for the launch and finishes its own sums.
+// The residuals of the two solves of a pair (A in ctx[0], B in ctx[1]).  With dense diagonal blocks in the top their
+// products are ONE launch for both vectors (k_dblk_symv<2>: every entry of the blocks read once) on A's stream:
+// B's stream hands its vector over, waits for the launch and finishes its own sums.
 void Engine::enqueue_residual_pair(double *eA, const double *bA, const double *xA, double *eB, const double *bB, const double *xB, int set) {
+    SolveCtx &A = ctx[0], &B = ctx[1];
     const bool two = dblk.nblk > 0 && dblk_pair_ok && !fold.k && pair_ev_a && pair_ev_b && !switches().no_dblk_pair && prof_family == PF_NONE;
     if (!two) {
-        enqueue_residual(eA, bA, xA, set);
-        swap_ctx();
-        enqueue_residual(eB, bB, xB, set);
-        swap_ctx();
+        enqueue_residual(A, eA, bA, xA, set);
+        enqueue_residual(B, eB, bB, xB, set);
         return;
     }
-    hipStream_t sA = stream, sB = alt.stream;
-    enqueue_residual(eA, bA, xA, set, 1);
-    swap_ctx();
-    enqueue_residual(eB, bB, xB, set, 1);
-    double *PB = dblk.P, *btB = bt_view;
-    swap_ctx();
-    (void)hipEventRecord(pair_ev_b, sB);
-    if (hipStreamWaitEvent(sA, pair_ev_b, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipEventSynchronize(pair_ev_b);
-    }
-    dev::dblk_symv2(sA, dblk, Kx, xA, xB, PB, bt_view);
+    enqueue_residual(A, eA, bA, xA, set, 1);
+    enqueue_residual(B, eB, bB, xB, set, 1);
+    wait_event_or_sync(A.stream, B.stream, pair_ev_b);
+    dev::dblk_symv2(A.stream, dblk_of(A), Kx, xA, xB, B.dblk_P, A.bt_view);
     dblk2_launches++;
-    (void)hipEventRecord(pair_ev_a, sA);
-    if (hipStreamWaitEvent(sB, pair_ev_a, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipEventSynchronize(pair_ev_a);
-    }
-    enqueue_residual(eA, bA, xA, set, 4);
-    swap_ctx();
-    dev::dblk_finish(stream, dblk, btB); // (this context's partial sums, written by the launch on the other stream)
-    enqueue_residual(eB, bB, xB, set, 4);
-    swap_ctx();
+    wait_event_or_sync(B.stream, A.stream, pair_ev_a);
+    enqueue_residual(A, eA, bA, xA, set, 4);
+    dev::dblk_finish(B.stream, dblk_of(B), B.bt_view); // (B's partial sums, written by the launch on A's stream)
+    enqueue_residual(B, eB, bB, xB, set, 4);
 }
 
-int Engine::zero_norm_sets() {
-    CHIP_HIP(hipMemsetAsync(nrm_dev, 0, (size_t)NRM_SETS * NRM_SET_WORDS * sizeof(unsigned long long), stream));
+int Engine::zero_norm_sets(SolveCtx &c) {
+    CHIP_HIP(hipMemsetAsync(c.nrm_dev, 0, (size_t)NRM_SETS * NRM_SET_WORDS * sizeof(unsigned long long), c.stream));
     return CHIP_OK;
 }
 
-int Engine::read_norms(int first, int count, double *out) {
-    CHIP_HIP(hipMemcpyAsync(nrm_host, norm_set(first), (size_t)count * NRM_SET_WORDS * sizeof(unsigned long long),
-                            hipMemcpyDeviceToHost, stream));
-    CHIP_HIP(hipStreamSynchronize(stream));
+int Engine::read_norms(SolveCtx &c, int first, int count, double *out) {
+    CHIP_HIP(hipMemcpyAsync(c.nrm_host, c.norm_set(first), (size_t)count * NRM_SET_WORDS * sizeof(unsigned long long),
+                            hipMemcpyDeviceToHost, c.stream));
+    CHIP_HIP(hipStreamSynchronize(c.stream));
     for (int k = 0; k < count; k++) {
         unsigned long long m = 0;
-        const unsigned long long *base = nrm_host + (size_t)k * NRM_SET_WORDS;
+        const unsigned long long *base = c.nrm_host + (size_t)k * NRM_SET_WORDS;
         for (int i = 0; i < dev::NRM_SLOTS; i++) m = std::max(m, base[(size_t)i * dev::NRM_STRIDE]);
         double d;
         std::memcpy(&d, &m, sizeof(d));
@@ -1865,7 +1762,7 @@ int Engine::read_norms(int first, int count, double *out) {
     }
     return CHIP_OK;
 }
-int Engine::read_norm(int set, double *out) { return read_norms(set, 1, out); }
+int Engine::read_norm(SolveCtx &c, int set, double *out) { return read_norms(c, set, 1, out); }
 
 // the caller's K.nzval order -> the device's T order (one staging copy + one gather kernel)
 int Engine::upload_values(const double *host_nzval) {

@@ -58,9 +58,31 @@ enum ProfFamily {
     PF_COUNT
 };
 
+// A solve context: everything a solve (substitution sweeps, residual, norms) writes besides its own vectors, and the stream
+// it runs on.  Two INDEPENDENT solves of an interior-point iteration (the constant right-hand side of kktsystem.rs:108-125
+// and the affine direction of core/solver.rs:351-361) run in two contexts on two streams: on systems whose top is
+// level-scheduled a sweep is a chain of small launches that leave most of the chip idle, and two such chains overlap.
+// Every solve-path method of the engine takes its context; nothing is swapped in or out.
+struct SolveCtx {
+    hipStream_t stream = nullptr;
+    double *sn_yt = nullptr;   // the forward sweep's output on the one-pass substitution matrices (snode_g.hip)
+    double *xs_view = nullptr; // x in the supernode-contiguous order (Engine::xperm)
+    double *bt_view = nullptr; // b minus the dense diagonal blocks' products (enqueue_residual)
+    double *dblk_P = nullptr;  // dev::DblkView::P
+    unsigned long long *nrm_dev = nullptr; // NRM_SETS slotted inf-norm accumulators
+    unsigned long long *nrm_host = nullptr; // pinned: the (at most 3) sets one read_norms() copies back
+    int *sn_flags = nullptr;   // dev::SnodeTriView: one flag per 64-column block of the wide supernodes
+    int *gs_ctl = nullptr;     // the persistent sweeps' grid barrier counters
+    unsigned long long *norm_set(int set) const { return nrm_dev + (size_t)set * NRM_SET_WORDS; }
+    int *norm_nan(int set) const { return (int *)(norm_set(set) + dev::NRM_SLOTS * dev::NRM_STRIDE); }
+};
+
 struct Engine {
     int device = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr; // the main stream (== ctx[0].stream; never changes after init)
+    // ctx[0]: filled by init.  ctx[1]: filled by ensure_alt() on the first pair of solves; its stream also carries the
+    // refactor's side work (hs_direct_prefill_async, factor_B beside the supernode chain)
+    SolveCtx ctx[2];
     chip_settings st{};
     int N = 0, nlevels = 0;
     i64 nnzK = 0, nnzL = 0, nnzS = 0;
@@ -111,9 +133,13 @@ struct Engine {
     long long *upd_ptr = nullptr;
     double *sn_d = nullptr; // pivots of the supernode members, packed (dev::SnodeView::sn_d)
     int *sn_cnt = nullptr;  // dev::SnodeView::sn_cnt
-    dev::DblkView dblk;       // dense diagonal blocks of the top in the residual (host.hpp: Symbolic::dblk_*)
+    dev::DblkView dblk;       // dense diagonal blocks of the top in the residual (host.hpp: Symbolic::dblk_*); P: per context
+    dev::DblkView dblk_of(const SolveCtx &c) const {
+        dev::DblkView d = dblk;
+        d.P = c.dblk_P;
+        return d;
+    }
     std::vector<i32> h_dblk_node, h_dblk_m; // (host copies: the cone layer matches its Hs blocks against them)
-    double *bt_view = nullptr; // b minus the blocks' products (enqueue_residual)
     // ancestor updates assembled per target column (dev::SnodeAsmView; host.hpp: Symbolic::asm_*)
     int *asm_tgt = nullptr, *asm_src_ptr = nullptr, *asm_doff = nullptr;
     long long *asm_src = nullptr, *asm_uoff = nullptr;
@@ -124,7 +150,7 @@ struct Engine {
     // supernodes take the path (all of them or none), the matrices, the build's task list, the forward sweep's output
     std::vector<char> sn_lvl_g;
     std::vector<i32> sn_lvl_wmax;
-    double *sn_Gx = nullptr, *sn_yt = nullptr;
+    double *sn_Gx = nullptr;
     long long *sn_g_off = nullptr;
     int *sn_g_tasks = nullptr;
     int sn_g_ntasks = 0;
@@ -137,7 +163,6 @@ struct Engine {
     std::vector<GRun> gs_runs;
     std::vector<i32> gs_run_f, gs_run_b; // per unit level: the run that STARTS there in the forward / backward sweep, or -1
     dev::GSweepLevel *gs_lv = nullptr;
-    int *gs_ctl = nullptr; // the grid barrier's counters (per solve context)
     bool gs_built = false;
     int gs_launches = 0; // (tests: persistent launches enqueued so far)
     // A persistent sweep whose level barrier timed out (a launch that was not co-resident) raises the solve's
@@ -149,9 +174,8 @@ struct Engine {
     int build_gsweeps();
     std::vector<i32> sn_lvl_ptr, sn_lvl_nblk, sn_lvl_hmax, sn_lvl_nbmax, h_sn_ptr, h_sn_col;
     // pipelined substitution through wide supernodes (dev::SnodeTriView): one flag per 64-column block
-    int *sn_blk_ptr = nullptr, *sn_flags = nullptr;
-    int *xperm = nullptr;      // supernode-contiguous order of the nodes (residual over the top rows)
-    double *xs_view = nullptr; // x in that order
+    int *sn_blk_ptr = nullptr;
+    int *xperm = nullptr; // supernode-contiguous order of the nodes (residual over the top rows)
     int sn_epoch = 0;
     dev::BundleView bundles{}; // subtree bundles (device arrays)
     dev::FoldView fold{};      // few dense top rows folded into the bundle kernels (k == 0: not used)
@@ -162,7 +186,6 @@ struct Engine {
     int NF = 0, tree_depth = 0;
     std::vector<i32> h_level;
     Mailbox *mb_dev = nullptr, *mb_host = nullptr;
-    unsigned long long *nrm_dev = nullptr, *nrm_host = nullptr; // NRM_SETS slotted inf-norm accumulators
     int *fill_idx = nullptr;
     int nfill = 0;
     long long fill_from = -1; // >= 0: Lx[fill_from .. nnzL) is cleared as a range before K's entries are scattered (host.hpp)
@@ -174,9 +197,10 @@ struct Engine {
     bool factored = false;
     i64 last_regularize_count = 0;
     std::vector<void *> allocs;
-    // settings.use_graph: the launch sequence of one LDL' solve captured once per (vector, addend)
-    // pair and replayed as a hipGraph (hundreds of launches for a tall top)
+    // settings.use_graph: the launch sequence of one LDL' solve captured once per (context, vector, addend)
+    // and replayed as a hipGraph (hundreds of launches for a tall top)
     struct SolveGraph {
+        const SolveCtx *ctx;
         double *xp;
         const double *addv;
         hipGraphExec_t exec;
@@ -262,42 +286,33 @@ struct Engine {
     int upload_values(const double *host_nzval);
     int download_values(double *host_nzval);
     // xp <- K^-1 xp (permuted numbering); with addv the result is xp <- K^-1 xp + addv
-    void enqueue_solve_inplace(double *xp, const double *addv = nullptr);
-    void enqueue_solve_direct(double *xp, const double *addv);
-    // two independent solves (context A = the active one, context B = alt; pair_begin() has run): systems whose wide chain
-    // supernodes have a form for two right-hand sides walk the levels ONCE, every other stage twice (a launch per context
-    // on its own stream), the wide levels as one launch that streams the panels for both vectors; everything else: two chains
+    void enqueue_solve_inplace(SolveCtx &c, double *xp, const double *addv = nullptr);
+    void enqueue_solve_direct(SolveCtx &c, double *xp, const double *addv);
+    // the forward and backward sweep over the top's unit levels (chain supernodes) for nc = 1 or 2 contexts.  Two contexts
+    // walk the levels ONCE: every stage is a launch per context on its own stream, the wide levels one launch on the first
+    // context's stream that streams the panels for both vectors
+    void enqueue_snode_sweeps(int nc, SolveCtx *const cs[], double *const xs[]);
+    // two independent solves, A in ctx[0] and B in ctx[1] (pair_begin() has run): systems whose wide chain supernodes have
+    // a form for two right-hand sides (pair_lockstep_ok) walk the levels once; everything else: two chains
     void enqueue_solve_pair(double *xa, const double *addva, double *xb, const double *addvb);
     bool pair_lockstep_ok();
     int tri2_launches = 0; // (tests: two-right-hand-side launches of k_snode_tri so far)
-    // e = b - K x (permuted numbering); ||e||inf is folded into norm set `set` (>= 0)
-    void enqueue_residual(double *e, const double *b, const double *x, int set, int phases = 7);
+    // e = b - K x (permuted numbering); ||e||inf is folded into norm set `set` (>= 0) of the context
+    void enqueue_residual(SolveCtx &c, double *e, const double *b, const double *x, int set, int phases = 7);
     void enqueue_residual_pair(double *eA, const double *bA, const double *xA, double *eB, const double *bB, const double *xB, int set);
     bool dblk_pair_ok = false; // k_dblk_symv<2> fits the LDS
     long long dblk2_launches = 0;
-    int zero_norm_sets();                                                    // enqueue
-    unsigned long long *norm_set(int set) const { return nrm_dev + (size_t)set * NRM_SET_WORDS; }
-    int *norm_nan(int set) const { return (int *)(norm_set(set) + dev::NRM_SLOTS * dev::NRM_STRIDE); }
-    int read_norm(int set, double *out);                                     // D2H + sync; NaN propagating
-    int read_norms(int first, int count, double *out);                       // `count` <= 3 contiguous sets, ONE D2H copy
+    int zero_norm_sets(SolveCtx &c);                                         // enqueue
+    int read_norm(SolveCtx &c, int set, double *out);                        // D2H + sync; NaN propagating
+    int read_norms(SolveCtx &c, int first, int count, double *out);          // `count` <= 3 contiguous sets, ONE D2H copy
     int read_mailbox();                                                      // D2H + sync
+    // (launch timing records on the main stream: the pair path is not taken while a family is timed)
     void prof_begin(int family);
     void prof_end(int family);
     void prof_pair(int family, hipEvent_t *ev0, hipEvent_t *ev1);
     void prof_collect();
     dev::SnodeView snode_view() const;
-    // ---- a second solve context (round 5): two INDEPENDENT solves of an interior-point iteration (the constant right-hand side
-    // of kktsystem.rs:108-125 and the affine direction of core/solver.rs:351-361) enqueued on two streams.  On systems whose
-    // top is level-scheduled a sweep is a chain of small launches that leave most of the chip idle; two such chains overlap.
-    // Everything a solve writes besides its own vectors lives here and is swapped with the engine's members by swap_ctx().
-    struct SolveCtx {
-        hipStream_t stream = nullptr;
-        double *sn_yt = nullptr, *xs_view = nullptr, *bt_view = nullptr, *dblk_P = nullptr;
-        unsigned long long *nrm_dev = nullptr, *nrm_host = nullptr;
-        int *sn_flags = nullptr, *gs_ctl = nullptr;
-    };
-    SolveCtx alt;
-    bool alt_ready = false, alt_active = false;
+    bool alt_ready = false;  // ctx[1] is set up
     bool alt_failed = false; // the second solve context could not be set up once: not tried again
     // the exchange of the sharded path (comm.cpp) as an event of this handle: a persistent launch (the fused solve, the
     // persistent sweeps) needs every workgroup co-resident and must not start beside the collective's kernels
@@ -308,9 +323,8 @@ struct Engine {
     bool pair_ok() const { return !ir_fused && fold.k == 0 && gfold.ng == 0 && topblk.nblocks == 0; } // (no shared accumulators)
     int ensure_alt();
     int ensure_alt_once();
-    void swap_ctx();
-    // makes the second stream wait for everything enqueued on the first one so far (the refactor), after the value mirrors a
-    // solve reads lazily (Rx, Sx) have been refreshed on the first stream
+    // makes the second context's stream wait for everything enqueued on the main one so far (the refactor), after the value
+    // mirrors a solve reads lazily (Rx, Sx) have been refreshed on the main stream
     int pair_begin();
     dev::LaunchProf launch_prof(); // hook handed to the launchers in snode.hip (nullptr-equivalent when off)
     // work model of the chain supernodes, per refactor / per sweep (host.hpp: Symbolic::sn_*), for the roofline

@@ -629,6 +629,89 @@ def test_paired_solves_match_separate_solves(hip, oracle, which, monkeypatch):
                 assert relerr(outs[k].numpy(), outs[2 + k].numpy()) <= (1e-10 if st is None else 1e-7)
 
 
+def _pair_call(hip, ks, n, rhs):
+    """one chip_kkt_solve2_dev_enqueue + collect for the two (rhsx, rhsz) of `rhs`; the two results on the host"""
+    dev = [(hip.DeviceArray(a), hip.DeviceArray(b)) for a, b in rhs]
+    outs = [hip.DeviceArray(len(rhs[0][0]) + len(rhs[0][1])) for _ in range(2)]
+    ks.solve2_dev_enqueue(dev[0][0].ptr, dev[0][1].ptr, outs[0].ptr, outs[0].ptr + 8 * n,
+                          dev[1][0].ptr, dev[1][1].ptr, outs[1].ptr, outs[1].ptr + 8 * n)
+    uok, sok = ks.collect()
+    assert uok and sok == [True, True]
+    return [o.numpy() for o in outs]
+
+
+def _separate_call(hip, ks, n, rhs):
+    """the same right-hand sides as separate calls on the same handle"""
+    res = []
+    for a, b in rhs:
+        da, db, out = hip.DeviceArray(a), hip.DeviceArray(b), hip.DeviceArray(len(a) + len(b))
+        ks.setrhs_dev(da.ptr, db.ptr)
+        ks.solve_dev_enqueue(out.ptr, out.ptr + 8 * n)
+        uok, sok = ks.collect()
+        assert uok and sok == [True]
+        res.append(out.numpy())
+    return res
+
+
+@pytest.mark.parametrize("env", [None, "CHIP_NO_PAIR_LOCKSTEP"])
+@pytest.mark.parametrize("which", ["chordal_sdp_wide", "qp_supernodes"])
+def test_paired_solves_no_cross_talk(hip, oracle, which, env, monkeypatch):
+    """the two solve contexts of a pair share nothing a solve writes: one side's right-hand side all zeros, the other's
+    random, then the roles reversed -- the zero side's result is exactly zero in every entry (a stage of one context
+    that read or wrote a scratch vector, flag array or norm set of the other would leave something there), the other
+    side's is what the same solve gives as a separate call.  chordal_sdp_wide reaches the two-vector launches (k_snode_tri,
+    k_dblk_symv<2>), the banded QP the persistent sweeps; CHIP_NO_PAIR_LOCKSTEP: two independent chains"""
+    hs = None
+    if which == "chordal_sdp_wide":
+        pr = problems.chordal_sdp(5, 40, 8, 5, 21, seed=5)
+        hs = pr["hsblocks"]
+    else:
+        pr = problems.random_qp(20000, 40000, band=50, seed=1)
+    n, m = pr["n"], pr["m"]
+    if env:
+        monkeypatch.setenv(env, "1")
+    ks, _, _ = _solvers(hip, oracle, pr)
+    if env:
+        monkeypatch.delenv(env)
+    assert ks.update_scaling(pr["s"], pr["z"]) and ks.update(hs)
+    rng = np.random.default_rng(6)
+    zero = (np.zeros(n), np.zeros(m))
+    for zero_side in (0, 1):
+        other = (rng.standard_normal(n), rng.standard_normal(m))
+        rhs = [other, other]
+        rhs[zero_side] = zero
+        got = _pair_call(hip, ks, n, rhs)
+        assert not np.any(got[zero_side]), (which, env, zero_side, np.flatnonzero(got[zero_side])[:8])
+        sep = _separate_call(hip, ks, n, [other])[0]
+        assert relerr(got[1 - zero_side], sep) <= 1e-10, (which, env, zero_side)
+    if which == "chordal_sdp_wide":  # (the two-vector launches did run when the pair may share them)
+        assert (hip.debug_counter(ks, "tri2_launches") > 0) == (env is None)
+        assert (hip.debug_counter(ks, "dblk2_launches") > 0) == (env is None)
+
+
+def test_paired_solves_as_hipgraphs(hip, oracle):
+    """settings.use_graph with a pair: each context captures its solves on its own stream (graphs exclude the walk of the
+    levels for two contexts); two paired calls on one handle, so that the second one replays what the first captured --
+    against the oracle and against separate calls"""
+    pr = problems.random_qp(20000, 40000, band=50, seed=1)
+    n, m = pr["n"], pr["m"]
+    ks, ko, cones = _solvers(hip, oracle, pr, settings=hip.Settings.default(use_graph=1))
+    assert len(ks.supernodes()) > 0
+    assert ks.update_scaling(pr["s"], pr["z"]) and ks.update(None)
+    assert cones.update_scaling(pr["s"], pr["z"]) and ko.update(None)
+    rng = np.random.default_rng(8)
+    for call in range(2):
+        rhs = [(rng.standard_normal(n), rng.standard_normal(m)) for _ in range(2)]
+        got = _pair_call(hip, ks, n, rhs)
+        sep = _separate_call(hip, ks, n, rhs)
+        for k in range(2):
+            ko.setrhs(*rhs[k])
+            ok, xo, zo = ko.solve()
+            assert ok
+            assert relerr(got[k], np.concatenate([xo, zo])) <= TOL, (call, k)
+            assert relerr(got[k], sep[k]) <= 1e-10, (call, k)
+
+
 def test_ir_fixed_one_round(hip, oracle):
     """the benchmark's refinement setting: max_iter=1, tolerances 0 => exactly one extra
     round, same on both sides"""
