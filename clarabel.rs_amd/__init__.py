@@ -1871,6 +1871,17 @@ def debug_counter(kkt, name):
     return out.value
 
 
+def debug_kkt_ints(kkt, name):
+    """test hook: one int32 array of a HipKKTSolver by name (include/clarabel_hip_testing.h: chip_debug_kkt_ints)"""
+    n = C.c_int64(0)
+    f = lib().chip_debug_kkt_ints
+    f.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.c_void_p]
+    _check(f(kkt._h, name.encode(), C.byref(n), None), "debug_kkt_ints")
+    out = np.zeros(n.value, dtype=np.int32)
+    _check(f(kkt._h, name.encode(), C.byref(n), out.ctypes.data_as(C.c_void_p)), "debug_kkt_ints")
+    return out
+
+
 def set_device(ordinal):
     """hipSetDevice for this thread (one process per GPU: the rank's local device)"""
     rc = _hiprt().hipSetDevice(C.c_int(int(ordinal)))

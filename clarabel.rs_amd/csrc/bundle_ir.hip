@@ -381,6 +381,132 @@ __device__ __forceinline__ void bundle_sweep_flat(const LdlView &v, const Bundle
     lds_barrier();
 }
 
+// The same stream of batches for a caller that requested the FIRST batch itself, a phase ahead (k_bundle_irs: the
+// entries do not depend on the vector, so the trip for them can run behind the previous phase's closing reduction or
+// a grid barrier instead of at the head of the sweep).  flat_request_first issues exactly the loads the sweep would
+// start with -- same level, same `t < ee` guards --; bundle_sweep_flat_ahead consumes them and goes on like the plain
+// entry.  The caller has the bundle's scalars (k_bundle_irs: from its record) and, for the backward sweep, has
+// scaled the slice by 1 / d itself.  256 threads only.
+struct FlatBatch {
+    int i[FLAT_U], j[FLAT_U];
+    double v[FLAT_U];
+};
+// (a batch that has been consumed is set to constants: left as it is, a variable that is assigned on some paths of the
+// round loop only is carried around the whole loop by the compiler, FLAT_U * 4 registers live across every phase)
+__device__ __forceinline__ void flat_batch_clear(FlatBatch &fb) {
+#pragma unroll
+    for (int u = 0; u < FLAT_U; ++u) fb.i[u] = -1, fb.j[u] = 0, fb.v[u] = 0.0;
+}
+template <bool FWDMODE, int TW>
+__device__ __forceinline__ void flat_request_first(const LdlView &v, const int *lev_e, int nl, int dl, int tid, FlatBatch &fb) {
+    int step = 0, base = 0, ee = 0;
+    while (step < nl) { // (first non-empty level, as bundle_sweep_flat: skip_empty)
+        const int l = FWDMODE ? step : nl - 1 - step;
+        base = lev_e[l];
+        ee = lev_e[l + 1];
+        if (base < ee) break;
+        ++step;
+    }
+    // (straight-line loads: a load under `t < ee ? .. : ..` is a branch of its own, and a value that is to stay in flight
+    // across a barrier must not sit behind one; a slot past the range reads the range's last entry and is marked empty)
+    if (step < nl) {
+#pragma unroll
+        for (int u = 0; u < FLAT_U; ++u) {
+            const int t = base + u * TW + tid;
+            const bool ok = t < ee;
+            const int tc = ok ? t : ee - 1;
+            const int ri = (int)v.Li16[tc + dl], rj = (int)v.Lj16[tc + dl];
+            const double rv = v.Lx[tc];
+            fb.i[u] = ok ? ri : -1;
+            fb.j[u] = ok ? rj : 0;
+            fb.v[u] = ok ? rv : 0.0;
+        }
+    } else {
+        flat_batch_clear(fb);
+    }
+}
+template <bool FWDMODE, int TW>
+__device__ __forceinline__ void bundle_sweep_flat_ahead(const LdlView &v, double *xs, const double *xt, double *tacc, int k,
+                                                        const int *lev_e, int dl, int nloc, int nl, const FlatBatch &first) {
+    static_assert(TW == 256, "two batches in flight: the 256-thread form only");
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid)); // (no hoisting of this phase's address arithmetic out of the caller's round loop)
+    const int lane = tid & 63;
+    if (FWDMODE && tid < 8) tacc[tid] = 0.0;
+    double tpart = 0.0;
+    int step = 0, base = 0, ee = 0;
+    auto level_range = [&](int st_, int &eb_, int &ee_) {
+        const int l = FWDMODE ? st_ : nl - 1 - st_;
+        eb_ = lev_e[l];
+        ee_ = lev_e[l + 1];
+    };
+    lds_barrier(); // (the slice as the caller left it, tacc)
+    while (step < nl) {
+        level_range(step, base, ee);
+        if (base < ee) break;
+        ++step;
+    }
+    int ci[FLAT_U], cj[FLAT_U], ni[FLAT_U], nj[FLAT_U];
+    double cv[FLAT_U], nv[FLAT_U];
+    auto request = [&](int bs, int en, int *ii, int *jj, double *vv) {
+#pragma unroll
+        for (int u = 0; u < FLAT_U; ++u) {
+            const int t = bs + u * TW + tid;
+            const bool ok = t < en;
+            ii[u] = ok ? (int)v.Li16[t + dl] : -1;
+            jj[u] = ok ? (int)v.Lj16[t + dl] : 0;
+            vv[u] = ok ? v.Lx[t] : 0.0;
+        }
+    };
+#pragma unroll
+    for (int u = 0; u < FLAT_U; ++u) {
+        ci[u] = first.i[u];
+        cj[u] = first.j[u];
+        cv[u] = first.v[u];
+    }
+    while (step < nl) {
+        // the batch after this one
+        int nstep = step, nbase = base + TW * FLAT_U, nee = ee;
+        if (nbase >= nee) {
+            nstep = step + 1;
+            while (nstep < nl) {
+                level_range(nstep, nbase, nee);
+                if (nbase < nee) break;
+                ++nstep;
+            }
+        }
+        if (nstep < nl) request(nbase, nee, ni, nj, nv);
+#pragma unroll
+        for (int u = 0; u < FLAT_U; ++u) {
+            const int i = ci[u];
+            if (i < 0) continue;
+            if (FWDMODE) {
+                const double val = cv[u] * xs[cj[u]];
+                if (i < nloc) atomicAdd(&xs[i], -val);
+                else if (k == 1) tpart += val;
+                else atomicAdd(&tacc[i - nloc], val);
+            } else {
+                atomicAdd(&xs[cj[u]], -(cv[u] * (i < nloc ? xs[i] : xt[i - nloc])));
+            }
+        }
+        if (nstep != step) lds_barrier(); // the level is complete
+        step = nstep;
+        base = nbase;
+        ee = nee;
+#pragma unroll
+        for (int u = 0; u < FLAT_U; ++u) {
+            ci[u] = ni[u];
+            cj[u] = nj[u];
+            cv[u] = nv[u];
+        }
+    }
+    if (FWDMODE && k == 1) {
+        tpart = wave_sum_all(tpart);
+        if (lane == 0 && tpart != 0.0) atomicAdd(&tacc[0], tpart);
+    }
+    lds_barrier();
+}
+
 // The residual of k_bundle_ir in the split LDS layout of bundle_symv_split, entry-parallel: the rows of the non-leaf
 // nodes are walked as ONE flat range of U entries (row Urow16, column Ucol16), both directions of every entry as LDS
 // atomics; the leaf rows (their e has no place in LDS) four rows per thread at once, their result to the spill vector.
@@ -1135,7 +1261,10 @@ template <int TW, int NPT, int NLP>
 __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, const int *runs, const double (&c)[NPT],
                                          bool keep_e, double *xs, double *red, double *tacc3, int k, int s0,
                                          int nloc, int nleaf, const double *xt, double *out_norm, double *out_share,
-                                         int du) {
+                                         int du, bool have_fl, int fl_b, int fl_e, bool next_fwd,
+                                         const int *lev_e, int nl, int dl, FlatBatch &nextb) {
+    // have_fl: the flat range [fl_b, fl_e) comes from the bundle's record.  next_fwd: the first batch of the NEXT round's forward sweep is requested in front of the closing
+    // reductions (nextb, flat_request_first).
     double cl[NLP]; // the candidate at the thread's leaf nodes, then (keep_e) their residual
     const int *__restrict__ Up = v.Up;
     const unsigned short *__restrict__ Ucol16 = v.Ucol16, *__restrict__ Urow16 = v.Urow16;
@@ -1152,7 +1281,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
         tb[u] = i < nleaf ? Up[s0 + i] : 0;
         te[u] = i < nleaf ? Up[s0 + i + 1] : 0;
     }
-    const int fb = Up[s0 + nleaf], fe = Up[s0 + nloc]; // the flat range: rows of the non-leaf nodes
+    const int fb = have_fl ? fl_b : Up[s0 + nleaf], fe = have_fl ? fl_e : Up[s0 + nloc]; // the flat range: rows of the non-leaf nodes
     {
         // the non-leaf rows' b and x into LDS (b through the runs from the caller's vectors)
         RunWalk rw{runs, 0};
@@ -1233,8 +1362,8 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
     }
     // ---- rows of the non-leaf nodes: flat over their entries, the next batch in flight while this one is consumed ----
     {
-        int ii[FLAT_U], jj[FLAT_U], ni[FLAT_U], nj[FLAT_U];
-        double vv[FLAT_U], nv[FLAT_U];
+        int fi[FLAT_U], fj[FLAT_U], ni[FLAT_U], nj[FLAT_U];
+        double fv[FLAT_U], nv[FLAT_U];
         auto request = [&](int bs, int *pi, int *pj, double *pv) {
 #pragma unroll
             for (int u = 0; u < FLAT_U; ++u) {
@@ -1245,7 +1374,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
                 pv[u] = ok ? Ux[t] : 0.0;
             }
         };
-        if (fb < fe) request(fb, ii, jj, vv);
+        if (fb < fe) request(fb, fi, fj, fv);
         for (int base = fb; base < fe; base += TW * FLAT_U) {
             if (base + TW * FLAT_U < fe) request(base + TW * FLAT_U, ni, nj, nv);
             else {
@@ -1254,28 +1383,29 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
             }
 #pragma unroll
             for (int u = 0; u < FLAT_U; ++u) {
-                const int i = ii[u], j = jj[u];
+                const int i = fi[u], j = fj[u];
                 if (i < 0) continue;
                 const double xi = xs[xpos(i - nleaf)];
                 if (j >= nloc) {
-                    atomicAdd(&xs[i], -(vv[u] * xt[j - nloc]));
-                    if (k == 1) tpart += vv[u] * xi;
-                    else atomicAdd(&tacc3[j - nloc], vv[u] * xi);
+                    atomicAdd(&xs[i], -(fv[u] * xt[j - nloc]));
+                    if (k == 1) tpart += fv[u] * xi;
+                    else atomicAdd(&tacc3[j - nloc], fv[u] * xi);
                 } else if (j == i) {
-                    atomicAdd(&xs[i], -(vv[u] * xi));
+                    atomicAdd(&xs[i], -(fv[u] * xi));
                 } else {
-                    atomicAdd(&xs[i], -(vv[u] * xs[xpos(j - nleaf)]));
-                    atomicAdd(&xs[j], -(vv[u] * xi));
+                    atomicAdd(&xs[i], -(fv[u] * xs[xpos(j - nleaf)]));
+                    atomicAdd(&xs[j], -(fv[u] * xi));
                 }
             }
 #pragma unroll
             for (int u = 0; u < FLAT_U; ++u) {
-                ii[u] = ni[u];
-                jj[u] = nj[u];
-                vv[u] = nv[u];
+                fi[u] = ni[u];
+                fj[u] = nj[u];
+                fv[u] = nv[u];
             }
         }
     }
+    if (next_fwd) flat_request_first<true, TW>(v, lev_e, nl, dl, tid, nextb);
     lds_barrier();
     double m = mleaf;
 #pragma unroll
@@ -1321,13 +1451,36 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
     // the bundle's entry offsets into the index arrays of L / U (IrView::pat_off; 0, 0: its own copy), stored once and
     // picked up as scalars at every phase's call site (loaded from the table per phase they cost scratch and registers)
     __shared__ int pat[2];
-    const int nb = bv.nb, G = gridDim.x, tid = threadIdx.x, b = blockIdx.x;
+    __shared__ int hdr[12]; // the head of the bundle's record (IrsDesc: s0 .. nruns)
+    const int nb = bv.nb, G = gridDim.x, b = blockIdx.x;
+    int tid = threadIdx.x; // (made opaque again at the top of every round, see there)
     const int k = fold.k;
     const bool folded = k > 0; // a barrier in the middle of every round
     const int NF = k ? fold.NF : ir.N;
     if (ir.test_drop && b == G - 1 && G > 1) return; // (tests: a launch that is not co-resident)
-    const int s0 = bv.bundle_ptr[b], nloc = bv.bundle_ptr[b + 1] - s0;
-    const int nleaf = bv.blvl[bv.blvl_ptr[b] + 1] - s0;
+    // The bundle's scalars, level table and runs.  With a record per bundle (IRS_F_DESC; kernels.hpp: IrsDesc) they arrive
+    // in ONE trip, a dword per lane of two waves; without, through the chain bundle_ptr / blvl_ptr / run_ptr -> blvl, runs
+    // -> Lp[..]: three to four dependent trips before the first byte of the right-hand side is asked for.
+    const bool use_desc = (ir.sf_flags & IRS_F_DESC) != 0;
+    // loads that do not depend on the vector are requested a phase ahead (the sweeps' first batches, 1 / d, the residual's
+    // leaf rows); IRS_F_CHAINED: where the phase itself stands, as before
+    const bool ahead = (ir.sf_flags & IRS_F_CHAINED) == 0;
+    static_assert(IRS_DESC_RUNS == IR_MAXRUNS && IRS_DESC_LEVELS + 1 <= FLAT_MAXLEV + 1 && TW >= IRS_DESC_INTS, "IrsDesc");
+    if (use_desc && tid < IRS_DESC_INTS) {
+        constexpr int LEV0 = offsetof(IrsDesc, lev_e) / sizeof(int), RUN0 = offsetof(IrsDesc, runs) / sizeof(int);
+        static_assert(LEV0 == 12 && offsetof(IrsDesc, dl) == 16, "IrsDesc: head of 12 ints");
+        const int w = ((const int *)(ir.desc + b))[tid];
+        if (tid < LEV0) hdr[tid] = w;
+        else if (tid < RUN0) lev_e[tid - LEV0] = w;
+        else st.runs[tid - RUN0] = w;
+        if (tid == 4 || tid == 5) pat[tid - 4] = w;
+    }
+    int s0 = 0, nloc = 0, nleaf = 0, nl = 0;
+    if (!use_desc) {
+        s0 = bv.bundle_ptr[b], nloc = bv.bundle_ptr[b + 1] - s0;
+        nleaf = bv.blvl[bv.blvl_ptr[b] + 1] - s0;
+        nl = bv.blvl_ptr[b + 1] - bv.blvl_ptr[b] - 1;
+    }
     // partial results: device-coherent stores before a barrier, reduced in a fixed order by its last arriver
     double *pnb = ir.part;                  // [nb]       ||b||inf of the bundles' rows
     double *pn = pnb + nb;                  // [2][nb]    ||e||inf of the bundles' rows
@@ -1344,8 +1497,10 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
         st.par = 0;
         st.gen = 0;
         st.pad = 0; // (1: the last verdict accepted its candidate)
-        pat[0] = ir.pat_off ? ir.pat_off[2 * b] : 0;
-        pat[1] = ir.pat_off ? ir.pat_off[2 * b + 1] : 0;
+        if (!use_desc) {
+            pat[0] = ir.pat_off ? ir.pat_off[2 * b] : 0;
+            pat[1] = ir.pat_off ? ir.pat_off[2 * b + 1] : 0;
+        }
         if (b == 0) {
             ir.res[0] = 0; // "did not finish" until the verdict is written at the very end
             ir.res[2] = 0;
@@ -1355,12 +1510,21 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
         st.ltt[tid] = 0.0;
         st.ktt[tid] = 0.0;
     }
-    {
+    if (!use_desc) {
         const int r0 = ir.run_ptr[b], nruns = ir.run_ptr[b + 1] - r0;
         if (tid < 3 * nruns) st.runs[tid] = ir.runs[3 * r0 + tid];
+        flat_level_table(v, bv, b, lev_e);
     }
-    flat_level_table(v, bv, b, lev_e);
     __syncthreads();
+    int fl_b = 0, fl_e = 0; // (the residual's flat range: from the record only)
+    if (use_desc) {
+        s0 = __builtin_amdgcn_readfirstlane(hdr[0]);
+        nloc = __builtin_amdgcn_readfirstlane(hdr[1]);
+        nleaf = __builtin_amdgcn_readfirstlane(hdr[2]);
+        nl = __builtin_amdgcn_readfirstlane(hdr[3]);
+        fl_b = __builtin_amdgcn_readfirstlane(hdr[6]);
+        fl_e = __builtin_amdgcn_readfirstlane(hdr[7]);
+    }
     auto load_top_constants = [&]() {
         if (tid < 8) {
             st.btop[tid] = tid < k ? rhs_of(ir.perm[NF + tid]) : 0.0;
@@ -1398,9 +1562,37 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
     //   fwd: this round's forward sums;  resid: norms / residual sums of the candidate whose partials have parity rpar
     const int nmsg = 2 * k + 2;
     const int tagbase = ir.epoch << 8;
-    auto barrier = [&](bool fwd, bool resid, int rpar, bool first) -> int {
+    // what the backward sweep starts with, requested beside the mid-round barrier and carried across it: the thread's
+    // 12 values of 1 / d and the first batch of entries (40 registers, beside a barrier that uses few)
+    double dinv[NPT];
+    FlatBatch fwdb, bwdb;
+    bool dinv_have = false, bwd_have = false, fwd_have = false;
+    flat_batch_clear(fwdb);
+    flat_batch_clear(bwdb);
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) dinv[u] = 0.0;
+    auto request_dinv = [&]() {
+        const int t_ = opaque_tid();
+#pragma unroll
+        for (int u = 0; u < NPT; ++u) {
+            const int i = t_ + u * TW;
+            dinv[u] = v.Dinv[s0 + (i < nloc ? i : nloc - 1)]; // (straight-line; a slot past the slice is never used)
+        }
+    };
+    auto barrier = [&](bool fwd, bool resid, int rpar, bool first, bool issue_bwd) -> int {
         if (tid == 0) st.gen += 1;
-        const int state = ir_arrive_nowait(ir.ctl, st.gen, G);
+        // (the requests for the backward sweep's head: behind the arrival's first barrier, see ir_arrive_nowait_issue)
+        auto issue = [&]() {
+            if (ahead) request_dinv();
+            if (ahead) flat_request_first<false, TW>(v, lev_e, nl, __builtin_amdgcn_readfirstlane(pat[0]), opaque_tid(), bwdb);
+        };
+        int state;
+        if (issue_bwd) {
+            state = ir_arrive_nowait_issue(ir.ctl, st.gen, G, issue);
+            dinv_have = bwd_have = ahead;
+        } else {
+            state = ir_arrive_nowait(ir.ctl, st.gen, G);
+        }
         const int tag = tagbase | (__builtin_amdgcn_readfirstlane(st.gen) & 0xff);
         if (state == IR_LAST) {
             double f0 = 0.0, r0 = 0.0, mb = 0.0, m = 0.0;
@@ -1521,6 +1713,10 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
             const int i = tid + u * TW;
             c[u] = i < nloc ? rhs_of(rw.orig(i)) : 0.0;
         }
+        if (ahead) { // (round 0's forward sweep: its first batch rides with the staging loads)
+            flat_request_first<true, TW>(v, lev_e, nl, __builtin_amdgcn_readfirstlane(pat[0]), opaque_tid(), fwdb);
+            fwd_have = true;
+        }
         double mx = 0.0;
         bool nan = false;
 #pragma unroll
@@ -1548,15 +1744,24 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
     bool spec_done = false; // the last candidate has been written to lhs
     for (int round = 0;; ++round) {
         const int par = round & 1;
+        // (opaque_tid for what the lambdas above compute from tid -- the barrier's reduction loops and message slots, the
+        // stamps, the top constants: hoisted in front of this loop they stayed live across every phase, a register each)
+        asm volatile("" : "+v"(tid));
         __syncthreads();
         stamp();
-        bundle_sweep_flat<true, TW>(v, bv, b, xs, nullptr, st.tacc, k, lev_e, __builtin_amdgcn_readfirstlane(pat[0]));
+        {
+            const int dl = __builtin_amdgcn_readfirstlane(pat[0]);
+            if (!fwd_have) flat_request_first<true, TW>(v, lev_e, nl, dl, opaque_tid(), fwdb);
+            fwd_have = false;
+            bundle_sweep_flat_ahead<true, TW>(v, xs, nullptr, st.tacc, k, lev_e, dl, nloc, nl, fwdb);
+            flat_batch_clear(fwdb);
+        }
         stamp();
         if (tid < k) ir_store(&shf[(size_t)b * k + tid], st.tacc[tid]);
         if (folded) {
             stamp();
             if (round == 0) load_top_constants();
-            if (barrier(true, pending, par ^ 1, round == 1) == IR_TIMEOUT) {
+            if (barrier(true, pending, par ^ 1, round == 1, true) == IR_TIMEOUT) {
                 if (tid == 0) ir.res[2] = 1;
                 return;
             }
@@ -1586,7 +1791,23 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
         }
         __syncthreads();
         stamp();
-        bundle_sweep_flat<false, TW>(v, bv, b, xs, st.dxt, nullptr, k, lev_e, __builtin_amdgcn_readfirstlane(pat[0]));
+        {
+            // x_j *= 1 / d_j for the whole slice from the registers, then the levels downwards
+            const int dl = __builtin_amdgcn_readfirstlane(pat[0]);
+            if (!dinv_have) request_dinv();
+            if (!bwd_have) flat_request_first<false, TW>(v, lev_e, nl, dl, opaque_tid(), bwdb);
+            dinv_have = bwd_have = false;
+            const int t_ = opaque_tid();
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) {
+                const int i = t_ + u * TW;
+                if (i < nloc) xs[i] *= dinv[u];
+            }
+            bundle_sweep_flat_ahead<false, TW>(v, xs, st.dxt, nullptr, k, lev_e, dl, nloc, nl, bwdb);
+            flat_batch_clear(bwdb); // (consumed: constants again, see flat_batch_clear)
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) dinv[u] = 0.0;
+        }
         stamp();
         // the candidate: x (round 0) or x + dx (directldlkktsolver.rs:300 axpby(1, x, 1)), into the registers
         const bool more_possible = ir.ir_enable && round < ir.maxiter;
@@ -1665,12 +1886,14 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
             stamp();
             irs_symv<TW, NPT, NLP>(v, ir, st.runs, c, more_possible, xs, red, tacc3, k, s0, nloc, nleaf, st.candt,
                                    &pn[(size_t)par * nb + b], &shs[(size_t)par * nb * k + (size_t)b * k],
-                                   __builtin_amdgcn_readfirstlane(pat[1]));
+                                   __builtin_amdgcn_readfirstlane(pat[1]), use_desc, fl_b, fl_e,
+                                   ahead && folded && more_possible, lev_e, nl, __builtin_amdgcn_readfirstlane(pat[0]), fwdb);
+            fwd_have = ahead && folded && more_possible; // (the next round's forward sweep follows at once)
         }
         pending = true;
         if (folded && more_possible) continue; // (the verdict rides on the next round's barrier)
         stamp();
-        if (barrier(false, true, par, round == 0) == IR_TIMEOUT) {
+        if (barrier(false, true, par, round == 0, false) == IR_TIMEOUT) {
             if (tid == 0) ir.res[2] = 1;
             return;
         }

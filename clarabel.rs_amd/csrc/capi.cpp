@@ -238,6 +238,16 @@ struct chip_kkt {
     // follows without a new setrhs() reads the noted vectors (rhs_x / rhs_z) again -- they stay borrowed until the next
     // setrhs (include/clarabel_hip.h)
     bool ir_sf = false, bp_stale = false;
+    // k_bundle_irs: one dev::IrsDesc per bundle (irs_descriptors below), built once here because nothing in it changes
+    // after creation; empty / nullptr: some bundle does not fit the record, the kernel keeps its chained prologue.
+    // The host copy is there on host-only handles too (tests read it back: chip_debug_kkt_ints).
+    std::vector<int> h_irs_desc;
+    int *irs_desc = nullptr;
+    bool irs_desc_shared = false; // the records on the device carry offsets into the SHARED index arrays
+#ifdef CHIP_TESTING
+    // host-only handles: the arrays the chained prologue walks, kept so that a test can walk them itself
+    std::vector<int> t_bundle_ptr, t_blvl_ptr, t_blvl, t_Lp, t_Up, t_run_ptr, t_runs, t_pat_off;
+#endif
     int pend_update = 0;             // 1: an update has been enqueued and its verdict not read; 2: read, kept
     int pend_update_ok = 1;
     std::vector<int> pend_slots;     // ring slots of the solves enqueued since the last collect
@@ -548,6 +558,60 @@ static std::vector<int> narrow_plain(const std::vector<i64> &v, size_t n) {
     return o;
 }
 
+// the permutation inside every bundle as maximal ascending runs that stay inside one of the ranges
+// [0, n) (rhsx), [n, n + m) (rhsz), [n + m, N) (zeros): run r = {first local index, first original index, length};
+// bundle b owns runs [rp[b], rp[b + 1])
+static void bundle_perm_runs(const Symbolic &S, i64 n, i64 m, std::vector<int> &rp, std::vector<int> &runs) {
+    rp.assign(1, 0);
+    runs.clear();
+    const std::vector<i32> &pm = S.perm;
+    const i64 n1 = n, n2 = n + m;
+    auto range_of = [&](i64 o) { return o < n1 ? 0 : (o < n2 ? 1 : 2); };
+    const int nb = S.bundle_ptr.empty() ? 0 : (int)S.bundle_ptr.size() - 1;
+    for (int b = 0; b < nb; b++) {
+        const int s0 = S.bundle_ptr[(size_t)b], s1 = S.bundle_ptr[(size_t)b + 1];
+        int t = s0;
+        while (t < s1) {
+            int e = t + 1;
+            while (e < s1 && pm[(size_t)e] == pm[(size_t)e - 1] + 1 && range_of(pm[(size_t)e]) == range_of(pm[(size_t)t])) e++;
+            runs.push_back(t - s0);
+            runs.push_back(pm[(size_t)t]);
+            runs.push_back(e - t);
+            t = e;
+        }
+        rp.push_back((int)(runs.size() / 3));
+    }
+}
+// One dev::IrsDesc per bundle for k_bundle_irs: what its prologue would chase through bundle_ptr, blvl_ptr -> blvl ->
+// Lp, Up, run_ptr -> runs and the pattern offsets (pat_off: 2 per bundle, or nullptr: every bundle reads its own copy of
+// the index arrays, offsets 0).  Empty when some bundle does not fit the record.
+static std::vector<int> irs_descriptors(const Symbolic &S, const std::vector<int> &rp, const std::vector<int> &runs,
+                                        const std::vector<i32> *pat_off) {
+    const int nb = S.bundle_ptr.empty() ? 0 : (int)S.bundle_ptr.size() - 1;
+    std::vector<int> out;
+    if (nb <= 0 || (int)rp.size() != nb + 1) return out;
+    for (int b = 0; b < nb; b++)
+        if (!dev::irs_desc_fits(S.blvl_ptr[(size_t)b + 1] - S.blvl_ptr[(size_t)b] - 1, rp[(size_t)b + 1] - rp[(size_t)b])) return out;
+    out.assign((size_t)nb * dev::IRS_DESC_INTS, 0);
+    for (int b = 0; b < nb; b++) {
+        dev::IrsDesc d{};
+        const i32 *lv = S.blvl.data() + S.blvl_ptr[(size_t)b];
+        d.s0 = S.bundle_ptr[(size_t)b];
+        d.nloc = S.bundle_ptr[(size_t)b + 1] - d.s0;
+        d.nleaf = lv[1] - d.s0;
+        d.nl = S.blvl_ptr[(size_t)b + 1] - S.blvl_ptr[(size_t)b] - 1;
+        d.dl = pat_off ? (*pat_off)[2 * (size_t)b] : 0;
+        d.du = pat_off ? (*pat_off)[2 * (size_t)b + 1] : 0;
+        d.fb = S.Up[(size_t)(d.s0 + d.nleaf)];
+        d.fe = S.Up[(size_t)(d.s0 + d.nloc)];
+        d.nruns = rp[(size_t)b + 1] - rp[(size_t)b];
+        for (int l = 0; l <= d.nl; l++) d.lev_e[l] = S.Lp[(size_t)lv[l]];
+        std::copy_n(&runs[3 * (size_t)rp[(size_t)b]], 3 * (size_t)d.nruns, d.runs);
+        std::memcpy(&out[(size_t)b * dev::IRS_DESC_INTS], &d, sizeof d);
+    }
+    return out;
+}
+
 int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pcolptr,
                         const uint64_t *Prowval, const double *Pnzval, const uint64_t *Acolptr,
                         const uint64_t *Arowval, const double *Anzval, int64_t ncones,
@@ -596,6 +660,7 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
     // within that kernel's limits: the host's part of the ir_sf conditions below); host analysis, so the figures are
     // there on a host-only handle too.  Every other system (a grouped fold, a level-scheduled top) skips all of it.
     PatternShare pat;
+    bool pat_cand = false;
     {
         const i32 nbun = S.bundle_ptr.empty() ? 0 : (i32)S.bundle_ptr.size() - 1;
         bool cand = !S.Li16.empty() && S.gf_ng == 0 && S.nfold >= 1 && nbun > 0;
@@ -609,8 +674,26 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
             E.note_patterns(pat);
             clk("pattern classes");
         }
+        pat_cand = cand;
+    }
+    // the kernel's per-bundle records (what decides whether the kernel takes the solves at all is below, on the device)
+    const bool pat_shared = !pat.off.empty() && !pat.mismatches && !switches().no_shared_pattern;
+    std::vector<int> run_ptr, runs;
+    if (pat_cand) {
+        bundle_perm_runs(S, K.n, K.m, run_ptr, runs);
+        bool fit = true;
+        for (size_t b = 0; b + 1 < run_ptr.size() && fit; b++) fit = run_ptr[b + 1] - run_ptr[b] <= dev::IRS_DESC_RUNS;
+        if (fit) h->h_irs_desc = irs_descriptors(S, run_ptr, runs, pat_shared ? &pat.off : nullptr);
+        clk("bundle descriptors");
     }
     if (st.device == CHIP_DEVICE_HOST_ONLY) {
+#ifdef CHIP_TESTING
+        if (pat_cand) {
+            h->t_bundle_ptr = S.bundle_ptr, h->t_blvl_ptr = S.blvl_ptr, h->t_blvl = S.blvl;
+            h->t_Lp = S.Lp, h->t_Up = S.Up, h->t_run_ptr = run_ptr, h->t_runs = runs;
+            if (pat_shared) h->t_pat_off = pat.off;
+        }
+#endif
         E.init_host_only(S, st);
         *out = h.release();
         return CHIP_OK;
@@ -865,25 +948,9 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
     if ((rc = E.alloc(&h->d_tmp, h->tmp_len))) return rc;
     CHIP_HIP(hipMemset(h->wk[0].bp, 0, (size_t)(K.N ? K.N : 1) * sizeof(double)));
     if (E.ir_fused) {
-        // the permutation inside every bundle as maximal ascending runs that stay inside one of the ranges
-        // [0, n) (rhsx), [n, n + m) (rhsz), [n + m, N) (zeros); used when they are long on average
-        std::vector<int> rp(1, 0), runs;
-        const std::vector<i32> &pm = E.h_perm;
-        const i64 n1 = K.n, n2 = K.n + K.m;
-        auto range_of = [&](i64 o) { return o < n1 ? 0 : (o < n2 ? 1 : 2); };
-        for (int b = 0; b < E.bundles.nb; b++) {
-            const int s0 = S.bundle_ptr[(size_t)b], s1 = S.bundle_ptr[(size_t)b + 1];
-            int t = s0;
-            while (t < s1) {
-                int e = t + 1;
-                while (e < s1 && pm[(size_t)e] == pm[(size_t)e - 1] + 1 && range_of(pm[(size_t)e]) == range_of(pm[(size_t)t])) e++;
-                runs.push_back(t - s0);
-                runs.push_back(pm[(size_t)t]);
-                runs.push_back(e - t);
-                t = e;
-            }
-            rp.push_back((int)(runs.size() / 3));
-        }
+        // the permutation inside every bundle as runs (bundle_perm_runs); used when they are long on average
+        if (run_ptr.empty()) bundle_perm_runs(S, K.n, K.m, run_ptr, runs);
+        const std::vector<int> &rp = run_ptr;
         if (!runs.empty() && (i64)(runs.size() / 3) * 64 <= (i64)E.NF) {
             if ((rc = E.upload(&h->ir_run_ptr, rp, rp.size()))) return rc;
             if ((rc = E.upload(&h->ir_runs, runs, runs.size()))) return rc;
@@ -899,6 +966,11 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
             }
             h->ir_sf = sf && dev::bundle_irs_capacity_ok(E.bundles);
             if (h->ir_sf && !switches().no_shared_pattern && (rc = E.upload_patterns(pat))) return rc;
+            // (the records carry the offsets of the shared arrays: only beside them, or with offsets 0 without them)
+            if (h->ir_sf && !h->h_irs_desc.empty() && (E.pat_off != nullptr) == pat_shared &&
+                (rc = E.upload(&h->irs_desc, h->h_irs_desc, h->h_irs_desc.size())))
+                return rc;
+            h->irs_desc_shared = pat_shared;
         }
     }
     clk("maps, cone tables");
@@ -1554,7 +1626,7 @@ static int fused_enqueue(chip_kkt *h, double *lhsx_dev, double *lhsz_dev, int *s
             return a && b_ && a < b_ + nb_ && b_ < a + na;
         };
         const size_t n = (size_t)h->K.n, m = (size_t)h->K.m;
-        const int flags = switches().irs_flags < 0 ? 3 : switches().irs_flags;
+        const int flags = (switches().irs_flags < 0 ? 3 : switches().irs_flags) & ~dev::IRS_F_DESC;
         ir.sf_flags = flags;
         ir.spec_out = (flags & 2) && !(overlap(lhsx_dev, n, ir.rx, n) || overlap(lhsx_dev, n, ir.rz, m) || overlap(lhsz_dev, m, ir.rx, n) ||
                         overlap(lhsz_dev, m, ir.rz, m));
@@ -1583,6 +1655,11 @@ static int fused_enqueue(chip_kkt *h, double *lhsx_dev, double *lhsz_dev, int *s
             lv.Ucol16 = E.pat_Ucol16;
             lv.Urow16 = E.pat_Urow16;
             ir.pat_off = E.pat_off;
+        }
+        // one record per bundle in the same slot (the offsets are inside) unless the chained prologue is asked for
+        if (h->irs_desc && !(ir.sf_flags & (dev::IRS_F_CHAINED)) && h->irs_desc_shared == (ir.pat_off != nullptr)) {
+            ir.desc = (const dev::IrsDesc *)h->irs_desc;
+            ir.sf_flags |= dev::IRS_F_DESC;
         }
         rc = dev::bundle_ir(E.stream, lv, E.bundles, E.fold, ir, E.ir_grid, E.ir_tw, E.gfold);
     } else {
@@ -2270,7 +2347,31 @@ int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out
     else if (k == "pattern_mismatches") *out = E.pat_mismatches;
     else if (k == "pattern_shared_bundles") // bundles whose fused solve launch reads a shared copy
         *out = (h->ir_sf && E.pat_off && !switches().no_shared_pattern) ? E.bundles.nb : 0;
+    else if (k == "irs_desc_bundles") { // bundles whose fused solve launch reads its record (dev::IrsDesc) under the current switches
+        const bool shared = E.pat_off && !switches().no_shared_pattern;
+        const int flags = switches().irs_flags < 0 ? 3 : switches().irs_flags;
+        *out = (h->ir_sf && h->irs_desc && !(flags & dev::IRS_F_CHAINED) && h->irs_desc_shared == shared) ? E.bundles.nb : 0;
+    }
     else return fail(CHIP_ERR_ARG, "chip_debug_counter: unknown name");
+    return CHIP_OK;
+}
+int32_t chip_debug_kkt_ints(const void *handle, const char *name, int64_t *len, int32_t *out) {
+    const chip_kkt *h = (const chip_kkt *)handle;
+    if (!h || !name || !len) return fail(CHIP_ERR_ARG, "chip_debug_kkt_ints: bad argument");
+    const std::string k(name);
+    const std::vector<int> *v = nullptr;
+    if (k == "irs_desc") v = &h->h_irs_desc;
+    else if (k == "bundle_ptr") v = &h->t_bundle_ptr;
+    else if (k == "blvl_ptr") v = &h->t_blvl_ptr;
+    else if (k == "blvl") v = &h->t_blvl;
+    else if (k == "Lp") v = &h->t_Lp;
+    else if (k == "Up") v = &h->t_Up;
+    else if (k == "run_ptr") v = &h->t_run_ptr;
+    else if (k == "runs") v = &h->t_runs;
+    else if (k == "pat_off") v = &h->t_pat_off;
+    else return fail(CHIP_ERR_ARG, "chip_debug_kkt_ints: unknown name");
+    *len = (int64_t)v->size();
+    if (out) std::copy(v->begin(), v->end(), out);
     return CHIP_OK;
 }
 // ---- the PSD cone kernels of cones.hip alone, one launch per call on host arrays (tests/test_psd_passes_gpu.py) ----

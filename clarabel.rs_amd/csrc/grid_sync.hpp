@@ -104,6 +104,28 @@ __device__ __forceinline__ int ir_arrive_nowait(int *ctl, int gen, int nwg) {
     __syncthreads();
     return s_state2;
 }
+// ir_arrive_nowait for a caller that wants loads IN FLIGHT across the arrival (k_bundle_irs requests the next phase's
+// first loads here): __syncthreads() waits for every outstanding load of the wave, so `issue` runs behind the first one
+// -- in thread 0's wave also behind its s_waitcnt(0) and the returning arrival atomics, which would otherwise wait for
+// those loads and delay the arrival -- and the verdict crosses the workgroup behind a barrier that waits for LDS only
+template <class F> __device__ __forceinline__ int ir_arrive_nowait_issue(int *ctl, int gen, int nwg, F &&issue) {
+    __shared__ int s_state5;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_s_waitcnt(0);
+        const int sub = blockIdx.x % IR_NSUB;
+        const int members = nwg / IR_NSUB + (sub < nwg % IR_NSUB ? 1 : 0);
+        int state = IR_WAITED;
+        if (atomicAdd(ctl + 32 * (1 + sub), 1) + 1 == members * gen) {
+            if (atomicAdd(ctl, 1) + 1 == min(IR_NSUB, nwg) * gen) state = IR_LAST;
+        }
+        s_state5 = state;
+    }
+    issue();
+    lds_barrier();
+    return s_state5;
+}
 __device__ __forceinline__ int ir_wait_word(const int *word, int gen) {
     __shared__ int s_state3;
     __syncthreads(); // (every thread has read the verdict of a previous call)

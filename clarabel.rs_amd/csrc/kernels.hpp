@@ -176,6 +176,27 @@ void bundle_bwd(hipStream_t s, const LdlView &v, const BundleView &bv, double *x
 void bundle_symv(hipStream_t s, const BundleView &bv, const int *Up, const int *Ucol, const double *Ux,
                  const double *x, const double *b, double *e, unsigned long long *nrm, int *nan, const FoldView &fold, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // ---- whole solve + iterative refinement in one persistent launch (k_bundle_ir) ----------------------
+// k_bundle_irs: everything a workgroup's prologue used to chase through the index arrays (bundle_ptr -> blvl_ptr ->
+// blvl -> Lp, Up, run_ptr -> runs, the pattern offsets), as ONE fixed-size record per bundle, written once when the
+// handle is created (capi.cpp: irs_descriptors) -- none of it changes afterwards.  The kernel reads it in one trip.
+constexpr int IRS_DESC_LEVELS = 19; // levels of a bundle the record holds (more: the handle keeps the chained prologue)
+constexpr int IRS_DESC_RUNS = 32;   // runs of the permutation slice (bundle_ir.hip: IR_MAXRUNS)
+struct alignas(16) IrsDesc {
+    int s0, nloc, nleaf, nl;            // first node, nodes, leaf nodes, levels
+    int dl, du;                         // entry offsets into the index arrays of L / U (host.hpp: PatternShare; 0: own copy)
+    int fb, fe;                         // Up[s0 + nleaf], Up[s0 + nloc]: the flat range of the residual
+    int nruns, pad[3];
+    int lev_e[IRS_DESC_LEVELS + 1];     // first L entry of every level, lev_e[nl]: one past the last level's
+    int runs[3 * IRS_DESC_RUNS];        // {first local index, first original index, length} per run
+};
+static_assert(sizeof(IrsDesc) == 512, "IrsDesc: 128 ints, read as one dword per lane by two waves");
+constexpr int IRS_DESC_INTS = (int)(sizeof(IrsDesc) / sizeof(int));
+inline bool irs_desc_fits(int nlevels, int nruns) { return nlevels >= 1 && nlevels <= IRS_DESC_LEVELS && nruns >= 1 && nruns <= IRS_DESC_RUNS; }
+// bits of IrView::sf_flags
+constexpr int IRS_F_X0_REGS = 1;   // round 0's iterate stays in registers
+constexpr int IRS_F_SPEC_OUT = 2;  // the last candidate may be written before its verdict
+constexpr int IRS_F_CHAINED = 4;   // no phase-ahead loads, chained prologue (the form before the descriptors; tests compare both)
+constexpr int IRS_F_DESC = 256;    // (set by the host, not by CHIP_IRS_FLAGS) the pat_off slot holds the descriptor table
 struct IrView {
     const double *rx, *rz; // right-hand side in the caller's order: entry o < n from rx, n <= o < n + m from rz,
                            // the sparse-cone rows are zero (directldlkktsolver.rs:160-166)
@@ -191,6 +212,7 @@ struct IrView {
         double *ebuf;      // k_bundle_ir (sf == 0): N, residual spill, used only when a workgroup owns several bundles
         const int *pat_off; // k_bundle_irs (sf != 0; it has no spill): per bundle the entry offsets {L, U} into the index arrays of the
                            // LdlView it is launched with (one shared copy per class of identical bundles, host.hpp: PatternShare), or nullptr: 0, 0
+        const IrsDesc *desc; // k_bundle_irs with sf_flags & IRS_F_DESC: one record per bundle (the offsets are inside)
     };
     double *lhsx, *lhsz;   // outputs in the caller's order (either may be nullptr)
     double *part;          // ir_part_doubles(nb, k) doubles of partial results
@@ -206,7 +228,7 @@ struct IrView {
     int flat;              // entry-parallel sweeps / residual (bundle_sweep_flat, bundle_symv_flat); 0: column per thread
     int *rel;              // k_bundle_irs: ir_rel_ints() ints, the barrier's release records (tagged messages; any content at launch)
     int epoch;             // k_bundle_irs: distinguishes this launch's messages from an earlier launch's (the host counts)
-    int sf_flags;          // k_bundle_irs, experiment bits (CHIP_IRS_FLAGS): 1 = round 0's iterate stays in registers
+    int sf_flags;          // k_bundle_irs, experiment bits (CHIP_IRS_FLAGS): IRS_F_* above
     int spec_out;          // k_bundle_irs: lhsx / lhsz do not overlap rx / rz -- the last candidate may be written before its verdict
     int sf;                // k_bundle_irs (one bundle per workgroup, the candidate in registers; bp may be nullptr: not written)
 };

@@ -25,9 +25,17 @@ int32_t chip_debug_set_switch(const char *name, const char *value_or_null);
  * "pattern_mismatches" (host analysis, on host-only handles too: classes of bundles with byte-equal 16-bit index
  * slices, the bundles, bytes of the shared index arrays and of the full ones, bundles whose offsets were checked against
  * the full arrays and how many differed), "pattern_shared_bundles" (bundles whose fused solve launch reads a shared copy:
- * 0 on a host-only handle or with CHIP_NO_SHARED_PATTERN).
+ * 0 on a host-only handle or with CHIP_NO_SHARED_PATTERN), "irs_desc_bundles" (bundles whose fused solve launch reads its
+ * per-bundle record under the current switches: 0 with CHIP_IRS_FLAGS bit 4, the chained prologue).
  * Returns CHIP_ERR_ARG for an unknown name. */
 int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out);
+/* one int32 array of a KKT handle by name; *len <- its length; out (may be NULL) receives it.  "irs_desc": the fused
+ * solve kernel's per-bundle records (csrc/kernels.hpp: IrsDesc, 128 ints each: s0, nloc, nleaf, levels, dl, du, fb, fe,
+ * runs, 3 of padding, 20 level entries, 32 x 3 run entries; empty when some bundle does not fit), on host-only handles
+ * too.  Host-only handles of systems that kernel can take also keep the arrays its chained prologue walks:
+ * "bundle_ptr", "blvl_ptr", "blvl", "Lp", "Up", "run_ptr", "runs", "pat_off" (empty: every bundle reads its own copy of
+ * the index arrays).  Returns CHIP_ERR_ARG for an unknown name. */
+int32_t chip_debug_kkt_ints(const void *kkt_handle, const char *name, int64_t *len, int32_t *out);
 /* a spinner of `blocks` x `threads` for `usec` microseconds on the stream of a communicator (opaque chip_comm *), behind
  * the collective enqueued last; the communicator's completion event moves behind it.  On one GPU this stands in for
  * the time RCCL's ring kernel holds CUs when several ranks exchange (bench.py --coresident). */
