@@ -1164,37 +1164,39 @@ class HipBatchSolver(_DataUpdates):
         return _torch_copy(px.value, n, "float64"), _torch_copy(ps.value, m, "float64"), \
             _torch_copy(pz.value, m, "float64")
 
-    def _grad_input(self, name, g, key):
-        """one incoming gradient -> ("none", None), ("host", float64 array) or ("dev", contiguous GPU tensor)"""
+    def _grad_input(self, name, g, key, fn="backward"):
+        """one incoming gradient (or, for jvp, one piece of a direction) -> ("none", None), ("host", float64 array) or
+        ("dev", contiguous GPU tensor)"""
+        name = "%s %s" % (fn, name)
         length = self._len[key]
         if g is None:
             return ("none", None)
         if isinstance(g, list) and len(g) > 0 and not np.isscalar(g[0]):
             off = self._offsets[key]
             if len(g) != len(self):
-                raise ChipError(ERR_DIM, "backward %s: %d list entries for %d members" % (name, len(g), len(self)))
+                raise ChipError(ERR_DIM, "%s: %d list entries for %d members" % (name, len(g), len(self)))
             out = np.zeros(length)
             for k, piece in enumerate(g):
                 if piece is None:
                     continue
                 if _is_torch(piece) and piece.is_cuda:
-                    raise TypeError("backward %s: member %d: the entries of a list are host arrays" % (name, k))
+                    raise TypeError("%s: member %d: the entries of a list are host arrays" % (name, k))
                 v = _host_array(piece, name, False)
                 if v.size != off[k + 1] - off[k]:
-                    raise ChipError(ERR_DIM, "backward %s: member %d: %d values for %d entries"
+                    raise ChipError(ERR_DIM, "%s: member %d: %d values for %d entries"
                                     % (name, k, v.size, off[k + 1] - off[k]))
                 out[off[k]:off[k + 1]] = v
             return ("host", out)
         if _is_torch(g) and g.is_cuda:
             import torch
             if g.dtype != torch.float64:
-                raise TypeError("backward %s: GPU values must be float64, not %s" % (name, g.dtype))
+                raise TypeError("%s: GPU values must be float64, not %s" % (name, g.dtype))
             if g.dim() != 1 or g.numel() != length:
-                raise ChipError(ERR_DIM, "backward %s: a vector of %d values is needed" % (name, length))
+                raise ChipError(ERR_DIM, "%s: a vector of %d values is needed" % (name, length))
             return ("dev", g.detach().contiguous())
         v = _host_array(g, name, False)
         if v.size != length:
-            raise ChipError(ERR_DIM, "backward %s: %d values for %d entries" % (name, v.size, length))
+            raise ChipError(ERR_DIM, "%s: %d values for %d entries" % (name, v.size, length))
         return ("host", _f(v))
 
     def backward(self, gx=None, gz=None, gs=None):
@@ -1230,7 +1232,52 @@ class HipBatchSolver(_DataUpdates):
                "chip_bgrad_get")
         return BatchGradient(dq, db, dP, dA, valid, self._offsets)
 
+    # ---- tangents (chip_bjvp_*): a direction in (q, b, P, A) of every member -> (dx, dz, ds) of every member ---------
+    def jvp(self, dq=None, db=None, dP=None, dA=None):
+        """the forward-mode derivative of the last solve(): how x, z and s of every member move when its q, b, P and A
+        move along (dq, db, dP, dA) -- stacked vectors, dP / dA in the order of the stack's nzval (the positions
+        update_P / update_A index; a stored (i, j), i < j, of P stands for both triangles); None = zeros.  The forms
+        are backward()'s: numpy arrays, float64 torch tensors on the GPU (the result then holds torch tensors on the
+        GPU and nothing crosses to the host), or a list with one host entry per member (None = zeros for that member).
+        Returns a BatchTangent.  Members that did not end Solved, or own a SecondOrder cone, have valid[k] = 0 and
+        exact zeros.  The first jvp (or backward) after a solve factors K at the final iterates; every further jvp of
+        that solve costs one KKT solve.  ChipError(ERR_ARG) before a solve and after an update that was not followed
+        by a solve."""
+        forms = [self._grad_input(nm, g, key, "jvp")
+                 for nm, g, key in (("dq", dq, "q"), ("db", db, "b"), ("dP", dP, "P"), ("dA", dA, "A"))]
+        kinds = {f[0] for f in forms} - {"none"}
+        if len(kinds) > 1:
+            raise TypeError("jvp: dq, db, dP and dA must all be host arrays or all GPU tensors")
+        n, m = self._len["q"], self._len["b"]
+        valid = np.zeros(len(self), dtype=np.int32)
+        if kinds == {"dev"}:
+            import torch
+            dev = [f[1] for f in forms if f[0] == "dev"][0].device
+            torch.cuda.current_stream(dev).synchronize()  # the values are written before the call reads them
+            ptr = [None if f[0] == "none" else C.c_void_p(f[1].data_ptr()) for f in forms]
+            _check(lib().chip_bjvp_apply_dev(self._h, *ptr), "chip_bjvp_apply_dev")
+            out = [C.c_void_p() for _ in range(3)]
+            _check(lib().chip_bjvp_get_dev(self._h, *[C.byref(o) for o in out], None), "chip_bjvp_get_dev")
+            _check(lib().chip_bjvp_get(self._h, None, None, None, valid.ctypes.data_as(P_I32)), "chip_bjvp_get")
+            dx, dz, ds = [_torch_copy(o.value, ln, "float64", dev) for o, ln in zip(out, (n, m, m))]
+            return BatchTangent(dx, dz, ds, valid, self._offsets)
+        ptr = [None if f[0] == "none" else _pf(f[1]) for f in forms]
+        _check(lib().chip_bjvp_apply(self._h, *ptr), "chip_bjvp_apply")
+        dx, dz, ds = np.zeros(n), np.zeros(m), np.zeros(m)
+        _check(lib().chip_bjvp_get(self._h, _pf(dx), _pf(dz), _pf(ds), valid.ctypes.data_as(P_I32)), "chip_bjvp_get")
+        return BatchTangent(dx, dz, ds, valid, self._offsets)
+
     # ---- test hooks (include/clarabel_hip_testing.h) ----
+    def debug_jvp_rhs(self, x, z, valid, dq=None, db=None, dP=None, dA=None):
+        """the right-hand side pass of jvp alone (no solve needed) -> the scaled (rx[n], rz[m])"""
+        keep = [None if v is None else _f(v) for v in (x, z, dq, db, dP, dA)]
+        valid = np.ascontiguousarray(valid, dtype=np.int32)
+        rx, rz = np.zeros(self._len["q"]), np.zeros(self._len["b"])
+        ptr = [None if v is None else _pf(v) for v in keep]
+        _check(lib().chip_debug_batch_jvp_rhs(self._h, ptr[0], ptr[1], valid.ctypes.data_as(P_I32), *ptr[2:],
+                                              _pf(rx), _pf(rz)), "chip_debug_batch_jvp_rhs")
+        return rx, rz
+
     def debug_inject_nan(self, member, iteration):
         _check(lib().chip_debug_batch_inject_nan(self._h, C.c_int64(member), C.c_int32(iteration)),
                "chip_debug_batch_inject_nan")
@@ -1255,6 +1302,20 @@ class BatchGradient:
         o = self._offsets
         return tuple(v[int(o[key][k]):int(o[key][k + 1])]
                      for v, key in ((self.dq, "q"), (self.db, "b"), (self.dP, "P"), (self.dA, "A")))
+
+
+class BatchTangent:
+    """the result of HipBatchSolver.jvp: dx[n], dz[m], ds[m] of the stack as numpy arrays or torch GPU tensors, and
+    valid[nprob] (numpy int32): 1 where the member has a derivative, else its entries are exact zeros"""
+
+    def __init__(self, dx, dz, ds, valid, offsets):
+        self.dx, self.dz, self.ds, self.valid = dx, dz, ds, valid
+        self._offsets = offsets
+
+    def per_member(self, k):
+        """member k's (dx, dz, ds): slices of the stacked vectors"""
+        o = self._offsets
+        return tuple(v[int(o[key][k]):int(o[key][k + 1])] for v, key in ((self.dx, "q"), (self.dz, "b"), (self.ds, "b")))
 
 
 def _torch_copy(ptr, n, dtype, device=None):

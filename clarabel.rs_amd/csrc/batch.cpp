@@ -20,6 +20,7 @@
 
 #include "batch.hpp"
 #include "batch_adjoint.hpp"
+#include "batch_tangent.hpp"
 #include "batch_update.hpp"
 #include "engine.hpp"
 #include "host_util.hpp"
@@ -221,6 +222,16 @@ struct chip_batch {
     double *g_dq = nullptr, *g_db = nullptr, *g_dP = nullptr, *g_dA = nullptr;
     double *g_in[3] = {nullptr, nullptr, nullptr}; // the staging of the host form's gx, gz, gs
     long grad_syncs = 0, grad_launches = 0;        // of the last backward
+    // the tangents (chip_bjvp_*): kkt_final: K is factored at the final iterates of the last solve (by a backward or an
+    // apply), so an apply needs no scaling update and no refactor; jvp_done: the buffers below hold the result of an
+    // apply since that solve.  Allocated by the first apply
+    bool kkt_final = false, jvp_done = false;
+    std::vector<int32_t> tvalid;
+    int *t_valid = nullptr;
+    double *t_dx = nullptr, *t_dz = nullptr, *t_ds = nullptr;
+    double *t_in[4] = {nullptr, nullptr, nullptr, nullptr}; // the staging of the host form's dq, db, dP, dA
+    long jvp_syncs = 0, jvp_launches = 0; // of the last apply
+    long jvp_refactors = 0;               // of the handle's life
 
     ~chip_batch() {
         if (stream) (void)hipStreamSynchronize(stream);
@@ -304,6 +315,8 @@ struct chip_batch {
     int update(int which, const int64_t *idx_dev, const double *vals_dev, int k);
     int backward_work();
     int backward(const double *gx_dev, const double *gz_dev, const double *gs_dev);
+    int jvp_work();
+    int jvp_apply(const double *dq_dev, const double *db_dev, const double *dP_dev, const double *dA_dev);
 };
 
 int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n,
@@ -754,7 +767,7 @@ int32_t chip_batch_solve(chip_batch *h) {
     h->held_done.assign((size_t)np, 0);
     h->t_solve0 = now_s();
     h->solve_time = h->setup_time;
-    h->solve_current = h->grad_done = false;
+    h->solve_current = h->grad_done = h->kkt_final = h->jvp_done = false;
     int rc;
     if ((rc = h->default_start())) return rc;
     for (int k = 0; k < np; k++) h->hm(M_ACTIVE, k) = 1;
@@ -1005,8 +1018,10 @@ int chip_batch::update(int which, const int64_t *idx_dev, const double *vals_dev
     if ((rc = update_work())) return rc;
     // from the first write on the last solve's iterate no longer belongs to the data: no gradient until the next solve
     // (chip_bgrad_*).  Only the refusal that has changed nothing puts the flag back; a call that fails on the way does not
+    // K's factorisation is not vouched for either (chip_bjvp_*); that flag stays down even after such a refusal, which
+    // costs the next apply one refactor
     const bool was_current = solve_current;
-    solve_current = false;
+    solve_current = kkt_final = false;
     const int len = (int)pd.update_len(which);
     const dev::EqMats &M = pd.M;
     hipStream_t s = stream;
@@ -1144,12 +1159,14 @@ int chip_batch::backward(const double *gx, const double *gz, const double *gs) {
     grad_launches += 2;
     if ((rc = kktsystem_spmv(sys, 2, workx, wn, -1.0, conicw))) return rc; // D gx - A^' (gs / e)
     grad_launches++;
+    kkt_final = false; // (a refactor that fails leaves nothing for chip_bjvp_* to reuse)
     if ((rc = chip_kkt_update_scaling_dev(kkt, ds, dz, 1.0, 0)) < 0) return rc;
     rc = chip_kkt_update(kkt, nullptr);
     grad_syncs++;
     grad_launches += 2;
     if (rc < 0) return rc;
     if (rc != 1) return fail(CHIP_ERR_ZERO_PIVOT, "chip_bgrad_backward: the factorisation at the final iterate failed");
+    kkt_final = true; // (an apply of chip_bjvp_* after this backward solves with this factorisation)
     if ((rc = chip_kkt_setrhs_dev(kkt, workx, workz))) return rc;
     rc = chip_kkt_solve_dev(kkt, x1, z1);
     grad_syncs++;
@@ -1229,6 +1246,121 @@ int32_t chip_bgrad_get_dev(chip_batch *h, double **dq_dev, double **db_dev, doub
     return CHIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Forward-mode derivatives of the members' solutions (chip_bjvp_*): the transpose of the gradients
+// above.  Along a direction (dq, db, dP, dA) in a member's data its solution moves by ONE KKT solve at the final
+// iterate, with the matrix backward solves with,
+//     rx = -(dq + dP_sym x + dA' z),  rz = db - dA x,  [dx; dz] = K^-1 [rx; rz],  ds = rz - A dx (Nonnegative rows).
+// In the equilibrated space of the stack the system is K^ [D^-1 dx; c_k E^-1 dz] = [c_k D rx; E rz] with rx, rz formed
+// from the unscaled solution (xo, zo), so dx = D vx^, dz = E vz^ / c_k and ds = E^-1 (E rz - A^ vx^): the transposes of
+// backward's scalings.  One apply: the right-hand side (bt_rhs), the scaling update and the refactor unless K is
+// already factored at the final iterates (kkt_final: set by a backward or an apply, cleared by an update and at the
+// start of a solve), one refined solve, one product with A^ and the output pass (bt_out); enqueues and synchronisations
+// are counted as backward counts them.  It overwrites work vectors only, none of them backward's results.
+// ---------------------------------------------------------------------------------------------------------------
+int chip_batch::jvp_work() {
+    if (t_valid) return CHIP_OK;
+    int rc;
+    const size_t n = (size_t)pd.n, m = (size_t)pd.m;
+    if ((rc = mem.alloc(&t_dx, n)) || (rc = mem.alloc(&t_dz, m)) || (rc = mem.alloc(&t_ds, m)) ||
+        (rc = mem.alloc(&t_in[0], n)) || (rc = mem.alloc(&t_in[1], m)) || (rc = mem.alloc(&t_in[2], (size_t)pd.M.nnzP)) ||
+        (rc = mem.alloc(&t_in[3], (size_t)pd.M.nnzA)) || (rc = mem.alloc(&t_valid, (size_t)nprob)))
+        return rc;
+    tvalid.assign((size_t)nprob, 0);
+    return CHIP_OK;
+}
+
+int chip_batch::jvp_apply(const double *dq, const double *db, const double *dP, const double *dA) {
+    int rc;
+    hipStream_t s = stream;
+    jvp_done = false; // (an apply that fails part-way leaves no result behind)
+    dev::SpPattern Psym, Arow, Acol;
+    if ((rc = kktsystem_pattern(sys, 0, &Psym)) || (rc = kktsystem_pattern(sys, 1, &Arow)) ||
+        (rc = kktsystem_pattern(sys, 2, &Acol)))
+        return rc;
+    for (int k = 0; k < nprob; k++) tvalid[k] = info[k].status == CHIP_SOLVER_SOLVED && !has_soc[k];
+    CHIP_HIP(hipMemcpyAsync(t_valid, tvalid.data(), (size_t)nprob * sizeof(int), hipMemcpyHostToDevice, s));
+    const bool refactor = !kkt_final;
+    dev::bt_rhs(s, plan, Psym, Acol, Arow,
+                dev::BtRhs{t_valid, xo, zo, dq, db, dP, dA, pd.d, pd.e, dc, workx, workz, vs, vz,
+                           refactor ? ds : nullptr, refactor ? dz : nullptr});
+    jvp_launches += 2;
+    if (refactor) {
+        if ((rc = chip_kkt_update_scaling_dev(kkt, ds, dz, 1.0, 0)) < 0) return rc;
+        rc = chip_kkt_update(kkt, nullptr);
+        jvp_syncs++;
+        jvp_launches += 2;
+        jvp_refactors++;
+        if (rc < 0) return rc;
+        if (rc != 1) return fail(CHIP_ERR_ZERO_PIVOT, "chip_bjvp_apply: the factorisation at the final iterate failed");
+        kkt_final = true;
+    }
+    if ((rc = chip_kkt_setrhs_dev(kkt, workx, workz))) return rc;
+    rc = chip_kkt_solve_dev(kkt, x1, z1);
+    jvp_syncs++;
+    jvp_launches++;
+    if (rc < 0) return rc;
+    if (rc != 1) return fail(CHIP_ERR_ZERO_PIVOT, "chip_bjvp_apply: the solve at the final iterate failed");
+    if ((rc = kktsystem_spmv(sys, 1, conicw, workz, -1.0, x1))) return rc; // E rz - A^ vx^
+    dev::bt_out(s, plan, dev::BtOut{t_valid, x1, z1, conicw, pd.d, pd.e, pd.einv, dc, t_dx, t_dz, t_ds});
+    jvp_launches += 2;
+    CHIP_HIP(hipGetLastError());
+    CHIP_HIP(hipStreamSynchronize(s));
+    jvp_syncs++;
+    jvp_done = true;
+    return CHIP_OK;
+}
+
+int32_t chip_bjvp_apply(chip_batch *h, const double *dq, const double *db, const double *dPx, const double *dAx) {
+    int rc = bg_ready(h, "chip_bjvp_apply");
+    if (rc) return rc;
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    h->jvp_syncs = h->jvp_launches = 0;
+    if ((rc = h->jvp_work())) return rc;
+    const double *src[4] = {dq, db, dPx, dAx};
+    const size_t len[4] = {(size_t)h->pd.n, (size_t)h->pd.m, (size_t)h->pd.M.nnzP, (size_t)h->pd.M.nnzA};
+    const double *in[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 4; i++) {
+        if (!src[i]) continue;
+        in[i] = h->t_in[i];
+        if (!len[i]) continue;
+        CHIP_HIP(hipMemcpyAsync(h->t_in[i], src[i], len[i] * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        h->jvp_launches++;
+    }
+    return h->jvp_apply(in[0], in[1], in[2], in[3]);
+}
+
+int32_t chip_bjvp_apply_dev(chip_batch *h, const double *dq_dev, const double *db_dev, const double *dPx_dev,
+                            const double *dAx_dev) {
+    int rc = bg_ready(h, "chip_bjvp_apply_dev");
+    if (rc) return rc;
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    h->jvp_syncs = h->jvp_launches = 0;
+    if ((rc = h->jvp_work())) return rc;
+    return h->jvp_apply(dq_dev, db_dev, dPx_dev, dAx_dev);
+}
+
+int32_t chip_bjvp_get(chip_batch *h, double *dx, double *dz, double *ds, int32_t *valid) {
+    if (!h) return fail(CHIP_ERR_ARG, "chip_bjvp_get: bad argument");
+    if (!h->jvp_done) return fail(CHIP_ERR_ARG, "chip_bjvp_get: no chip_bjvp_apply since the last solve");
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    if (dx && h->pd.n) CHIP_HIP(hipMemcpy(dx, h->t_dx, (size_t)h->pd.n * 8, hipMemcpyDeviceToHost));
+    if (dz && h->pd.m) CHIP_HIP(hipMemcpy(dz, h->t_dz, (size_t)h->pd.m * 8, hipMemcpyDeviceToHost));
+    if (ds && h->pd.m) CHIP_HIP(hipMemcpy(ds, h->t_ds, (size_t)h->pd.m * 8, hipMemcpyDeviceToHost));
+    if (valid) std::copy(h->tvalid.begin(), h->tvalid.end(), valid);
+    return CHIP_OK;
+}
+
+int32_t chip_bjvp_get_dev(chip_batch *h, double **dx_dev, double **dz_dev, double **ds_dev, int32_t **valid_dev) {
+    if (!h) return fail(CHIP_ERR_ARG, "chip_bjvp_get_dev: bad argument");
+    if (!h->jvp_done) return fail(CHIP_ERR_ARG, "chip_bjvp_get_dev: no chip_bjvp_apply since the last solve");
+    if (dx_dev) *dx_dev = h->t_dx;
+    if (dz_dev) *dz_dev = h->t_dz;
+    if (ds_dev) *ds_dev = h->t_ds;
+    if (valid_dev) *valid_dev = h->t_valid;
+    return CHIP_OK;
+}
+
 #ifdef CHIP_TESTING
 #include "../../include/clarabel_hip_testing.h"
 int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration) {
@@ -1249,6 +1381,9 @@ int32_t chip_debug_batch_counter(void *batch, const char *name, double *out) {
     else if (nm == "update_host_syncs") *out = (double)h->upd_syncs;
     else if (nm == "backward_launches") *out = (double)h->grad_launches;
     else if (nm == "backward_host_syncs") *out = (double)h->grad_syncs;
+    else if (nm == "jvp_launches") *out = (double)h->jvp_launches;
+    else if (nm == "jvp_host_syncs") *out = (double)h->jvp_syncs;
+    else if (nm == "jvp_refactors") *out = (double)h->jvp_refactors;
     else return fail(CHIP_ERR_ARG, "chip_debug_batch_counter: unknown name");
     return CHIP_OK;
 }
@@ -1327,6 +1462,36 @@ struct DebugStage {
     }
 };
 } // namespace
+
+int32_t chip_debug_batch_jvp_rhs(void *batch, const double *x, const double *z, const int32_t *valid, const double *dq,
+                                 const double *db, const double *dPx, const double *dAx, double *rx, double *rz) {
+    chip_batch *h = (chip_batch *)batch;
+    if (!h || !valid || (h->pd.n && (!x || !rx)) || (h->pd.m && (!z || !rz)))
+        return fail(CHIP_ERR_ARG, "chip_debug_batch_jvp_rhs: bad argument");
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    int rc;
+    dev::SpPattern Psym, Arow, Acol;
+    if ((rc = kktsystem_pattern(h->sys, 0, &Psym)) || (rc = kktsystem_pattern(h->sys, 1, &Arow)) ||
+        (rc = kktsystem_pattern(h->sys, 2, &Acol)))
+        return rc;
+    DebugStage st;
+    const size_t n = (size_t)h->pd.n, m = (size_t)h->pd.m;
+    const double *dx_, *dz_, *ddq, *ddb, *ddP, *ddA;
+    const int32_t *dvalid;
+    double *drx, *drz;
+    if ((rc = st.in(x, n, &dx_)) || (rc = st.in(z, m, &dz_)) || (rc = st.in(valid, (size_t)h->nprob, &dvalid)) ||
+        (rc = st.in(dq, n, &ddq)) || (rc = st.in(db, m, &ddb)) || (rc = st.in(dPx, (size_t)h->pd.M.nnzP, &ddP)) ||
+        (rc = st.in(dAx, (size_t)h->pd.M.nnzA, &ddA)) || (rc = st.out(rx, n, &drx)) || (rc = st.out(rz, m, &drz)))
+        return rc;
+    hipStream_t s = nullptr;
+    CHIP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    dev::bt_rhs(s, h->plan, Psym, Acol, Arow,
+                dev::BtRhs{dvalid, dx_, dz_, ddq, ddb, ddP, ddA, h->pd.d, h->pd.e, h->dc, drx, drz, nullptr, nullptr,
+                           nullptr, nullptr});
+    rc = st.finish(s);
+    (void)hipStreamDestroy(s);
+    return rc;
+}
 
 int32_t chip_debug_bplan_create(void **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t ncones,
                                 const int32_t *cone_tags, const int64_t *cone_dims) {

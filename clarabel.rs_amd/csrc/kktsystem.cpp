@@ -15,6 +15,7 @@
 #include "equilibrate.hpp"
 #include "batch.hpp"
 #include "problem_update.hpp"
+#include "batch_tangent.hpp"
 
 using namespace chip;
 
@@ -276,6 +277,14 @@ int chip::kktsystem_spmv(chip_kktsystem *h, int which, double *y, const double *
     const SpMat &M = which == 0 ? h->Psym : which == 1 ? h->Arow : h->Acol;
     if (M.rows) h->spmv(M, y, aux, alpha, x);
     CHIP_HIP(hipGetLastError());
+    return CHIP_OK;
+}
+
+// the batched solver's tangent pass (batch_tangent.hip) walks the same rows with the caller's values in place of val
+int chip::kktsystem_pattern(chip_kktsystem *h, int which, dev::SpPattern *out) {
+    if (!h || !out || which < 0 || which > 2) return CHIP_ERR_ARG;
+    const SpMat &M = which == 0 ? h->Psym : which == 1 ? h->Arow : h->Acol;
+    *out = dev::SpPattern{M.rows, M.ptr, M.idx, M.map};
     return CHIP_OK;
 }
 

@@ -9,7 +9,11 @@ tensors on the GPU nothing crosses to the host in either direction.
 
 q[n], b[m], Px[nnz(P)], Ax[nnz(A)] are stacked float64 vectors in the stack's order (the positions update_P /
 update_A index); any of them may be None: that piece keeps the solver's current values and gets no gradient.  Members
-that did not end Solved, or own a SecondOrder cone, get zero gradients (solver.last_gradient.valid tells which)."""
+that did not end Solved, or own a SecondOrder cone, get zero gradients (solver.last_gradient.valid tells which).
+
+Forward mode works through the same Function: under torch.autograd.forward_ad.dual_level() (or torch.func.jvp) the
+tangents of (x, z, s) come from HipBatchSolver.jvp (chip_bjvp_*: one KKT solve at the final iterates per direction,
+DESIGN.md 4.16); solver.last_tangent.valid tells which members have one."""
 import torch
 
 
@@ -40,3 +44,14 @@ class BatchQPFunction(torch.autograd.Function):
         grads = [None if like is None or not need else o.to(device=like[0], dtype=like[1])
                  for o, like, need in zip(outs, ctx.like, ctx.needs_input_grad[:4])]
         return grads[0], grads[1], grads[2], grads[3], None
+
+    @staticmethod
+    def jvp(ctx, tq, tb, tPx, tAx, _):
+        solver = ctx.solver
+        if solver.generation != ctx.generation:
+            raise RuntimeError("BatchQPFunction.jvp: the solver has been solved again since this forward")
+        dev = ctx.device
+        prep = lambda t: None if t is None else t.detach().to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
+        t = solver.jvp(dq=prep(tq), db=prep(tb), dP=prep(tPx), dA=prep(tAx))
+        solver.last_tangent = t
+        return t.dx, t.dz, t.ds

@@ -778,6 +778,34 @@ int32_t chip_bgrad_get(chip_batch *h, double *dq, double *db, double *dPx, doubl
 int32_t chip_bgrad_get_dev(chip_batch *h, double **dq_dev, double **db_dev, double **dPx_dev, double **dAx_dev,
                            int32_t **valid_dev);
 
+/* ---- forward-mode derivatives of a batch's solutions (Jacobian-vector products): how x, z, s of every member move
+ * when its q, b, P, A move along a direction (dq, db, dP, dA) -- sensitivities for MPC and parametric programming,
+ * torch.autograd.forward_ad / torch.func.jvp through the layer, Gauss-Newton products.  With H and K as above, dP on
+ * P's stored triu pattern (a stored (i, j), i < j, stands for both triangles: dP_sym) and dA on A's pattern:
+ *     rx = -(dq + dP_sym x + dA' z)      rz = db - dA x
+ *     [dx; dz] = K^-1 [rx; rz]           ds = rz - A dx on the Nonnegative rows, +0.0 on the Zero rows
+ * the exact transpose of chip_bgrad_backward: gx.dx + gz.dz + gs.ds = dL/dq.dq + dL/db.db + dL/dP.dP + dL/dA.dA.
+ * One call costs the right-hand side, one refined KKT solve and the output pass, whatever nprob; the KKT update is
+ * paid only by the first apply or backward after a solve: later applies reuse the factorisation at the final iterates,
+ * so the columns of a Jacobian cost one solve each.
+ *   chip_bjvp_apply   dq[n], db[m], dPx[nnz(P)], dAx[nnz(A)]: stacked host vectors in the order of the stack's nzval
+ *                     -- the positions chip_bdata_update_P / _A index -- any may be NULL (= zeros; all NULL gives
+ *                     zeros).  _dev: device pointers (the caller must have finished writing them before the call).
+ *                     Needs a finished chip_batch_solve on the data the handle holds now: before the first solve, or
+ *                     after a chip_bdata_update_{P,A,q,b} that changed something, CHIP_ERR_ARG and nothing changes.
+ *   chip_bjvp_get     host copies (any may be NULL): dx[n], dz[m], ds[m] and valid[nprob].  _dev: the handle's own
+ *                     device buffers, valid until the next apply, solve, update or destroy.  CHIP_ERR_ARG when no
+ *                     apply has run since the last solve.
+ *   valid[k] = 1 iff member k ended CHIP_SOLVER_SOLVED and owns only Zero / Nonnegative cones.  Every other member has
+ *   valid[k] = 0 and exact +0.0 in dx, dz, ds; nothing of it is read as a number, neither its iterate nor its part of
+ *   the four inputs.  An apply does not disturb the buffers of chip_bgrad_get[_dev], a backward does not disturb
+ *   these.  A following chip_batch_solve behaves as if apply had not run. */
+int32_t chip_bjvp_apply(chip_batch *h, const double *dq, const double *db, const double *dPx, const double *dAx);
+int32_t chip_bjvp_apply_dev(chip_batch *h, const double *dq_dev, const double *db_dev, const double *dPx_dev,
+                            const double *dAx_dev);
+int32_t chip_bjvp_get(chip_batch *h, double *dx, double *dz, double *ds, int32_t *valid);
+int32_t chip_bjvp_get_dev(chip_batch *h, double **dx_dev, double **dz_dev, double **ds_dev, int32_t **valid_dev);
+
 /* ===========================================================================
  * Sharded path: one process per GPU, whole connected components of the elimination
  * forest per rank (BASELINE config 4: 1024 independent SOCPs, 128 per GPU at 8 GPUs).  Factorisation,

@@ -81,9 +81,17 @@ int32_t chip_debug_ipm_info_update(double *info, const double *sq, double tau, d
  * solve's iterations, default_start and post-processing excluded), "loop_iterations" (iterations run);
  * "update_launches" / "update_host_syncs" (kernel, memset and copy enqueues / host synchronisations of the last
  * chip_bdata_update_* call); "backward_launches" / "backward_host_syncs" (the same of the last chip_bgrad_backward*
- * call). */
+ * call); "jvp_launches" / "jvp_host_syncs" (the same of the last chip_bjvp_apply* call) and "jvp_refactors" (the
+ * scaling updates + refactors that applies have paid over the handle's life: an apply that finds K factored at the
+ * final iterates pays none).
+ * chip_debug_batch_jvp_rhs: the right-hand side pass of chip_bjvp_apply (csrc/batch_tangent.hip: bt_rhs) alone on a
+ * created handle, on a private stream; no solve is needed.  HOST arrays: x[n], z[m] (the unscaled solution the pass
+ * reads), valid[nprob], the direction dq[n], db[m], dPx[nnz(P)], dAx[nnz(A)] (any of the four may be NULL = zeros);
+ * returns the SCALED right-hand side rx[n] = c_k d (-(dq + dP_sym x + dA' z)), rz[m] = e (db - dA x). */
 int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration);
 int32_t chip_debug_batch_counter(void *batch, const char *name, double *out);
+int32_t chip_debug_batch_jvp_rhs(void *batch, const double *x, const double *z, const int32_t *valid, const double *dq,
+                                 const double *db, const double *dPx, const double *dAx, double *rx, double *rz);
 /* ---- the batched solver's partition and its device passes (csrc/batch.hpp), each alone ----
  * chip_debug_bplan_create: the partition chip_batch_create builds for nprob members of n_part[k] columns and m_part[k]
  * rows with the given cones (Zero / Nonnegative / SecondOrder), by the same code and with the same refusals; host only,
