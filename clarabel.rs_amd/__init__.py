@@ -1199,6 +1199,36 @@ class HipBatchSolver(_DataUpdates):
             raise ChipError(ERR_DIM, "%s: %d values for %d entries" % (name, v.size, length))
         return ("host", _f(v))
 
+    def _derivative(self, fn, inputs, values, entry, outputs, result):
+        """one derivative pass `fn` ("backward" / "jvp"): inputs = the (name, key) of its arguments, values = what the
+        caller gave for them, entry = the C calls "chip_bgrad" / "chip_bjvp" + (pass, pass_dev, "get", "get_dev"),
+        outputs = the keys of the results' lengths, result = the class that carries them"""
+        run, run_dev, get, get_dev = entry
+        forms = [self._grad_input(nm, g, key, fn) for (nm, key), g in zip(inputs, values)]
+        kinds = {f[0] for f in forms} - {"none"}
+        if len(kinds) > 1:
+            names = [nm for nm, _ in inputs]
+            raise TypeError("%s: %s and %s must all be host arrays or all GPU tensors"
+                            % (fn, ", ".join(names[:-1]), names[-1]))
+        lens = [self._len[key] for key in outputs]
+        valid = np.zeros(len(self), dtype=np.int32)
+        L = lib()
+        if kinds == {"dev"}:
+            import torch
+            dev = [f[1] for f in forms if f[0] == "dev"][0].device
+            torch.cuda.current_stream(dev).synchronize()  # the values are written before the call reads them
+            ptr = [None if f[0] == "none" else C.c_void_p(f[1].data_ptr()) for f in forms]
+            _check(getattr(L, run_dev)(self._h, *ptr), run_dev)
+            out = [C.c_void_p() for _ in lens]
+            _check(getattr(L, get_dev)(self._h, *[C.byref(o) for o in out], None), get_dev)
+            _check(getattr(L, get)(self._h, *[None] * len(lens), valid.ctypes.data_as(P_I32)), get)
+            return result(*[_torch_copy(o.value, ln, "float64", dev) for o, ln in zip(out, lens)], valid, self._offsets)
+        ptr = [None if f[0] == "none" else _pf(f[1]) for f in forms]
+        _check(getattr(L, run)(self._h, *ptr), run)
+        res = [np.zeros(ln) for ln in lens]
+        _check(getattr(L, get)(self._h, *[_pf(v) for v in res], valid.ctypes.data_as(P_I32)), get)
+        return result(*res, valid, self._offsets)
+
     def backward(self, gx=None, gz=None, gs=None):
         """the gradients of a loss with respect to q, b, P and A of every member from its gradients with respect to
         the members' x, z and s of the last solve() (stacked vectors; None = zeros): numpy arrays, torch tensors on
@@ -1207,30 +1237,9 @@ class HipBatchSolver(_DataUpdates):
         form -- gradients that live on the GPU go in as stacked tensors).  Returns a BatchGradient.  Members that did not end
         Solved, or own a SecondOrder cone, have valid[k] = 0 and exact zeros.  ChipError(ERR_ARG) before a solve and
         after an update that was not followed by a solve."""
-        forms = [self._grad_input(nm, g, key) for nm, g, key in (("gx", gx, "q"), ("gz", gz, "b"), ("gs", gs, "b"))]
-        kinds = {f[0] for f in forms} - {"none"}
-        if len(kinds) > 1:
-            raise TypeError("backward: gx, gz and gs must all be host arrays or all GPU tensors")
-        n, m, nP, nA = self._len["q"], self._len["b"], self._len["P"], self._len["A"]
-        valid = np.zeros(len(self), dtype=np.int32)
-        if kinds == {"dev"}:
-            import torch
-            dev = [f[1] for f in forms if f[0] == "dev"][0].device
-            torch.cuda.current_stream(dev).synchronize()  # the values are written before the call reads them
-            ptr = [None if f[0] == "none" else C.c_void_p(f[1].data_ptr()) for f in forms]
-            _check(lib().chip_bgrad_backward_dev(self._h, *ptr), "chip_bgrad_backward_dev")
-            out = [C.c_void_p() for _ in range(4)]
-            _check(lib().chip_bgrad_get_dev(self._h, *[C.byref(o) for o in out], None), "chip_bgrad_get_dev")
-            _check(lib().chip_bgrad_get(self._h, None, None, None, None, valid.ctypes.data_as(P_I32)),
-                   "chip_bgrad_get")
-            dq, db, dP, dA = [_torch_copy(o.value, ln, "float64", dev) for o, ln in zip(out, (n, m, nP, nA))]
-            return BatchGradient(dq, db, dP, dA, valid, self._offsets)
-        ptr = [None if f[0] == "none" else _pf(f[1]) for f in forms]
-        _check(lib().chip_bgrad_backward(self._h, *ptr), "chip_bgrad_backward")
-        dq, db, dP, dA = np.zeros(n), np.zeros(m), np.zeros(nP), np.zeros(nA)
-        _check(lib().chip_bgrad_get(self._h, _pf(dq), _pf(db), _pf(dP), _pf(dA), valid.ctypes.data_as(P_I32)),
-               "chip_bgrad_get")
-        return BatchGradient(dq, db, dP, dA, valid, self._offsets)
+        return self._derivative("backward", (("gx", "q"), ("gz", "b"), ("gs", "b")), (gx, gz, gs),
+                                ("chip_bgrad_backward", "chip_bgrad_backward_dev", "chip_bgrad_get",
+                                 "chip_bgrad_get_dev"), "qbPA", BatchGradient)
 
     # ---- tangents (chip_bjvp_*): a direction in (q, b, P, A) of every member -> (dx, dz, ds) of every member ---------
     def jvp(self, dq=None, db=None, dP=None, dA=None):
@@ -1243,29 +1252,9 @@ class HipBatchSolver(_DataUpdates):
         exact zeros.  The first jvp (or backward) after a solve factors K at the final iterates; every further jvp of
         that solve costs one KKT solve.  ChipError(ERR_ARG) before a solve and after an update that was not followed
         by a solve."""
-        forms = [self._grad_input(nm, g, key, "jvp")
-                 for nm, g, key in (("dq", dq, "q"), ("db", db, "b"), ("dP", dP, "P"), ("dA", dA, "A"))]
-        kinds = {f[0] for f in forms} - {"none"}
-        if len(kinds) > 1:
-            raise TypeError("jvp: dq, db, dP and dA must all be host arrays or all GPU tensors")
-        n, m = self._len["q"], self._len["b"]
-        valid = np.zeros(len(self), dtype=np.int32)
-        if kinds == {"dev"}:
-            import torch
-            dev = [f[1] for f in forms if f[0] == "dev"][0].device
-            torch.cuda.current_stream(dev).synchronize()  # the values are written before the call reads them
-            ptr = [None if f[0] == "none" else C.c_void_p(f[1].data_ptr()) for f in forms]
-            _check(lib().chip_bjvp_apply_dev(self._h, *ptr), "chip_bjvp_apply_dev")
-            out = [C.c_void_p() for _ in range(3)]
-            _check(lib().chip_bjvp_get_dev(self._h, *[C.byref(o) for o in out], None), "chip_bjvp_get_dev")
-            _check(lib().chip_bjvp_get(self._h, None, None, None, valid.ctypes.data_as(P_I32)), "chip_bjvp_get")
-            dx, dz, ds = [_torch_copy(o.value, ln, "float64", dev) for o, ln in zip(out, (n, m, m))]
-            return BatchTangent(dx, dz, ds, valid, self._offsets)
-        ptr = [None if f[0] == "none" else _pf(f[1]) for f in forms]
-        _check(lib().chip_bjvp_apply(self._h, *ptr), "chip_bjvp_apply")
-        dx, dz, ds = np.zeros(n), np.zeros(m), np.zeros(m)
-        _check(lib().chip_bjvp_get(self._h, _pf(dx), _pf(dz), _pf(ds), valid.ctypes.data_as(P_I32)), "chip_bjvp_get")
-        return BatchTangent(dx, dz, ds, valid, self._offsets)
+        return self._derivative("jvp", (("dq", "q"), ("db", "b"), ("dP", "P"), ("dA", "A")), (dq, db, dP, dA),
+                                ("chip_bjvp_apply", "chip_bjvp_apply_dev", "chip_bjvp_get", "chip_bjvp_get_dev"),
+                                "qbb", BatchTangent)
 
     # ---- test hooks (include/clarabel_hip_testing.h) ----
     def debug_jvp_rhs(self, x, z, valid, dq=None, db=None, dP=None, dA=None):
@@ -1288,34 +1277,35 @@ class HipBatchSolver(_DataUpdates):
         return out.value
 
 
-class BatchGradient:
+class _BatchDerivative:
+    """stacked result vectors (numpy arrays or torch GPU tensors) named by FIELDS = ((attribute, offset key), ...),
+    and valid[nprob] (numpy int32): 1 where the member has a derivative, else its entries are exact zeros"""
+    FIELDS = ()
+
+    def __init__(self, *args):
+        *vectors, self.valid, self._offsets = args
+        if len(vectors) != len(self.FIELDS):
+            raise TypeError("%s: %d vectors, valid and offsets are needed" % (type(self).__name__, len(self.FIELDS)))
+        for (name, _), v in zip(self.FIELDS, vectors):
+            setattr(self, name, v)
+
+    def per_member(self, k):
+        """member k's slices of the stacked vectors, in the order of FIELDS"""
+        o = self._offsets
+        return tuple(getattr(self, name)[int(o[key][k]):int(o[key][k + 1])] for name, key in self.FIELDS)
+
+
+class BatchGradient(_BatchDerivative):
     """the result of HipBatchSolver.backward: dq[n], db[m], dP[nnz(P)], dA[nnz(A)] of the stack (dP, dA in the order
     of the stack's nzval, the positions update_P / update_A index) as numpy arrays or torch GPU tensors, and
     valid[nprob] (numpy int32): 1 where the member has a gradient, else its entries are exact zeros"""
-
-    def __init__(self, dq, db, dP, dA, valid, offsets):
-        self.dq, self.db, self.dP, self.dA, self.valid = dq, db, dP, dA, valid
-        self._offsets = offsets
-
-    def per_member(self, k):
-        """member k's (dq, db, dP, dA): slices of the stacked vectors"""
-        o = self._offsets
-        return tuple(v[int(o[key][k]):int(o[key][k + 1])]
-                     for v, key in ((self.dq, "q"), (self.db, "b"), (self.dP, "P"), (self.dA, "A")))
+    FIELDS = (("dq", "q"), ("db", "b"), ("dP", "P"), ("dA", "A"))
 
 
-class BatchTangent:
+class BatchTangent(_BatchDerivative):
     """the result of HipBatchSolver.jvp: dx[n], dz[m], ds[m] of the stack as numpy arrays or torch GPU tensors, and
     valid[nprob] (numpy int32): 1 where the member has a derivative, else its entries are exact zeros"""
-
-    def __init__(self, dx, dz, ds, valid, offsets):
-        self.dx, self.dz, self.ds, self.valid = dx, dz, ds, valid
-        self._offsets = offsets
-
-    def per_member(self, k):
-        """member k's (dx, dz, ds): slices of the stacked vectors"""
-        o = self._offsets
-        return tuple(v[int(o[key][k]):int(o[key][k + 1])] for v, key in ((self.dx, "q"), (self.dz, "b"), (self.ds, "b")))
+    FIELDS = (("dx", "q"), ("dz", "b"), ("ds", "b"))
 
 
 def _torch_copy(ptr, n, dtype, device=None):

@@ -10,6 +10,8 @@
 // The L2 cone operations without a scalar (affine ds, ds from dz, Hs products, scaling update, unit initialisation)
 // run on the whole stack as they are; combined_ds_shift runs with sigma mu = 0 and the member's sigma mu is then
 // subtracted at the unit vector's entries, which is the same arithmetic for Nonnegative and SecondOrder cones.
+// This file: the partition, create / destroy, the loop, the getters and the data updates.  The handle itself is in
+// batch_handle.hpp, the derivative passes in batch_deriv.cpp, the test hooks in batch_debug.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -18,17 +20,8 @@
 #include <string>
 #include <vector>
 
-#include "batch.hpp"
-#include "batch_adjoint.hpp"
-#include "batch_tangent.hpp"
+#include "batch_handle.hpp"
 #include "batch_update.hpp"
-#include "engine.hpp"
-#include "host_util.hpp"
-#include "ipm_info.hpp"
-#include "problem_data.hpp"
-#include "problem_update.hpp"
-
-using namespace chip;
 
 namespace {
 // per-member device scalars (slot * nprob + k) and masks
@@ -38,18 +31,7 @@ enum { M_ACTIVE, M_QP, M_LP, M_SEL, M_SEL2, M_COUNT };
 enum { R_QX, R_XPX, R_NX, R_NRXI, R_NPX, R_NRX, R_BADX, R_BZ, R_SZ, R_NZ, R_NS, R_NRZI, R_NRZ, R_BADSZ, R_COUNT };
 // the direction passes
 enum { D_QX1, D_BZ1, D_XIPX1, D_DPD, D_BAD, D_COUNT };
-
-// the fixed partition of a batch on the host (dev::BatchPlan, batch.hpp, is its device copy), with what the cones give
-// per member.  parts_ok: the parts themselves were accepted, so xoff / zoff / xmem / zmem are filled even when a cone
-// was refused after them
-struct HostPlan {
-    int nprob = 0, n = 0, m = 0, ncx = 0, ncz = 0;
-    std::vector<int> xoff, zoff, xmem, zmem, ch_beg, ch_end, cx_first, cz_first, it_beg, it_end, it_type, it_first, rtype;
-    std::vector<int64_t> degree;
-    std::vector<char> has_soc;
-    std::vector<ConeSpec> cones;
-    bool parts_ok = false;
-};
+} // namespace
 
 int batch_cones_supported(int64_t ncones, const int32_t *cone_tags) {
     for (int64_t i = 0; i < ncones; i++)
@@ -159,165 +141,6 @@ int host_plan_upload(DevPool &mem, const HostPlan &hp, dev::BatchPlan *pl) {
                          d_czf,    hp.ncx, hp.ncz, d_itb, d_ite, d_itt, d_itf, (int)hp.it_beg.size(), d_rt};
     return CHIP_OK;
 }
-} // namespace
-
-struct chip_batch {
-    int nprob = 0;
-    chip_solver_settings st{};
-    DevPool mem;
-    std::vector<int> xoff, zoff;
-    dev::BatchPlan plan{};
-    ProblemData pd; // the whole stack
-    double *negq = nullptr;
-    // for the data updates (chip_bdata_*): the unscaled q and b (the members' norms are taken from them, as create
-    // takes them from the user's data) and the members' cost scales on the device
-    double *uq = nullptr, *ub = nullptr, *dc = nullptr;
-    std::vector<double> c, normq, normb;
-    std::vector<int64_t> degree;
-    std::vector<int> lp_init; // the member's P has no stored entry: the LP initial point (kktsystem.rs:197-215)
-    bool anyP = false, anyLP = false;
-    chip_kkt *kkt = nullptr;
-    chip_kktsystem *sys = nullptr; // its sparse operators only (kktsystem_spmv)
-    hipStream_t stream = nullptr;
-    // iterates: the current and previous one (swapped by the step), the held last finite iterate of members that ended
-    // NumericalError, the direction and right-hand side
-    double *vx = nullptr, *vs = nullptr, *vz = nullptr, *px = nullptr, *ps = nullptr, *pz = nullptr;
-    double *hx = nullptr, *hs = nullptr, *hz = nullptr;
-    double *lx = nullptr, *ls = nullptr, *lz = nullptr, *dx = nullptr, *ds = nullptr, *dz = nullptr;
-    double *x1 = nullptr, *z1 = nullptr, *x2 = nullptr, *z2 = nullptr, *workx = nullptr, *workx2 = nullptr,
-           *wn = nullptr, *wn2 = nullptr, *wn3 = nullptr, *workz = nullptr, *conicw = nullptr;
-    double *rx = nullptr, *rz = nullptr, *rx_inf = nullptr, *rz_inf = nullptr, *Pxv = nullptr;
-    double *xo = nullptr, *so = nullptr, *zo = nullptr;
-    double *dsc = nullptr, *dred = nullptr, *seg_scr = nullptr, *cone_scr = nullptr;
-    int *dmask = nullptr;
-    std::vector<double> hsc, hred;
-    std::vector<int> hmask;
-    // per member on the host
-    std::vector<double> tau, kappa, ptau, pkappa, htau, hkappa, mu, sigma, alpha, dtau, qx2, bz2, x2Px2;
-    std::vector<IpmInfo> info, pinfo, hinfo; // (out5 of a member: the dots of its last residual pass)
-    std::vector<char> active, held, held_done; // held: 1 = the current iterate, 2 = the previous one
-    std::vector<double> obj_val, obj_val_dual;
-    double setup_time = 0, equilibration_time = 0, iteration_time = 0, solve_time = 0;
-    double t_solve0 = 0;
-    bool solved_once = false;
-    // test hooks and counters
-    int64_t nan_member = -1;
-    int nan_iter = -1;
-    long syncs = 0, launches = 0, loop_iters = 0;
-    // work buffers of the data updates, allocated by the first one; the staging of the host forms grows on demand
-    int *upos = nullptr, *uflag = nullptr;
-    unsigned long long *unpart = nullptr, *ubpart = nullptr;
-    double *unout = nullptr, *ubout = nullptr;
-    UpdateStage stage;
-    int64_t *clean = nullptr;
-    size_t clean_cap = 0;
-    std::vector<double> unorm;
-    long upd_syncs = 0, upd_launches = 0; // of the last update call
-    // the gradients (chip_bgrad_*): solve_current: the last solve ran on the data the handle holds now; grad_done: the
-    // buffers below hold the result of a backward since that solve.  Allocated by the first backward
-    std::vector<char> has_soc; // the member owns a SecondOrder cone: no gradient
-    std::vector<int32_t> gvalid;
-    bool solve_current = false, grad_done = false;
-    int *g_valid = nullptr;
-    double *g_dq = nullptr, *g_db = nullptr, *g_dP = nullptr, *g_dA = nullptr;
-    double *g_in[3] = {nullptr, nullptr, nullptr}; // the staging of the host form's gx, gz, gs
-    long grad_syncs = 0, grad_launches = 0;        // of the last backward
-    // the tangents (chip_bjvp_*): kkt_final: K is factored at the final iterates of the last solve (by a backward or an
-    // apply), so an apply needs no scaling update and no refactor; jvp_done: the buffers below hold the result of an
-    // apply since that solve.  Allocated by the first apply
-    bool kkt_final = false, jvp_done = false;
-    std::vector<int32_t> tvalid;
-    int *t_valid = nullptr;
-    double *t_dx = nullptr, *t_dz = nullptr, *t_ds = nullptr;
-    double *t_in[4] = {nullptr, nullptr, nullptr, nullptr}; // the staging of the host form's dq, db, dP, dA
-    long jvp_syncs = 0, jvp_launches = 0; // of the last apply
-    long jvp_refactors = 0;               // of the handle's life
-
-    ~chip_batch() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        (void)hipFree(clean);
-        chip_kktsystem_destroy(sys);
-        chip_kkt_destroy(kkt);
-    }
-    double *sc(int slot) { return dsc + (size_t)slot * nprob; }
-    double &hs_(int slot, int k) { return hsc[(size_t)slot * nprob + k]; }
-    int *mk(int slot) { return dmask + (size_t)slot * nprob; }
-    int &hm(int slot, int k) { return hmask[(size_t)slot * nprob + k]; }
-    // the per-member scalars and masks travel in a ring of device (and host staging) slots: a kernel enqueued before
-    // the next upload keeps reading its own slot, and the loop synchronises far more often than the ring wraps
-    static constexpr int RING = 32;
-    double *dsc_ring = nullptr;
-    int *dmask_ring = nullptr;
-    std::vector<double> hsc_ring;
-    std::vector<int> hmask_ring;
-    int ring_s = 0, ring_m = 0;
-    int push_scalars() {
-        const size_t len = hsc.size();
-        ring_s = (ring_s + 1) % RING;
-        double *src = hsc_ring.data() + (size_t)ring_s * len;
-        std::memcpy(src, hsc.data(), len * 8);
-        dsc = dsc_ring + (size_t)ring_s * len;
-        launches++;
-        CHIP_HIP(hipMemcpyAsync(dsc, src, len * 8, hipMemcpyHostToDevice, stream));
-        return CHIP_OK;
-    }
-    int push_masks() {
-        const size_t len = hmask.size();
-        ring_m = (ring_m + 1) % RING;
-        int *src = hmask_ring.data() + (size_t)ring_m * len;
-        std::memcpy(src, hmask.data(), len * sizeof(int));
-        dmask = dmask_ring + (size_t)ring_m * len;
-        launches++;
-        CHIP_HIP(hipMemcpyAsync(dmask, src, len * sizeof(int), hipMemcpyHostToDevice, stream));
-        return CHIP_OK;
-    }
-    // one device-to-host copy of `count` doubles of the reduction output and one synchronisation
-    int read_red(size_t count) {
-        CHIP_HIP(hipGetLastError());
-        CHIP_HIP(hipMemcpyAsync(hred.data(), dred, count * 8, hipMemcpyDeviceToHost, stream));
-        CHIP_HIP(hipStreamSynchronize(stream));
-        launches++;
-        syncs++;
-        return CHIP_OK;
-    }
-    double red(int slot, int k) const { return hred[(size_t)slot * nprob + k]; }
-    void lin(double *w, const double *x, const double *y, const double *sa, const double *sb, double ca, double cb,
-             int space, const int *mask, int mode) {
-        dev::blin(stream, plan, dev::BLin{w, x, y, sa, sb, ca, cb, space, mask, mode});
-        launches++;
-    }
-    void copy_members(double *wx, double *ws, double *wz, const double *x, const double *s, const double *z,
-                      const int *mask) { // masked copy: members with mask[k] != 0 take (x, s, z)
-        lin(wx, x, nullptr, nullptr, nullptr, 1.0, 0.0, 0, mask, dev::MASK_KEEP);
-        lin(ws, s, nullptr, nullptr, nullptr, 1.0, 0.0, 1, mask, dev::MASK_KEEP);
-        lin(wz, z, nullptr, nullptr, nullptr, 1.0, 0.0, 1, mask, dev::MASK_KEEP);
-    }
-    int spmv(int which, double *y, const double *aux, double alpha_, const double *x) {
-        launches++;
-        return kktsystem_spmv(sys, which, y, aux, alpha_, x);
-    }
-    int default_start();
-    int residual_pass();
-    void member_info(int k);
-    int solve_direction(const double *conic, const std::vector<double> &rtau, const std::vector<double> &rkap,
-                        std::vector<double> &lkappa, bool *global_ok, int iter);
-    int step_length(const std::vector<double> &lkappa, bool combined);
-    int constant_rhs(bool *global_ok, int iter);
-    int hold_and_reset();
-    int post_process();
-    int end_member(int k, int status, int iterations, bool from_prev);
-    int update_work();
-    static constexpr const char *UPD_PREFIX = "chip_bdata_update_";
-    static int update_args(chip_batch *h, int which, const void *idx, const double *vals, int64_t k);
-    int stage_upload(const uint64_t *idx, const double *vals, size_t k) {
-        return stage.upload(stream, idx, vals, k, &upd_launches, &upd_syncs);
-    }
-    int update(int which, const int64_t *idx_dev, const double *vals_dev, int k);
-    int backward_work();
-    int backward(const double *gx_dev, const double *gz_dev, const double *gs_dev);
-    int jvp_work();
-    int jvp_apply(const double *dq_dev, const double *db_dev, const double *dP_dev, const double *dA_dev);
-};
 
 int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n,
                           int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval, const double *Pnzval,
@@ -767,7 +590,7 @@ int32_t chip_batch_solve(chip_batch *h) {
     h->held_done.assign((size_t)np, 0);
     h->t_solve0 = now_s();
     h->solve_time = h->setup_time;
-    h->solve_current = h->grad_done = h->kkt_final = h->jvp_done = false;
+    h->solve_current = h->kkt_final = h->grad.done = h->tan.done = false;
     int rc;
     if ((rc = h->default_start())) return rc;
     for (int k = 0; k < np; k++) h->hm(M_ACTIVE, k) = 1;
@@ -1119,568 +942,3 @@ int32_t chip_bdata_get_scaled(chip_batch *h, double *Px, double *Ax, double *q, 
     if (normb) std::copy(h->normb.begin(), h->normb.end(), normb);
     return CHIP_OK;
 }
-
-// ---------------------------------------------------------------------------------------------------------------
-// Gradients of the members' solutions (chip_bgrad_*).  With the incoming gradients (gx, gz, gs) of a
-// member's unscaled (x, z, s), its adjoint is ONE KKT solve at the final iterate,
-//     [vx; vz] = K^-1 [gx - A' gs; gz],   K = [P A'; A -H],   H = diag(s / z) on Nonnegative rows, 0 on Zero rows,
-// which is the matrix chip_kkt factors after a scaling update with (s, z).  The solve runs in the equilibrated space
-// of the stack (x = D x^, z = E z^ / c_k, s = E^-1 s^; P^ = c_k D P D, q^ = c_k D q, A^ = E A D, b^ = E b), where the
-// incoming gradients are D gx, E gz / c_k and E^-1 gs; its solution multiplied back, ux = c_k D vx^ and uz = E vz^,
-// is the adjoint pair of the unscaled problem, so the four gradients are the unscaled formulas on the unscaled
-// solution the solve has already written (xo, zo).  H is s / z of the internal iterate: tau cancels.
-// One backward: a fixed number of enqueues (counted as batch.cpp counts them everywhere: one per kernel, copy or call
-// into the KKT layer, whatever that call launches itself), the synchronisations of one chip_kkt_update and one
-// chip_kkt_solve_dev and one at the end.  It leaves K factored at the final iterate and overwrites work vectors only; chip_batch_solve starts
-// from default_start, which rescales and refactors, so a following solve does not see it.
-// ---------------------------------------------------------------------------------------------------------------
-int chip_batch::backward_work() {
-    if (g_valid) return CHIP_OK;
-    int rc;
-    const size_t n = (size_t)pd.n, m = (size_t)pd.m;
-    if ((rc = mem.alloc(&g_dq, n)) || (rc = mem.alloc(&g_db, m)) || (rc = mem.alloc(&g_dP, (size_t)pd.M.nnzP)) ||
-        (rc = mem.alloc(&g_dA, (size_t)pd.M.nnzA)) || (rc = mem.alloc(&g_in[0], n)) || (rc = mem.alloc(&g_in[1], m)) ||
-        (rc = mem.alloc(&g_in[2], m)) || (rc = mem.alloc(&g_valid, (size_t)nprob)))
-        return rc;
-    gvalid.assign((size_t)nprob, 0);
-    return CHIP_OK;
-}
-
-int chip_batch::backward(const double *gx, const double *gz, const double *gs) {
-    int rc;
-    hipStream_t s = stream;
-    grad_done = false; // (a backward that fails part-way leaves no result behind)
-    // a gradient exists for the members that ended Solved and own only Zero / Nonnegative cones; every other member
-    // takes the cones' unit vector for (s, z), as a member that ended NumericalError does in the loop, and a zero
-    // right-hand side: its block of K stays well posed and its part of the solution is 0
-    for (int k = 0; k < nprob; k++) gvalid[k] = info[k].status == CHIP_SOLVER_SOLVED && !has_soc[k];
-    CHIP_HIP(hipMemcpyAsync(g_valid, gvalid.data(), (size_t)nprob * sizeof(int), hipMemcpyHostToDevice, s));
-    dev::ba_rhs(s, plan, dev::BaRhs{g_valid, gx, gz, gs, pd.d, pd.e, dc, vs, vz, wn, conicw, workz, ds, dz});
-    grad_launches += 2;
-    if ((rc = kktsystem_spmv(sys, 2, workx, wn, -1.0, conicw))) return rc; // D gx - A^' (gs / e)
-    grad_launches++;
-    kkt_final = false; // (a refactor that fails leaves nothing for chip_bjvp_* to reuse)
-    if ((rc = chip_kkt_update_scaling_dev(kkt, ds, dz, 1.0, 0)) < 0) return rc;
-    rc = chip_kkt_update(kkt, nullptr);
-    grad_syncs++;
-    grad_launches += 2;
-    if (rc < 0) return rc;
-    if (rc != 1) return fail(CHIP_ERR_ZERO_PIVOT, "chip_bgrad_backward: the factorisation at the final iterate failed");
-    kkt_final = true; // (an apply of chip_bjvp_* after this backward solves with this factorisation)
-    if ((rc = chip_kkt_setrhs_dev(kkt, workx, workz))) return rc;
-    rc = chip_kkt_solve_dev(kkt, x1, z1);
-    grad_syncs++;
-    grad_launches++;
-    if (rc < 0) return rc;
-    if (rc != 1) return fail(CHIP_ERR_ZERO_PIVOT, "chip_bgrad_backward: the solve at the final iterate failed");
-    const dev::BaGrad g{g_valid, x1, z1, gs, pd.d, pd.e, dc, xo, zo, x2, z2, g_dq, g_db, g_dP, g_dA};
-    dev::ba_grad_vectors(s, plan, g);
-    dev::ba_grad_matrices(s, plan, pd.M, g);
-    grad_launches += 2;
-    CHIP_HIP(hipGetLastError());
-    CHIP_HIP(hipStreamSynchronize(s));
-    grad_syncs++;
-    grad_done = true;
-    return CHIP_OK;
-}
-
-namespace {
-int bg_ready(chip_batch *h, const char *fn) {
-    if (!h) return fail(CHIP_ERR_ARG, std::string(fn) + ": bad argument");
-    if (!h->solve_current)
-        return fail(CHIP_ERR_ARG, std::string(fn) + ": needs a finished chip_batch_solve on the current data");
-    return CHIP_OK;
-}
-} // namespace
-
-int32_t chip_bgrad_backward(chip_batch *h, const double *gx, const double *gz, const double *gs) {
-    int rc = bg_ready(h, "chip_bgrad_backward");
-    if (rc) return rc;
-    CHIP_HIP(hipSetDevice(h->pd.device));
-    h->grad_syncs = h->grad_launches = 0;
-    if ((rc = h->backward_work())) return rc;
-    const double *src[3] = {gx, gz, gs};
-    const double *in[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < 3; i++) {
-        const size_t len = (size_t)(i == 0 ? h->pd.n : h->pd.m);
-        if (!src[i]) continue;
-        in[i] = h->g_in[i];
-        if (!len) continue;
-        CHIP_HIP(hipMemcpyAsync(h->g_in[i], src[i], len * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        h->grad_launches++;
-    }
-    return h->backward(in[0], in[1], in[2]);
-}
-
-int32_t chip_bgrad_backward_dev(chip_batch *h, const double *gx_dev, const double *gz_dev, const double *gs_dev) {
-    int rc = bg_ready(h, "chip_bgrad_backward_dev");
-    if (rc) return rc;
-    CHIP_HIP(hipSetDevice(h->pd.device));
-    h->grad_syncs = h->grad_launches = 0;
-    if ((rc = h->backward_work())) return rc;
-    return h->backward(gx_dev, gz_dev, gs_dev);
-}
-
-int32_t chip_bgrad_get(chip_batch *h, double *dq, double *db, double *dPx, double *dAx, int32_t *valid) {
-    if (!h) return fail(CHIP_ERR_ARG, "chip_bgrad_get: bad argument");
-    if (!h->grad_done) return fail(CHIP_ERR_ARG, "chip_bgrad_get: no chip_bgrad_backward since the last solve");
-    CHIP_HIP(hipSetDevice(h->pd.device));
-    const dev::EqMats &M = h->pd.M;
-    if (dq && h->pd.n) CHIP_HIP(hipMemcpy(dq, h->g_dq, (size_t)h->pd.n * 8, hipMemcpyDeviceToHost));
-    if (db && h->pd.m) CHIP_HIP(hipMemcpy(db, h->g_db, (size_t)h->pd.m * 8, hipMemcpyDeviceToHost));
-    if (dPx && M.nnzP) CHIP_HIP(hipMemcpy(dPx, h->g_dP, (size_t)M.nnzP * 8, hipMemcpyDeviceToHost));
-    if (dAx && M.nnzA) CHIP_HIP(hipMemcpy(dAx, h->g_dA, (size_t)M.nnzA * 8, hipMemcpyDeviceToHost));
-    if (valid) std::copy(h->gvalid.begin(), h->gvalid.end(), valid);
-    return CHIP_OK;
-}
-
-int32_t chip_bgrad_get_dev(chip_batch *h, double **dq_dev, double **db_dev, double **dPx_dev, double **dAx_dev,
-                           int32_t **valid_dev) {
-    if (!h) return fail(CHIP_ERR_ARG, "chip_bgrad_get_dev: bad argument");
-    if (!h->grad_done) return fail(CHIP_ERR_ARG, "chip_bgrad_get_dev: no chip_bgrad_backward since the last solve");
-    if (dq_dev) *dq_dev = h->g_dq;
-    if (db_dev) *db_dev = h->g_db;
-    if (dPx_dev) *dPx_dev = h->g_dP;
-    if (dAx_dev) *dAx_dev = h->g_dA;
-    if (valid_dev) *valid_dev = h->g_valid;
-    return CHIP_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Forward-mode derivatives of the members' solutions (chip_bjvp_*): the transpose of the gradients
-// above.  Along a direction (dq, db, dP, dA) in a member's data its solution moves by ONE KKT solve at the final
-// iterate, with the matrix backward solves with,
-//     rx = -(dq + dP_sym x + dA' z),  rz = db - dA x,  [dx; dz] = K^-1 [rx; rz],  ds = rz - A dx (Nonnegative rows).
-// In the equilibrated space of the stack the system is K^ [D^-1 dx; c_k E^-1 dz] = [c_k D rx; E rz] with rx, rz formed
-// from the unscaled solution (xo, zo), so dx = D vx^, dz = E vz^ / c_k and ds = E^-1 (E rz - A^ vx^): the transposes of
-// backward's scalings.  One apply: the right-hand side (bt_rhs), the scaling update and the refactor unless K is
-// already factored at the final iterates (kkt_final: set by a backward or an apply, cleared by an update and at the
-// start of a solve), one refined solve, one product with A^ and the output pass (bt_out); enqueues and synchronisations
-// are counted as backward counts them.  It overwrites work vectors only, none of them backward's results.
-// ---------------------------------------------------------------------------------------------------------------
-int chip_batch::jvp_work() {
-    if (t_valid) return CHIP_OK;
-    int rc;
-    const size_t n = (size_t)pd.n, m = (size_t)pd.m;
-    if ((rc = mem.alloc(&t_dx, n)) || (rc = mem.alloc(&t_dz, m)) || (rc = mem.alloc(&t_ds, m)) ||
-        (rc = mem.alloc(&t_in[0], n)) || (rc = mem.alloc(&t_in[1], m)) || (rc = mem.alloc(&t_in[2], (size_t)pd.M.nnzP)) ||
-        (rc = mem.alloc(&t_in[3], (size_t)pd.M.nnzA)) || (rc = mem.alloc(&t_valid, (size_t)nprob)))
-        return rc;
-    tvalid.assign((size_t)nprob, 0);
-    return CHIP_OK;
-}
-
-int chip_batch::jvp_apply(const double *dq, const double *db, const double *dP, const double *dA) {
-    int rc;
-    hipStream_t s = stream;
-    jvp_done = false; // (an apply that fails part-way leaves no result behind)
-    dev::SpPattern Psym, Arow, Acol;
-    if ((rc = kktsystem_pattern(sys, 0, &Psym)) || (rc = kktsystem_pattern(sys, 1, &Arow)) ||
-        (rc = kktsystem_pattern(sys, 2, &Acol)))
-        return rc;
-    for (int k = 0; k < nprob; k++) tvalid[k] = info[k].status == CHIP_SOLVER_SOLVED && !has_soc[k];
-    CHIP_HIP(hipMemcpyAsync(t_valid, tvalid.data(), (size_t)nprob * sizeof(int), hipMemcpyHostToDevice, s));
-    const bool refactor = !kkt_final;
-    dev::bt_rhs(s, plan, Psym, Acol, Arow,
-                dev::BtRhs{t_valid, xo, zo, dq, db, dP, dA, pd.d, pd.e, dc, workx, workz, vs, vz,
-                           refactor ? ds : nullptr, refactor ? dz : nullptr});
-    jvp_launches += 2;
-    if (refactor) {
-        if ((rc = chip_kkt_update_scaling_dev(kkt, ds, dz, 1.0, 0)) < 0) return rc;
-        rc = chip_kkt_update(kkt, nullptr);
-        jvp_syncs++;
-        jvp_launches += 2;
-        jvp_refactors++;
-        if (rc < 0) return rc;
-        if (rc != 1) return fail(CHIP_ERR_ZERO_PIVOT, "chip_bjvp_apply: the factorisation at the final iterate failed");
-        kkt_final = true;
-    }
-    if ((rc = chip_kkt_setrhs_dev(kkt, workx, workz))) return rc;
-    rc = chip_kkt_solve_dev(kkt, x1, z1);
-    jvp_syncs++;
-    jvp_launches++;
-    if (rc < 0) return rc;
-    if (rc != 1) return fail(CHIP_ERR_ZERO_PIVOT, "chip_bjvp_apply: the solve at the final iterate failed");
-    if ((rc = kktsystem_spmv(sys, 1, conicw, workz, -1.0, x1))) return rc; // E rz - A^ vx^
-    dev::bt_out(s, plan, dev::BtOut{t_valid, x1, z1, conicw, pd.d, pd.e, pd.einv, dc, t_dx, t_dz, t_ds});
-    jvp_launches += 2;
-    CHIP_HIP(hipGetLastError());
-    CHIP_HIP(hipStreamSynchronize(s));
-    jvp_syncs++;
-    jvp_done = true;
-    return CHIP_OK;
-}
-
-int32_t chip_bjvp_apply(chip_batch *h, const double *dq, const double *db, const double *dPx, const double *dAx) {
-    int rc = bg_ready(h, "chip_bjvp_apply");
-    if (rc) return rc;
-    CHIP_HIP(hipSetDevice(h->pd.device));
-    h->jvp_syncs = h->jvp_launches = 0;
-    if ((rc = h->jvp_work())) return rc;
-    const double *src[4] = {dq, db, dPx, dAx};
-    const size_t len[4] = {(size_t)h->pd.n, (size_t)h->pd.m, (size_t)h->pd.M.nnzP, (size_t)h->pd.M.nnzA};
-    const double *in[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < 4; i++) {
-        if (!src[i]) continue;
-        in[i] = h->t_in[i];
-        if (!len[i]) continue;
-        CHIP_HIP(hipMemcpyAsync(h->t_in[i], src[i], len[i] * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        h->jvp_launches++;
-    }
-    return h->jvp_apply(in[0], in[1], in[2], in[3]);
-}
-
-int32_t chip_bjvp_apply_dev(chip_batch *h, const double *dq_dev, const double *db_dev, const double *dPx_dev,
-                            const double *dAx_dev) {
-    int rc = bg_ready(h, "chip_bjvp_apply_dev");
-    if (rc) return rc;
-    CHIP_HIP(hipSetDevice(h->pd.device));
-    h->jvp_syncs = h->jvp_launches = 0;
-    if ((rc = h->jvp_work())) return rc;
-    return h->jvp_apply(dq_dev, db_dev, dPx_dev, dAx_dev);
-}
-
-int32_t chip_bjvp_get(chip_batch *h, double *dx, double *dz, double *ds, int32_t *valid) {
-    if (!h) return fail(CHIP_ERR_ARG, "chip_bjvp_get: bad argument");
-    if (!h->jvp_done) return fail(CHIP_ERR_ARG, "chip_bjvp_get: no chip_bjvp_apply since the last solve");
-    CHIP_HIP(hipSetDevice(h->pd.device));
-    if (dx && h->pd.n) CHIP_HIP(hipMemcpy(dx, h->t_dx, (size_t)h->pd.n * 8, hipMemcpyDeviceToHost));
-    if (dz && h->pd.m) CHIP_HIP(hipMemcpy(dz, h->t_dz, (size_t)h->pd.m * 8, hipMemcpyDeviceToHost));
-    if (ds && h->pd.m) CHIP_HIP(hipMemcpy(ds, h->t_ds, (size_t)h->pd.m * 8, hipMemcpyDeviceToHost));
-    if (valid) std::copy(h->tvalid.begin(), h->tvalid.end(), valid);
-    return CHIP_OK;
-}
-
-int32_t chip_bjvp_get_dev(chip_batch *h, double **dx_dev, double **dz_dev, double **ds_dev, int32_t **valid_dev) {
-    if (!h) return fail(CHIP_ERR_ARG, "chip_bjvp_get_dev: bad argument");
-    if (!h->jvp_done) return fail(CHIP_ERR_ARG, "chip_bjvp_get_dev: no chip_bjvp_apply since the last solve");
-    if (dx_dev) *dx_dev = h->t_dx;
-    if (dz_dev) *dz_dev = h->t_dz;
-    if (ds_dev) *ds_dev = h->t_ds;
-    if (valid_dev) *valid_dev = h->t_valid;
-    return CHIP_OK;
-}
-
-#ifdef CHIP_TESTING
-#include "../../include/clarabel_hip_testing.h"
-int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration) {
-    chip_batch *h = (chip_batch *)batch;
-    if (!h) return fail(CHIP_ERR_ARG, "chip_debug_batch_inject_nan: bad argument");
-    h->nan_member = member;
-    h->nan_iter = iteration;
-    return CHIP_OK;
-}
-int32_t chip_debug_batch_counter(void *batch, const char *name, double *out) {
-    chip_batch *h = (chip_batch *)batch;
-    if (!h || !name || !out) return fail(CHIP_ERR_ARG, "chip_debug_batch_counter: bad argument");
-    const std::string nm(name);
-    if (nm == "host_syncs") *out = (double)h->syncs;
-    else if (nm == "launches") *out = (double)h->launches;
-    else if (nm == "loop_iterations") *out = (double)h->loop_iters;
-    else if (nm == "update_launches") *out = (double)h->upd_launches;
-    else if (nm == "update_host_syncs") *out = (double)h->upd_syncs;
-    else if (nm == "backward_launches") *out = (double)h->grad_launches;
-    else if (nm == "backward_host_syncs") *out = (double)h->grad_syncs;
-    else if (nm == "jvp_launches") *out = (double)h->jvp_launches;
-    else if (nm == "jvp_host_syncs") *out = (double)h->jvp_syncs;
-    else if (nm == "jvp_refactors") *out = (double)h->jvp_refactors;
-    else return fail(CHIP_ERR_ARG, "chip_debug_batch_counter: unknown name");
-    return CHIP_OK;
-}
-
-// ---- the partition alone, and one launch of every launcher of batch.hpp on host arrays (tests/test_batch_plan_host.py,
-// tests/test_batch_passes_gpu.py).  The plan is the one chip_batch_create builds (host_plan_build / host_plan_upload)
-namespace {
-struct DebugPlan {
-    HostPlan hp;
-    DevPool mem;
-    dev::BatchPlan plan{};
-    bool uploaded = false;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    double *seg_scr = nullptr, *cone_scr = nullptr;
-    ~DebugPlan() {
-        if (stream) {
-            (void)hipStreamSynchronize(stream);
-            (void)hipStreamDestroy(stream);
-        }
-    }
-    int ready() { // the first runner uploads the plan; chip_debug_bplan_create itself touches no device
-        if (uploaded) {
-            CHIP_HIP(hipSetDevice(device));
-            return CHIP_OK;
-        }
-        if (chip_device_count() < 1) return fail(CHIP_ERR_NO_DEVICE, "chip_debug_bplan: no HIP device");
-        CHIP_HIP(hipGetDevice(&device));
-        int rc;
-        if ((rc = host_plan_upload(mem, hp, &plan)) || (rc = mem.alloc(&seg_scr, dev::seg_scratch_doubles(plan))) ||
-            (rc = mem.alloc(&cone_scr, dev::cone_scratch_doubles(plan))))
-            return rc;
-        CHIP_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        uploaded = true;
-        return CHIP_OK;
-    }
-};
-// the device buffers of one runner call: one per distinct host array (so operands that alias on the host alias on the
-// device), NULL stays NULL; out() arrays are uploaded too and copied back by finish()
-struct DebugStage {
-    DevPool mem;
-    struct Buf {
-        const void *host;
-        void *dev;
-        size_t bytes;
-        bool out;
-    };
-    std::vector<Buf> bufs;
-    template <typename T> int map(const T *host, size_t len, bool is_out, T **devp) {
-        *devp = nullptr;
-        if (!host) return CHIP_OK;
-        for (Buf &b : bufs)
-            if (b.host == (const void *)host) {
-                b.out = b.out || is_out;
-                *devp = (T *)b.dev;
-                return CHIP_OK;
-            }
-        int rc = mem.upload(devp, host, len);
-        if (rc) return rc;
-        bufs.push_back(Buf{host, *devp, len * sizeof(T), is_out});
-        return CHIP_OK;
-    }
-    template <typename T> int in(const T *host, size_t len, const T **devp) {
-        T *d;
-        int rc = map(host, len, false, &d);
-        *devp = d;
-        return rc;
-    }
-    template <typename T> int out(T *host, size_t len, T **devp) { return map(host, len, true, devp); }
-    int finish(hipStream_t s) {
-        CHIP_HIP(hipGetLastError());
-        CHIP_HIP(hipStreamSynchronize(s));
-        for (const Buf &b : bufs)
-            if (b.out && b.bytes) CHIP_HIP(hipMemcpy((void *)b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
-        return CHIP_OK;
-    }
-};
-} // namespace
-
-int32_t chip_debug_batch_jvp_rhs(void *batch, const double *x, const double *z, const int32_t *valid, const double *dq,
-                                 const double *db, const double *dPx, const double *dAx, double *rx, double *rz) {
-    chip_batch *h = (chip_batch *)batch;
-    if (!h || !valid || (h->pd.n && (!x || !rx)) || (h->pd.m && (!z || !rz)))
-        return fail(CHIP_ERR_ARG, "chip_debug_batch_jvp_rhs: bad argument");
-    CHIP_HIP(hipSetDevice(h->pd.device));
-    int rc;
-    dev::SpPattern Psym, Arow, Acol;
-    if ((rc = kktsystem_pattern(h->sys, 0, &Psym)) || (rc = kktsystem_pattern(h->sys, 1, &Arow)) ||
-        (rc = kktsystem_pattern(h->sys, 2, &Acol)))
-        return rc;
-    DebugStage st;
-    const size_t n = (size_t)h->pd.n, m = (size_t)h->pd.m;
-    const double *dx_, *dz_, *ddq, *ddb, *ddP, *ddA;
-    const int32_t *dvalid;
-    double *drx, *drz;
-    if ((rc = st.in(x, n, &dx_)) || (rc = st.in(z, m, &dz_)) || (rc = st.in(valid, (size_t)h->nprob, &dvalid)) ||
-        (rc = st.in(dq, n, &ddq)) || (rc = st.in(db, m, &ddb)) || (rc = st.in(dPx, (size_t)h->pd.M.nnzP, &ddP)) ||
-        (rc = st.in(dAx, (size_t)h->pd.M.nnzA, &ddA)) || (rc = st.out(rx, n, &drx)) || (rc = st.out(rz, m, &drz)))
-        return rc;
-    hipStream_t s = nullptr;
-    CHIP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    dev::bt_rhs(s, h->plan, Psym, Acol, Arow,
-                dev::BtRhs{dvalid, dx_, dz_, ddq, ddb, ddP, ddA, h->pd.d, h->pd.e, h->dc, drx, drz, nullptr, nullptr,
-                           nullptr, nullptr});
-    rc = st.finish(s);
-    (void)hipStreamDestroy(s);
-    return rc;
-}
-
-int32_t chip_debug_bplan_create(void **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t ncones,
-                                const int32_t *cone_tags, const int64_t *cone_dims) {
-    if (!out) return fail(CHIP_ERR_ARG, "chip_debug_bplan_create: bad argument");
-    *out = nullptr;
-    if (nprob < 1 || !n_part || !m_part || ncones < 0 || (ncones && (!cone_tags || !cone_dims)))
-        return fail(CHIP_ERR_ARG, "chip_debug_bplan_create: bad argument");
-    if (int rc = batch_cones_supported(ncones, cone_tags)) return rc;
-    if (nprob >= (1ll << 31)) return fail(CHIP_ERR_DIM, "chip_debug_bplan_create: sizes out of int32 range");
-    int64_t n = 0, m = 0;
-    for (int64_t k = 0; k < nprob; k++) {
-        if (n_part[k] < 0 || m_part[k] < 0) return fail(CHIP_ERR_ARG, "chip_debug_bplan_create: negative part");
-        n += n_part[k];
-        m += m_part[k];
-        if (n >= (1ll << 31) || m >= (1ll << 31) || n + 2 * m >= (1ll << 31))
-            return fail(CHIP_ERR_DIM, "chip_debug_bplan_create: sizes out of int32 range");
-    }
-    std::unique_ptr<DebugPlan> h(new DebugPlan());
-    std::vector<int64_t> dims2((size_t)ncones, 0);
-    if (int rc = host_plan_build(h->hp, nprob, n_part, m_part, n, m, ncones, cone_tags, cone_dims, dims2.data()))
-        return rc;
-    *out = h.release();
-    return CHIP_OK;
-}
-void chip_debug_bplan_destroy(void *h) { delete (DebugPlan *)h; }
-
-int32_t chip_debug_bplan_get(const void *handle, const char *name, int64_t *len, int32_t *out) {
-    const DebugPlan *h = (const DebugPlan *)handle;
-    if (!h || !name || !len) return fail(CHIP_ERR_ARG, "chip_debug_bplan_get: bad argument");
-    const HostPlan &hp = h->hp;
-    const std::string nm(name);
-    const std::vector<int> sizes{hp.nprob, hp.n, hp.m, hp.ncx, hp.ncz, (int)hp.it_beg.size()};
-    const std::vector<int> *v = nm == "sizes"      ? &sizes
-                                : nm == "xoff"     ? &hp.xoff
-                                : nm == "zoff"     ? &hp.zoff
-                                : nm == "xmem"     ? &hp.xmem
-                                : nm == "zmem"     ? &hp.zmem
-                                : nm == "ch_beg"   ? &hp.ch_beg
-                                : nm == "ch_end"   ? &hp.ch_end
-                                : nm == "cx_first" ? &hp.cx_first
-                                : nm == "cz_first" ? &hp.cz_first
-                                : nm == "it_beg"   ? &hp.it_beg
-                                : nm == "it_end"   ? &hp.it_end
-                                : nm == "it_type"  ? &hp.it_type
-                                : nm == "it_first" ? &hp.it_first
-                                : nm == "rtype"    ? &hp.rtype
-                                                   : nullptr;
-    if (!v) return fail(CHIP_ERR_ARG, "chip_debug_bplan_get: unknown name");
-    *len = (int64_t)v->size();
-    if (out && !v->empty()) std::memcpy(out, v->data(), v->size() * sizeof(int));
-    return CHIP_OK;
-}
-
-int32_t chip_debug_bplan_seg_reduce(void *handle, int32_t count, const int32_t *kind, const int32_t *space,
-                                    const int32_t *slot, const double *const *a, const double *const *b,
-                                    int32_t nslots, double *out) {
-    DebugPlan *h = (DebugPlan *)handle;
-    if (!h || count < 0 || count > dev::SEG_MAX || nslots < 0 || (count && (!kind || !space || !slot || !a || !b || !out)))
-        return fail(CHIP_ERR_ARG, "chip_debug_bplan_seg_reduce: bad argument");
-    for (int j = 0; j < count; j++)
-        if (kind[j] < dev::SEG_DOT || kind[j] > dev::SEG_NONFINITE || (space[j] != 0 && space[j] != 1) || slot[j] < 0 ||
-            slot[j] >= nslots || !a[j] || (!b[j] && (kind[j] == dev::SEG_DOT || kind[j] == dev::SEG_WSQ)))
-            return fail(CHIP_ERR_ARG, "chip_debug_bplan_seg_reduce: bad spec");
-    int rc;
-    if ((rc = h->ready())) return rc;
-    DebugStage st;
-    dev::SegBatch bt{};
-    bt.count = count;
-    for (int j = 0; j < count; j++) {
-        const size_t len = space[j] ? (size_t)h->hp.m : (size_t)h->hp.n;
-        const double *da, *db;
-        if ((rc = st.in(a[j], len, &da)) || (rc = st.in(b[j], len, &db))) return rc;
-        bt.s[j] = dev::SegSpec{da, db, kind[j], space[j], slot[j]};
-    }
-    double *dout;
-    if ((rc = st.out(out, (size_t)nslots * h->hp.nprob, &dout))) return rc;
-    dev::seg_reduce(h->stream, h->plan, bt, dout, h->seg_scr);
-    return st.finish(h->stream);
-}
-
-int32_t chip_debug_bplan_cone_minima(void *handle, int32_t op, const double *dz, const double *ds, const double *z,
-                                     const double *sv, const double *amax, double *out_min, double *out_sum_or_null) {
-    DebugPlan *h = (DebugPlan *)handle;
-    const bool step = op == dev::CONE_STEP;
-    if (!h || op < dev::CONE_STEP || op > dev::CONE_INTERIOR || !z || !out_min || (step && (!dz || !ds || !sv || !amax)) ||
-        (op == dev::CONE_INTERIOR && !sv))
-        return fail(CHIP_ERR_ARG, "chip_debug_bplan_cone_minima: bad argument");
-    int rc;
-    if ((rc = h->ready())) return rc;
-    DebugStage st;
-    const size_t m = (size_t)h->hp.m, np = (size_t)h->hp.nprob;
-    const double *ddz, *dds, *dzz, *dsv, *dam;
-    double *dmin, *dsum;
-    if ((rc = st.in(dz, m, &ddz)) || (rc = st.in(ds, m, &dds)) || (rc = st.in(z, m, &dzz)) || (rc = st.in(sv, m, &dsv)) ||
-        (rc = st.in(amax, np, &dam)) || (rc = st.out(out_min, np, &dmin)) || (rc = st.out(out_sum_or_null, np, &dsum)))
-        return rc;
-    dev::cone_minima(h->stream, h->plan, op, ddz, dds, dzz, dsv, dam, dmin, dsum, h->cone_scr);
-    return st.finish(h->stream);
-}
-
-int32_t chip_debug_bplan_blin(void *handle, double *w, const double *x, const double *y, const double *sa,
-                              const double *sb, double ca, double cb, int32_t space, const int32_t *mask,
-                              int32_t mask_mode) {
-    DebugPlan *h = (DebugPlan *)handle;
-    if (!h || !w || !x || (space != 0 && space != 1) || mask_mode < dev::MASK_ZERO || mask_mode > dev::MASK_KEEP ||
-        (mask && mask_mode == dev::MASK_Y && !y))
-        return fail(CHIP_ERR_ARG, "chip_debug_bplan_blin: bad argument");
-    int rc;
-    if ((rc = h->ready())) return rc;
-    DebugStage st;
-    const size_t len = space ? (size_t)h->hp.m : (size_t)h->hp.n, np = (size_t)h->hp.nprob;
-    double *dw;
-    const double *dx, *dy, *dsa, *dsb;
-    const int *dmask;
-    if ((rc = st.out(w, len, &dw)) || (rc = st.in(x, len, &dx)) || (rc = st.in(y, len, &dy)) ||
-        (rc = st.in(sa, np, &dsa)) || (rc = st.in(sb, np, &dsb)) || (rc = st.in((const int *)mask, np, &dmask)))
-        return rc;
-    dev::blin(h->stream, h->plan, dev::BLin{dw, dx, dy, dsa, dsb, ca, cb, space, dmask, mask_mode});
-    return st.finish(h->stream);
-}
-
-int32_t chip_debug_bplan_bresid(void *handle, double *rx, const double *rx_inf, const double *Px, const double *q,
-                                double *rz, const double *rz_inf, const double *b, const double *tau) {
-    DebugPlan *h = (DebugPlan *)handle;
-    if (!h || !rx || !rx_inf || !Px || !q || !rz || !rz_inf || !b || !tau)
-        return fail(CHIP_ERR_ARG, "chip_debug_bplan_bresid: bad argument");
-    int rc;
-    if ((rc = h->ready())) return rc;
-    DebugStage st;
-    const size_t n = (size_t)h->hp.n, m = (size_t)h->hp.m, np = (size_t)h->hp.nprob;
-    double *drx, *drz;
-    const double *drxi, *dPx, *dq, *drzi, *db, *dtau;
-    if ((rc = st.out(rx, n, &drx)) || (rc = st.in(rx_inf, n, &drxi)) || (rc = st.in(Px, n, &dPx)) ||
-        (rc = st.in(q, n, &dq)) || (rc = st.out(rz, m, &drz)) || (rc = st.in(rz_inf, m, &drzi)) ||
-        (rc = st.in(b, m, &db)) || (rc = st.in(tau, np, &dtau)))
-        return rc;
-    dev::bresid(h->stream, h->plan, drx, drxi, dPx, dq, drz, drzi, db, dtau);
-    return st.finish(h->stream);
-}
-
-int32_t chip_debug_bplan_bunit_shift(void *handle, double *z, const double *alpha, int32_t primal,
-                                     const int32_t *mask) {
-    DebugPlan *h = (DebugPlan *)handle;
-    if (!h || !z || !alpha) return fail(CHIP_ERR_ARG, "chip_debug_bplan_bunit_shift: bad argument");
-    int rc;
-    if ((rc = h->ready())) return rc;
-    DebugStage st;
-    double *dz;
-    const double *dal;
-    const int *dmask;
-    if ((rc = st.out(z, (size_t)h->hp.m, &dz)) || (rc = st.in(alpha, (size_t)h->hp.nprob, &dal)) ||
-        (rc = st.in((const int *)mask, (size_t)h->hp.nprob, &dmask)))
-        return rc;
-    dev::bunit_shift(h->stream, h->plan, dz, dal, primal, dmask);
-    return st.finish(h->stream);
-}
-
-int32_t chip_debug_bplan_bunit_reset(void *handle, double *x, double *sv, double *z, const int32_t *flag) {
-    DebugPlan *h = (DebugPlan *)handle;
-    if (!h || !x || !sv || !z || !flag) return fail(CHIP_ERR_ARG, "chip_debug_bplan_bunit_reset: bad argument");
-    int rc;
-    if ((rc = h->ready())) return rc;
-    DebugStage st;
-    double *dx, *dsv, *dz;
-    const int *dflag;
-    if ((rc = st.out(x, (size_t)h->hp.n, &dx)) || (rc = st.out(sv, (size_t)h->hp.m, &dsv)) ||
-        (rc = st.out(z, (size_t)h->hp.m, &dz)) || (rc = st.in((const int *)flag, (size_t)h->hp.nprob, &dflag)))
-        return rc;
-    dev::bunit_reset(h->stream, h->plan, dx, dsv, dz, dflag);
-    return st.finish(h->stream);
-}
-
-int32_t chip_debug_bplan_bunscale(void *handle, double *xo, const double *x, const double *d, double *zo,
-                                  const double *z, const double *e, double *so, const double *sv, const double *einv,
-                                  const double *sx, const double *sz) {
-    DebugPlan *h = (DebugPlan *)handle;
-    if (!h || !xo || !x || !d || !zo || !z || !e || !so || !sv || !einv || !sx || !sz)
-        return fail(CHIP_ERR_ARG, "chip_debug_bplan_bunscale: bad argument");
-    int rc;
-    if ((rc = h->ready())) return rc;
-    DebugStage st;
-    const size_t n = (size_t)h->hp.n, m = (size_t)h->hp.m, np = (size_t)h->hp.nprob;
-    double *dxo, *dzo, *dso;
-    const double *dx, *dd, *dz, *de, *dsv, *dei, *dsx, *dsz;
-    if ((rc = st.out(xo, n, &dxo)) || (rc = st.in(x, n, &dx)) || (rc = st.in(d, n, &dd)) || (rc = st.out(zo, m, &dzo)) ||
-        (rc = st.in(z, m, &dz)) || (rc = st.in(e, m, &de)) || (rc = st.out(so, m, &dso)) || (rc = st.in(sv, m, &dsv)) ||
-        (rc = st.in(einv, m, &dei)) || (rc = st.in(sx, np, &dsx)) || (rc = st.in(sz, np, &dsz)))
-        return rc;
-    dev::bunscale(h->stream, h->plan, dxo, dx, dd, dzo, dz, de, dso, dsv, dei, dsx, dsz);
-    return st.finish(h->stream);
-}
-#endif

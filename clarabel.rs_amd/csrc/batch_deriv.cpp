@@ -1,0 +1,233 @@
+// batch_deriv.cpp -- the derivative passes of the batched solver (chip_bgrad_*, chip_bjvp_*) on the handle of
+// batch_handle.hpp
+#include "batch_adjoint.hpp"
+#include "batch_handle.hpp"
+#include "batch_tangent.hpp"
+
+// ---------------------------------------------------------------------------------------------------------------
+// The derivatives of the members' solutions: the gradients (chip_bgrad_*) and their exact transpose,
+// the forward-mode derivatives (chip_bjvp_*).  Either is ONE refined KKT solve at the final iterates
+// with K = [P A'; A -H], H = diag(s / z) on Nonnegative rows and 0 on Zero rows: the matrix chip_kkt factors after a
+// scaling update with (s, z) of the internal iterate (tau cancels), in the equilibrated space of the stack
+// (x = D x^, z = E z^ / c_k, s = E^-1 s^; P^ = c_k D P D, q^ = c_k D q, A^ = E A D, b^ = E b).  The steps below are
+// shared; a pass itself is what differs mathematically: its right-hand side, its product with A' or A, its outputs.
+// A derivative exists for the members that ended Solved and own only Zero / Nonnegative cones; every other member
+// takes the cones' unit vector for (s, z), as a member that ended NumericalError does in the loop, and a zero
+// right-hand side: its block of K stays well posed and its part of the solution is 0.
+// Enqueues are counted as batch.cpp counts them everywhere (one per kernel, copy or call into the KKT layer, whatever
+// that call launches itself); the synchronisations are chip_kkt_update's, chip_kkt_solve_dev's and one at the end.
+// A pass overwrites work vectors and its own results only; chip_batch_solve starts from default_start, which rescales
+// and refactors, so a following solve does not see it.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+typedef DerivPass chip_batch::*PassOf;
+
+int deriv_alloc(chip_batch *h, DerivPass &p, std::initializer_list<size_t> in_len,
+                std::initializer_list<size_t> out_len) {
+    if (p.valid) return CHIP_OK;
+    p.nin = (int)in_len.size();
+    p.nout = (int)out_len.size();
+    std::copy(in_len.begin(), in_len.end(), p.in_len);
+    std::copy(out_len.begin(), out_len.end(), p.out_len);
+    p.hvalid.assign((size_t)h->nprob, 0);
+    int rc = CHIP_OK;
+    for (int i = 0; i < p.nout && !rc; i++) rc = h->mem.alloc(&p.out[i], p.out_len[i]);
+    for (int i = 0; i < p.nin && !rc; i++) rc = h->mem.alloc(&p.in[i], p.in_len[i]);
+    return rc ? rc : h->mem.alloc(&p.valid, (size_t)h->nprob); // (last: it marks the allocation as done)
+}
+
+// the start of a pass's entry point `fn`: refused without a finished solve on the current data
+int deriv_begin(chip_batch *h, const char *fn, PassOf which, int (chip_batch::*work)()) {
+    if (!h) return fail(CHIP_ERR_ARG, std::string(fn) + ": bad argument");
+    if (!h->solve_current)
+        return fail(CHIP_ERR_ARG, std::string(fn) + ": needs a finished chip_batch_solve on the current data");
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    (h->*which).syncs = (h->*which).launches = 0;
+    return (h->*work)();
+}
+
+// the host form: a NULL input stays NULL, a given one becomes its staging buffer (one copy, none for an empty input)
+int deriv_stage(chip_batch *h, DerivPass &p, const double **in) {
+    for (int i = 0; i < p.nin; i++) {
+        const double *src = in[i];
+        if (!src) continue;
+        in[i] = p.in[i];
+        if (!p.in_len[i]) continue;
+        CHIP_HIP(hipMemcpyAsync(p.in[i], src, p.in_len[i] * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        p.launches++;
+    }
+    return CHIP_OK;
+}
+
+int deriv_valid(chip_batch *h, DerivPass &p) {
+    for (int k = 0; k < h->nprob; k++) p.hvalid[k] = h->info[k].status == CHIP_SOLVER_SOLVED && !h->has_soc[k];
+    CHIP_HIP(hipMemcpyAsync(p.valid, p.hvalid.data(), (size_t)h->nprob * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    p.launches++;
+    return CHIP_OK;
+}
+
+// K at the final iterates: the scaling update with the (s, z) the right-hand side pass left in (ds, dz), the refactor
+int deriv_factor(chip_batch *h, DerivPass &p) {
+    int rc;
+    h->kkt_final = false; // (a refactor that fails leaves nothing to reuse)
+    if ((rc = chip_kkt_update_scaling_dev(h->kkt, h->ds, h->dz, 1.0, 0)) < 0) return rc;
+    rc = chip_kkt_update(h->kkt, nullptr);
+    p.syncs++;
+    p.launches += 2;
+    p.refactors++;
+    if (rc < 0) return rc;
+    if (rc != 1)
+        return fail(CHIP_ERR_ZERO_PIVOT, std::string(p.name) + ": the factorisation at the final iterate failed");
+    h->kkt_final = true; // (an apply after this solves with this factorisation)
+    return CHIP_OK;
+}
+
+// [x1; z1] = K^-1 [workx; workz], refined
+int deriv_solve(chip_batch *h, DerivPass &p) {
+    int rc;
+    if ((rc = chip_kkt_setrhs_dev(h->kkt, h->workx, h->workz))) return rc;
+    rc = chip_kkt_solve_dev(h->kkt, h->x1, h->z1);
+    p.syncs++;
+    p.launches++;
+    if (rc < 0) return rc;
+    if (rc != 1) return fail(CHIP_ERR_ZERO_PIVOT, std::string(p.name) + ": the solve at the final iterate failed");
+    return CHIP_OK;
+}
+
+int deriv_end(chip_batch *h, DerivPass &p) {
+    CHIP_HIP(hipGetLastError());
+    CHIP_HIP(hipStreamSynchronize(h->stream));
+    p.syncs++;
+    p.done = true;
+    return CHIP_OK;
+}
+
+// the read-outs of entry point `fn`: refused without a pass since the last solve
+int deriv_result(chip_batch *h, const char *fn, PassOf which) {
+    if (!h) return fail(CHIP_ERR_ARG, std::string(fn) + ": bad argument");
+    if (!(h->*which).done)
+        return fail(CHIP_ERR_ARG, std::string(fn) + ": no " + (h->*which).name + " since the last solve");
+    return CHIP_OK;
+}
+
+int deriv_get(chip_batch *h, const char *fn, PassOf which, std::initializer_list<double *> dst, int32_t *valid) {
+    if (int rc = deriv_result(h, fn, which)) return rc;
+    const DerivPass &p = h->*which;
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    for (int i = 0; i < p.nout; i++)
+        if (dst.begin()[i] && p.out_len[i])
+            CHIP_HIP(hipMemcpy(dst.begin()[i], p.out[i], p.out_len[i] * 8, hipMemcpyDeviceToHost));
+    if (valid) std::copy(p.hvalid.begin(), p.hvalid.end(), valid);
+    return CHIP_OK;
+}
+
+int deriv_get_dev(chip_batch *h, const char *fn, PassOf which, std::initializer_list<double **> dst,
+                  int32_t **valid_dev) {
+    if (int rc = deriv_result(h, fn, which)) return rc;
+    const DerivPass &p = h->*which;
+    for (int i = 0; i < p.nout; i++)
+        if (dst.begin()[i]) *dst.begin()[i] = p.out[i];
+    if (valid_dev) *valid_dev = p.valid;
+    return CHIP_OK;
+}
+} // namespace
+
+// ---- the gradients.  With the incoming gradients (gx, gz, gs) of a member's unscaled (x, z, s), its adjoint is
+//     [vx; vz] = K^-1 [gx - A' gs; gz].
+// In the equilibrated space the incoming gradients are D gx, E gz / c_k and E^-1 gs; the solution multiplied back,
+// ux = c_k D vx^ and uz = E vz^, is the adjoint pair of the unscaled problem, so the four gradients are the unscaled
+// formulas on the unscaled solution the solve has already written (xo, zo).  A backward always refactors
+int chip_batch::backward_work() {
+    const size_t n = (size_t)pd.n, m = (size_t)pd.m;
+    return deriv_alloc(this, grad, {n, m, m}, {n, m, (size_t)pd.M.nnzP, (size_t)pd.M.nnzA});
+}
+
+int chip_batch::backward(const double *gx, const double *gz, const double *gs) {
+    int rc;
+    grad.done = false; // (a backward that fails part-way leaves no result behind)
+    if ((rc = deriv_valid(this, grad))) return rc;
+    dev::ba_rhs(stream, plan, dev::BaRhs{grad.valid, gx, gz, gs, pd.d, pd.e, dc, vs, vz, wn, conicw, workz, ds, dz});
+    grad.launches++;
+    if ((rc = kktsystem_spmv(sys, 2, workx, wn, -1.0, conicw))) return rc; // D gx - A^' (gs / e)
+    grad.launches++;
+    if ((rc = deriv_factor(this, grad)) || (rc = deriv_solve(this, grad))) return rc;
+    double *const *o = grad.out; // dq, db, dP, dA
+    const dev::BaGrad g{grad.valid, x1, z1, gs, pd.d, pd.e, dc, xo, zo, x2, z2, o[0], o[1], o[2], o[3]};
+    dev::ba_grad_vectors(stream, plan, g);
+    dev::ba_grad_matrices(stream, plan, pd.M, g);
+    grad.launches += 2;
+    return deriv_end(this, grad);
+}
+
+int32_t chip_bgrad_backward(chip_batch *h, const double *gx, const double *gz, const double *gs) {
+    const double *in[3] = {gx, gz, gs};
+    int rc = deriv_begin(h, "chip_bgrad_backward", &chip_batch::grad, &chip_batch::backward_work);
+    if (rc || (rc = deriv_stage(h, h->grad, in))) return rc;
+    return h->backward(in[0], in[1], in[2]);
+}
+
+int32_t chip_bgrad_backward_dev(chip_batch *h, const double *gx_dev, const double *gz_dev, const double *gs_dev) {
+    const int rc = deriv_begin(h, "chip_bgrad_backward_dev", &chip_batch::grad, &chip_batch::backward_work);
+    return rc ? rc : h->backward(gx_dev, gz_dev, gs_dev);
+}
+
+int32_t chip_bgrad_get(chip_batch *h, double *dq, double *db, double *dPx, double *dAx, int32_t *valid) {
+    return deriv_get(h, "chip_bgrad_get", &chip_batch::grad, {dq, db, dPx, dAx}, valid);
+}
+
+int32_t chip_bgrad_get_dev(chip_batch *h, double **dq_dev, double **db_dev, double **dPx_dev, double **dAx_dev,
+                           int32_t **valid_dev) {
+    return deriv_get_dev(h, "chip_bgrad_get_dev", &chip_batch::grad, {dq_dev, db_dev, dPx_dev, dAx_dev}, valid_dev);
+}
+
+// ---- the tangents.  Along a direction (dq, db, dP, dA) in a member's data its solution moves by
+//     rx = -(dq + dP_sym x + dA' z),  rz = db - dA x,  [dx; dz] = K^-1 [rx; rz],  ds = rz - A dx (Nonnegative rows).
+// In the equilibrated space the system is K^ [D^-1 dx; c_k E^-1 dz] = [c_k D rx; E rz] with rx, rz formed from the
+// unscaled solution (xo, zo), so dx = D vx^, dz = E vz^ / c_k and ds = E^-1 (E rz - A^ vx^): the transposes of
+// backward's scalings.  An apply refactors only when K is not factored at the final iterates already (kkt_final: set
+// by a backward or an apply, cleared by an update and at the start of a solve)
+int chip_batch::jvp_work() {
+    const size_t n = (size_t)pd.n, m = (size_t)pd.m;
+    return deriv_alloc(this, tan, {n, m, (size_t)pd.M.nnzP, (size_t)pd.M.nnzA}, {n, m, m});
+}
+
+int chip_batch::jvp_apply(const double *dq, const double *db, const double *dP, const double *dA) {
+    int rc;
+    tan.done = false; // (an apply that fails part-way leaves no result behind)
+    dev::SpPattern Psym, Arow, Acol;
+    if ((rc = kktsystem_pattern(sys, 0, &Psym)) || (rc = kktsystem_pattern(sys, 1, &Arow)) ||
+        (rc = kktsystem_pattern(sys, 2, &Acol)) || (rc = deriv_valid(this, tan)))
+        return rc;
+    const bool refactor = !kkt_final;
+    dev::bt_rhs(stream, plan, Psym, Acol, Arow,
+                dev::BtRhs{tan.valid, xo, zo, dq, db, dP, dA, pd.d, pd.e, dc, workx, workz, vs, vz,
+                           refactor ? ds : nullptr, refactor ? dz : nullptr});
+    tan.launches++;
+    if ((refactor && (rc = deriv_factor(this, tan))) || (rc = deriv_solve(this, tan))) return rc;
+    if ((rc = kktsystem_spmv(sys, 1, conicw, workz, -1.0, x1))) return rc; // E rz - A^ vx^
+    double *const *o = tan.out; // dx, dz, ds
+    dev::bt_out(stream, plan, dev::BtOut{tan.valid, x1, z1, conicw, pd.d, pd.e, pd.einv, dc, o[0], o[1], o[2]});
+    tan.launches += 2;
+    return deriv_end(this, tan);
+}
+
+int32_t chip_bjvp_apply(chip_batch *h, const double *dq, const double *db, const double *dPx, const double *dAx) {
+    const double *in[4] = {dq, db, dPx, dAx};
+    int rc = deriv_begin(h, "chip_bjvp_apply", &chip_batch::tan, &chip_batch::jvp_work);
+    if (rc || (rc = deriv_stage(h, h->tan, in))) return rc;
+    return h->jvp_apply(in[0], in[1], in[2], in[3]);
+}
+
+int32_t chip_bjvp_apply_dev(chip_batch *h, const double *dq_dev, const double *db_dev, const double *dPx_dev,
+                            const double *dAx_dev) {
+    const int rc = deriv_begin(h, "chip_bjvp_apply_dev", &chip_batch::tan, &chip_batch::jvp_work);
+    return rc ? rc : h->jvp_apply(dq_dev, db_dev, dPx_dev, dAx_dev);
+}
+
+int32_t chip_bjvp_get(chip_batch *h, double *dx, double *dz, double *ds, int32_t *valid) {
+    return deriv_get(h, "chip_bjvp_get", &chip_batch::tan, {dx, dz, ds}, valid);
+}
+
+int32_t chip_bjvp_get_dev(chip_batch *h, double **dx_dev, double **dz_dev, double **ds_dev, int32_t **valid_dev) {
+    return deriv_get_dev(h, "chip_bjvp_get_dev", &chip_batch::tan, {dx_dev, dz_dev, ds_dev}, valid_dev);
+}
