@@ -1933,6 +1933,29 @@ def debug_kkt_ints(kkt, name):
     return out
 
 
+def debug_factor_updates(kkt, bundle, what):
+    """test hook: the update records of the flat bundle factorisation of one bundle of a host-only HipKKTSolver
+    (include/clarabel_hip_testing.h: chip_debug_factor_updates): "records" / "leftover" as rows {level, a, b, k, target},
+    "runs" as rows {level, first a, b, k, target, strides of a, b, k, target, count}"""
+    n = C.c_int64(0)
+    f = lib().chip_debug_factor_updates
+    f.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.POINTER(C.c_int64), C.c_void_p]
+    _check(f(kkt._h, int(bundle), what.encode(), C.byref(n), None), "debug_factor_updates")
+    out = np.zeros(n.value, dtype=np.int32)
+    _check(f(kkt._h, int(bundle), what.encode(), C.byref(n), out.ctypes.data_as(C.c_void_p)), "debug_factor_updates")
+    return out.reshape(-1, 10 if what == "runs" else 5)
+
+
+def debug_kkt_factors(kkt):
+    """test hook: (Lx, D) of a HipKKTSolver as its last refactor left them (permuted numbering, CSC order of symbolic())"""
+    nnzL = int(kkt.linear_solver_info().nnzL)
+    Lx, D = np.zeros(max(nnzL, 1)), np.zeros(kkt.N)
+    f = lib().chip_debug_kkt_factors
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(f(kkt._h, Lx.ctypes.data_as(C.c_void_p), D.ctypes.data_as(C.c_void_p)), "debug_kkt_factors")
+    return Lx[:nnzL], D
+
+
 def set_device(ordinal):
     """hipSetDevice for this thread (one process per GPU: the rank's local device)"""
     rc = _hiprt().hipSetDevice(C.c_int(int(ordinal)))

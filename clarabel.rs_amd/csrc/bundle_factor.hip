@@ -753,6 +753,74 @@ __global__ __launch_bounds__(FLWG) void k_bundle_factor_lds(LdlView v, BundleVie
 // diagonal rows, per level the records and the columns' pointers, a closing pass over Lp -> Li16 for the top row's
 // share): ~43 us per workgroup for 300 KB, two rounds of workgroups per launch.  The single folded top row's pivot
 // share sum l_tc^2 d_c now arrives through the records as well (target nE + nloc, symbolic.cpp), no closing pass.
+// ---- phases that the two entry-parallel kernels below share (k_bundle_factor_flat, k_bundle_factor_runs) ----
+// diagnostics (CHIP_IR_DEBUG=3): phase boundaries of every workgroup on the 100 MHz clock
+__device__ __forceinline__ void ff_stamp(const BundleView &bv, int b, int tid, int &dbgn) {
+    if (bv.fdbg && tid == 0 && dbgn < 31) {
+        if (dbgn == 0)
+            bv.fdbg[(size_t)b * 32] = (long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 4) |
+                                      ((long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 20) << 32);
+        bv.fdbg[(size_t)b * 32 + 1 + dbgn++] = wall_clock64();
+    }
+}
+// one pass of U entries (slot | row << 16, value) to their slots: 0xFFFF = the diagonal of that row, 0xFFFE = nothing
+template <int UF>
+__device__ __forceinline__ void ff_scatter_u(double *Ls, double *Ds, const unsigned (&usr)[UF], const double (&uval)[UF]) {
+#pragma unroll
+    for (int q = 0; q < UF; ++q) {
+        const unsigned slot = usr[q] & 0xFFFFu;
+        if (slot == 0xFFFFu) Ds[usr[q] >> 16] = uval[q];
+        else if (slot != 0xFFFEu) Ls[slot] = uval[q];
+    }
+}
+// static regularisation of the diagonal (directldlkktsolver.rs:217-250), before any update lands on it
+template <int CPT>
+__device__ __forceinline__ void ff_static_reg(double *Ds, unsigned csgm, int nloc, double eps, int tid, int wg) {
+#pragma unroll
+    for (int q = 0; q < CPT; ++q) {
+        const int j = tid + q * wg;
+        if (j < nloc) Ds[j] = ((csgm >> q) & 1u) ? Ds[j] + eps : Ds[j] - eps;
+    }
+}
+// the columns lb .. le of a level are final: pivot rule (qdldl.rs:645-665), scale -- the thread's own columns of this level
+// (column = first slot | length << 16, signs as a bit mask; D and 1 / D leave in one coalesced pass at the end)
+template <int CPT>
+__device__ __forceinline__ void ff_level_pivots(const LdlView &v, double *Ls, double *Ds, const unsigned (&ccol)[CPT], unsigned csgm,
+                                                int lb, int le, int tid, int wg) {
+#pragma unroll
+    for (int q = 0; q < CPT; ++q) {
+        const int j = tid + q * wg;
+        if (j >= lb && j < le) {
+            double d = Ds[j];
+            const double sign = ((csgm >> q) & 1u) ? 1.0 : -1.0;
+            if (d * sign < v.reg_eps) {
+                d = v.reg_delta * sign;
+                atomicAdd(&v.status[2], 1); // rare
+            }
+            if (d == 0.0) v.status[1] = 1;
+            const double dinv = 1.0 / d;
+            if (!isfinite(dinv)) v.status[0] = 1;
+            Ds[j] = d;
+            const int cb = (int)(ccol[q] & 0xFFFFu), cn = (int)(ccol[q] >> 16);
+            for (int t = cb; t < cb + cn; ++t) Ls[t] *= dinv;
+        }
+    }
+}
+// the single folded top row's pivot share (collected in Ds[nloc] as its negative; k_fold_top_pivot applies the pivot
+// rule), then L, D and 1 / D to memory, coalesced
+__device__ __forceinline__ void ff_write_out(const LdlView &v, const FoldView &fold, const double *Ls, const double *Ds, int b, int s0,
+                                             int nloc, int e0, int nE, int tid, int wg) {
+    if (fold.k == 1 && tid == 0) {
+        const double sacc = -Ds[nloc];
+        if (sacc != 0.0) atomicAdd(&fold.acc[fold_acc_index(2, 0, b % FOLD_SLOTS)], sacc);
+    }
+    for (int q = tid; q < nE; q += wg) v.Lx[e0 + q] = Ls[q];
+    for (int j = tid; j < nloc; j += wg) {
+        const double d = Ds[j];
+        v.D[s0 + j] = d;
+        v.Dinv[s0 + j] = 1.0 / d;
+    }
+}
 template <int CPT>
 __global__ __launch_bounds__(FFWG) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_bundle_factor_flat(LdlView v, BundleView bv, FoldView fold) {
     extern __shared__ __attribute__((aligned(16))) char ff_smem[];
@@ -768,14 +836,7 @@ __global__ __launch_bounds__(FFWG) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     constexpr int FU = 8; // records in flight per thread
     constexpr int UF = 8; // U entries per thread and pass
     int dbgn = 0;
-    auto stamp = [&]() { // diagnostics (CHIP_IR_DEBUG=3): phase boundaries of every workgroup on the 100 MHz clock
-        if (bv.fdbg && tid == 0 && dbgn < 31) {
-            if (dbgn == 0)
-                bv.fdbg[(size_t)b * 32] = (long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 4) |
-                                          ((long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 20) << 32);
-            bv.fdbg[(size_t)b * 32 + 1 + dbgn++] = wall_clock64();
-        }
-    };
+    auto stamp = [&]() { ff_stamp(bv, b, tid, dbgn); };
     stamp();
     // ---- requests: own columns, first pass of U entries, first batch of records ----
     // (packed: 64 registers per thread -- two workgroups per CU -- must hold all of it: column = first slot | length << 16,
@@ -823,12 +884,7 @@ __global__ __launch_bounds__(FFWG) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     const double eps = s_eps;
     // ---- initial values: the U entries to their slots ----
     for (int ubase = ub;;) {
-#pragma unroll
-        for (int q = 0; q < UF; ++q) {
-            const unsigned slot = usr[q] & 0xFFFFu;
-            if (slot == 0xFFFFu) Ds[usr[q] >> 16] = uval[q];
-            else if (slot != 0xFFFEu) Ls[slot] = uval[q];
-        }
+        ff_scatter_u<UF>(Ls, Ds, usr, uval);
         ubase += UF * FFWG;
         if (ubase >= ue) break;
         request_u(ubase);
@@ -836,34 +892,10 @@ __global__ __launch_bounds__(FFWG) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     request(base); // (the first batch of records: in flight under the regulariser pass and the first level's pivots)
     lds_barrier();
     stamp();
-    if (eps_on) { // static regularisation of the diagonal (directldlkktsolver.rs:217-250), before any update lands on it
-#pragma unroll
-        for (int q = 0; q < CPT; ++q) {
-            const int j = tid + q * FFWG;
-            if (j < nloc) Ds[j] = ((csgm >> q) & 1u) ? Ds[j] + eps : Ds[j] - eps;
-        }
-    }
+    if (eps_on) ff_static_reg<CPT>(Ds, csgm, nloc, eps, tid, FFWG);
     for (int l = 0; l < nl; ++l) {
-        // the level's columns are final: pivot rule (qdldl.rs:645-665), scale -- the thread's own columns of this level
         const int lb = lv[l] - s0, le = lv[l + 1] - s0;
-#pragma unroll
-        for (int q = 0; q < CPT; ++q) {
-            const int j = tid + q * FFWG;
-            if (j >= lb && j < le) {
-                double d = Ds[j];
-                const double sign = ((csgm >> q) & 1u) ? 1.0 : -1.0;
-                if (d * sign < v.reg_eps) {
-                    d = v.reg_delta * sign;
-                    atomicAdd(&v.status[2], 1); // rare
-                }
-                if (d == 0.0) v.status[1] = 1;
-                const double dinv = 1.0 / d;
-                if (!isfinite(dinv)) v.status[0] = 1;
-                Ds[j] = d; // (D and 1 / D leave in one coalesced pass at the end)
-                const int cb = (int)(ccol[q] & 0xFFFFu), cn = (int)(ccol[q] >> 16);
-                for (int t = cb; t < cb + cn; ++t) Ls[t] *= dinv;
-            }
-        }
+        ff_level_pivots<CPT>(v, Ls, Ds, ccol, csgm, lb, le, tid, FFWG);
         lds_barrier();
         stamp();
         const int rb = tp[l], re = tp[l + 1];
@@ -890,18 +922,137 @@ __global__ __launch_bounds__(FFWG) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         lds_barrier();
         stamp();
     }
-    if (fold.k == 1 && tid == 0) {
-        // a single dense top row: d_t -= sum l_tc^2 d_c over this bundle's columns -- collected by the records of the
-        // (top, top) pairs in Ds[nloc] (as its negative); k_fold_top_pivot applies the pivot rule
-        const double sacc = -Ds[nloc];
-        if (sacc != 0.0) atomicAdd(&fold.acc[fold_acc_index(2, 0, b % FOLD_SLOTS)], sacc);
+    ff_write_out(v, fold, Ls, Ds, b, s0, nloc, e0, nE, tid, FFWG);
+    stamp();
+    static_eps_epilogue(v, eps);
+}
+// ---------------------------------------------------------------------------
+// The same factorisation over RUN-CODED records (host.hpp: Symbolic::fr_desc).  The records of a level are almost all
+// members of a few affine runs (config 3: 10 runs cover 10 000 of a bundle's 10 007 records), so 80 KB of records per
+// bundle become a few 32-byte descriptors, and a record's ~40 instructions (two thirds of them slot unpacking and the
+// wave-uniform-target test of lds_scatter_add) become ~10 per run element: addresses are first + stride * e, a run
+// with target stride 0 is known to be a reduction, any other has distinct targets.  Per level: the descriptors, then
+// the level's records outside runs in the 8-byte record format, one per thread (the launcher takes this kernel only
+// where no bundle has more than FFWG of them and more than 4 FFWG nodes).
+// A kernel of its own, not a branch of k_bundle_factor_flat: beside the 8-record batch the run loop spills (68 B of
+// scratch against 44), without the batch it needs no scratch.
+// No index table is loaded through another: the prologue is ONE trip for the bundle's record (host.hpp: fr_bdesc, 64
+// ints, one per lane, fields picked by v_readlane) where k_bundle_factor_flat walks bundle_ptr -> Lp / Up / blvl_ptr ->
+// blvl / fu_ptr; the run descriptors travel the same way, 8 per vector register, the next 8 requested a chunk ahead.
+// Everything but the values of K is read from one copy per class of identical bundles (host.hpp: fc_usr, fc_col,
+// fc_sgn, the descriptors, the records), in the packed form the registers hold.
+// A level's runs are dealt to the waves: with G runs in a level, wave w takes run w mod G together with the other
+// waves of that residue, so a reduction run costs one wave sum per wave that works on it -- 16 per level instead of
+// 16 per run (config 3, level 2: six reductions of 1000).
+// ---------------------------------------------------------------------------
+constexpr int RCPT = 4; // columns per thread: bundles of up to 4 FFWG nodes
+__global__ __launch_bounds__(FFWG) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_bundle_factor_runs(LdlView v, BundleView bv, FoldView fold) {
+    extern __shared__ __attribute__((aligned(16))) char ff_smem[];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr int NW = FFWG / 64;
+    const int bd = v.fr_bdesc[(size_t)b * 64 + lane]; // the bundle's record
+    auto field = [&](int i) { return __builtin_amdgcn_readlane(bd, i); };
+    const int s0 = field(0), nloc = field(1), e0 = field(2), nE = field(3), ub = field(4), ue = field(5), nl = field(6);
+    const int uo = field(7), co = field(62); // where the bundle's class starts in the shared arrays
+    double *Ls = (double *)ff_smem, *Ds = Ls + nE; // (contiguous: a target addresses either; Ds[nloc]: the top row's share)
+    typedef unsigned short fu_v4 __attribute__((ext_vector_type(4)));
+    const fu_v4 *rec = (const fu_v4 *)v.fr_rec;
+    constexpr int UF = 8; // U entries per thread and pass
+    int dbgn = 0;
+    auto stamp = [&]() { ff_stamp(bv, b, tid, dbgn); };
+    stamp();
+    // ---- requests: own columns, first pass of U entries, the first two chunks of descriptors, the records ----
+    unsigned ccol[RCPT];
+    unsigned csgm = 0;
+#pragma unroll
+    for (int q = 0; q < RCPT; ++q) {
+        const int j = tid + q * FFWG;
+        const bool ok = j < nloc;
+        ccol[q] = ok ? v.fc_col[co + j] : 0u;
+        if (ok && v.fc_sgn[co + j] == 1) csgm |= 1u << q;
     }
-    for (int q = tid; q < nE; q += FFWG) v.Lx[e0 + q] = Ls[q];
-    for (int j = tid; j < nloc; j += FFWG) {
-        const double d = Ds[j];
-        v.D[s0 + j] = d;
-        v.Dinv[s0 + j] = 1.0 / d;
+    unsigned usr[UF];
+    double uval[UF];
+    auto request_u = [&](int base) {
+#pragma unroll
+        for (int q = 0; q < UF; ++q) {
+            const int u = base + q * FFWG + tid;
+            const bool ok = u < ue;
+            usr[q] = ok ? v.fc_usr[uo + (u - ub)] : 0xFFFEu; // (slot 0xFFFE: nothing)
+            uval[q] = ok ? v.Ux[u] : 0.0;
+        }
+    };
+    request_u(ub);
+    const int dend = field(44 + nl);
+    auto request_desc = [&](int first) { // descriptors first .. first + 8: int `lane` of the 64
+        const int i = first * 8 + lane;
+        return i < dend * 8 ? v.fr_desc[i] : 0;
+    };
+    int dbase = field(44);
+    int dcur = request_desc(dbase), dnxt = request_desc(dbase + 8);
+    const int rbase = field(26), rend = field(26 + nl); // (at most FFWG records outside runs: thread tid holds record rbase + tid)
+    const fu_v4 r = rbase + tid < rend ? rec[rbase + tid] : fu_v4{0, 0, 0, 0xFFFF};
+    bool eps_on;
+    __shared__ double s_eps;
+    (void)static_eps(v, &eps_on, &s_eps);
+    for (int q = tid; q <= nE + nloc; q += FFWG) Ls[q] = 0.0; // (fill-in slots stay zero; Ds[nloc] collects the top row's share)
+    lds_barrier();
+    stamp();
+    const double eps = s_eps;
+    // ---- initial values: the U entries to their slots ----
+    for (int ubase = ub;;) {
+        ff_scatter_u<UF>(Ls, Ds, usr, uval);
+        ubase += UF * FFWG;
+        if (ubase >= ue) break;
+        request_u(ubase);
     }
+    lds_barrier();
+    stamp();
+    if (eps_on) ff_static_reg<RCPT>(Ds, csgm, nloc, eps, tid, FFWG);
+    for (int l = 0; l < nl; ++l) {
+        const int lb = field(8 + l), le = field(9 + l);
+        ff_level_pivots<RCPT>(v, Ls, Ds, ccol, csgm, lb, le, tid, FFWG);
+        lds_barrier();
+        stamp();
+        // ---- the level's runs, G = min(runs left in the chunk, waves) at a time: wave wv takes run wv mod G ----
+        const int d1 = field(45 + l);
+        for (int d = field(44 + l); d < d1;) {
+            if (d >= dbase + 8) { // (wave-uniform: the next chunk was requested while this one was walked)
+                dcur = dnxt;
+                dbase += 8;
+                dnxt = request_desc(dbase + 8);
+            }
+            const int G = min(min(d1, dbase + 8) - d, NW);
+            const int g = wv % G, part = wv / G, parts = (NW - g + G - 1) / G; // this wave: part `part` of `parts` of run d + g
+            const int o = (d + g - dbase) * 8;
+            const int a0 = __builtin_amdgcn_readlane(dcur, o), b0 = __builtin_amdgcn_readlane(dcur, o + 1);
+            const int k0 = __builtin_amdgcn_readlane(dcur, o + 2), t0 = __builtin_amdgcn_readlane(dcur, o + 3);
+            const int sab = __builtin_amdgcn_readlane(dcur, o + 4), skt = __builtin_amdgcn_readlane(dcur, o + 5);
+            const int cnt = __builtin_amdgcn_readlane(dcur, o + 6);
+            const int sa = (int)(short)(sab & 0xFFFF), sb = sab >> 16, sk = (int)(short)(skt & 0xFFFF), st = skt >> 16;
+            if (st != 0) { // distinct targets (another run of the level may hit them too: atomics)
+                for (int e = part * 64 + lane; e < cnt; e += parts * 64)
+                    atomicAdd(&Ls[t0 + st * e], -(Ls[a0 + sa * e] * (Ls[b0 + sb * e] * Ds[k0 + sk * e])));
+            } else if (part * 64 < cnt) { // a reduction onto one slot: the pivot or a coupling entry of a separator column
+                double sum = 0.0;
+                for (int e = part * 64 + lane; e < cnt; e += parts * 64) sum += Ls[a0 + sa * e] * (Ls[b0 + sb * e] * Ds[k0 + sk * e]);
+                sum = wave_sum_all(sum);
+                if (lane == 0) atomicAdd(&Ls[t0], -sum);
+            }
+            d += G;
+        }
+        // ---- ... and its records outside runs ----
+        {
+            const int t = rbase + tid;
+            const bool ok = t >= field(26 + l) && t < field(27 + l);
+            const double val = ok ? Ls[r.x] * (Ls[r.y] * Ds[r.z]) : 0.0;
+            lds_scatter_add(Ls, ok ? (int)r.w : -1, -val);
+        }
+        lds_barrier();
+        stamp();
+    }
+    ff_write_out(v, fold, Ls, Ds, b, s0, nloc, e0, nE, tid, FFWG);
     stamp();
     static_eps_epilogue(v, eps);
 }
@@ -1072,16 +1223,23 @@ bool bundle_factor_lds_ok(int lds_doubles) {
     if (fa.sharedSizeBytes + lds > 80 * 1024 - 512) return false; // two workgroups per CU
     if (raise_dynamic_lds((const void *)k_bundle_factor_lds, (size_t)lds) != hipSuccess ||
         raise_dynamic_lds((const void *)k_bundle_factor_flat<4>, (size_t)lds) != hipSuccess ||
-        raise_dynamic_lds((const void *)k_bundle_factor_flat<8>, (size_t)lds) != hipSuccess) {
+        raise_dynamic_lds((const void *)k_bundle_factor_flat<8>, (size_t)lds) != hipSuccess ||
+        raise_dynamic_lds((const void *)k_bundle_factor_runs, (size_t)lds) != hipSuccess) {
         (void)hipGetLastError();
         return false;
     }
     return true;
 }
+bool bundle_factor_runs_ok(int max_nodes, int max_leftover, int max_levels) {
+    return max_nodes <= RCPT * FFWG && max_leftover <= FFWG && max_levels <= 17; // (17: the level tables of the bundle's record)
+}
 int bundle_factor(hipStream_t s, const LdlView &v, const BundleView &bv, const FoldView &fold, int lds_doubles) {
     if (!bv.nb) return 0;
     const bool no_flat = switches().no_factor_flat;
-    if (lds_doubles > 0 && v.fu_rec && !no_flat && bv.max_nodes <= 8 * FFWG) {
+    if (lds_doubles > 0 && v.fr_desc && !no_flat) {
+        // run-coded records (host.hpp: Symbolic::fr_desc; the engine uploads them only within bundle_factor_runs_ok)
+        k_bundle_factor_runs<<<bv.nb, FFWG, factor_lds_bytes(lds_doubles), s>>>(v, bv, fold);
+    } else if (lds_doubles > 0 && v.fu_rec && !no_flat && bv.max_nodes <= 8 * FFWG) {
         if (bv.max_nodes <= 4 * FFWG) k_bundle_factor_flat<4><<<bv.nb, FFWG, factor_lds_bytes(lds_doubles), s>>>(v, bv, fold);
         else k_bundle_factor_flat<8><<<bv.nb, FFWG, factor_lds_bytes(lds_doubles), s>>>(v, bv, fold);
     }

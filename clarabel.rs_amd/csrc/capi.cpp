@@ -247,6 +247,9 @@ struct chip_kkt {
 #ifdef CHIP_TESTING
     // host-only handles: the arrays the chained prologue walks, kept so that a test can walk them itself
     std::vector<int> t_bundle_ptr, t_blvl_ptr, t_blvl, t_Lp, t_Up, t_run_ptr, t_runs, t_pat_off;
+    // ... and the update records of the flat bundle factorisation, plain and run-coded (chip_debug_factor_updates)
+    std::vector<uint16_t> t_fu_rec, t_fr_rec;
+    std::vector<int> t_fu_ptr, t_fr_desc, t_fr_ptr, t_fr_rptr, t_fu_lvl_ptr, t_fr_bdesc, t_fc_usr, t_fc_col, t_fc_sgn, t_fc_desc, t_fc_rec;
 #endif
     int pend_update = 0;             // 1: an update has been enqueued and its verdict not read; 2: read, kept
     int pend_update_ok = 1;
@@ -695,6 +698,16 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
         }
 #endif
         E.init_host_only(S, st);
+#ifdef CHIP_TESTING
+        h->t_fu_lvl_ptr = S.blvl_ptr;
+        h->t_fu_rec = std::move(S.fu_rec), h->t_fu_ptr = std::move(S.fu_ptr);
+        h->t_fr_rec = std::move(S.fr_rec), h->t_fr_desc = std::move(S.fr_desc);
+        h->t_fr_ptr = std::move(S.fr_ptr), h->t_fr_rptr = std::move(S.fr_rptr);
+        h->t_fr_bdesc = std::move(S.fr_bdesc);
+        h->t_fc_usr.assign(S.fc_usr.begin(), S.fc_usr.end()), h->t_fc_col.assign(S.fc_col.begin(), S.fc_col.end()); // (bit patterns)
+        h->t_fc_sgn.assign(S.fc_sgn.begin(), S.fc_sgn.end()), h->t_fc_rec.assign(S.fc_rec.begin(), S.fc_rec.end());
+        h->t_fc_desc = std::move(S.fc_desc);
+#endif
         *out = h.release();
         return CHIP_OK;
     }
@@ -2347,6 +2360,18 @@ int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out
     else if (k == "pattern_mismatches") *out = E.pat_mismatches;
     else if (k == "pattern_shared_bundles") // bundles whose fused solve launch reads a shared copy
         *out = (h->ir_sf && E.pat_off && !switches().no_shared_pattern) ? E.bundles.nb : 0;
+    // run-coded update records of the flat bundle factorisation (host.hpp: Symbolic::fr_desc): host analysis, on host-only
+    // handles too; "factor_run_kernel": 1 when the refactor of this handle launches the run form (device handles)
+    else if (k == "factor_runs") *out = E.fr_runs;
+    else if (k == "factor_record_bundles") *out = E.fr_bundles;
+    else if (k == "factor_classes") *out = E.fc_classes;
+    else if (k == "factor_class_verified") *out = E.fc_verified;
+    else if (k == "factor_class_mismatches") *out = E.fc_mismatches;
+    else if (k == "factor_run_leftover") *out = E.fr_left;
+    else if (k == "factor_run_max_leftover") *out = E.fr_max_left;
+    else if (k == "factor_run_invalid") *out = E.fr_invalid;
+    else if (k == "factor_run_kernel") *out = (E.fr_desc && E.factor_lds_doubles > 0 && !switches().no_factor_flat && !(E.gstep_factor_on && !switches().no_step_kernel)) ? 1 : 0;
+    else if (k == "factor_records_on_device") *out = E.fu_rec ? 1 : 0;
     else if (k == "irs_desc_bundles") { // bundles whose fused solve launch reads its record (dev::IrsDesc) under the current switches
         const bool shared = E.pat_off && !switches().no_shared_pattern;
         const int flags = switches().irs_flags < 0 ? 3 : switches().irs_flags;
@@ -2369,9 +2394,58 @@ int32_t chip_debug_kkt_ints(const void *handle, const char *name, int64_t *len, 
     else if (k == "run_ptr") v = &h->t_run_ptr;
     else if (k == "runs") v = &h->t_runs;
     else if (k == "pat_off") v = &h->t_pat_off;
+    else if (k == "factor_bundle_desc") v = &h->t_fr_bdesc;
+    else if (k == "factor_class_usr") v = &h->t_fc_usr;
+    else if (k == "factor_class_col") v = &h->t_fc_col;
+    else if (k == "factor_class_sgn") v = &h->t_fc_sgn;
+    else if (k == "factor_class_desc") v = &h->t_fc_desc;
+    else if (k == "factor_class_rec") v = &h->t_fc_rec;
     else return fail(CHIP_ERR_ARG, "chip_debug_kkt_ints: unknown name");
     *len = (int64_t)v->size();
     if (out) std::copy(v->begin(), v->end(), out);
+    return CHIP_OK;
+}
+int32_t chip_debug_kkt_factors(void *handle, double *Lx, double *D) {
+    chip_kkt *h = (chip_kkt *)handle;
+    if (!h) return fail(CHIP_ERR_ARG, "chip_debug_kkt_factors: bad argument");
+    Engine &E = h->E;
+    NEED_DEVICE(E);
+    CHIP_HIP(hipSetDevice(E.device));
+    CHIP_HIP(hipStreamSynchronize(E.stream));
+    if (Lx && E.nnzL) CHIP_HIP(hipMemcpy(Lx, E.Lx, (size_t)E.nnzL * sizeof(double), hipMemcpyDeviceToHost));
+    if (D && E.N) CHIP_HIP(hipMemcpy(D, E.D, (size_t)E.N * sizeof(double), hipMemcpyDeviceToHost));
+    return CHIP_OK;
+}
+int32_t chip_debug_factor_updates(const void *handle, int32_t bundle, const char *what, int64_t *len, int32_t *out) {
+    const chip_kkt *h = (const chip_kkt *)handle;
+    if (!h || !what || !len) return fail(CHIP_ERR_ARG, "chip_debug_factor_updates: bad argument");
+    const std::string k(what);
+    const int nb = h->t_fu_lvl_ptr.empty() ? 0 : (int)h->t_fu_lvl_ptr.size() - 1;
+    if (bundle < 0 || bundle >= nb) return fail(CHIP_ERR_ARG, "chip_debug_factor_updates: no such bundle (host-only handles)");
+    const int lb0 = h->t_fu_lvl_ptr[(size_t)bundle], nl = h->t_fu_lvl_ptr[(size_t)bundle + 1] - lb0 - 1;
+    std::vector<int32_t> res;
+    auto records = [&](const std::vector<uint16_t> &rec, const std::vector<int> &ptr) {
+        if (ptr.empty()) return;
+        for (int l = 0; l < nl; l++)
+            for (int t = ptr[(size_t)lb0 + l]; t < ptr[(size_t)lb0 + l + 1]; t++) {
+                res.push_back(l);
+                for (int f = 0; f < 4; f++) res.push_back(rec[(size_t)t * 4 + f]);
+            }
+    };
+    if (k == "records") records(h->t_fu_rec, h->t_fu_ptr);
+    else if (k == "leftover") records(h->t_fr_rec, h->t_fr_rptr);
+    else if (k == "runs") {
+        if (!h->t_fr_ptr.empty())
+            for (int l = 0; l < nl; l++)
+                for (int d = h->t_fr_ptr[(size_t)lb0 + l]; d < h->t_fr_ptr[(size_t)lb0 + l + 1]; d++) {
+                    const int *e = h->t_fr_desc.data() + (size_t)d * 8;
+                    const int32_t row[10] = {l, e[0], e[1], e[2], e[3], (int16_t)(e[4] & 0xFFFF), (int16_t)(e[4] >> 16),
+                                             (int16_t)(e[5] & 0xFFFF), (int16_t)(e[5] >> 16), e[6]};
+                    res.insert(res.end(), row, row + 10);
+                }
+    } else return fail(CHIP_ERR_ARG, "chip_debug_factor_updates: unknown name");
+    *len = (int64_t)res.size();
+    if (out) std::copy(res.begin(), res.end(), out);
     return CHIP_OK;
 }
 // ---- the PSD cone kernels of cones.hip alone, one launch per call on host arrays (tests/test_psd_passes_gpu.py) ----

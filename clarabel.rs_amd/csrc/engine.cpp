@@ -112,6 +112,7 @@ void Engine::init_host_only(const Symbolic &S, const chip_settings &settings) {
     h_sn_col = S.sn_col;
     nsn = (int)S.sn_ptr.size() - 1;
     nfaclevels = S.nfaclevels;
+    note_factor_runs(S);
 }
 
 int Engine::get_symbolic(uint64_t *etree, uint64_t *oLp, uint64_t *oLi, uint64_t *lvlptr) const {
@@ -533,6 +534,7 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
         bundles.blvl = lv;
         bundles.max_nodes = S.max_bundle_nodes;
         bundles.max_levels = S.max_bundle_levels;
+        note_factor_runs(S);
         if (!S.sLi16.empty()) {
             if ((rc = upload(&sLi16, S.sLi16, S.sLi16.size()))) return rc;
             if ((rc = upload(&sLj16, S.sLj16, S.sLj16.size()))) return rc;
@@ -545,7 +547,8 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
                     need = std::max(need, (int)(S.Lp[s1] - S.Lp[s0]) + (s1 - s0) + 1); // (+ 1: the folded top row's share)
                 }
                 if (dev::bundle_factor_lds_ok(need)) {
-                    if ((rc = upload(&fu_rec, S.fu_rec, S.fu_rec.size()))) return rc;
+                    if ((rc = upload_factor_runs(S))) return rc;
+                    if (!fr_desc && (rc = upload(&fu_rec, S.fu_rec, S.fu_rec.size()))) return rc; // (the plain records: only where the launch reads them)
                     if ((rc = upload(&fu_slot, S.fu_slot, S.fu_slot.size()))) return rc;
                     if ((rc = upload(&fu_ptr, S.fu_ptr, S.fu_ptr.size()))) return rc;
                     if ((rc = upload(&Urow16, S.Urow16, S.Urow16.size()))) return rc;
@@ -643,7 +646,10 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
                 }
                 if (ok && dev::bundle_factor_lds_ok(need)) factor_lds_doubles = need;
                 if (factor_lds_doubles > 0 && !S.fu_rec.empty()) {
-                    if ((rc = upload(&fu_rec, S.fu_rec, S.fu_rec.size()))) return rc;
+                    // (the plain records: only where a kernel still reads them -- k_gstep_factor on a grouped fold, or
+                    // k_bundle_factor_flat itself on a handle without runs)
+                    if ((rc = upload_factor_runs(S))) return rc;
+                    if ((grouped || !fr_desc) && (rc = upload(&fu_rec, S.fu_rec, S.fu_rec.size()))) return rc;
                     if ((rc = upload(&fu_slot, S.fu_slot, S.fu_slot.size()))) return rc;
                     if ((rc = upload(&fu_ptr, S.fu_ptr, S.fu_ptr.size()))) return rc;
                 }
@@ -850,7 +856,7 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
     CHIP_HIP(hipMemset(dslot_dev, 0, (size_t)2 * NRM_SET_WORDS * sizeof(unsigned long long)));
     // fast preparation (refactor_enqueue): the grouped-fold step factorisation, or an arrow with ONE top column whose
     // only top-top entry of K is its diagonal, factored by the flat bundle kernel
-    fast_prep_ok = gstep_factor_on || (ir_fused && fold.k == 1 && factor_lds_doubles > 0 && fu_rec != nullptr && nfill == 0 && fill_from < 0 &&
+    fast_prep_ok = gstep_factor_on || (ir_fused && fold.k == 1 && factor_lds_doubles > 0 && factor_flat_ready() && nfill == 0 && fill_from < 0 &&
                                        nnzK - nnzU == 1 && nsn == 0);
     if (fast_prep_ok && fold.k == 1) {
         if ((rc = alloc(&fold_cnt, (size_t)32))) return rc;
@@ -860,6 +866,18 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
     CHIP_HIP(hipMemset(ctx[0].nrm_dev, 0, (size_t)NRM_SETS * NRM_SET_WORDS * sizeof(unsigned long long)));
     CHIP_HIP(hipHostMalloc((void **)&ctx[0].nrm_host, 3 * NRM_SET_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
     return CHIP_OK;
+}
+
+// the run-coded update records of k_bundle_factor_flat (host.hpp: Symbolic::fr_desc); nothing when S kept no runs
+int Engine::upload_factor_runs(const Symbolic &S) {
+    if (S.fr_bdesc.empty() || !dev::bundle_factor_runs_ok(S.max_bundle_nodes, S.fr_max_left, S.max_bundle_levels)) return CHIP_OK;
+    int rc;
+    if ((rc = upload(&fr_bdesc, S.fr_bdesc, S.fr_bdesc.size()))) return rc;
+    if ((rc = upload(&fc_usr, S.fc_usr, S.fc_usr.size()))) return rc;
+    if ((rc = upload(&fc_col, S.fc_col, S.fc_col.size()))) return rc;
+    if ((rc = upload(&fc_sgn, S.fc_sgn, S.fc_sgn.size()))) return rc;
+    if ((rc = upload(&fr_rec, S.fc_rec, S.fc_rec.size()))) return rc;
+    return upload(&fr_desc, S.fc_desc, S.fc_desc.size()); // (last: fr_desc != nullptr says that all six are there)
 }
 
 // one shared copy of the bundles' index pattern for k_bundle_irs (host.hpp: PatternShare); nothing when P has no arrays
@@ -902,6 +920,12 @@ dev::LdlView Engine::view() const {
     v.fu_rec = fu_rec;
     v.fu_slot = fu_slot;
     v.fu_ptr = fu_ptr;
+    v.fr_desc = fr_desc;
+    v.fr_bdesc = fr_bdesc;
+    v.fc_usr = fc_usr;
+    v.fc_col = fc_col;
+    v.fc_sgn = fc_sgn;
+    v.fr_rec = fr_rec;
     v.Ro16 = Ro16;
     v.Ucol16 = Ucol16;
     v.mirror_rows = ir_fused ? 0 : 1;
@@ -1436,7 +1460,7 @@ int Engine::refactor_enqueue(bool static_reg, const int *diag_idx_dev, double st
         sx_valid = true;
     }
     // (the entry-parallel bundle factorisation keeps no row-major mirror either)
-    rx_valid = !ir_fused && !(factor_lds_doubles > 0 && fu_rec && !switches().no_factor_flat);
+    rx_valid = !ir_fused && !(factor_lds_doubles > 0 && factor_flat_ready() && !switches().no_factor_flat);
     return CHIP_OK;
 }
 int Engine::refactor_collect() {

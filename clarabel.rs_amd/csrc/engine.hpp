@@ -222,6 +222,23 @@ struct Engine {
     unsigned short *sLi16 = nullptr, *sLj16 = nullptr; // dev::LdlView::sLi16
     unsigned short *fu_rec = nullptr, *fu_slot = nullptr;
     int *fu_ptr = nullptr;
+    // ... run-coded (host.hpp: Symbolic::fr_desc): on the device where the analysis kept runs; the plain records fu_rec are
+    // then uploaded only for the kernels that still read them (k_gstep_factor on a grouped fold).
+    // The figures are there on host-only handles too.
+    int *fr_desc = nullptr, *fr_bdesc = nullptr;
+    unsigned short *fr_rec = nullptr;
+    unsigned *fc_usr = nullptr, *fc_col = nullptr;
+    int8_t *fc_sgn = nullptr;
+    int fc_classes = 0, fc_verified = 0, fc_mismatches = 0;
+    int fr_runs = 0, fr_left = 0, fr_max_left = 0, fr_invalid = 0, fr_bundles = 0;
+    bool factor_flat_ready() const { return fu_rec != nullptr || fr_desc != nullptr; } // k_bundle_factor_flat has its index data
+    void note_factor_runs(const Symbolic &S) {
+        fr_runs = (int)(S.fr_desc.size() / 8), fr_left = S.fr_rec.empty() ? 0 : (int)(S.fr_rec.size() / 4) - 1;
+        fr_max_left = S.fr_max_left, fr_invalid = S.fr_invalid;
+        fc_classes = S.fc_classes, fc_verified = S.fc_verified, fc_mismatches = S.fc_mismatches;
+        fr_bundles = S.fu_ptr.empty() || S.bundle_ptr.empty() ? 0 : (int)S.bundle_ptr.size() - 1; // bundles with update records
+    }
+    int upload_factor_runs(const Symbolic &S);
     // pattern classes of the bundles (host.hpp: PatternShare).  The figures are kept on every handle of a system that
     // k_bundle_irs can take (capi.cpp: chip_kkt_create; all 0 elsewhere), host-only ones included; the shared index
     // arrays and the offset table are on the device only where k_bundle_irs takes the solves (pat_off == nullptr: that

@@ -164,6 +164,39 @@ struct Symbolic {
     // has nE + nloc >= 65535.
     std::vector<uint16_t> fu_rec, fu_slot;
     std::vector<i32> fu_ptr;
+    // ... and the same updates RUN-CODED (symbolic.cpp: code_factor_runs): the records of a (bundle, level) are almost all
+    // members of a few AFFINE RUNS -- stretches of the sorted range whose four fields each advance by a constant (a
+    // problem of SOC blocks under a coupling row: 10 runs cover 9999 of a bundle's 10 007 records).  A run of at least
+    // FU_RUN_MIN records (CHIP_FACTOR_RUN_MIN, tests) becomes one descriptor of 8 ints: first slot a, first slot b, first
+    // column k, first target, strides of a | b << 16 and of k | target << 16 (signed 16 bit each), count, 0.  Target
+    // stride 0: a reduction onto one slot; any other: distinct targets.  fr_ptr (indexed like fu_ptr) gives a level's
+    // descriptors; the records outside runs keep the 8-byte format in fr_rec, level ranges fr_rptr.  Updates of a level
+    // commute, so only the order of summation differs from the plain records.  Empty (the handle keeps the plain
+    // records alone): CHIP_NO_FACTOR_RUNS, runs that cover less than half of the records, or a descriptor that failed
+    // its range check (fr_invalid counts those).
+    static constexpr i32 FU_RUN_MIN = 64;
+    std::vector<i32> fr_desc, fr_ptr, fr_rptr;
+    // What the DEVICE gets is one copy of that index data per CLASS of bundles (a problem of identical blocks has the same
+    // bytes in every bundle), in the form the kernel holds it: fc_usr per U entry (landing slot | bundle-local row << 16),
+    // fc_col per node (first slot | length << 16), fc_sgn per node, fc_desc the run descriptors, fc_rec the records
+    // outside runs.  Two bundles are in one class iff all of these, their level tables and sizes are equal; with
+    // CHIP_NO_SHARED_PATTERN every bundle is a class of its own.  One record of FR_BDESC ints per bundle makes the
+    // kernel's prologue one trip instead of the chain bundle_ptr -> Lp / Up / blvl_ptr -> blvl / fu_ptr: [0] first node,
+    // [1] nodes, [2] first entry of L, [3] entries, [4], [5] its range of U entries (the values), [6] levels nl, [7] where
+    // its class's U entries start in fc_usr; [8 .. 8 + nl] first node of every level (bundle-local) and the node count;
+    // [26 .. 26 + nl] the levels' ranges in fc_rec; [44 .. 44 + nl] in fc_desc; [62] where its class's nodes start in
+    // fc_col / fc_sgn; [63] the class.  Every bundle's own data is compared with what its record reaches before the
+    // tables are handed out (fc_verified / fc_mismatches: a mismatch leaves the handle with the plain records).  A
+    // handle with a bundle of more than FR_MAX_LEVELS levels keeps the plain records too.
+    static constexpr i32 FR_BDESC = 64, FR_MAX_LEVELS = 17;
+    std::vector<i32> fr_bdesc, fc_desc;
+    std::vector<uint32_t> fc_usr, fc_col;
+    std::vector<int8_t> fc_sgn;
+    std::vector<uint16_t> fc_rec;
+    i32 fc_classes = 0, fc_verified = 0, fc_mismatches = 0;
+    std::vector<uint16_t> fr_rec;
+    i32 fr_max_left = 0; // most records outside runs in one bundle
+    i32 fr_invalid = 0;
     std::vector<i32> lvlptr;
     // Chain supernodes of the top (symbolic.cpp): supernode s = columns sn_col[sn_ptr[s] .. sn_ptr[s+1])
     // (ascending, each the parent of the previous one); all its columns are padded to the dense

@@ -40,6 +40,12 @@ struct LdlView {
     const unsigned short *Rk16, *Ro16;   // rows of L inside the bundles: bundle-local column, offset inside that column
     const unsigned short *fu_rec, *fu_slot; // entry-parallel bundle factorisation (host.hpp: Symbolic::fu_rec), or nullptr
     const int *fu_ptr;
+    // ... run-coded (host.hpp: Symbolic::fr_desc), or nullptr: descriptors of 8 ints and
+    // the records outside runs; their level ranges are in the bundle's record
+    const int *fr_desc, *fr_bdesc; // ... and one record of 64 ints per bundle (host.hpp: Symbolic::fr_bdesc)
+    const unsigned short *fr_rec;
+    const unsigned *fc_usr, *fc_col; // one copy per class of bundles: U entries' slot | row << 16, columns' first slot | length << 16
+    const int8_t *fc_sgn;            // ... and the nodes' signs
     int mirror_rows;
     // systems with a level-scheduled top: bundle-local row (0xFFFF: a top row) / column of the entries of the bundle columns,
     // for the entry-parallel stand-alone sweeps (k_bundle_sweep_flat; host.hpp: Symbolic::sLi16), or nullptr
@@ -162,6 +168,8 @@ void scale_values(hipStream_t s, double *Kx, const int *map, int k, double scale
 // returns hipSuccess (0) or the launch error
 int bundle_factor(hipStream_t s, const LdlView &v, const BundleView &bv, const FoldView &fold, int lds_doubles = 0);
 bool bundle_factor_lds_ok(int lds_doubles);
+// ... and whether its run-coded form (k_bundle_factor_runs) takes a handle: nodes / records outside runs / levels of its largest bundle
+bool bundle_factor_runs_ok(int max_nodes, int max_leftover, int max_levels);
 void fold_top_pivot(hipStream_t s, const LdlView &v, const FoldView &fold);
 // fold.k > 0: every bundle also subtracts its part of the k top rows of L from x[NF + i]
 void bundle_fwd(hipStream_t s, const LdlView &v, const BundleView &bv, double *x, const FoldView &fold);

@@ -33,6 +33,8 @@ const Entry TABLE[] = {
     {"CHIP_NO_SNODE", Entry::FLAG, SW(no_snode), 0},
     {"CHIP_NO_TOPFOLD", Entry::FLAG, SW(no_topfold), 0},
     {"CHIP_NO_FACTOR_FLAT", Entry::FLAG, SW(no_factor_flat), 0},
+    {"CHIP_NO_FACTOR_RUNS", Entry::FLAG, SW(no_factor_runs), 0},
+    {"CHIP_FACTOR_RUN_MIN", Entry::INT, SW(factor_run_min), 0},
     {"CHIP_NO_TOPBLK", Entry::FLAG, SW(no_topblk), 0},
     {"CHIP_NO_SNX_HOIST", Entry::FLAG, SW(no_snx_hoist), 0},
     {"CHIP_NO_PSD_MFMA", Entry::FLAG, SW(no_psd_mfma), 0},

@@ -28,6 +28,8 @@ struct Switches {
     bool no_snode = false;          // CHIP_NO_SNODE
     bool no_topfold = false;        // CHIP_NO_TOPFOLD
     bool no_factor_flat = false;    // CHIP_NO_FACTOR_FLAT (also read by the launcher of the bundle factorisation)
+    bool no_factor_runs = false;    // CHIP_NO_FACTOR_RUNS: the update records of the flat bundle factorisation are not coded into affine runs (host.hpp: Symbolic::fr_desc)
+    int factor_run_min = 0;         // CHIP_FACTOR_RUN_MIN: fewest records of a run (tests; 0: Symbolic::FU_RUN_MIN)
     bool no_topblk = false;         // CHIP_NO_TOPBLK
     long long snb_chunk = 0;        // CHIP_SNB_CHUNK: fewest updates of a chunk of the bundle columns' contributions into a supernode member (0: default)
     bool no_snx_hoist = false;      // CHIP_NO_SNX_HOIST: the bundle columns' contributions into supernode members stay in the launches of the members' unit levels

@@ -1354,6 +1354,212 @@ int analyse(i64 n, const i64 *Ap, const i64 *Ai, const int8_t *dsigns, const std
             }
         }
     }
+    // ---- ... run-coded (host.hpp: fr_desc) ----------------------------------------------------------
+    // Greedy scan of every (bundle, level) range in its sorted order: the longest stretch from record i whose four
+    // fields advance by constants is a run when it has enough records; otherwise its records stay records, except the
+    // last one, which may open the next stretch.  Two passes over the records (count, fill), threads over bundles.
+    if (!S.fu_rec.empty() && !switches().no_factor_runs) {
+        const i32 nbun = (i32)S.bundle_ptr.size() - 1;
+        const i32 min_len = std::max(2, switches().factor_run_min > 0 ? switches().factor_run_min : (int)Symbolic::FU_RUN_MIN);
+        const uint16_t *rec = S.fu_rec.data();
+        // on_run(first record, strides, count), on_left(record)
+        auto scan = [&](i64 rb, i64 re, auto &&on_run, auto &&on_left) {
+            i64 i = rb;
+            while (i < re) {
+                i64 e = i + 1;
+                i32 st[4] = {0, 0, 0, 0};
+                if (e < re) {
+                    for (int f = 0; f < 4; f++) st[f] = (i32)rec[e * 4 + f] - (i32)rec[i * 4 + f];
+                    for (e++; e < re; e++) {
+                        bool same = true;
+                        for (int f = 0; f < 4; f++) same = same && (i32)rec[e * 4 + f] - (i32)rec[(e - 1) * 4 + f] == st[f];
+                        if (!same) break;
+                    }
+                }
+                bool fits = true; // (strides are signed 16 bit in the descriptor)
+                for (int f = 0; f < 4; f++) fits = fits && st[f] >= -32768 && st[f] <= 32767;
+                if (e - i >= min_len && fits) {
+                    on_run(i, st, (i32)(e - i));
+                    i = e;
+                } else {
+                    const i64 stop = (e - i >= 2 && e < re) ? e - 1 : e;
+                    for (; i < stop; i++) on_left(i);
+                }
+            }
+        };
+        std::vector<i64> nrun((size_t)nbun + 1, 0), nleft((size_t)nbun + 1, 0);
+        const int T = par_threads((i64)S.fu_rec.size() / 4);
+        run_threads(T, [&](int t, int TT) {
+            for (i32 b = t; b < nbun; b += TT) {
+                const i32 lb0 = S.blvl_ptr[b], nl = S.blvl_ptr[b + 1] - lb0 - 1;
+                i64 r = 0, lf = 0;
+                for (i32 l = 0; l < nl; l++)
+                    scan(S.fu_ptr[lb0 + l], S.fu_ptr[lb0 + l + 1], [&](i64, const i32 *, i32) { r++; }, [&](i64) { lf++; });
+                nrun[b + 1] = r;
+                nleft[b + 1] = lf;
+            }
+        });
+        i64 max_left = 0;
+        for (i32 b = 0; b < nbun; b++) {
+            max_left = std::max(max_left, nleft[b + 1]);
+            nrun[b + 1] += nrun[b];
+            nleft[b + 1] += nleft[b];
+        }
+        // (a handle whose runs cover less than half of its records keeps the plain records alone: a second copy of
+        // nearly all of them would buy nothing)
+        const i64 total = (i64)S.fu_rec.size() / 4 - 1;
+        if (nrun[nbun] > 0 && 2 * nleft[nbun] <= total && S.max_bundle_levels <= Symbolic::FR_MAX_LEVELS) {
+            S.fr_desc.assign((size_t)nrun[nbun] * 8, 0);
+            S.fr_rec.assign((size_t)nleft[nbun] * 4 + 4, 0);
+            S.fr_ptr.assign(S.blvl.size() + 1, 0);
+            S.fr_rptr.assign(S.blvl.size() + 1, 0);
+            S.fr_max_left = (i32)max_left;
+            std::vector<i32> bad((size_t)T, 0);
+            run_threads(T, [&](int t, int TT) {
+                for (i32 b = t; b < nbun; b += TT) {
+                    const i32 s0 = S.bundle_ptr[b], s1 = S.bundle_ptr[b + 1], nloc = s1 - s0, nE = S.Lp[s1] - S.Lp[s0];
+                    const i32 lb0 = S.blvl_ptr[b], nl = S.blvl_ptr[b + 1] - lb0 - 1;
+                    i64 r = nrun[b], lf = nleft[b];
+                    for (i32 l = 0; l < nl; l++) {
+                        S.fr_ptr[lb0 + l] = (i32)r;
+                        S.fr_rptr[lb0 + l] = (i32)lf;
+                        scan(S.fu_ptr[lb0 + l], S.fu_ptr[lb0 + l + 1],
+                             [&](i64 i, const i32 *st, i32 cnt) {
+                                 i32 *d = S.fr_desc.data() + (size_t)r * 8;
+                                 const uint16_t *f = rec + i * 4;
+                                 // first and last address of every operand inside the bundle's store: slots a, b < nE, column
+                                 // k < nloc, target <= nE + nloc (pivots behind the entries, the top row's share last)
+                                 const i32 lim[4] = {nE - 1, nE - 1, nloc - 1, nE + nloc};
+                                 for (int q = 0; q < 4; q++) {
+                                     const i32 last = (i32)f[q] + st[q] * (cnt - 1);
+                                     if ((i32)f[q] > lim[q] || last < 0 || last > lim[q]) bad[(size_t)t]++;
+                                 }
+                                 // (target stride 0: a reduction; the range is sorted by target, so any other stride is
+                                 // positive and the run's targets are pairwise distinct)
+                                 if (st[3] < 0) bad[(size_t)t]++;
+                                 d[0] = f[0], d[1] = f[1], d[2] = f[2], d[3] = f[3];
+                                 d[4] = (st[0] & 0xFFFF) | (i32)((uint32_t)st[1] << 16);
+                                 d[5] = (st[2] & 0xFFFF) | (i32)((uint32_t)st[3] << 16);
+                                 d[6] = cnt;
+                                 r++;
+                             },
+                             [&](i64 i) {
+                                 std::copy(rec + i * 4, rec + i * 4 + 4, S.fr_rec.data() + (size_t)lf * 4);
+                                 lf++;
+                             });
+                    }
+                    S.fr_ptr[lb0 + nl] = (i32)r; // (also the first range of the next bundle, like fu_ptr)
+                    S.fr_rptr[lb0 + nl] = (i32)lf;
+                }
+            });
+            for (i32 x : bad) S.fr_invalid += x;
+            if (S.fr_invalid) { // (never seen: the records were built from the same slots)
+                S.fr_desc.clear(), S.fr_rec.clear(), S.fr_ptr.clear(), S.fr_rptr.clear();
+                S.fr_max_left = 0;
+            } else if (!S.dsigns.empty() && !S.Urow16.empty()) {
+                // ---- classes of bundles with equal index data, the shared arrays, the per-bundle records (host.hpp: fc_*) ----
+                // a bundle's signature: everything the kernel reads through its record, in sections of known length
+                auto signature = [&](i32 b, std::vector<uint32_t> &g) {
+                    const i32 s0 = S.bundle_ptr[b], s1 = S.bundle_ptr[b + 1], e0 = S.Lp[s0];
+                    const i32 lb0 = S.blvl_ptr[b], nl = S.blvl_ptr[b + 1] - lb0 - 1;
+                    g.clear();
+                    g.push_back((uint32_t)(s1 - s0)), g.push_back((uint32_t)(S.Lp[s1] - e0)), g.push_back((uint32_t)nl);
+                    for (i32 u = S.Up[s0]; u < S.Up[s1]; u++) g.push_back((uint32_t)S.fu_slot[u] | ((uint32_t)S.Urow16[u] << 16));
+                    for (i32 j = s0; j < s1; j++) g.push_back((uint32_t)(S.Lp[j] - e0) | ((uint32_t)(S.Lp[j + 1] - S.Lp[j]) << 16));
+                    for (i32 j = s0; j < s1; j++) g.push_back((uint32_t)(uint8_t)S.dsigns[j]);
+                    for (i64 q = (i64)S.fr_ptr[lb0] * 8; q < (i64)S.fr_ptr[lb0 + nl] * 8; q++) g.push_back((uint32_t)S.fr_desc[q]);
+                    for (i64 q = (i64)S.fr_rptr[lb0] * 4; q < (i64)S.fr_rptr[lb0 + nl] * 4; q++) g.push_back(S.fr_rec[q]);
+                    for (i32 l = 0; l <= nl; l++) {
+                        g.push_back((uint32_t)(S.blvl[lb0 + l] - s0));
+                        g.push_back((uint32_t)(S.fr_rptr[lb0 + l] - S.fr_rptr[lb0]));
+                        g.push_back((uint32_t)(S.fr_ptr[lb0 + l] - S.fr_ptr[lb0]));
+                    }
+                };
+                std::vector<std::vector<uint32_t>> sig((size_t)nbun);
+                std::vector<uint64_t> hash((size_t)nbun);
+                run_threads(T, [&](int t, int TT) {
+                    for (i32 b = t; b < nbun; b += TT) {
+                        signature(b, sig[(size_t)b]);
+                        uint64_t h = 1469598103934665603ull; // (FNV-1a)
+                        for (uint32_t w : sig[(size_t)b]) h = (h ^ w) * 1099511628211ull;
+                        hash[(size_t)b] = h;
+                    }
+                });
+                const bool share = !switches().no_shared_pattern;
+                std::vector<i32> order((size_t)nbun), cls((size_t)nbun, -1), rep;
+                std::iota(order.begin(), order.end(), 0);
+                if (share) std::stable_sort(order.begin(), order.end(), [&](i32 x, i32 y) { return hash[(size_t)x] < hash[(size_t)y]; });
+                for (i32 p = 0, q; p < nbun; p = q) { // one run of equal hashes, decided by the full comparison
+                    const size_t first = rep.size();
+                    for (q = p; q < nbun && (q == p || (share && hash[(size_t)order[(size_t)q]] == hash[(size_t)order[(size_t)p]])); q++) {
+                        const i32 b = order[(size_t)q];
+                        for (size_t c = first; c < rep.size() && cls[(size_t)b] < 0; c++)
+                            if (sig[(size_t)b] == sig[(size_t)rep[c]]) cls[(size_t)b] = (i32)c;
+                        if (cls[(size_t)b] < 0) cls[(size_t)b] = (i32)rep.size(), rep.push_back(b);
+                    }
+                }
+                S.fc_classes = (i32)rep.size();
+                std::vector<i64> cu((size_t)rep.size()), cn((size_t)rep.size()), cd((size_t)rep.size()), cr((size_t)rep.size());
+                for (size_t c = 0; c < rep.size(); c++) { // a class's slices: those of its first member, one after the other
+                    const i32 b = rep[c], s0 = S.bundle_ptr[b], s1 = S.bundle_ptr[b + 1], e0 = S.Lp[s0];
+                    const i32 lb0 = S.blvl_ptr[b], nl = S.blvl_ptr[b + 1] - lb0 - 1;
+                    cu[c] = (i64)S.fc_usr.size(), cn[c] = (i64)S.fc_col.size(), cd[c] = (i64)S.fc_desc.size() / 8, cr[c] = (i64)S.fc_rec.size() / 4;
+                    for (i32 u = S.Up[s0]; u < S.Up[s1]; u++) S.fc_usr.push_back((uint32_t)S.fu_slot[u] | ((uint32_t)S.Urow16[u] << 16));
+                    for (i32 j = s0; j < s1; j++) {
+                        S.fc_col.push_back((uint32_t)(S.Lp[j] - e0) | ((uint32_t)(S.Lp[j + 1] - S.Lp[j]) << 16));
+                        S.fc_sgn.push_back(S.dsigns[j]);
+                    }
+                    S.fc_desc.insert(S.fc_desc.end(), S.fr_desc.begin() + (size_t)S.fr_ptr[lb0] * 8, S.fr_desc.begin() + (size_t)S.fr_ptr[lb0 + nl] * 8);
+                    S.fc_rec.insert(S.fc_rec.end(), S.fr_rec.begin() + (size_t)S.fr_rptr[lb0] * 4, S.fr_rec.begin() + (size_t)S.fr_rptr[lb0 + nl] * 4);
+                }
+                S.fc_usr.push_back(0), S.fc_col.push_back(0), S.fc_sgn.push_back(0); // (padding, like the other index arrays)
+                S.fc_desc.insert(S.fc_desc.end(), 8, 0), S.fc_rec.insert(S.fc_rec.end(), 4, 0);
+                S.fr_bdesc.assign((size_t)nbun * Symbolic::FR_BDESC, 0);
+                for (i32 b = 0; b < nbun; b++) {
+                    i32 *d = S.fr_bdesc.data() + (size_t)b * Symbolic::FR_BDESC;
+                    const i32 s0 = S.bundle_ptr[b], s1 = S.bundle_ptr[b + 1], c = cls[(size_t)b];
+                    const i32 lb0 = S.blvl_ptr[b], nl = S.blvl_ptr[b + 1] - lb0 - 1;
+                    d[0] = s0, d[1] = s1 - s0, d[2] = S.Lp[s0], d[3] = S.Lp[s1] - S.Lp[s0], d[4] = S.Up[s0], d[5] = S.Up[s1], d[6] = nl;
+                    d[7] = (i32)cu[(size_t)c], d[62] = (i32)cn[(size_t)c], d[63] = c;
+                    for (i32 l = 0; l <= nl; l++) {
+                        d[8 + l] = S.blvl[lb0 + l] - s0;
+                        d[26 + l] = (i32)cr[(size_t)c] + (S.fr_rptr[lb0 + l] - S.fr_rptr[lb0]);
+                        d[44 + l] = (i32)cd[(size_t)c] + (S.fr_ptr[lb0 + l] - S.fr_ptr[lb0]);
+                    }
+                }
+                // what the kernel will read, against every bundle's own data: through the records alone
+                std::vector<i32> wrong((size_t)T, 0);
+                run_threads(T, [&](int t, int TT) {
+                    std::vector<uint32_t> g;
+                    for (i32 b = t; b < nbun; b += TT) {
+                        const i32 *d = S.fr_bdesc.data() + (size_t)b * Symbolic::FR_BDESC;
+                        const i32 nloc = d[1], nl = d[6], un = d[5] - d[4];
+                        g.clear();
+                        g.push_back((uint32_t)nloc), g.push_back((uint32_t)d[3]), g.push_back((uint32_t)nl);
+                        bool ok = d[7] >= 0 && (size_t)d[7] + un < S.fc_usr.size() && d[62] >= 0 && (size_t)d[62] + nloc < S.fc_col.size() &&
+                                  d[44] >= 0 && d[44] <= d[44 + nl] && (size_t)d[44 + nl] * 8 < S.fc_desc.size() && d[26] >= 0 &&
+                                  d[26] <= d[26 + nl] && (size_t)d[26 + nl] * 4 < S.fc_rec.size();
+                        if (ok) {
+                            for (i32 u = 0; u < un; u++) g.push_back(S.fc_usr[(size_t)d[7] + u]);
+                            for (i32 j = 0; j < nloc; j++) g.push_back(S.fc_col[(size_t)d[62] + j]);
+                            for (i32 j = 0; j < nloc; j++) g.push_back((uint32_t)(uint8_t)S.fc_sgn[(size_t)d[62] + j]);
+                            for (i64 q = (i64)d[44] * 8; q < (i64)d[44 + nl] * 8; q++) g.push_back((uint32_t)S.fc_desc[(size_t)q]);
+                            for (i64 q = (i64)d[26] * 4; q < (i64)d[26 + nl] * 4; q++) g.push_back(S.fc_rec[(size_t)q]);
+                            for (i32 l = 0; l <= nl; l++)
+                                g.push_back((uint32_t)d[8 + l]), g.push_back((uint32_t)(d[26 + l] - d[26])), g.push_back((uint32_t)(d[44 + l] - d[44]));
+                            ok = g == sig[(size_t)b];
+                        }
+                        if (!ok) wrong[(size_t)t]++;
+                    }
+                });
+                S.fc_verified = nbun;
+                for (i32 x : wrong) S.fc_mismatches += x;
+                if (S.fc_mismatches) { // (never seen) the handle keeps the plain records
+                    S.fr_bdesc.clear(), S.fc_usr.clear(), S.fc_col.clear(), S.fc_sgn.clear(), S.fc_desc.clear(), S.fc_rec.clear();
+                }
+            }
+        }
+    }
     // ---- blocked substitution for tall tops -----------------------------------
     {
         const i32 ntop = (i32)n - S.NF;

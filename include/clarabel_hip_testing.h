@@ -34,8 +34,25 @@ int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out
  * runs, 3 of padding, 20 level entries, 32 x 3 run entries; empty when some bundle does not fit), on host-only handles
  * too.  Host-only handles of systems that kernel can take also keep the arrays its chained prologue walks:
  * "bundle_ptr", "blvl_ptr", "blvl", "Lp", "Up", "run_ptr", "runs", "pat_off" (empty: every bundle reads its own copy of
- * the index arrays).  Returns CHIP_ERR_ARG for an unknown name. */
+ * the index arrays), and "factor_bundle_desc": the run-coded bundle factorisation's per-bundle records (csrc/host.hpp:
+ * Symbolic::fr_bdesc, 64 ints each; empty: no runs) with the shared arrays they point into, one copy per class of
+ * identical bundles: "factor_class_usr", "factor_class_col" (bit patterns of unsigned words), "factor_class_sgn",
+ * "factor_class_desc" (8 ints per run), "factor_class_rec" (4 per record); chip_debug_counter: "factor_classes",
+ * "factor_class_verified" (bundles compared with what their record reaches), "factor_class_mismatches".  Returns CHIP_ERR_ARG for an unknown name. */
 int32_t chip_debug_kkt_ints(const void *kkt_handle, const char *name, int64_t *len, int32_t *out);
+/* the update records of the flat bundle factorisation (csrc/host.hpp: Symbolic::fu_rec / fr_desc) of one bundle of a
+ * HOST-ONLY KKT handle, levels in order; *len <- ints; out (may be NULL) receives them.  "records": every update,
+ * 5 ints each {level, slot a, slot b, column k, target}; "runs": the affine runs the analysis coded, 10 ints each {level,
+ * first a, first b, first k, first target, strides of a, b, k, target, count} (none: the handle keeps the plain records
+ * alone); "leftover": the records outside runs, 5 ints each like "records".  chip_debug_counter has the handle's totals,
+ * on device handles too: "factor_record_bundles" (bundles that have update records at all), "factor_runs", "factor_run_leftover", "factor_run_max_leftover" (most in one bundle),
+ * "factor_run_invalid" (descriptors that failed their range check: the handle then has no runs), "factor_run_kernel" (1:
+ * the refactor launches the run form), "factor_records_on_device" (1: the plain records were uploaded).
+ * CHIP_ERR_ARG for an unknown name, a bundle out of range or a handle with a device. */
+int32_t chip_debug_factor_updates(const void *kkt_handle, int32_t bundle, const char *what, int64_t *len, int32_t *out);
+/* the factor of a KKT handle as the last refactor left it on the device, permuted numbering: Lx[nnzL] (CSC order of
+ * chip_kkt_get_symbolic), D[N]; either may be NULL.  Waits for the handle's stream. */
+int32_t chip_debug_kkt_factors(void *kkt_handle, double *Lx, double *D);
 /* a spinner of `blocks` x `threads` for `usec` microseconds on the stream of a communicator (opaque chip_comm *), behind
  * the collective enqueued last; the communicator's completion event moves behind it.  On one GPU this stands in for
  * the time RCCL's ring kernel holds CUs when several ranks exchange (bench.py --coresident). */
