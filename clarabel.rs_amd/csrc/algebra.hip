@@ -198,7 +198,7 @@ __global__ __launch_bounds__(WG) void k_diag_absmax(const double *__restrict__ K
 }
 __global__ void k_eps_from_max(double c, double prop, unsigned long long *scal) {
     double m = __longlong_as_double((long long)scal[1]);
-    if (scal[2]) m = __longlong_as_double(0x7ff8000000000000ll);
+    if (scal[2]) m = nan_marker();
     ((double *)scal)[0] = c + prop * m; // directldlkktsolver.rs:324-329
 }
 
@@ -214,7 +214,7 @@ __global__ void k_eps_from_slots(unsigned long long *slots, double c, double pro
     if (lane == 0) {
         m = fmax(m, static_max);
         int *nanflag = (int *)(slots + (size_t)NRM_SLOTS * NRM_STRIDE);
-        if (*nanflag || static_max != static_max) m = __longlong_as_double(0x7ff8000000000000ll);
+        if (*nanflag || static_max != static_max) m = nan_marker();
         *nanflag = 0;
         scal[0] = c + prop * m; // directldlkktsolver.rs:324-329
     }

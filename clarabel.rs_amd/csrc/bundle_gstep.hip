@@ -21,6 +21,7 @@
 // directldlkktsolver.rs:160-189, 205-215, 266-347 (setrhs / getlhs, refinement, residual against the unregularised K).
 #include "dev_common.hpp"
 #include "grid_sync.hpp"
+#include "ir_refine.hpp"
 
 namespace chip {
 namespace dev {
@@ -30,9 +31,7 @@ namespace {
 constexpr int GS_TW = 256;
 
 // per-workgroup state shared through LDS (written by thread 0 / wave 0, read after a barrier)
-struct GsState {
-    double normb, norme, lastnorme;
-    int rounds, ok, done, sel, gen, accept;
+struct GsState : IrVerdict {
     double btop[8], dinvt[8], ltt[64], ktt[64];
     double fsum[8], rsum[8];         // the group's totals of the published shares
     double dxt[8], acct[8], candt[8], rtop[8];
@@ -41,7 +40,7 @@ struct GsState {
     double vn, vb;                   // the verdict's inputs: ||e||inf, ||b||inf over the whole system
     int lev[GS_MAXL + 2];
     int tnode[8], torig[8];          // node / original index of the group's top rows
-    int timeout;
+    int timeout, gen;
 };
 
 // Poll the messages of the bundles [gb0, gb0 + gnb) until all carry their tag, one round trip per poll for everything:
@@ -153,13 +152,8 @@ void k_gstep_solve(LdlView v, BundleView bv, IrView ir, GFoldView gf, GStepView 
         }
         if (tid <= nl + 1) st.lev[tid] = dsc[16 + tid];
         if (tid == 0) {
-            st.normb = st.norme = st.lastnorme = 0.0;
-            st.rounds = 0;
-            st.ok = 1;
-            st.done = 0;
-            st.sel = 0;
+            ir_verdict_init(st);
             st.gen = 0;
-            st.accept = 0;
             st.timeout = 0;
             if (b == 0) {
                 ir.res[0] = 0; // "did not finish" until the verdict is written at the very end
@@ -216,8 +210,7 @@ void k_gstep_solve(LdlView v, BundleView bv, IrView ir, GFoldView gf, GStepView 
                 bs[i] = breg[u];
                 dis[i] = dreg[u];
                 ir.bp[s0 + i] = breg[u];
-                if (breg[u] != breg[u]) nan = true;
-                else mx = fmax(mx, fabs(breg[u]));
+                norm_take(breg[u], mx, nan);
             }
         }
         if (tid < 8) {
@@ -334,11 +327,7 @@ void k_gstep_solve(LdlView v, BundleView bv, IrView ir, GFoldView gf, GStepView 
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
             const int i = tid + u * TW;
-            if (i < nloc) {
-                const double val = xs[i];
-                if (val != val) nan = true;
-                else m = fmax(m, fabs(val));
-            }
+            if (i < nloc) norm_take(xs[i], m, nan);
         }
         return lds_block_nanmax(m, nan, red);
     };
@@ -352,58 +341,17 @@ void k_gstep_solve(LdlView v, BundleView bv, IrView ir, GFoldView gf, GStepView 
     // the reference's decisions (as k_bundle_ir) from the system-wide norms in st.vn / st.vb
     auto decide = [&](int round) {
         if (tid == 0) {
-            const double newnorm = st.vn;
             if (round == 0) st.normb = st.vb;
-            const double tol = ir.abstol + ir.reltol * st.normb;
-            bool accept, done = false;
-            if (round == 0) {
-                accept = true;
-                st.norme = newnorm;
-                if (!(newnorm - newnorm == 0.0)) { // non-finite (:284-286; without refinement: x.is_finite(), :180)
-                    st.ok = 0;
-                    done = true;
-                } else if (!ir.ir_enable || ir.maxiter <= 0 || newnorm <= tol) {
-                    done = true;
-                }
-            } else {
-                st.rounds += 1;
-                if (!(newnorm - newnorm == 0.0)) { // :305-307
-                    st.ok = 0;
-                    accept = false;
-                    done = true;
-                } else {
-                    const double improved = st.lastnorme / newnorm;
-                    accept = !(improved < ir.stopratio) || improved > 1.0; // :309-318
-                    if (improved < ir.stopratio) done = true;
-                    if (accept) st.norme = newnorm;
-                }
-            }
-            if (accept) {
-                st.sel ^= 1; // the candidate becomes the accepted iterate
+            if (ir_verdict(st, ir, round, st.vn)) // the candidate becomes the accepted iterate
                 for (int i = 0; i < 8; ++i) st.acct[i] = st.candt[i];
-            }
-            if (!done && (st.rounds >= ir.maxiter || st.norme <= tol)) done = true; // :288-293
-            st.lastnorme = st.norme;
-            st.done = done ? 1 : 0;
         }
         lds_barrier();
     };
     // the k x k top part of both sweeps (every workgroup of the group alike): rhs - (the group's forward shares)
     auto top_solve = [&](int round) {
-        if (tid == 0) {
-            // (y in LDS, st.dxt: a private array indexed by a loop variable lives in scratch memory -- its reloads sat on
-            // the critical path of every round; round 6, found on k_bundle_irs)
-            for (int i = 0; i < k; ++i) {
-                double sacc = (round == 0 ? st.btop[i] : st.rtop[i]) - st.fsum[i];
-                for (int j = 0; j < i; ++j) sacc -= st.ltt[i * 8 + j] * st.dxt[j];
-                st.dxt[i] = sacc;
-            }
-            for (int i = k - 1; i >= 0; --i) {
-                double sacc = st.dxt[i] * st.dinvt[i];
-                for (int j = i + 1; j < k; ++j) sacc -= st.ltt[j * 8 + i] * st.dxt[j];
-                st.dxt[i] = sacc;
-            }
-        }
+        if (tid == 0)
+            ir_top_solve(k, [&](int i) { return (round == 0 ? st.btop[i] : st.rtop[i]) - st.fsum[i]; }, st.ltt, st.dinvt,
+                         st.dxt);
     };
     // top rows of the residual of the candidate in st.candt from the group's residual shares st.rsum -> st.rtop;
     // returns max |rtop| (NaN propagating).  Thread 0.
@@ -543,7 +491,7 @@ void k_gstep_solve(LdlView v, BundleView bv, IrView ir, GFoldView gf, GStepView 
             const int i = tid + u * TW;
             if (i < nloc) cnd[i] = round == 0 ? xs[i] : 1.0 * acc[i] + 1.0 * xs[i];
         }
-        if (tid < 8) st.candt[tid] = round == 0 ? st.dxt[tid] : 1.0 * st.acct[tid] + 1.0 * st.dxt[tid];
+        if (tid < 8) st.candt[tid] = ir_top_cand(round, st.acct[tid], st.dxt[tid]);
         lds_barrier();
         double mine;
         if (!ir.ir_enable) { // no refinement: only x.is_finite() is asked for (:180)
@@ -552,11 +500,7 @@ void k_gstep_solve(LdlView v, BundleView bv, IrView ir, GFoldView gf, GStepView 
 #pragma unroll
             for (int u = 0; u < NR; ++u) {
                 const int i = tid + u * TW;
-                if (i < nloc) {
-                    const double val = cnd[i];
-                    if (val != val) nan = true;
-                    else mx = fmax(mx, fabs(val));
-                }
+                if (i < nloc) norm_take(cnd[i], mx, nan);
             }
             mine = lds_block_nanmax(mx, nan, red);
             if (tid < 8) st.tacc[tid] = 0.0;
@@ -582,19 +526,12 @@ void k_gstep_solve(LdlView v, BundleView bv, IrView ir, GFoldView gf, GStepView 
     const int ok = __builtin_amdgcn_readfirstlane(st.ok);
     if (ok) {
         const double *acc = __builtin_amdgcn_readfirstlane(st.sel) ? A1 : A0;
-        auto put = [&](int o, double val) {
-            if (o < ir.n) {
-                if (ir.lhsx) ir.lhsx[o] = val;
-            } else if (o < ir.n + ir.m) {
-                if (ir.lhsz) ir.lhsz[o - ir.n] = val;
-            }
-        };
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
             const int i = tid + u * TW;
-            if (i < nloc) put(og[i], acc[i]);
+            if (i < nloc) ir_put(ir, og[i], acc[i]);
         }
-        if (gfirst && tid < k) put(st.torig[tid], st.acct[tid]);
+        if (gfirst && tid < k) ir_put(ir, st.torig[tid], st.acct[tid]);
     }
     if (b == 0 && tid == 0) {
         ir.res[0] = ok ? 1 : -1; // (0 = the kernel never got here)

@@ -3,6 +3,7 @@
 // dev_common.hpp)
 #include "dev_common.hpp"
 #include "bundle_symv.hpp"
+#include "ir_refine.hpp"
 #include "grid_sync.hpp"
 
 namespace chip {
@@ -256,17 +257,59 @@ __device__ __forceinline__ void flat_level_table(const LdlView &v, const BundleV
     const int nl = bv.blvl_ptr[b + 1] - bv.blvl_ptr[b] - 1;
     if ((int)threadIdx.x <= nl && nl <= FLAT_MAXLEV) lev_e[threadIdx.x] = v.Lp[lv[threadIdx.x]];
 }
+// bundle_sweep_flat_ahead is the one copy of the stream of batches.  Its caller may have requested the FIRST batch
+// itself, a phase ahead (k_bundle_irs: the entries do not depend on the vector, so the trip for them can run behind the
+// previous phase's closing reduction or a grid barrier instead of at the head of the sweep): flat_request_first issues
+// exactly the loads the sweep would start with -- same level, same `t < ee` guards --, the sweep consumes them and goes
+// on.  The caller has the bundle's scalars (k_bundle_irs: from its record; k_bundle_ir: bundle_sweep_flat, below) and,
+// for the backward sweep, has scaled the slice by 1 / d itself.  Not for 512 threads.
+struct FlatBatch {
+    int i[FLAT_U], j[FLAT_U];
+    double v[FLAT_U];
+};
+// (a batch that has been consumed is set to constants: left as it is, a variable that is assigned on some paths of the
+// round loop only is carried around the whole loop by the compiler, FLAT_U * 4 registers live across every phase)
+__device__ __forceinline__ void flat_batch_clear(FlatBatch &fb) {
+#pragma unroll
+    for (int u = 0; u < FLAT_U; ++u) fb.i[u] = -1, fb.j[u] = 0, fb.v[u] = 0.0;
+}
 template <bool FWDMODE, int TW>
-__device__ __forceinline__ void bundle_sweep_flat(const LdlView &v, const BundleView &bv, int b, double *xs,
-                                                  const double *xt, double *tacc, int k, const int *lev_e, int dl = 0) {
-    const int s0 = bv.bundle_ptr[b], nloc = bv.bundle_ptr[b + 1] - s0;
-    const int nl = bv.blvl_ptr[b + 1] - bv.blvl_ptr[b] - 1;
+__device__ __forceinline__ void flat_request_first(const LdlView &v, const int *lev_e, int nl, int dl, int tid, FlatBatch &fb) {
+    int step = 0, base = 0, ee = 0;
+    while (step < nl) { // (first non-empty level, as the opening loop of bundle_sweep_flat_ahead)
+        const int l = FWDMODE ? step : nl - 1 - step;
+        base = lev_e[l];
+        ee = lev_e[l + 1];
+        if (base < ee) break;
+        ++step;
+    }
+    // (straight-line loads: a load under `t < ee ? .. : ..` is a branch of its own, and a value that is to stay in flight
+    // across a barrier must not sit behind one; a slot past the range reads the range's last entry and is marked empty)
+    if (step < nl) {
+#pragma unroll
+        for (int u = 0; u < FLAT_U; ++u) {
+            const int t = base + u * TW + tid;
+            const bool ok = t < ee;
+            const int tc = ok ? t : ee - 1;
+            const int ri = (int)v.Li16[tc + dl], rj = (int)v.Lj16[tc + dl];
+            const double rv = v.Lx[tc];
+            fb.i[u] = ok ? ri : -1;
+            fb.j[u] = ok ? rj : 0;
+            fb.v[u] = ok ? rv : 0.0;
+        }
+    } else {
+        flat_batch_clear(fb);
+    }
+}
+// HAVE_FIRST = false (k_bundle_ir): the sweep requests its first batch itself, behind its opening barrier.
+template <bool FWDMODE, int TW, bool HAVE_FIRST = true>
+__device__ __forceinline__ void bundle_sweep_flat_ahead(const LdlView &v, double *xs, const double *xt, double *tacc, int k,
+                                                        const int *lev_e, int dl, int nloc, int nl, const FlatBatch &first) {
+    static_assert(TW != 512, "two batches in flight: not within the 80 registers of the 512-thread form");
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid)); // (no hoisting of this phase's address arithmetic out of the caller's round loop)
     const int lane = tid & 63;
     if (FWDMODE && tid < 8) tacc[tid] = 0.0;
-    if (!FWDMODE)
-        for (int i = tid; i < nloc; i += TW) xs[i] *= v.Dinv[s0 + i];
     double tpart = 0.0;
     // a stream of batches of TW * FLAT_U entries, level after level; the next batch's loads are issued before the
     // current one is consumed -- across a level boundary too (the entries do not depend on x), so a level costs its
@@ -277,54 +320,12 @@ __device__ __forceinline__ void bundle_sweep_flat(const LdlView &v, const Bundle
         eb_ = lev_e[l];
         ee_ = lev_e[l + 1];
     };
-    auto skip_empty = [&]() { // -> first non-empty level at or after `step`
-        while (step < nl) {
-            level_range(step, base, ee);
-            if (base < ee) return;
-            ++step;
-        }
-    };
-    lds_barrier(); // (lev_e, the scaled slice)
-    if (TW == 512) {
-        // (80 registers per thread in the 512-thread variant: no second batch in flight)
-        for (int st_ = 0; st_ < nl; ++st_) {
-            int eb_, ee_;
-            level_range(st_, eb_, ee_);
-            for (int bs = eb_; bs < ee_; bs += TW * FLAT_U) {
-                int ii[FLAT_U], jj[FLAT_U];
-                double vv[FLAT_U];
-#pragma unroll
-                for (int u = 0; u < FLAT_U; ++u) {
-                    const int t = bs + u * TW + tid;
-                    const bool ok = t < ee_;
-                    ii[u] = ok ? (int)v.Li16[t + dl] : -1;
-                    jj[u] = ok ? (int)v.Lj16[t + dl] : 0;
-                    vv[u] = ok ? v.Lx[t] : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < FLAT_U; ++u) {
-                    const int i = ii[u];
-                    if (i < 0) continue;
-                    if (FWDMODE) {
-                        const double val = vv[u] * xs[jj[u]];
-                        if (i < nloc) atomicAdd(&xs[i], -val);
-                        else if (k == 1) tpart += val;
-                        else atomicAdd(&tacc[i - nloc], val);
-                    } else {
-                        atomicAdd(&xs[jj[u]], -(vv[u] * (i < nloc ? xs[i] : xt[i - nloc])));
-                    }
-                }
-            }
-            lds_barrier();
-        }
-        if (FWDMODE && k == 1) {
-            tpart = wave_sum_all(tpart);
-            if (lane == 0 && tpart != 0.0) atomicAdd(&tacc[0], tpart);
-        }
-        lds_barrier();
-        return;
+    lds_barrier(); // (the slice as the caller left it, tacc; k_bundle_ir: lev_e)
+    while (step < nl) { // first non-empty level
+        level_range(step, base, ee);
+        if (base < ee) break;
+        ++step;
     }
-    skip_empty();
     int ci[FLAT_U], cj[FLAT_U], ni[FLAT_U], nj[FLAT_U];
     double cv[FLAT_U], nv[FLAT_U];
     auto request = [&](int bs, int en, int *ii, int *jj, double *vv) {
@@ -337,7 +338,16 @@ __device__ __forceinline__ void bundle_sweep_flat(const LdlView &v, const Bundle
             vv[u] = ok ? v.Lx[t] : 0.0;
         }
     };
-    if (step < nl) request(base, ee, ci, cj, cv);
+    if (HAVE_FIRST) {
+#pragma unroll
+        for (int u = 0; u < FLAT_U; ++u) {
+            ci[u] = first.i[u];
+            cj[u] = first.j[u];
+            cv[u] = first.v[u];
+        }
+    } else if (step < nl) {
+        request(base, ee, ci, cj, cv);
+    }
     while (step < nl) {
         // the batch after this one
         int nstep = step, nbase = base + TW * FLAT_U, nee = ee;
@@ -381,130 +391,79 @@ __device__ __forceinline__ void bundle_sweep_flat(const LdlView &v, const Bundle
     lds_barrier();
 }
 
-// The same stream of batches for a caller that requested the FIRST batch itself, a phase ahead (k_bundle_irs: the
-// entries do not depend on the vector, so the trip for them can run behind the previous phase's closing reduction or
-// a grid barrier instead of at the head of the sweep).  flat_request_first issues exactly the loads the sweep would
-// start with -- same level, same `t < ee` guards --; bundle_sweep_flat_ahead consumes them and goes on like the plain
-// entry.  The caller has the bundle's scalars (k_bundle_irs: from its record) and, for the backward sweep, has
-// scaled the slice by 1 / d itself.  256 threads only.
-struct FlatBatch {
-    int i[FLAT_U], j[FLAT_U];
-    double v[FLAT_U];
-};
-// (a batch that has been consumed is set to constants: left as it is, a variable that is assigned on some paths of the
-// round loop only is carried around the whole loop by the compiler, FLAT_U * 4 registers live across every phase)
-__device__ __forceinline__ void flat_batch_clear(FlatBatch &fb) {
-#pragma unroll
-    for (int u = 0; u < FLAT_U; ++u) fb.i[u] = -1, fb.j[u] = 0, fb.v[u] = 0.0;
-}
+// k_bundle_ir's entry: the bundle's scalars from the views, 1 / d of the backward sweep applied here.  256 / 1024 threads:
+// the stream above; 512 threads: one batch at a time (80 registers per thread: no second batch in flight).
 template <bool FWDMODE, int TW>
-__device__ __forceinline__ void flat_request_first(const LdlView &v, const int *lev_e, int nl, int dl, int tid, FlatBatch &fb) {
-    int step = 0, base = 0, ee = 0;
-    while (step < nl) { // (first non-empty level, as bundle_sweep_flat: skip_empty)
-        const int l = FWDMODE ? step : nl - 1 - step;
-        base = lev_e[l];
-        ee = lev_e[l + 1];
-        if (base < ee) break;
-        ++step;
-    }
-    // (straight-line loads: a load under `t < ee ? .. : ..` is a branch of its own, and a value that is to stay in flight
-    // across a barrier must not sit behind one; a slot past the range reads the range's last entry and is marked empty)
-    if (step < nl) {
-#pragma unroll
-        for (int u = 0; u < FLAT_U; ++u) {
-            const int t = base + u * TW + tid;
-            const bool ok = t < ee;
-            const int tc = ok ? t : ee - 1;
-            const int ri = (int)v.Li16[tc + dl], rj = (int)v.Lj16[tc + dl];
-            const double rv = v.Lx[tc];
-            fb.i[u] = ok ? ri : -1;
-            fb.j[u] = ok ? rj : 0;
-            fb.v[u] = ok ? rv : 0.0;
-        }
-    } else {
-        flat_batch_clear(fb);
-    }
-}
-template <bool FWDMODE, int TW>
-__device__ __forceinline__ void bundle_sweep_flat_ahead(const LdlView &v, double *xs, const double *xt, double *tacc, int k,
-                                                        const int *lev_e, int dl, int nloc, int nl, const FlatBatch &first) {
-    static_assert(TW == 256, "two batches in flight: the 256-thread form only");
+__device__ __forceinline__ void bundle_sweep_flat(const LdlView &v, const BundleView &bv, int b, double *xs,
+                                                  const double *xt, double *tacc, int k, const int *lev_e, int dl = 0) {
+    const int s0 = bv.bundle_ptr[b], nloc = bv.bundle_ptr[b + 1] - s0;
+    const int nl = bv.blvl_ptr[b + 1] - bv.blvl_ptr[b] - 1;
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid)); // (no hoisting of this phase's address arithmetic out of the caller's round loop)
-    const int lane = tid & 63;
-    if (FWDMODE && tid < 8) tacc[tid] = 0.0;
-    double tpart = 0.0;
-    int step = 0, base = 0, ee = 0;
-    auto level_range = [&](int st_, int &eb_, int &ee_) {
-        const int l = FWDMODE ? st_ : nl - 1 - st_;
-        eb_ = lev_e[l];
-        ee_ = lev_e[l + 1];
-    };
-    lds_barrier(); // (the slice as the caller left it, tacc)
-    while (step < nl) {
-        level_range(step, base, ee);
-        if (base < ee) break;
-        ++step;
-    }
-    int ci[FLAT_U], cj[FLAT_U], ni[FLAT_U], nj[FLAT_U];
-    double cv[FLAT_U], nv[FLAT_U];
-    auto request = [&](int bs, int en, int *ii, int *jj, double *vv) {
+    if (!FWDMODE)
+        for (int i = tid; i < nloc; i += TW) xs[i] *= v.Dinv[s0 + i];
+    if constexpr (TW != 512) {
+        bundle_sweep_flat_ahead<FWDMODE, TW, false>(v, xs, xt, tacc, k, lev_e, dl, nloc, nl, FlatBatch{});
+    } else {
+        const int lane = tid & 63;
+        if (FWDMODE && tid < 8) tacc[tid] = 0.0;
+        double tpart = 0.0;
+        lds_barrier(); // (lev_e, the scaled slice)
+        for (int st_ = 0; st_ < nl; ++st_) {
+            const int l = FWDMODE ? st_ : nl - 1 - st_;
+            const int eb_ = lev_e[l], ee_ = lev_e[l + 1];
+            for (int bs = eb_; bs < ee_; bs += TW * FLAT_U) {
+                int ii[FLAT_U], jj[FLAT_U];
+                double vv[FLAT_U];
 #pragma unroll
-        for (int u = 0; u < FLAT_U; ++u) {
-            const int t = bs + u * TW + tid;
-            const bool ok = t < en;
-            ii[u] = ok ? (int)v.Li16[t + dl] : -1;
-            jj[u] = ok ? (int)v.Lj16[t + dl] : 0;
-            vv[u] = ok ? v.Lx[t] : 0.0;
-        }
-    };
+                for (int u = 0; u < FLAT_U; ++u) {
+                    const int t = bs + u * TW + tid;
+                    const bool ok = t < ee_;
+                    ii[u] = ok ? (int)v.Li16[t + dl] : -1;
+                    jj[u] = ok ? (int)v.Lj16[t + dl] : 0;
+                    vv[u] = ok ? v.Lx[t] : 0.0;
+                }
 #pragma unroll
-    for (int u = 0; u < FLAT_U; ++u) {
-        ci[u] = first.i[u];
-        cj[u] = first.j[u];
-        cv[u] = first.v[u];
-    }
-    while (step < nl) {
-        // the batch after this one
-        int nstep = step, nbase = base + TW * FLAT_U, nee = ee;
-        if (nbase >= nee) {
-            nstep = step + 1;
-            while (nstep < nl) {
-                level_range(nstep, nbase, nee);
-                if (nbase < nee) break;
-                ++nstep;
+                for (int u = 0; u < FLAT_U; ++u) {
+                    const int i = ii[u];
+                    if (i < 0) continue;
+                    if (FWDMODE) {
+                        const double val = vv[u] * xs[jj[u]];
+                        if (i < nloc) atomicAdd(&xs[i], -val);
+                        else if (k == 1) tpart += val;
+                        else atomicAdd(&tacc[i - nloc], val);
+                    } else {
+                        atomicAdd(&xs[jj[u]], -(vv[u] * (i < nloc ? xs[i] : xt[i - nloc])));
+                    }
+                }
             }
+            lds_barrier();
         }
-        if (nstep < nl) request(nbase, nee, ni, nj, nv);
-#pragma unroll
-        for (int u = 0; u < FLAT_U; ++u) {
-            const int i = ci[u];
-            if (i < 0) continue;
-            if (FWDMODE) {
-                const double val = cv[u] * xs[cj[u]];
-                if (i < nloc) atomicAdd(&xs[i], -val);
-                else if (k == 1) tpart += val;
-                else atomicAdd(&tacc[i - nloc], val);
-            } else {
-                atomicAdd(&xs[cj[u]], -(cv[u] * (i < nloc ? xs[i] : xt[i - nloc])));
-            }
+        if (FWDMODE && k == 1) {
+            tpart = wave_sum_all(tpart);
+            if (lane == 0 && tpart != 0.0) atomicAdd(&tacc[0], tpart);
         }
-        if (nstep != step) lds_barrier(); // the level is complete
-        step = nstep;
-        base = nbase;
-        ee = nee;
-#pragma unroll
-        for (int u = 0; u < FLAT_U; ++u) {
-            ci[u] = ni[u];
-            cj[u] = nj[u];
-            cv[u] = nv[u];
-        }
+        lds_barrier();
     }
-    if (FWDMODE && k == 1) {
-        tpart = wave_sum_all(tpart);
-        if (lane == 0 && tpart != 0.0) atomicAdd(&tacc[0], tpart);
+}
+
+// the residual's closing reduction: m / nan = the thread's part of ||e||inf over the bundle's rows; tpart (k == 1) /
+// tacc3 (k > 1, LDS) = its shares of (K x)[top rows].  LDS_ONLY: the barrier in front of tacc3 as the caller had it
+// (k_bundle_irs keeps its loads in flight across it: lds_barrier)
+template <bool LDS_ONLY>
+__device__ __forceinline__ void symv_close(double m, bool nan, double tpart, int k, int tid, const double *tacc3, double *red,
+                                           double *out_norm, double *out_share) {
+    m = block_norm_or_nan(m, nan, red);
+    if (tid == 0) ir_store(out_norm, m);
+    if (k == 1) {
+        tpart = block_sum(tpart, red);
+        if (tid == 0) ir_store(out_share, tpart);
+    } else if (k > 1) {
+        if (LDS_ONLY) lds_barrier();
+        else __syncthreads();
+        if (tid == 0)
+            for (int i = 0; i < k; ++i) ir_store(out_share + i, tacc3[i]);
     }
-    lds_barrier();
 }
 
 // The residual of k_bundle_ir in the split LDS layout of bundle_symv_split, entry-parallel: the rows of the non-leaf
@@ -544,6 +503,9 @@ __device__ __forceinline__ void bundle_symv_flat(const LdlView &v, const BundleV
     bool nan = false;
     __syncthreads();
     // ---- leaf rows ----
+    // (the leaf rows and the flat range below are written again in irs_symv: as phases shared with it, parameterised by
+    // where x_i, b_i and e_i live, they cost k_bundle_irs<256, 4> 124 instead of 68 bytes of scratch per lane and
+    // k_bundle_ir<512, false / true> 288 / 316 instead of 268 / 292; only the closing reduction is shared: symv_close)
     for (int w0 = 0; w0 < nleaf; w0 += LR * TW) {
         int jj[LR][LS];
         double vv[LR][LS], xi[LR], bi[LR], acc[LR];
@@ -642,28 +604,14 @@ __device__ __forceinline__ void bundle_symv_flat(const LdlView &v, const BundleV
         else m = fmax(m, fabs(val));
     }
     for (int i = tid; i < nleaf; i += TW) xs[i] = spill[s0 + i]; // (every thread re-reads what it wrote itself)
-    m = block_max(m, red);
-    const bool anynan = __syncthreads_or(nan);
-    if (tid == 0)
-        __hip_atomic_store(out_norm, anynan ? __longlong_as_double(0x7ff8000000000000ll) : m, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    if (k == 1) {
-        tpart = block_sum(tpart, red);
-        if (tid == 0) __hip_atomic_store(out_share, tpart, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if (k > 1) {
-        __syncthreads();
-        if (tid == 0)
-            for (int i = 0; i < k; ++i)
-                __hip_atomic_store(out_share + i, tacc3[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    symv_close<false>(m, nan, tpart, k, tid, tacc3, red, out_norm, out_share);
 }
 
 constexpr int IR_MAXRUNS = 32;
 // per-workgroup state of k_bundle_ir, kept in LDS so that nothing but loop counters stays in registers
 // across the sweeps (their inner loops need the whole 64-register budget of 8 waves per SIMD)
-struct IrState {
-    double normb, norme, lastnorme;
-    int rounds, ok, done, sel, par, gen, pad;
+struct IrState : IrVerdict {
+    int par, gen;
     double btop[8], rtop[8], dxt[8], curt[8], candt[8];
     double dinvt[8], ltt[64], ktt[64]; // constants of the folded top: 1/d, L(top, top), K(top, top) (full rows)
     double tacc[8];                    // this bundle's shares of the top rows in the forward sweep
@@ -710,16 +658,8 @@ void k_bundle_ir(LdlView v, BundleView bv, FoldView fold, IrView ir, GFoldView g
     double *shs = shf + (size_t)nb * kp;    // [2][nb*k]  residual: shares of (K x)[top]
     double *pub = shs + 2 * (size_t)nb * kp; // [2][32]   published reductions: [0..8) forward sums, [8] ||e||,
                                             //            [9] ||b||, [16..24) residual sums
-    auto rhs_at = [&](int j) { // permuted right-hand side entry j (directldlkktsolver.rs:160-166)
-        const int o = ir.perm[j];
-        return o < ir.n ? ir.rx[o] : (o < ir.n + ir.m ? ir.rz[o - ir.n] : 0.0);
-    };
     if (tid == 0) {
-        st.normb = st.norme = st.lastnorme = 0.0;
-        st.rounds = 0;
-        st.ok = 1;
-        st.done = 0;
-        st.sel = 0;
+        ir_verdict_init(st);
         st.par = 0;
         st.gen = 0;
         if (blockIdx.x == 0) {
@@ -736,7 +676,7 @@ void k_bundle_ir(LdlView v, BundleView bv, FoldView fold, IrView ir, GFoldView g
     // the first grid barrier, where the workgroup waits anyway -- not ahead of the staging pass
     auto load_top_constants = [&]() {
         if (tid < 8) {
-            st.btop[tid] = tid < k ? rhs_at(topnode(tid)) : 0.0;
+            st.btop[tid] = tid < k ? ir_rhs(ir, ir.perm[topnode(tid)]) : 0.0;
             // (bp must hold the WHOLE permuted right-hand side afterwards: a second solve() without a new
             // setrhs() restarts from bp, directldlkktsolver.rs:168-175 keeps self.b)
             if (tid < k && (GR ? gfirst : blockIdx.x == 0)) ir.bp[topnode(tid)] = st.btop[tid];
@@ -838,37 +778,8 @@ void k_bundle_ir(LdlView v, BundleView bv, FoldView fold, IrView ir, GFoldView g
                 m = nanmax(m, fabs(st.rtop[i]));
             }
             // (rtop = top rows of the candidate's residual: consumed only if it is accepted and a round follows)
-            const double newnorm = m, tol = ir.abstol + ir.reltol * st.normb;
-            bool accept, done = false;
-            if (round == 0) {
-                accept = true;
-                st.norme = newnorm;
-                if (!(newnorm - newnorm == 0.0)) { // non-finite (:284-286; without refinement: x.is_finite(), :180)
-                    st.ok = 0;
-                    done = true;
-                } else if (!ir.ir_enable || ir.maxiter <= 0 || newnorm <= tol) {
-                    done = true;
-                }
-            } else {
-                st.rounds += 1;
-                if (!(newnorm - newnorm == 0.0)) { // :305-307
-                    st.ok = 0;
-                    accept = false;
-                    done = true;
-                } else {
-                    const double improved = st.lastnorme / newnorm;
-                    accept = !(improved < ir.stopratio) || improved > 1.0; // :309-318
-                    if (improved < ir.stopratio) done = true;
-                    if (accept) st.norme = newnorm;
-                }
-            }
-            if (accept) {
-                st.sel ^= 1;
+            if (ir_verdict(st, ir, round, m))
                 for (int i = 0; i < k; ++i) st.curt[i] = st.candt[i];
-            }
-            if (!done && (st.rounds >= ir.maxiter || st.norme <= tol)) done = true; // :288-293
-            st.lastnorme = st.norme;
-            st.done = done ? 1 : 0;
         }
         __syncthreads();
     };
@@ -891,19 +802,15 @@ void k_bundle_ir(LdlView v, BundleView bv, FoldView fold, IrView ir, GFoldView g
                 __syncthreads();
                 double mx = 0.0;
                 bool nan = false;
-                int r = 0;
+                RunWalk rw{st.runs, 0};
                 for (int i = tid; i < nloc; i += TW) {
-                    while (i >= st.runs[3 * r] + st.runs[3 * r + 2]) ++r; // (runs ascend in the local index)
-                    const int o = st.runs[3 * r + 1] + (i - st.runs[3 * r]);
-                    const double val = o < ir.n ? ir.rx[o] : (o < ir.n + ir.m ? ir.rz[o - ir.n] : 0.0);
+                    const double val = ir_rhs(ir, rw.orig(i));
                     xs[i] = val;
                     ir.bp[s0 + i] = val;
-                    if (val != val) nan = true;
-                    else mx = fmax(mx, fabs(val));
+                    norm_take(val, mx, nan);
                 }
-                mx = block_max(mx, red);
-                const bool anynan = __syncthreads_or(nan);
-                if (tid == 0) ir_store(&pnb[b], anynan ? __longlong_as_double(0x7ff8000000000000ll) : mx);
+                mx = block_norm_or_nan(mx, nan, red);
+                if (tid == 0) ir_store(&pnb[b], mx);
             } else if (round == 0) {
                 double mx = 0.0;
                 bool nan = false;
@@ -914,20 +821,18 @@ void k_bundle_ir(LdlView v, BundleView bv, FoldView fold, IrView ir, GFoldView g
                     for (int u = 0; u < 4; ++u) o[u] = i0 + u * TW < nloc ? ir.perm[s0 + i0 + u * TW] : -1;
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
-                        val[u] = o[u] < 0 ? 0.0 : (o[u] < ir.n ? ir.rx[o[u]] : (o[u] < ir.n + ir.m ? ir.rz[o[u] - ir.n] : 0.0));
+                        val[u] = o[u] < 0 ? 0.0 : ir_rhs(ir, o[u]);
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
                         if (o[u] >= 0) {
                             const int i = i0 + u * TW;
                             xs[i] = val[u];
                             ir.bp[s0 + i] = val[u];
-                            if (val[u] != val[u]) nan = true;
-                            else mx = fmax(mx, fabs(val[u]));
+                            norm_take(val[u], mx, nan);
                         }
                 }
-                mx = block_max(mx, red);
-                const bool anynan = __syncthreads_or(nan);
-                if (tid == 0) ir_store(&pnb[b], anynan ? __longlong_as_double(0x7ff8000000000000ll) : mx);
+                mx = block_norm_or_nan(mx, nan, red);
+                if (tid == 0) ir_store(&pnb[b], mx);
             } else if (!single) {
                 for (int i = tid; i < nloc; i += TW) xs[i] = ir.ebuf[s0 + i];
             } // (single: xs still holds this bundle's residual)
@@ -956,8 +861,7 @@ void k_bundle_ir(LdlView v, BundleView bv, FoldView fold, IrView ir, GFoldView g
                     if (ir_group_arrive(gf.gcnt + grp * 32, gnb * gph)) {
                         group_sums(gf.fsh);
                         if (tid == 0) {
-                            // (y in LDS, st.dxt -- rewritten from the group's record after the barrier: a private array
-                            // indexed by a loop variable lives in scratch memory)
+                            // (st.dxt is rewritten from the group's record after the barrier)
                             double nt = 0.0, nbt = 0.0;
                             for (int i = 0; i < k; ++i) {
                                 const double rhs_i = round == 0 ? st.btop[i] : ir_load(&grec[(par ^ 1) * 32 + 16 + i]);
@@ -1038,8 +942,10 @@ void k_bundle_ir(LdlView v, BundleView bv, FoldView fold, IrView ir, GFoldView g
                 }
                 if (tid == 0) {
                     // the k x k top part of both sweeps, by every workgroup alike (k <= 8)
-                    // (y in LDS, st.dxt: a private array indexed by a loop variable lives in scratch memory, and its
-                    // reloads sat on the critical path right behind the barrier)
+                    // (ir_top_solve, ir_refine.hpp, written out here and at the group's last arriver above: through the
+                    // function k_bundle_ir<512, false> has 182 / 49 scratch loads / stores instead of 185 / 52 -- 181 / 48
+                    // with an in-place form, which measured 0.5 % slower on 256 trees of config 4 -- and <512, true> 450
+                    // more instructions; in-place 225 / 78 scratch loads / stores instead of 187 / 50)
                     for (int i = 0; i < k; ++i) {
                         double sacc = (round == 0 ? st.btop[i] : st.rtop[i]) - ir_load(&pub[par * 32 + i]);
                         for (int j = 0; j < i; ++j) sacc -= st.ltt[i * 8 + j] * st.dxt[j];
@@ -1083,14 +989,9 @@ void k_bundle_ir(LdlView v, BundleView bv, FoldView fold, IrView ir, GFoldView g
                 if (!ir.ir_enable) { // no refinement: only x.is_finite() is asked for (:180)
                     double mx = 0.0;
                     bool nan = false;
-                    for (int i = tid; i < nloc; i += TW) {
-                        const double val = xs[i];
-                        if (val != val) nan = true;
-                        else mx = fmax(mx, fabs(val));
-                    }
-                    mx = block_max(mx, red);
-                    const bool anynan = __syncthreads_or(nan);
-                    if (tid == 0) ir_store(&pn[(size_t)par * nb + b], anynan ? __longlong_as_double(0x7ff8000000000000ll) : mx);
+                    for (int i = tid; i < nloc; i += TW) norm_take(xs[i], mx, nan);
+                    mx = block_norm_or_nan(mx, nan, red);
+                    if (tid == 0) ir_store(&pn[(size_t)par * nb + b], mx);
                     continue;
                 }
                 __syncthreads(); // the candidate's slice is visible workgroup-wide
@@ -1164,14 +1065,6 @@ void k_bundle_ir(LdlView v, BundleView bv, FoldView fold, IrView ir, GFoldView g
     const int ok = __builtin_amdgcn_readfirstlane(st.ok);
     if (ok) {
         double *cur = __builtin_amdgcn_readfirstlane(st.sel) ? ir.xb : ir.xa;
-        auto put = [&](int j, double val) {
-            const int o = ir.perm[j];
-            if (o < ir.n) {
-                if (ir.lhsx) ir.lhsx[o] = val;
-            } else if (o < ir.n + ir.m) {
-                if (ir.lhsz) ir.lhsz[o - ir.n] = val;
-            }
-        };
         for (int b = blockIdx.x; b < nb; b += G) {
             const int s0 = bv.bundle_ptr[b], nloc = bv.bundle_ptr[b + 1] - s0;
             const int nruns = ir.runs ? ir.run_ptr[b + 1] - ir.run_ptr[b] : 0;
@@ -1179,6 +1072,8 @@ void k_bundle_ir(LdlView v, BundleView bv, FoldView fold, IrView ir, GFoldView g
                 __syncthreads();
                 if (tid < 3 * nruns) st.runs[tid] = ir.runs[3 * ir.run_ptr[b] + tid];
                 __syncthreads();
+                // (RunWalk + ir_put, ir_refine.hpp, written out: through them k_bundle_ir<512, true> has 208 / 58 scratch
+                // loads / stores instead of the 187 / 50 it has this way, <512, false> 186 / 52 instead of 185 / 52)
                 int r = 0;
                 for (int i = tid; i < nloc; i += TW) {
                     while (i >= st.runs[3 * r] + st.runs[3 * r + 2]) ++r;
@@ -1191,11 +1086,11 @@ void k_bundle_ir(LdlView v, BundleView bv, FoldView fold, IrView ir, GFoldView g
                     }
                 }
             } else {
-                for (int i = tid; i < nloc; i += TW) put(s0 + i, cur[s0 + i]);
+                for (int i = tid; i < nloc; i += TW) ir_put(ir, ir.perm[s0 + i], cur[s0 + i]);
             }
         }
         if ((GR ? gfirst : blockIdx.x == 0) && tid < k) {
-            put(topnode(tid), st.curt[tid]);
+            ir_put(ir, ir.perm[topnode(tid)], st.curt[tid]);
             cur[topnode(tid)] = st.curt[tid];
         }
     }
@@ -1243,16 +1138,6 @@ __device__ __forceinline__ int opaque_tid() {
     return t;
 }
 
-// original index of bundle-local node i through the runs (LDS); successive calls with ascending i: one monotone walk
-struct RunWalk {
-    const int *runs;
-    int r;
-    __device__ __forceinline__ int orig(int i) {
-        while (i >= runs[3 * r] + runs[3 * r + 2]) ++r; // (runs ascend in the local index)
-        return runs[3 * r + 1] + (i - runs[3 * r]);
-    }
-};
-
 // e = b - K c for the rows of the workgroup's bundle, c = the candidate in the threads' registers; split LDS layout of
 // bundle_symv_split (e of the non-leaf rows at xs[nleaf .. nloc), x of the non-leaf nodes in the space around it).
 // keep_e: a further round can follow -- the leaves' residual is put into xs[0 .. nleaf) at the end, so xs holds the whole
@@ -1271,7 +1156,6 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
     const double *__restrict__ Ux = v.Ux;
     const int tid = opaque_tid();
     auto xpos = [&](int t) { return t < nleaf ? t : nloc + (t - nleaf); }; // x of non-leaf t
-    auto rhs_of = [&](int o) { return o < ir.n ? ir.rx[o] : (o < ir.n + ir.m ? ir.rz[o - ir.n] : 0.0); };
     constexpr int LR = 4, LS = 3;
     static_assert(NLP % LR == 0 && NLP <= NPT, "leaf passes");
     int tb[LR], te[LR];
@@ -1289,7 +1173,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
 #pragma unroll
         for (int u = 0; u < NPT; ++u) {
             const int i = tid + u * TW;
-            bq[u] = (i >= nleaf && i < nloc) ? rhs_of(rw.orig(i)) : 0.0;
+            bq[u] = (i >= nleaf && i < nloc) ? ir_rhs(ir, rw.orig(i)) : 0.0;
         }
         lds_barrier(); // (every thread has taken its candidate entries out of xs)
 #pragma unroll
@@ -1309,6 +1193,8 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
     bool nan = false;
     lds_barrier();
     // ---- leaf rows: the thread's own, four per pass; x_i from the registers ----
+    // (these and the flat range below repeat bundle_symv_flat's with the `du` pattern offset: as shared phases they cost
+    // this kernel 124 instead of 68 bytes of scratch per lane, see there)
     RunWalk rl{runs, 0};
 #pragma unroll
     for (int p = 0; p < NLP / LR; ++p) {
@@ -1318,7 +1204,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
 #pragma unroll
             for (int u = 0; u < LR; ++u) {
                 const int i = (p * LR + u) * TW + tid;
-                bi[u] = i < nleaf ? rhs_of(rl.orig(i)) : 0.0;
+                bi[u] = i < nleaf ? ir_rhs(ir, rl.orig(i)) : 0.0;
                 acc[u] = 0.0;
 #pragma unroll
                 for (int q = 0; q < LS; ++q) {
@@ -1422,20 +1308,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
         for (int u = 0; u < NLP; ++u)
             if (tid + u * TW < nleaf) xs[tid + u * TW] = cl[u];
     }
-    m = block_max(m, red);
-    const bool anynan = __syncthreads_or(nan);
-    if (tid == 0)
-        __hip_atomic_store(out_norm, anynan ? __longlong_as_double(0x7ff8000000000000ll) : m, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    if (k == 1) {
-        tpart = block_sum(tpart, red);
-        if (tid == 0) __hip_atomic_store(out_share, tpart, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if (k > 1) {
-        lds_barrier();
-        if (tid == 0)
-            for (int i = 0; i < k; ++i)
-                __hip_atomic_store(out_share + i, tacc3[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    symv_close<true>(m, nan, tpart, k, tid, tacc3, red, out_norm, out_share);
 }
 
 template <int TW, int NLP>
@@ -1487,16 +1360,10 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
     double *shf = pn + 2 * nb;              // [nb*k]     forward sweep: shares of the top rows
     double *shs = shf + (size_t)nb * k;     // [2][nb*k]  residual: shares of (K x)[top]
     double *pub = shs + 2 * (size_t)nb * k; // [2][32]    published reductions
-    auto rhs_of = [&](int o) { return o < ir.n ? ir.rx[o] : (o < ir.n + ir.m ? ir.rz[o - ir.n] : 0.0); };
     if (tid == 0) {
-        st.normb = st.norme = st.lastnorme = 0.0;
-        st.rounds = 0;
-        st.ok = 1;
-        st.done = 0;
-        st.sel = 0;
+        ir_verdict_init(st);
         st.par = 0;
         st.gen = 0;
-        st.pad = 0; // (1: the last verdict accepted its candidate)
         if (!use_desc) {
             pat[0] = ir.pat_off ? ir.pat_off[2 * b] : 0;
             pat[1] = ir.pat_off ? ir.pat_off[2 * b + 1] : 0;
@@ -1527,7 +1394,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
     }
     auto load_top_constants = [&]() {
         if (tid < 8) {
-            st.btop[tid] = tid < k ? rhs_of(ir.perm[NF + tid]) : 0.0;
+            st.btop[tid] = tid < k ? ir_rhs(ir, ir.perm[NF + tid]) : 0.0;
             if (ir.bp && tid < k && b == 0) ir.bp[NF + tid] = st.btop[tid];
             st.curt[tid] = 0.0;
             st.dinvt[tid] = tid < k ? v.Dinv[NF + tid] : 0.0;
@@ -1668,6 +1535,9 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
                 st.rtop[i] = ir.ir_enable ? st.btop[i] - sacc : st.candt[i];
                 m = nanmax(m, fabs(st.rtop[i]));
             }
+            // (ir_verdict's body, ir_refine.hpp, written out: through the shared function -- by reference, by value, as a
+            // template -- this kernel takes 84 instead of 68 bytes of scratch per lane; with the function's two switches
+            // made opaque it keeps 68 and a launch takes 140.4 instead of 139.5 us)
             const double newnorm = m, tol = ir.abstol + ir.reltol * st.normb;
             bool accept, done = false;
             if (round == 0) {
@@ -1692,7 +1562,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
                     if (accept) st.norme = newnorm;
                 }
             }
-            st.pad = accept ? 1 : 0;
+            st.accept = accept ? 1 : 0;
             if (accept) {
                 st.sel ^= 1;
                 for (int i = 0; i < k; ++i) st.curt[i] = st.candt[i];
@@ -1711,7 +1581,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
 #pragma unroll
         for (int u = 0; u < NPT; ++u) {
             const int i = tid + u * TW;
-            c[u] = i < nloc ? rhs_of(rw.orig(i)) : 0.0;
+            c[u] = i < nloc ? ir_rhs(ir, rw.orig(i)) : 0.0;
         }
         if (ahead) { // (round 0's forward sweep: its first batch rides with the staging loads)
             flat_request_first<true, TW>(v, lev_e, nl, __builtin_amdgcn_readfirstlane(pat[0]), opaque_tid(), fwdb);
@@ -1725,13 +1595,11 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
             if (i < nloc) {
                 xs[i] = c[u];
                 if (ir.bp) ir.bp[s0 + i] = c[u]; // (only when the host asks for the permuted copy)
-                if (c[u] != c[u]) nan = true;
-                else mx = fmax(mx, fabs(c[u]));
+                norm_take(c[u], mx, nan);
             }
         }
-        mx = block_max(mx, red);
-        const bool anynan = __syncthreads_or(nan);
-        if (tid == 0) ir_store(&pnb[b], anynan ? __longlong_as_double(0x7ff8000000000000ll) : mx);
+        mx = block_norm_or_nan(mx, nan, red);
+        if (tid == 0) ir_store(&pnb[b], mx);
     }
     bool pending = false;   // a candidate whose residual partials have been stored but not yet reduced
     // Where the iterates live.  Round 0's candidate x0 stays in the threads' REGISTERS (xk) when a round can follow: it
@@ -1773,20 +1641,9 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
             }
             if (tid == 0) {
                 // the k x k top part of both sweeps, by every workgroup alike (k <= 8)
-                // (y in LDS, st.dxt: a private array indexed by a loop variable lives in scratch memory, and its
-                // reloads sat on the critical path right behind the barrier)
-                for (int i = 0; i < k; ++i) {
-                    double sacc = (round == 0 ? st.btop[i] : st.rtop[i]) - st.pubv[i];
-                    for (int j = 0; j < i; ++j) sacc -= st.ltt[i * 8 + j] * st.dxt[j];
-                    st.dxt[i] = sacc;
-                }
-                for (int i = k - 1; i >= 0; --i) {
-                    double sacc = st.dxt[i] * st.dinvt[i];
-                    for (int j = i + 1; j < k; ++j) sacc -= st.ltt[j * 8 + i] * st.dxt[j];
-                    st.dxt[i] = sacc;
-                }
-                for (int i = 0; i < k; ++i)
-                    st.candt[i] = round == 0 ? st.dxt[i] : 1.0 * st.curt[i] + 1.0 * st.dxt[i];
+                ir_top_solve(k, [&](int i) { return (round == 0 ? st.btop[i] : st.rtop[i]) - st.pubv[i]; }, st.ltt, st.dinvt,
+                             st.dxt);
+                for (int i = 0; i < k; ++i) st.candt[i] = ir_top_cand(round, st.curt[i], st.dxt[i]);
             }
         }
         __syncthreads();
@@ -1857,14 +1714,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
 #pragma unroll
                 for (int u = 0; u < NPT; ++u) {
                     const int i = tid + u * TW;
-                    if (i < nloc) {
-                        const int o = rw.orig(i);
-                        if (o < ir.n) {
-                            if (ir.lhsx) ir.lhsx[o] = c[u];
-                        } else if (o < ir.n + ir.m) {
-                            if (ir.lhsz) ir.lhsz[o - ir.n] = c[u];
-                        }
-                    }
+                    if (i < nloc) ir_put(ir, rw.orig(i), c[u]);
                 }
                 spec_done = true;
             }
@@ -1873,15 +1723,10 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
             double mx = 0.0;
             bool nan = false;
 #pragma unroll
-            for (int u = 0; u < NPT; ++u) {
-                if (tid + u * TW < nloc) {
-                    if (c[u] != c[u]) nan = true;
-                    else mx = fmax(mx, fabs(c[u]));
-                }
-            }
-            mx = block_max(mx, red);
-            const bool anynan = __syncthreads_or(nan);
-            if (tid == 0) ir_store(&pn[(size_t)par * nb + b], anynan ? __longlong_as_double(0x7ff8000000000000ll) : mx);
+            for (int u = 0; u < NPT; ++u)
+                if (tid + u * TW < nloc) norm_take(c[u], mx, nan);
+            mx = block_norm_or_nan(mx, nan, red);
+            if (tid == 0) ir_store(&pn[(size_t)par * nb + b], mx);
         } else {
             stamp();
             irs_symv<TW, NPT, NLP>(v, ir, st.runs, c, more_possible, xs, red, tacc3, k, s0, nloc, nleaf, st.candt,
@@ -1908,7 +1753,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
     if (ok) {
         // the last candidate is on its way already (spec_done) and the verdict accepted it: nothing to do; else the
         // accepted iterate from the registers (x0) or from xa / xb
-        const bool accepted_last = __builtin_amdgcn_readfirstlane(st.pad) != 0;
+        const bool accepted_last = __builtin_amdgcn_readfirstlane(st.accept) != 0;
         if (!(spec_done && accepted_last)) {
             const int tid = opaque_tid();
             const double *cur = __builtin_amdgcn_readfirstlane(st.sel) ? ir.xb : ir.xa;
@@ -1923,24 +1768,10 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
 #pragma unroll
             for (int u = 0; u < NPT; ++u) {
                 const int i = tid + u * TW;
-                if (i < nloc) {
-                    const int o = rw.orig(i);
-                    if (o < ir.n) {
-                        if (ir.lhsx) ir.lhsx[o] = xk[u];
-                    } else if (o < ir.n + ir.m) {
-                        if (ir.lhsz) ir.lhsz[o - ir.n] = xk[u];
-                    }
-                }
+                if (i < nloc) ir_put(ir, rw.orig(i), xk[u]);
             }
         }
-        if (b == 0 && tid < k) {
-            const int o = ir.perm[NF + tid];
-            if (o < ir.n) {
-                if (ir.lhsx) ir.lhsx[o] = st.curt[tid];
-            } else if (o < ir.n + ir.m) {
-                if (ir.lhsz) ir.lhsz[o - ir.n] = st.curt[tid];
-            }
-        }
+        if (b == 0 && tid < k) ir_put(ir, ir.perm[NF + tid], st.curt[tid]);
     }
     if (b == 0 && tid == 0) {
         ir.res[0] = ok ? 1 : -1; // (0 = the kernel never got here)

@@ -127,7 +127,7 @@ __device__ __forceinline__ void bundle_symv_body(const BundleView &bv, const int
         const bool anynan = __syncthreads_or(nan);
         // (device-coherent stores: read by another workgroup inside the same launch, see ir_arrive_wait)
         if (threadIdx.x == 0)
-            __hip_atomic_store(out_norm, anynan ? __longlong_as_double(0x7ff8000000000000ll) : m, __ATOMIC_RELAXED,
+            __hip_atomic_store(out_norm, norm_or_nan(m, anynan), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
         if (fold.k == 1) {
             tpart = block_sum(tpart, red);
@@ -266,7 +266,7 @@ __device__ __forceinline__ void bundle_symv_split(const BundleView &bv, const in
     m = block_max(m, red);
     const bool anynan = __syncthreads_or(nan);
     if (threadIdx.x == 0)
-        __hip_atomic_store(out_norm, anynan ? __longlong_as_double(0x7ff8000000000000ll) : m, __ATOMIC_RELAXED,
+        __hip_atomic_store(out_norm, norm_or_nan(m, anynan), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     if (k == 1) {
         tpart = block_sum(tpart, red);

@@ -84,6 +84,7 @@ inline hipError_t raise_dynamic_lds(const void *fn, size_t bytes) {
 
 __device__ __forceinline__ double wave_sum_all(double v);
 __device__ __forceinline__ double wave_max_all(double v);
+__device__ __forceinline__ double nan_marker();
 // sum / max over the 64 lanes of a wavefront (every lane receives the result)
 __device__ __forceinline__ double wave_sum(double v) { return wave_sum_all(v); }
 // The same sum by data-parallel-primitive moves inside the vector ALU (row_shr 1, 2, 4, 8 inside the rows of 16
@@ -196,7 +197,7 @@ __device__ __forceinline__ double static_eps(const LdlView &v, bool *on, double 
         const int nanflag = *(const int *)(v.eps_slots + (size_t)NRM_SLOTS * NRM_STRIDE);
         m = wave_max_all(m);
         m = fmax(m, v.eps_static_max);
-        if (nanflag || v.eps_static_max != v.eps_static_max) m = __longlong_as_double(0x7ff8000000000000ll);
+        if (nanflag || v.eps_static_max != v.eps_static_max) m = nan_marker();
         const double eps = v.eps_c + v.eps_prop * m;
         if (lane == 0) *share = eps;
         return eps;
@@ -286,6 +287,9 @@ __device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v
 }
 
 __device__ __forceinline__ double nanmax(double a, double b) { return (a != a || b != b) ? (a != a ? a : b) : fmax(a, b); }
+// "this norm is NaN": the quiet NaN that stands for a norm over values of which at least one was NaN (fmax drops them)
+__device__ __forceinline__ double nan_marker() { return __longlong_as_double(0x7ff8000000000000ll); }
+__device__ __forceinline__ double norm_or_nan(double m, bool anynan) { return anynan ? nan_marker() : m; }
 
 } // namespace
 

@@ -185,7 +185,7 @@ __device__ __forceinline__ double lds_block_nanmax(double m, bool bad, double *r
     const bool wbad = __ballot(bad) != 0ull;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     lds_barrier(); // (red may still be read from an earlier call)
-    if (lane == 0) red[wv] = wbad ? __longlong_as_double(0x7ff8000000000000ll) : m;
+    if (lane == 0) red[wv] = norm_or_nan(m, wbad);
     lds_barrier();
     double t = red[0];
     for (int i = 1; i < (int)(blockDim.x >> 6); ++i) t = nanmax(t, red[i]);

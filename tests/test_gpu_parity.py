@@ -1338,6 +1338,26 @@ def test_grouped_fold_ragged_forest(hip, oracle, late, monkeypatch):
     assert ks2.work_model()["fold_groups"] == 0
 
 
+@pytest.mark.parametrize("case", ["1024", "512_grouped"])
+def test_fused_solve_wide_workgroups(hip, oracle, case, monkeypatch):
+    """k_bundle_ir in the workgroup sizes the other tests do not select, entry-parallel sweeps and residual, for bundles
+    of 6000 nodes (four 256-thread workgroups do not fit a CU's LDS): 1024 threads for whole trees, at most one per CU,
+    no fold; 512 threads in the grouped form for a forest of more such bundles than CUs, every tree cut in two with its
+    top folded.  Against the oracle, rounds included.  (1024 threads in the grouped form: no shape found that selects
+    it -- by default the trees of a forest with that few bundles are cut into many small ones, which take 256 threads,
+    and with CHIP_GROUPFOLD_MIN raised the same forest is not grouped at all.)"""
+    if case == "1024":
+        monkeypatch.setenv("CHIP_NO_GROUPFOLD", "1")
+        pr, tw, groups = problems.batched_socp(4, 2000, 2, seed=100), 1024, 0
+    else:
+        pr, tw, groups = problems.batched_socp(129, 4000, 2, seed=100), 512, 129
+    ks, ko = _check_update_and_solve(hip, oracle, pr, nrhs=2)
+    wm = ks.work_model()
+    assert wm["fused_threads"] == tw and wm["fold_groups"] == groups, wm
+    assert ks.step_kernels() == 0 and ks.fused_fallbacks() == 0
+    assert ks.linear_solver_info().last_ir_iterations == ko.last_ir_iters
+
+
 @pytest.mark.parametrize("which", ["arrow", "forest", "qp", "expcone"])
 def test_update_scaled_enqueue_matches_the_two_calls(hip, oracle, which):
     """chip_kkt_update_scaled_enqueue = cones.update_scaling + the KKT update as one enqueue (core/solver.rs:334-352): the

@@ -27,6 +27,16 @@ DESIGNED = {
     "14k_snode_extendE": ("snode.hip", 4, 64),
     "19k_snode_extend_wideILi4E": ("snode.hip", 2, 0),  # two workgroups of 4 waves per CU, 128 accumulator registers
     "12k_bundle_irsILi256ELi4E": ("bundle_ir.hip", 4, 96),  # 1000 co-resident workgroups of 256 threads: four per CU
+    # the general fused solve <threads, grouped fold>: 256 / 1024 threads on 128 registers, 512 threads on 80 (three
+    # workgroups per CU); the step kernel's register-resident form <LR, UR, NR>: four workgroups of 256 threads per CU
+    "11k_bundle_irILi256ELb0E": ("bundle_ir.hip", 4, 80),
+    "11k_bundle_irILi256ELb1E": ("bundle_ir.hip", 4, 96),
+    "11k_bundle_irILi1024ELb0E": ("bundle_ir.hip", 4, 80),
+    "11k_bundle_irILi1024ELb1E": ("bundle_ir.hip", 4, 96),
+    "11k_bundle_irILi512ELb0E": ("bundle_ir.hip", 6, 268),
+    "11k_bundle_irILi512ELb1E": ("bundle_ir.hip", 6, 292),
+    "13k_gstep_solveILi6ELi8ELi3E": ("bundle_gstep.hip", 4, 20),
+    "13k_gstep_solveILi8ELi10ELi4E": ("bundle_gstep.hip", 4, 68),
     "11k_dblk_symvILi1E": ("algebra.hip", 4, 0),
     "11k_dblk_symvILi2E": ("algebra.hip", 4, 0),     # two vectors: still two workgroups of 8 waves per CU
 }
