@@ -430,7 +430,8 @@ def test_psd_scaling_failure_reported(hip):
 @pytest.mark.parametrize("strategy", [0, 1])
 def test_mixed_conic_exp_pow_on_device(hip, oracle, strategy):
     """Exponential / Power cone scalings computed ON THE DEVICE (expcone.rs:106-124,
-    powcone.rs:99-117, nonsymmetric_common.rs:53-143), both scaling strategies"""
+    powcone.rs:99-117, nonsymmetric_common.rs:53-143), both scaling strategies
+    (the kernels on every size path, late iterates and branch points: tests/test_nonsym_passes_gpu.py)"""
     pr = problems.mixed_conic(seed=11)
     ks, ko, cones = _solvers(hip, oracle, pr)
     mu = 0.43
@@ -956,7 +957,8 @@ def test_cone_step_operations(hip, oracle, late):
 def test_nonsymmetric_cone_step_operations(hip, oracle, strategy):
     """Exponential / Power cones mixed with Zero / NN / SOC: affine_ds, combined_ds_shift (3rd-order
     correction, expcone.rs:254-308 / powcone.rs:260-337), ds_from_dz_offset, step_length (backtracking
-    after the symmetric cones, compositecone.rs:300-340), compute_barrier, unit_initialization"""
+    after the symmetric cones, compositecone.rs:300-340), compute_barrier, unit_initialization
+    (the kernels on every size path, late iterates and branch points: tests/test_nonsym_passes_gpu.py)"""
     pr = problems.mixed_conic(nexp=300, npow=300, seed=21)
     P = hip.CscMatrix(pr["n"], pr["n"], *pr["P"])
     A = hip.CscMatrix(pr["m"], pr["n"], *pr["A"])
@@ -1085,7 +1087,8 @@ def test_psd_cone_operations(hip, oracle, dim):
 
 def test_genpow_cone_on_device(hip, oracle):
     """GenPowerCone (genpowcone.rs): dual scaling, Hs diagonal + the [q, r, p] sparse expansion written
-    into K (datamaps.rs:322-343), mul_Hs, step operations, barrier; vs the oracle, plus a KKT solve"""
+    into K (datamaps.rs:322-343), mul_Hs, step operations, barrier; vs the oracle, plus a KKT solve
+    (the kernels on every size path, late iterates and branch points: tests/test_nonsym_passes_gpu.py)"""
     rng = np.random.default_rng(77)
     cones, s_parts, z_parts = [(1, 5)], [rng.uniform(0.5, 2, 5)], [rng.uniform(0.5, 2, 5)]
     for d1, d2 in ((2, 1), (3, 2), (6, 4), (40, 25)):
