@@ -1056,12 +1056,28 @@ __global__ __launch_bounds__(FFWG) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     stamp();
     static_eps_epilogue(v, eps);
 }
-__global__ void k_fold_top_pivot(LdlView v, FoldView fold) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__global__ void k_fold_top_pivot(LdlView v, FoldView fold, MailboxMirror mm) {
+    if (blockIdx.x != 0) return;
+    // the 16 slots of the pivot's shares in ONE trip (lanes 0..15 load, lane 0 sums in slot order) -- thread 0 alone
+    // walked them as 16 loads behind one another
+    static_assert(FOLD_SLOTS <= 64, "one lane per slot");
+    const int lane = threadIdx.x;
+    double share = 0.0;
+    if (lane < FOLD_SLOTS) {
+        double *a = &fold.acc[fold_acc_index(2, 0, lane)];
+        share = *a;
+        *a = 0.0;
+    }
+    double shares[FOLD_SLOTS];
+#pragma unroll
+    for (int q = 0; q < FOLD_SLOTS; ++q)
+        shares[q] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(share), q), __builtin_amdgcn_readlane(__double2loint(share), q));
+    if (lane != 0) return;
     // the top column's initial pivot: as k_scatter_init left it in D, or -- fast preparation (fold.top_k) -- K's diagonal
     // entry shifted by the static regulariser the bundle factorisation published (LdlView::eps_out).
-    // (Folding this into the bundle kernel as a last-arriver epilogue was measured: inlined it cost that kernel 40 %,
-    // out of line 170 %, although one thread runs it once.)
+    // (Folding this into the bundle kernel as a last-arriver epilogue was measured: inlined it cost k_bundle_factor_flat
+    // 40 %, out of line 170 %, although one thread runs it once; in k_bundle_factor_runs -- a barrier, a release fence and
+    // an arrival per workgroup, 61 VGPRs and no scratch as before -- the launch went from 51.7 to 93.4 us.)
     double d;
     if (fold.top_k) {
         d = fold.top_k[0];
@@ -1069,12 +1085,23 @@ __global__ void k_fold_top_pivot(LdlView v, FoldView fold) {
     } else {
         d = v.D[fold.NF];
     }
-    for (int q = 0; q < FOLD_SLOTS; ++q) {
-        double *a = &fold.acc[fold_acc_index(2, 0, q)];
-        d -= *a;
-        *a = 0.0;
-    }
+#pragma unroll
+    for (int q = 0; q < FOLD_SLOTS; ++q) d -= shares[q];
     (void)pivot_rule(v, fold.NF, d);
+    if (mm.h_eps) {
+        // this launch is the update's last: its verdict words, as they now stand in the device mailbox (this thread's own
+        // writes above included: fenced, then read past the caches), once more into the host's mirror -- plain stores
+        __threadfence();
+        const double eps = __hip_atomic_load(mm.eps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        int w[5];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) w[q] = __hip_atomic_load(mm.status + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        w[4] = __hip_atomic_load(mm.soc_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *mm.h_eps = eps;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mm.h_status[q] = w[q];
+        *mm.h_soc_fail = w[4];
+    }
 }
 
 // B: a column with a huge row count (> 16384 contributions).  Each workgroup
@@ -1208,8 +1235,8 @@ void factor_T(hipStream_t s, const LdlView &v, ListView c) {
 void factor_W(hipStream_t s, const LdlView &v, ListView c) {
     if (c.count) k_factor_W<<<c.count, 1024, 0, s>>>(v, c.idx, c.count);
 }
-void fold_top_pivot(hipStream_t s, const LdlView &v, const FoldView &fold) {
-    if (fold.k == 1) k_fold_top_pivot<<<1, 64, 0, s>>>(v, fold);
+void fold_top_pivot(hipStream_t s, const LdlView &v, const FoldView &fold, const MailboxMirror &mm) {
+    if (fold.k == 1) k_fold_top_pivot<<<1, 64, 0, s>>>(v, fold, mm);
 }
 static size_t factor_lds_bytes(int lds_doubles) { return ((size_t)lds_doubles * sizeof(double) + 15) & ~(size_t)15; }
 bool bundle_factor_lds_ok(int lds_doubles) {

@@ -1311,6 +1311,11 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
     symv_close<true>(m, nan, tpart, k, tid, tacc3, red, out_norm, out_share);
 }
 
+// a grid barrier of k_bundle_irs ran out of its budget: said in the ring slot and in its host mirror
+__device__ __forceinline__ void irs_flag_timeout(const IrView &ir) {
+    ir.res[2] = 1;
+    if (ir.res_host) ir.res_host[2] = 1;
+}
 template <int TW, int NLP>
 __global__ __launch_bounds__(TW) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
@@ -1371,6 +1376,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
         if (b == 0) {
             ir.res[0] = 0; // "did not finish" until the verdict is written at the very end
             ir.res[2] = 0;
+            if (ir.res_host) ir.res_host[0] = 0, ir.res_host[2] = 0; // (the host's mirror of the slot: plain stores)
         }
     }
     if (tid < 64) {
@@ -1630,7 +1636,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
             stamp();
             if (round == 0) load_top_constants();
             if (barrier(true, pending, par ^ 1, round == 1, true) == IR_TIMEOUT) {
-                if (tid == 0) ir.res[2] = 1;
+                if (tid == 0) irs_flag_timeout(ir);
                 return;
             }
             stamp();
@@ -1739,7 +1745,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
         if (folded && more_possible) continue; // (the verdict rides on the next round's barrier)
         stamp();
         if (barrier(false, true, par, round == 0, false) == IR_TIMEOUT) {
-            if (tid == 0) ir.res[2] = 1;
+            if (tid == 0) irs_flag_timeout(ir);
             return;
         }
         stamp();
@@ -1777,6 +1783,11 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
         ir.res[0] = ok ? 1 : -1; // (0 = the kernel never got here)
         ir.res[1] = st.rounds;
         ir.res[3] = st.sel;
+        if (ir.res_host) { // ... and once more where the host reads it without a copy (plain stores)
+            ir.res_host[0] = ok ? 1 : -1;
+            ir.res_host[1] = st.rounds;
+            ir.res_host[3] = st.sel;
+        }
         pub[64] = st.normb;
         pub[65] = st.norme;
     }

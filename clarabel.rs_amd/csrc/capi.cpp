@@ -978,6 +978,8 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
                 sf = dev::irs_bundle_ok(nloc, nleaf, nlev, rp[(size_t)b + 1] - rp[(size_t)b]);
             }
             h->ir_sf = sf && dev::bundle_irs_capacity_ok(E.bundles);
+            // (update and solves each end in a launch that can leave its verdict in the host's mirror of the mailbox)
+            E.mb_mirror_on = h->ir_sf && E.fold.k == 1 && E.fast_prep_ok;
             if (h->ir_sf && !switches().no_shared_pattern && (rc = E.upload_patterns(pat))) return rc;
             // (the records carry the offsets of the shared arrays: only beside them, or with offsets 0 without them)
             if (h->ir_sf && !h->h_irs_desc.empty() && (E.pat_off != nullptr) == pat_shared &&
@@ -1083,6 +1085,7 @@ int32_t chip_kkt_update_scaling_dev(chip_kkt *h, const double *s_dev, const doub
     dev::gpw_update_scaling(E.stream, h->gpw, z_dev, mu);
     dev::psd_update_scaling(E.stream, h->psd, s_dev, z_dev);
     CHIP_HIP(hipGetLastError());
+    E.note_mailbox_writer(false); // (the cones' verdict is in the device mailbox alone)
     h->scaling_pending_check = h->soc.ncones > 0 || h->psd.ncones > 0; // verdict folded into the next update()
     return 1;
 }
@@ -1194,8 +1197,28 @@ int32_t chip_kkt_update_scaled_enqueue(chip_kkt *h, const double *s_dev, const d
     // Nonnegative rows: an empty grid) and when the factor kernel that reads the slots is the one that will run
     const bool cone_clears = E.fast_prep_ok && !switches().no_fast_prep && (h->soc.ncones + h->nn_count) > 0 &&
                              (E.gstep_factor_on || !switches().no_factor_flat);
-    dev::sym_scale_write(E.stream, h->soc, h->nn_rows, h->nn_hsidx, h->nn_count, s_dev, z_dev, h->d_w, h->d_lam, h->mapHs, E.Kx,
+    dev::SocView sview = h->soc;
+    long long *sdbg = nullptr;
+    if (switches().ir_debug >= 3 && sview.ncones > 0) { // stamps of every cone workgroup -> <CHIP_IR_DEBUG_FILE>.scale
+        (void)hipMalloc((void **)&sdbg, (size_t)sview.ncones * 32 * sizeof(long long));
+        (void)hipMemsetAsync(sdbg, 0, (size_t)sview.ncones * 32 * sizeof(long long), E.stream);
+    }
+    sview.dbg = sdbg;
+    dev::sym_scale_write(E.stream, sview, h->nn_rows, h->nn_hsidx, h->nn_count, s_dev, z_dev, h->d_w, h->d_lam, h->mapHs, E.Kx,
                          E.diag_slots(), cone_clears ? E.mb_dev->status : nullptr);
+    if (sdbg) {
+        (void)hipStreamSynchronize(E.stream);
+        std::vector<long long> t((size_t)sview.ncones * 32);
+        (void)hipMemcpy(t.data(), sdbg, t.size() * sizeof(long long), hipMemcpyDeviceToHost);
+        (void)hipFree(sdbg);
+        const std::string path = (switches().ir_debug_file.empty() ? std::string("/tmp/chip_ir_stamps.bin") : switches().ir_debug_file) + ".scale";
+        if (FILE *f = std::fopen(path.c_str(), "wb")) {
+            const int g = sview.ncones;
+            std::fwrite(&g, sizeof(int), 1, f);
+            std::fwrite(t.data(), sizeof(long long), t.size(), f);
+            std::fclose(f);
+        }
+    }
     CHIP_HIP(hipGetLastError());
     int rc = E.refactor_enqueue(true, nullptr, h->static_diag_max, cone_clears);
     if (rc) return rc;
@@ -1600,6 +1623,7 @@ static int fused_enqueue(chip_kkt *h, double *lhsx_dev, double *lhsz_dev, int *s
     ir.rel = E.ir_rel;
     ir.epoch = (E.ir_epoch = (E.ir_epoch + 1) & 0x3fffff); // (tags are epoch << 8 | barrier number)
     ir.res = E.ir_res + 4 * *slot;
+    ir.res_host = nullptr;
     ir.abstol = st.iterative_refinement_abstol;
     ir.reltol = st.iterative_refinement_reltol;
     ir.stopratio = st.iterative_refinement_stop_ratio;
@@ -1674,12 +1698,14 @@ static int fused_enqueue(chip_kkt *h, double *lhsx_dev, double *lhsz_dev, int *s
             ir.desc = (const dev::IrsDesc *)h->irs_desc;
             ir.sf_flags |= dev::IRS_F_DESC;
         }
+        if (E.mirror_writes()) ir.res_host = E.mb_mirror->ring + 4 * *slot; // (workgroup 0 writes the verdict there as well)
         rc = dev::bundle_ir(E.stream, lv, E.bundles, E.fold, ir, E.ir_grid, E.ir_tw, E.gfold);
     } else {
         rc = dev::bundle_ir(E.stream, E.view(), E.bundles, E.fold, ir, E.ir_grid, E.ir_tw, E.gfold);
     }
     E.prof_end(PF_IR);
     if (rc) return fail(CHIP_ERR_HIP, hip_err((hipError_t)rc, "fused solve launch"));
+    E.note_mailbox_writer(ir.res_host != nullptr);
     if (dbg_all_on) {
         (void)hipStreamSynchronize(E.stream);
         std::vector<long long> t((size_t)E.ir_grid * 32);
@@ -2377,6 +2403,9 @@ int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out
         const int flags = switches().irs_flags < 0 ? 3 : switches().irs_flags;
         *out = (h->ir_sf && h->irs_desc && !(flags & dev::IRS_F_CHAINED) && h->irs_desc_shared == shared) ? E.bundles.nb : 0;
     }
+    else if (k == "mailbox_mirror_on") *out = E.mirror_writes() ? 1 : 0;   // update and solves end in launches that write the host mirror
+    else if (k == "mailbox_copies") *out = (double)E.mailbox_copies;       // collects that copied the mailbox
+    else if (k == "mailbox_mirror_reads") *out = (double)E.mailbox_mirror_reads; // ... that read the host mirror the kernels wrote
     else return fail(CHIP_ERR_ARG, "chip_debug_counter: unknown name");
     return CHIP_OK;
 }

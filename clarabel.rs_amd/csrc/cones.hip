@@ -40,7 +40,7 @@ __device__ __forceinline__ double block_norm_tail(const double *x, int n, double
 // one cone each, the following ones a slab of Nonnegative rows (nonnegativecone.rs:77-90)
 __device__ __forceinline__ void soc_update_scaling_body(const SocView &v, const double *__restrict__ sv,
                                                         const double *__restrict__ zv, int c, double *red);
-template <bool KKT>
+template <bool KKT, bool STAMPS = false>
 __device__ __forceinline__ bool soc_scaling_reg(const SocView &v, const double *__restrict__ sv, const double *__restrict__ zv,
                                                 int c, double *red, double *Kx, unsigned long long *dslots);
 __global__ __launch_bounds__(WG) void k_sym_update_scaling(SocView v, const int *__restrict__ nn_rows, int nn,
@@ -220,6 +220,22 @@ __device__ __forceinline__ void soc_write_kkt_body(const SocView &v, double *Kx,
 // the registers, the K positions requested with the cone's data.  Returns false when the cone does not fit (dim too
 // large: the caller takes the memory-walking bodies).
 constexpr int SOC_RPT = 4;
+// diagnostics (CHIP_IR_DEBUG=3): phase boundaries of every cone workgroup of k_sym_scale_write on the 100 MHz clock, in the
+// layout of ff_stamp (bundle_factor.hip): [0] hardware id, [1..] stamps.  The stamping wave first waits for its own
+// outstanding loads and stores, so that a stamp closes the phase before it.
+__device__ __forceinline__ void soc_stamp(long long *dbg, int c, int &dbgn) {
+    if (dbg && threadIdx.x == 0 && dbgn < 31) {
+        __builtin_amdgcn_s_waitcnt(0);
+        if (dbgn == 0)
+            dbg[(size_t)c * 32] = (long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 4) |
+                                  ((long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 20) << 32);
+        dbg[(size_t)c * 32 + 1 + dbgn++] = wall_clock64();
+    }
+}
+// (the values are evaluated before the stamp that follows, not wherever the stores that use them end up)
+__device__ __forceinline__ void soc_keep(double a, double b, double c, double d, double e, double f) {
+    asm volatile("" ::"v"(a), "v"(b), "v"(c), "v"(d), "v"(e), "v"(f));
+}
 __device__ __forceinline__ double reg_norm_tail(const double (&x)[SOC_RPT], const bool (&in)[SOC_RPT], double *red) {
     double amax = 0.0;
 #pragma unroll
@@ -237,9 +253,12 @@ __device__ __forceinline__ double reg_norm_tail(const double (&x)[SOC_RPT], cons
     ss = block_sum(ss, red);
     return amax * sqrt(ss);
 }
-template <bool KKT>
+template <bool KKT, bool STAMPS>
 __device__ __forceinline__ bool soc_scaling_reg(const SocView &v, const double *__restrict__ sv, const double *__restrict__ zv,
                                                 int c, double *red, double *Kx, unsigned long long *dslots) {
+    int dbgn = 0;
+    long long *const dbg = (KKT && STAMPS) ? v.dbg : nullptr; // (the instance without stamps is the kernel as it was)
+    soc_stamp(dbg, c, dbgn);
     const int n = v.dim[c];
     if (n > 1 + SOC_RPT * WG) return false;
     const int start = v.start[c], tid = threadIdx.x;
@@ -251,6 +270,7 @@ __device__ __forceinline__ bool soc_scaling_reg(const SocView &v, const double *
     const int sidx = v.sparse_idx[c];
     const int *pmh = v.mapHs + v.hs_start[c];
     const int *pmu = (KKT && sidx >= 0) ? v.mapU + v.sp_ptr[sidx] : pmh, *pmv = (KKT && sidx >= 0) ? v.mapV + v.sp_ptr[sidx] : pmh;
+    soc_stamp(dbg, c, dbgn); // the scalar tables
 #pragma unroll
     for (int u = 0; u < SOC_RPT; ++u) {
         const int i = 1 + tid + u * WG;
@@ -265,8 +285,11 @@ __device__ __forceinline__ bool soc_scaling_reg(const SocView &v, const double *
         }
     }
     const double z0 = z[0], s0 = s[0];
+    soc_stamp(dbg, c, dbgn); // the vector loads
     const double z1n = reg_norm_tail(zr, in, red);
+    soc_stamp(dbg, c, dbgn);
     const double s1n = reg_norm_tail(sr, in, red);
+    soc_stamp(dbg, c, dbgn);
     const double zres = (z0 - z1n) * (z0 + z1n), sres = (s0 - s1n) * (s0 + s1n);
     const double zscale = zres > 0.0 ? sqrt(zres) : 0.0;
     const double sscale = sres > 0.0 ? sqrt(sres) : 0.0;
@@ -280,6 +303,7 @@ __device__ __forceinline__ bool soc_scaling_reg(const SocView &v, const double *
     for (int u = 0; u < SOC_RPT; ++u) wr[u] = mrz * zr[u] + 1.0 * (sr[u] * rs);
     const double w0a = s0 * rs + z0 / zscale;
     const double w1n = reg_norm_tail(wr, in, red);
+    soc_stamp(dbg, c, dbgn);
     const double wres = (w0a - w1n) * (w0a + w1n);
     const double wscale = wres > 0.0 ? sqrt(wres) : 0.0;
     if (wscale == 0.0) {
@@ -294,6 +318,7 @@ __device__ __forceinline__ bool soc_scaling_reg(const SocView &v, const double *
         if (in[u]) sq += wr[u] * wr[u];
     }
     const double w1sq = block_sum(sq, red);
+    soc_stamp(dbg, c, dbgn);
     const double w0 = sqrt(1.0 + w1sq);
     // lambda, socone.rs:174-184
     const double gamma = 0.5 * wscale;
@@ -308,6 +333,8 @@ __device__ __forceinline__ bool soc_scaling_reg(const SocView &v, const double *
     const double u0 = sqrt(wsq - d);
     const double u1 = alpha / u0;
     const double v1 = sqrt(2.0 * (2.0 + wsqinv) / (2.0 * wsq - wsqinv));
+    if (dbg) soc_keep(ca, cb, sc, sqz, u1, v1);
+    soc_stamp(dbg, c, dbgn); // the scalars
 #pragma unroll
     for (int u = 0; u < SOC_RPT; ++u)
         if (in[u]) {
@@ -326,6 +353,7 @@ __device__ __forceinline__ bool soc_scaling_reg(const SocView &v, const double *
         st[4] = v1;
     }
     if (!KKT) return true;
+    soc_stamp(dbg, c, dbgn); // the w / lam stores
     // ---- get_Hs negated + the sparse expansion columns (socone.rs:217-246, datamaps.rs:199-220) ----
     const double eta2 = eta * eta;
     if (sidx >= 0) {
@@ -352,12 +380,14 @@ __device__ __forceinline__ bool soc_scaling_reg(const SocView &v, const double *
         __syncthreads(); // (dense form, dim <= 4: thread 0 reads w back)
         soc_write_kkt_body(v, Kx, dslots, c);
     }
+    soc_stamp(dbg, c, dbgn); // the K stores
     return true;
 }
 
 // update_scaling and the KKT update's get_Hs scatter of the same rows in ONE launch (solver.rs:334-352 calls them back to
 // back): a cone's workgroup scales it and writes its K entries while w is hot; a slab of Nonnegative rows reads s, z once
 // and writes lambda, w and -w^2.  status: the refactor's 4 status words, cleared here (its preparation launch is skipped).
+template <bool STAMPS>
 __global__ __launch_bounds__(WG) void k_sym_scale_write(SocView v, const int *__restrict__ nn_rows,
                                                         const int *__restrict__ nn_hsidx, int nn,
                                                         const double *__restrict__ sv, const double *__restrict__ zv,
@@ -366,7 +396,7 @@ __global__ __launch_bounds__(WG) void k_sym_scale_write(SocView v, const int *__
     __shared__ double red[16];
     if (status && blockIdx.x == 0 && threadIdx.x < 4) status[threadIdx.x] = 0;
     if ((int)blockIdx.x < v.ncones) {
-        if (soc_scaling_reg<true>(v, sv, zv, blockIdx.x, red, Kx, dslots)) return;
+        if (soc_scaling_reg<true, STAMPS>(v, sv, zv, blockIdx.x, red, Kx, dslots)) return;
         soc_update_scaling_body(v, sv, zv, blockIdx.x, red);
         __syncthreads(); // (w and the cone's state, written by this workgroup, are read back below)
         soc_write_kkt_body(v, Kx, dslots, blockIdx.x);
@@ -2177,7 +2207,10 @@ void sym_scale_write(hipStream_t s, const SocView &v, const int *nn_rows, const 
                      const double *zv, double *w, double *lam, const int *mapHs, double *Kx, unsigned long long *dslots,
                      int *status_or_null) {
     const int grid = v.ncones + nn_blocks(nn);
-    if (grid) k_sym_scale_write<<<grid, WG, 0, s>>>(v, nn_rows, nn_hsidx, nn, sv, zv, w, lam, mapHs, Kx, dslots, status_or_null);
+    if (!grid) return;
+    // (the stamped instance only when stamps are asked for: it needs 26 registers more and loses a wave per SIMD)
+    if (v.dbg) k_sym_scale_write<true><<<grid, WG, 0, s>>>(v, nn_rows, nn_hsidx, nn, sv, zv, w, lam, mapHs, Kx, dslots, status_or_null);
+    else k_sym_scale_write<false><<<grid, WG, 0, s>>>(v, nn_rows, nn_hsidx, nn, sv, zv, w, lam, mapHs, Kx, dslots, status_or_null);
 }
 void sym_write_kkt(hipStream_t s, const SocView &v, const int *nn_rows, const int *nn_hsidx, int nn, const double *w,
                    const int *mapHs, double *Kx, unsigned long long *dslots) {

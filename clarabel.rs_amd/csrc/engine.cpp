@@ -846,8 +846,12 @@ int Engine::init(const Symbolic &S, const chip_settings &settings) {
     }
     if ((rc = alloc(&mb_dev, 1))) return rc;
     CHIP_HIP(hipMemset(mb_dev, 0, sizeof(Mailbox)));
-    CHIP_HIP(hipHostMalloc((void **)&mb_host, sizeof(Mailbox), hipHostMallocDefault));
+    CHIP_HIP(hipHostMalloc((void **)&mb_host, sizeof(Mailbox), hipHostMallocMapped | hipHostMallocCoherent));
     std::memset(mb_host, 0, sizeof(Mailbox));
+    if (hipHostGetDevicePointer((void **)&mb_mirror, mb_host, 0) != hipSuccess) { // (no mirror: every collect copies)
+        (void)hipGetLastError();
+        mb_mirror = nullptr;
+    }
     if (need_ring) {
         ir_res = mb_dev->ring; // (address arithmetic only)
         ir_res_host = mb_host->ring;
@@ -1225,7 +1229,16 @@ bool Engine::hs_direct_begin() {
     return true;
 }
 int Engine::read_mailbox() {
-    CHIP_HIP(hipMemcpyAsync(mb_host, mb_dev, sizeof(Mailbox), hipMemcpyDeviceToHost, stream));
+    // every launch whose words are awaited stored them into mb_host itself: complete, and visible, once the stream is idle
+    const bool mirrored = mb_pending && mb_all_mirrored && mb_mirror && !switches().no_host_mailbox;
+    mb_pending = false;
+    mb_all_mirrored = true;
+    if (mirrored) {
+        mailbox_mirror_reads++;
+    } else {
+        mailbox_copies++;
+        CHIP_HIP(hipMemcpyAsync(mb_host, mb_dev, sizeof(Mailbox), hipMemcpyDeviceToHost, stream));
+    }
     CHIP_HIP(hipStreamSynchronize(stream));
     return CHIP_OK;
 }
@@ -1289,6 +1302,7 @@ int Engine::refactor_enqueue(bool static_reg, const int *diag_idx_dev, double st
         dev::scatter_init(stream, Kx + nnzU, v2l, (int)(nnzK - nnzU), (int)nnzL, Lx, D, dsigns, eps_ptr, fill_idx, nfill,
                           mb_dev->status);
     const bool top_folded = fold.k == 1 || gfold.ng > 0;
+    bool mirrored = false; // the verdict words reach the host's mirror of the mailbox from the last launch
     prof_begin(PF_BFACTOR);
     if (gstep_factor_on && !switches().no_step_kernel) {
         // grouped fold with small bundles: bundle columns, Schur shares and the groups' k x k tops in ONE launch
@@ -1349,7 +1363,15 @@ int Engine::refactor_enqueue(bool static_reg, const int *diag_idx_dev, double st
             return CHIP_ERR_HIP;
         }
         // single top column: pivot accumulated by the bundles; grouped fold: the k x k tops from the bundles' Schur shares
-        if (fold.k == 1) dev::fold_top_pivot(stream, v, ffold); // (fast preparation: reads the top's K entry itself)
+        if (fold.k == 1) { // (fast preparation: reads the top's K entry itself)
+            // the update's last launch (nothing of the top is left to factor): with the mirror on, its verdict words go to
+            // the host from here
+            dev::MailboxMirror mm{};
+            mirrored = fast && mirror_writes() && gfold.ng == 0 && nsn <= 0 && sn_g_ntasks <= 0 && topblk.nblocks == 0;
+            if (mirrored)
+                mm = dev::MailboxMirror{&mb_dev->eps, mb_dev->status, &mb_dev->soc_fail, &mb_mirror->eps, mb_mirror->status, &mb_mirror->soc_fail};
+            dev::fold_top_pivot(stream, v, ffold, mm);
+        }
         if (gfold.ng > 0) dev::gfold_top_factor(stream, v, bundles, gfold);
     }
     const bool use_chain = !switches().no_factor_chain;
@@ -1461,6 +1483,7 @@ int Engine::refactor_enqueue(bool static_reg, const int *diag_idx_dev, double st
     }
     // (the entry-parallel bundle factorisation keeps no row-major mirror either)
     rx_valid = !ir_fused && !(factor_lds_doubles > 0 && factor_flat_ready() && !switches().no_factor_flat);
+    note_mailbox_writer(mirrored);
     return CHIP_OK;
 }
 int Engine::refactor_collect() {

@@ -186,6 +186,20 @@ struct Engine {
     int NF = 0, tree_depth = 0;
     std::vector<i32> h_level;
     Mailbox *mb_dev = nullptr, *mb_host = nullptr;
+    // mb_host is page-locked and mapped: mb_mirror is the device's address of it.  Where an update ends in the top pivot's
+    // launch (fold.k == 1, fast preparation) and k_bundle_irs takes the solves (mb_mirror_on, set by the handle), these
+    // launches store their verdict words into the mirror beside the device mailbox, and a read_mailbox() whose pending
+    // items ALL had such a writer only waits for the stream: no copy launch.  Every enqueue that leaves verdict words in
+    // the mailbox says whether it wrote the mirror too (note_mailbox_writer); anything else keeps the copy.
+    Mailbox *mb_mirror = nullptr;
+    bool mb_mirror_on = false;
+    bool mb_pending = false, mb_all_mirrored = true;
+    long long mailbox_copies = 0, mailbox_mirror_reads = 0;
+    void note_mailbox_writer(bool mirrored) {
+        mb_pending = true;
+        mb_all_mirrored = mb_all_mirrored && mirrored;
+    }
+    bool mirror_writes() const { return mb_mirror_on && mb_mirror && !switches().no_host_mailbox; }
     int *fill_idx = nullptr;
     int nfill = 0;
     long long fill_from = -1; // >= 0: Lx[fill_from .. nnzL) is cleared as a range before K's entries are scattered (host.hpp)
@@ -322,7 +336,7 @@ struct Engine {
     int zero_norm_sets(SolveCtx &c);                                         // enqueue
     int read_norm(SolveCtx &c, int set, double *out);                        // D2H + sync; NaN propagating
     int read_norms(SolveCtx &c, int first, int count, double *out);          // `count` <= 3 contiguous sets, ONE D2H copy
-    int read_mailbox();                                                      // D2H + sync
+    int read_mailbox();                                                      // (D2H, unless the mirror holds it all) + sync
     // (launch timing records on the main stream: the pair path is not taken while a family is timed)
     void prof_begin(int family);
     void prof_end(int family);

@@ -170,7 +170,16 @@ int bundle_factor(hipStream_t s, const LdlView &v, const BundleView &bv, const F
 bool bundle_factor_lds_ok(int lds_doubles);
 // ... and whether its run-coded form (k_bundle_factor_runs) takes a handle: nodes / records outside runs / levels of its largest bundle
 bool bundle_factor_runs_ok(int max_nodes, int max_leftover, int max_levels);
-void fold_top_pivot(hipStream_t s, const LdlView &v, const FoldView &fold);
+// The verdict words of an update as its LAST launch leaves them, stored a second time into page-locked host memory (plain
+// stores; the host then only waits for the stream, no copy launch): eps, status[0..3] and soc_fail of the device mailbox
+// -> the same words of its host mirror.  h_eps == nullptr: no mirror.
+struct MailboxMirror {
+    const double *eps;
+    const int *status, *soc_fail;
+    double *h_eps;
+    int *h_status, *h_soc_fail;
+};
+void fold_top_pivot(hipStream_t s, const LdlView &v, const FoldView &fold, const MailboxMirror &mm);
 // fold.k > 0: every bundle also subtracts its part of the k top rows of L from x[NF + i]
 void bundle_fwd(hipStream_t s, const LdlView &v, const BundleView &bv, double *x, const FoldView &fold);
 // the k x k top-top part of the forward sweep, D^-1, and the backward sweep, in one tiny launch
@@ -239,6 +248,7 @@ struct IrView {
     int sf_flags;          // k_bundle_irs, experiment bits (CHIP_IRS_FLAGS): IRS_F_* above
     int spec_out;          // k_bundle_irs: lhsx / lhsz do not overlap rx / rz -- the last candidate may be written before its verdict
     int sf;                // k_bundle_irs (one bundle per workgroup, the candidate in registers; bp may be nullptr: not written)
+    int *res_host;         // k_bundle_irs: the same 4 ints in page-locked host memory, written beside res (plain stores), or nullptr
 };
 int ir_rel_ints();
 int ir_ctl_ints();                 // (+ 32 per group of a grouped fold, appended: GFoldView::gcnt)
@@ -484,6 +494,7 @@ struct SocView {
     double *eta, *d;             // per-cone state
     int *fail;                   // a cone that leaves its interior stores fail_gen here (no clearing between updates)
     int fail_gen;
+    long long *dbg;              // diagnostics (CHIP_IR_DEBUG=3): 32 words per cone workgroup of k_sym_scale_write, or nullptr
 };
 // Exponential / Power cones (3-dimensional, non-symmetric): per-cone state of 18 doubles
 // = Hs[6] | H_dual[6] | grad[3] | z[3]

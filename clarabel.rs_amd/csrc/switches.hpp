@@ -52,6 +52,7 @@ struct Switches {
     std::string ir_debug_file;      // CHIP_IR_DEBUG_FILE
     bool no_step_kernel = false;    // CHIP_NO_STEP_KERNEL: the grouped-fold step kernels of round 4 off
     bool no_fast_prep = false;      // CHIP_NO_FAST_PREP: the refactor keeps its preparation launches (eps, scatter, top pivot)
+    bool no_host_mailbox = false;   // CHIP_NO_HOST_MAILBOX: every collect copies the mailbox, also where the kernels wrote the host mirror
     // ---- supernode kernels (snode.hip) ----
     int sn_xb_cap = 0;              // CHIP_SN_XB_CAP (0: default)
     int sn_debug = 0;               // CHIP_SN_DEBUG

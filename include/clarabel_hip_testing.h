@@ -26,7 +26,11 @@ int32_t chip_debug_set_switch(const char *name, const char *value_or_null);
  * slices, the bundles, bytes of the shared index arrays and of the full ones, bundles whose offsets were checked against
  * the full arrays and how many differed), "pattern_shared_bundles" (bundles whose fused solve launch reads a shared copy:
  * 0 on a host-only handle or with CHIP_NO_SHARED_PATTERN), "irs_desc_bundles" (bundles whose fused solve launch reads its
- * per-bundle record under the current switches: 0 with CHIP_IRS_FLAGS bit 4, the chained prologue).
+ * per-bundle record under the current switches: 0 with CHIP_IRS_FLAGS bit 4, the chained prologue),
+ * "mailbox_mirror_on" (1: the handle's update and
+ * solves end in launches that store their verdict words into the host mirror of the mailbox; 0 with
+ * CHIP_NO_HOST_MAILBOX), "mailbox_copies" / "mailbox_mirror_reads" (collects that copied the mailbox / that only waited
+ * for the stream and read the mirror).
  * Returns CHIP_ERR_ARG for an unknown name. */
 int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out);
 /* one int32 array of a KKT handle by name; *len <- its length; out (may be NULL) receives it.  "irs_desc": the fused
@@ -38,7 +42,8 @@ int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out
  * Symbolic::fr_bdesc, 64 ints each; empty: no runs) with the shared arrays they point into, one copy per class of
  * identical bundles: "factor_class_usr", "factor_class_col" (bit patterns of unsigned words), "factor_class_sgn",
  * "factor_class_desc" (8 ints per run), "factor_class_rec" (4 per record); chip_debug_counter: "factor_classes",
- * "factor_class_verified" (bundles compared with what their record reaches), "factor_class_mismatches".  Returns CHIP_ERR_ARG for an unknown name. */
+ * "factor_class_verified" (bundles compared with what their record reaches), "factor_class_mismatches".
+ * Returns CHIP_ERR_ARG for an unknown name. */
 int32_t chip_debug_kkt_ints(const void *kkt_handle, const char *name, int64_t *len, int32_t *out);
 /* the update records of the flat bundle factorisation (csrc/host.hpp: Symbolic::fu_rec / fr_desc) of one bundle of a
  * HOST-ONLY KKT handle, levels in order; *len <- ints; out (may be NULL) receives them.  "records": every update,
