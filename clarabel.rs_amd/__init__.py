@@ -901,6 +901,53 @@ class _DataUpdates:
         _check(getattr(lib(), name)(self._h, None if idx is None else C.c_void_p(idx.data_ptr()),
                                     C.c_void_p(vals.data_ptr()), C.c_int64(vals.numel())), name)
 
+    _REEQUILIBRATE = None
+
+    def reequilibrate(self, P, q, A, b):
+        """New FULL data on the handle's patterns, equilibrated from scratch on the device as a fresh handle would
+        equilibrate it, without a new symbolic setup (<_REEQUILIBRATE>[_dev]): afterwards the handle holds what a fresh
+        one created on these values would hold, later update()s scale with the new d, e, c, and the next solve()
+        restarts from default_start.  Each of the four is a value vector (numpy, or a torch tensor on the host or on
+        the GPU), P / A may also be a CscMatrix or a scipy matrix with the handle's pattern, and for a HipBatchSolver
+        each may be a LIST with one full entry per member.  Any GPU tensor selects the device entry point, and then all four must be GPU
+        tensors.  Everything is classified before the library is called: ChipError(ERR_DIM) for a wrong length or
+        another pattern, TypeError for a partial form, a missing piece or a mix of host and GPU data."""
+        self._check_update_allowed()
+        forms = {}
+        for k, v in (("P", P), ("q", q), ("A", A), ("b", b)):
+            if v is None:
+                raise TypeError("reequilibrate: %s is required (all four, in full)" % k)
+            if k in "PA" and hasattr(v, "tocsc"):  # a scipy matrix: held to the handle's pattern like a CscMatrix
+                v = CscMatrix.from_scipy(v)
+            f = self._classify(k, v)
+            if f[0] in ("partial", "dev_partial"):
+                # (a batch's list of full members arrives as the positions 0 .. len - 1 in order)
+                if f[0] == "dev_partial" or not np.array_equal(f[1], np.arange(self._len[k], dtype=u64)):
+                    raise TypeError("reequilibrate: %s must be given in full" % k)
+                f = ("full", None, f[2])
+            if f[0] == "none" and self._len[k] != 0:
+                raise ChipError(ERR_DIM, "reequilibrate: %s: 0 values for %d entries" % (k, self._len[k]))
+            forms[k] = f
+        on_gpu = [f[0] == "dev_full" for f in forms.values() if f[0] != "none"]
+        if any(on_gpu) and not all(on_gpu):
+            raise TypeError("reequilibrate: P, q, A, b must all be host arrays or all GPU tensors")
+        name = self._REEQUILIBRATE
+        if any(on_gpu):
+            import torch
+            dev = next(f[2].device for f in forms.values() if f[0] == "dev_full")
+            torch.cuda.current_stream(dev).synchronize()  # the values are written before the call reads them
+            pad = torch.zeros(2, dtype=torch.float64, device=dev)  # (an empty piece is still not NULL)
+            keep = [pad if forms[k][0] == "none" else forms[k][2] for k in "PqAb"]
+            name += "_dev"
+            _check(getattr(lib(), name)(self._h, *[C.c_void_p(t.data_ptr()) for t in keep]), name)
+        else:
+            keep = [np.zeros(1) if forms[k][0] == "none" else forms[k][2] for k in "PqAb"]
+            _check(getattr(lib(), name)(self._h, *[_pf(a) for a in keep]), name)
+        self._after_reequilibrate()
+
+    def _after_reequilibrate(self):
+        pass
+
     def update_settings(self, settings=None, **kw):
         """DefaultSolver::update_settings (for a HipBatchSolver: of every member): a SolverSettings, or keyword
         overrides of the current settings (linear-system fields go to .linsys).  An immutable field that differs
@@ -919,6 +966,7 @@ class HipSolver(_DataUpdates):
     (5, len(alpha), dim2, alpha))."""
 
     _UPDATE_PREFIX = "chip_problem_update_"
+    _REEQUILIBRATE = "chip_reequilibrate_problem"
 
     def __init__(self, P, q, A, b, cones, settings=None):
         n, m = P.n, A.m
@@ -1062,6 +1110,7 @@ class HipBatchSolver(_DataUpdates):
     members moves only their values."""
 
     _UPDATE_PREFIX = "chip_bdata_update_"
+    _REEQUILIBRATE = "chip_reequilibrate_bdata"
 
     def __init__(self, problems, settings=None):
         problems = list(problems)
@@ -1141,6 +1190,9 @@ class HipBatchSolver(_DataUpdates):
         if isinstance(data, list) and len(data) > 0 and not np.isscalar(data[0]):
             return batch_list_update(key, data, self._offsets[key], self._mpattern.get(key))
         return super()._classify(key, data)
+
+    def _after_reequilibrate(self):
+        self.generation += 1  # (a backward of a solve before it no longer meets its own data)
 
     def scaled_data(self):
         """the stack's data as the handle holds it after the equilibration, and the members' norms of the unscaled
@@ -1920,6 +1972,26 @@ def debug_counter(kkt, name):
     lib().chip_debug_counter.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
     _check(lib().chip_debug_counter(kkt._h, name.encode(), C.byref(out)), "debug_counter")
     return out.value
+
+
+def debug_create_count(which):
+    """test hook: how often this process entered chip_kkt_create (which = 0) / chip_kktsystem_create (1)"""
+    out = C.c_double(0.0)
+    _check(lib().chip_debug_create_count(C.c_int32(which), C.byref(out)), "chip_debug_create_count")
+    return int(out.value)
+
+
+def debug_reload_pass(src, cap=False, raw=False, misalign=0, fill=-7.0):
+    """test hook: the load pass of a re-equilibration alone on the values src (chip_debug_reload_pass).  Returns
+    (dst, raw or None, o_dst, o_raw): the whole len + 4 buffers, pre-filled with `fill`, and where the written range
+    [o, o + len) starts in each (misalign bits: 1 = dst, 2 = raw, 4 = src start 8 bytes past a 16-byte boundary)"""
+    src = _f(src)
+    dst = np.full(len(src) + 4, fill)
+    rw = np.full(len(src) + 4, fill) if raw else None
+    _check(lib().chip_debug_reload_pass(_pf(dst), None if rw is None else _pf(rw), _pf(src if len(src) else np.zeros(1)),
+                                        C.c_int64(len(src)), C.c_int32(int(cap)), C.c_int32(misalign)),
+           "chip_debug_reload_pass")
+    return dst, rw, (1 if misalign & 1 else 2), (1 if misalign & 2 else 2)
 
 
 def debug_kkt_ints(kkt, name):

@@ -199,6 +199,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     h->zoff = zoff;
     h->degree = hp.degree;
     h->has_soc = hp.has_soc;
+    h->cones = hp.cones;
     h->lp_init = lp_init;
     h->anyP = a.nnzP() > 0;
     h->anyLP = std::find(lp_init.begin(), lp_init.end(), 1) != lp_init.end();
@@ -923,6 +924,77 @@ int chip_batch::update_args(chip_batch *h, int which, const void *idx, const dou
 }
 
 CHIP_UPDATE_ENTRIES(chip_bdata_update_, chip_batch)
+
+// ---------------------------------------------------------------------------------------------------------------
+// Re-equilibration of the stack: new full data on the fixed patterns, equilibrated from d = e = 1,
+// c_k = 1 by create's own ProblemData::equilibrate on the handle's stream, then every copy and derived value of the
+// audit refreshed by the data updates' passes; the partition, chip_kkt and chip_kktsystem are left alone.  The number
+// of enqueues does not depend on nprob, and the one host synchronisation is equilibrate's own: the members' c_k, their
+// norms and max |P_ii| come back in it.
+// ---------------------------------------------------------------------------------------------------------------
+int chip_batch::reequilibrate_gate(const char *) {
+    upd_syncs = upd_launches = 0;
+    return CHIP_OK;
+}
+
+int chip_batch::reequilibrate(const double *P_dev, const double *q_dev, const double *A_dev, const double *b_dev) {
+    int rc;
+    if ((rc = update_work())) return rc;
+    const size_t np = (size_t)nprob;
+    if (!req_out && ((rc = mem.alloc(&eq_colsum, np)) || (rc = mem.alloc(&req_out, 2 * np + 3)))) return rc;
+    req_host.assign(2 * np + 3, 0.0);
+    // as after an update that changed something: no gradient and no reuse of K's factorisation until the next solve
+    solve_current = kkt_final = grad.done = tan.done = false;
+    const double te = now_s();
+    hipStream_t s = stream;
+    const dev::EqMats &M = pd.M;
+    // the raw values with the unscaled copies of q and (capped) b, and the members' norms of those copies
+    pd.reload(s, P_dev, q_dev, A_dev, b_dev, uq, ub);
+    dev::bu_norms(s, plan, 0, uq, ubpart, req_out);
+    dev::bu_norms(s, plan, 1, ub, ubpart, req_out + np);
+    CHIP_HIP(hipGetLastError());
+    upd_launches += 8;
+    auto ruiz_step = [&](unsigned long long *bits, double *cstate) {
+        dev::batch_eq_ruiz_step(s, plan, M, pd.q, pd.b, pd.d, pd.e, bits, seg_scr, eq_colsum, cstate,
+                                st.equilibrate_min_scaling, st.equilibrate_max_scaling);
+        upd_launches += 2; // (with the clear of bits)
+    };
+    rc = pd.equilibrate(s, st, cones, nprob, dev::batch_eq_bits_words(pd.n, pd.m, nprob), ruiz_step, c.data(),
+                        [&](const double *cstate) -> int {
+        // the members' cost scales on the device, then the copies the loop reads (4.14's audit), from the
+        // equilibrated arrays in place
+        CHIP_HIP(hipMemcpyAsync(dc, cstate, np * 8, hipMemcpyDeviceToDevice, s));
+        int rc1;
+        if ((rc1 = kkt_update_values_dev(kkt, UPD_P, M.Px, nullptr, M.nnzP)) ||
+            (rc1 = kkt_update_values_dev(kkt, UPD_A, M.Ax, nullptr, M.nnzA)) ||
+            (rc1 = kktsystem_update_data_dev(sys, M.Px, M.Ax, pd.q, pd.b)))
+            return rc1;
+        dev::waxpby(s, negq, -1.0, pd.q, 0.0, nullptr, pd.n);
+        dev::pu_norms(s, 4, nullptr, nullptr, 0, nullptr, nullptr, 0, M.Prow, M.Pcol, M.Px, M.nnzP, unpart,
+                      req_out + 2 * np);
+        CHIP_HIP(hipGetLastError());
+        CHIP_HIP(hipMemcpyAsync(req_host.data(), req_out, req_host.size() * 8, hipMemcpyDeviceToHost, s));
+        upd_launches += 1 + 2 + 5 + 1 + 2 + 1;
+        return (int)CHIP_OK;
+    });
+    upd_launches += 7; // d, e, cstate, the rectification, the inversion (or dinv, einv), the c_k
+    upd_syncs++;
+    if (rc) return rc;
+    normq.assign(req_host.begin(), req_host.begin() + nprob);
+    normb.assign(req_host.begin() + nprob, req_host.begin() + 2 * nprob);
+    kkt_set_static_diag_max(kkt, req_host[2 * np + 2]);
+    equilibration_time = now_s() - te;
+    return CHIP_OK;
+}
+
+int32_t chip_reequilibrate_bdata(chip_batch *h, const double *Pnzval, const double *q, const double *Anzval,
+                                 const double *b) {
+    return reequilibrate_entry("chip_reequilibrate_bdata", h, Pnzval, q, Anzval, b, true);
+}
+int32_t chip_reequilibrate_bdata_dev(chip_batch *h, const double *Pnzval_dev, const double *q_dev,
+                                     const double *Anzval_dev, const double *b_dev) {
+    return reequilibrate_entry("chip_reequilibrate_bdata_dev", h, Pnzval_dev, q_dev, Anzval_dev, b_dev, false);
+}
 
 // update_settings with validate_as_update (settings.rs:307): the immutable fields of chip_problem_update_settings
 int32_t chip_bdata_update_settings(chip_batch *h, const chip_solver_settings *settings) {

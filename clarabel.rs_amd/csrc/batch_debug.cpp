@@ -325,4 +325,32 @@ int32_t chip_debug_bplan_bunscale(void *handle, double *xo, const double *x, con
     dev::bunscale(h->stream, h->plan, dxo, dx, dd, dzo, dz, de, dso, dsv, dei, dsx, dsz);
     return st.finish(h->stream);
 }
+
+// ---- the re-equilibration's load pass (reequilibrate.hip: re_load) alone, and the create counters
+int32_t chip_debug_reload_pass(double *dst, double *raw_or_null, const double *src, int64_t len, int32_t cap,
+                               int32_t misalign) {
+    if (!dst || !src || len < 0 || len >= (1ll << 31) || misalign < 0 || misalign > 7)
+        return fail(CHIP_ERR_ARG, "chip_debug_reload_pass: bad argument");
+    if (chip_device_count() < 1) return fail(CHIP_ERR_NO_DEVICE, "chip_debug_reload_pass: no HIP device");
+    const size_t n = (size_t)len, full = n + 4;
+    DevPool mem;
+    double *ddst, *draw = nullptr, *dsrc;
+    int rc;
+    if ((rc = mem.upload(&ddst, dst, full)) || (rc = mem.alloc(&dsrc, full))) return rc;
+    if (raw_or_null && (rc = mem.upload(&draw, raw_or_null, full))) return rc;
+    const size_t od = misalign & 1 ? 1 : 2, orw = misalign & 2 ? 1 : 2, os = misalign & 4 ? 1 : 2;
+    if (n) CHIP_HIP(hipMemcpy(dsrc + os, src, n * 8, hipMemcpyHostToDevice));
+    dev::re_load(nullptr, ddst + od, draw ? draw + orw : nullptr, dsrc + os, (int)len, cap != 0);
+    CHIP_HIP(hipGetLastError());
+    CHIP_HIP(hipDeviceSynchronize());
+    CHIP_HIP(hipMemcpy(dst, ddst, full * 8, hipMemcpyDeviceToHost));
+    if (draw) CHIP_HIP(hipMemcpy(raw_or_null, draw, full * 8, hipMemcpyDeviceToHost));
+    return CHIP_OK;
+}
+
+int32_t chip_debug_create_count(int32_t which, double *out) {
+    if (which < 0 || which > 1 || !out) return fail(CHIP_ERR_ARG, "chip_debug_create_count: bad argument");
+    *out = (double)create_count(which);
+    return CHIP_OK;
+}
 #endif

@@ -109,7 +109,13 @@ struct chip_batch {
     int64_t *clean = nullptr;
     size_t clean_cap = 0;
     std::vector<double> unorm;
-    long upd_syncs = 0, upd_launches = 0; // of the last update call
+    long upd_syncs = 0, upd_launches = 0; // of the last update or re-equilibration call
+    // a re-equilibration (chip_reequilibrate_bdata) runs create's Ruiz loop again: the cones it rectifies, the column
+    // sums of a Ruiz step, and what its one synchronisation reads back ([normq nprob][normb nprob][-, -, max |P_ii|]);
+    // the two buffers are allocated by the first one
+    std::vector<ConeSpec> cones;
+    double *eq_colsum = nullptr, *req_out = nullptr;
+    std::vector<double> req_host;
     // the derivatives (chip_bgrad_*, chip_bjvp_*).  solve_current: the last solve ran on the data
     // the handle holds now; kkt_final: K is factored at the final iterates of that solve (by a backward or an apply),
     // so an apply needs no scaling update and no refactor
@@ -198,6 +204,11 @@ struct chip_batch {
         return stage.upload(stream, idx, vals, k, &upd_launches, &upd_syncs);
     }
     int update(int which, const int64_t *idx_dev, const double *vals_dev, int k);
+    int reequilibrate_gate(const char *fn);
+    int stage_upload4(const double *const src[4], const size_t len[4], const double *at[4]) {
+        return stage.upload4(stream, src, len, at, &upd_launches, &upd_syncs);
+    }
+    int reequilibrate(const double *P_dev, const double *q_dev, const double *A_dev, const double *b_dev);
     int backward_work();
     int backward(const double *gx_dev, const double *gz_dev, const double *gs_dev);
     int jvp_work();

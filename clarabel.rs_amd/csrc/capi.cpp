@@ -623,6 +623,9 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
                         const uint64_t *perm_or_null) {
     if (!out || n < 0 || m < 0 || !Pcolptr || !Acolptr) return fail(CHIP_ERR_ARG, "chip_kkt_create: bad argument");
     *out = nullptr;
+#ifdef CHIP_TESTING
+    create_count(0)++;
+#endif
     switches_reload(); // the CHIP_* diagnostic switches are read from the environment here, never in a launch loop
     chip_settings st;
     if (settings) st = *settings;

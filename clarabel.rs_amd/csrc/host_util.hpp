@@ -53,6 +53,15 @@ template <typename T> int grow_dev(T **buf, size_t *cap, size_t need, hipStream_
     return CHIP_OK;
 }
 
+#ifdef CHIP_TESTING
+// test build only: how often chip_kkt_create (0) and chip_kktsystem_create (1) were entered in this process
+// (chip_debug_create_count: a re-equilibration must make neither)
+inline long &create_count(int which) {
+    static long counts[2] = {0, 0};
+    return counts[which];
+}
+#endif
+
 // ---- the data updates' front end ------------------------------------------------------------------------------------
 enum { UPD_P = 0, UPD_A = 1, UPD_Q = 2, UPD_B = 3 };
 // the entry point's name in error texts: prefix "chip_problem_update_" or "chip_bdata_update_" + P / A / q / b
@@ -73,6 +82,24 @@ struct UpdateStage {
         // (an index past 2^63 - 1 reads as negative and is refused like any other out-of-range index)
         if (idx) CHIP_HIP(hipMemcpyAsync(i, idx, k * sizeof(int64_t), hipMemcpyHostToDevice, s));
         if (launches) *launches += idx ? 2 : 1;
+        return CHIP_OK;
+    }
+    // the host form of a re-equilibration: the four arrays P, q, A, b one after the other in v, each starting on a
+    // 16-byte boundary; at[j]: where array j went.  One enqueue per non-empty array
+    int upload4(hipStream_t s, const double *const src[4], const size_t len[4], const double *at[4],
+                long *launches = nullptr, long *syncs = nullptr) {
+        size_t off[4], total = 0;
+        for (int j = 0; j < 4; j++) {
+            off[j] = total;
+            total += (len[j] + 1) & ~(size_t)1;
+        }
+        if (int rc = grow_dev(&v, &v_cap, std::max<size_t>(total, 2), s, syncs)) return rc;
+        for (int j = 0; j < 4; j++) {
+            at[j] = v + off[j];
+            if (!len[j]) continue;
+            CHIP_HIP(hipMemcpyAsync(v + off[j], src[j], len[j] * sizeof(double), hipMemcpyHostToDevice, s));
+            if (launches) ++*launches;
+        }
         return CHIP_OK;
     }
     UpdateStage() = default;
@@ -128,6 +155,25 @@ template <typename H> int update_dev(H *h, int which, const int64_t *idx, const 
     CHIP_UPDATE_ENTRY(prefix, H, A, chip::UPD_A)    \
     CHIP_UPDATE_ENTRY(prefix, H, q, chip::UPD_Q)    \
     CHIP_UPDATE_ENTRY(prefix, H, b, chip::UPD_B)
+
+// the two forms of a re-equilibration of handle type H (chip_reequilibrate_problem / chip_reequilibrate_bdata and their
+// _dev forms): CHIP_ERR_ARG before any device is touched, the handle's own refusal (reequilibrate_gate(fn), which also
+// resets its counters), the host form's upload into the handle's staging (stage_upload4), then the device path
+// h->reequilibrate(P, q, A, b).  The lengths are those of the handle's patterns
+template <typename H>
+int reequilibrate_entry(const char *fn, H *h, const double *P, const double *q, const double *A, const double *b,
+                        bool host) {
+    if (!h || !P || !q || !A || !b) return fail(CHIP_ERR_ARG, std::string(fn) + ": bad argument");
+    if (int rc = h->reequilibrate_gate(fn)) return rc;
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    const double *src[4] = {P, q, A, b}, *at[4] = {P, q, A, b};
+    if (host) {
+        const size_t len[4] = {(size_t)h->pd.update_len(UPD_P), (size_t)h->pd.update_len(UPD_Q),
+                               (size_t)h->pd.update_len(UPD_A), (size_t)h->pd.update_len(UPD_B)};
+        if (int rc = h->stage_upload4(src, len, at)) return rc;
+    }
+    return h->reequilibrate(at[0], at[1], at[2], at[3]);
+}
 
 // validate_as_update (settings.rs:307) for chip_problem_update_settings / chip_bdata_update_settings (fn: the caller's
 // name in the error text): copies the two line-search fields into nw.linsys as create does (create_settings,

@@ -151,6 +151,9 @@ int32_t chip_kktsystem_create(chip_kktsystem **out, chip_kkt *kkt, const uint64_
                               const double *Anzval, const double *q, const double *b) {
     if (!out || !kkt || !Pcolptr || !Acolptr) return CHIP_ERR_ARG;
     *out = nullptr;
+#ifdef CHIP_TESTING
+    create_count(1)++;
+#endif
     if (kkt_host_only(kkt)) return fail(CHIP_ERR_NO_DEVICE, "host-only handle: no numeric work without a GPU");
     int64_t dims[8];
     int rc = chip_kkt_dims(kkt, dims);

@@ -12,6 +12,7 @@
 #include "equilibrate.hpp"
 #include "host_util.hpp"
 #include "ipm_info.hpp"
+#include "reequilibrate.hpp"
 
 namespace chip {
 
@@ -114,27 +115,37 @@ struct ProblemData {
     // DefaultProblemData::equilibrate (problemdata.rs:231-312) on stream s: every Ruiz step enqueued without a host
     // synchronisation, the ncost cost scales (1, or one per member) on the device until the end, then in c_out.
     // ruiz_step(bits, cstate) enqueues one step on s: bits are nbits words, cleared here before every step; cstate is
-    // [c_k][the step's factor_k], 2 ncost doubles starting at 1
+    // [c_k][the step's factor_k], 2 ncost doubles starting at 1.  tail(cstate) runs once everything else is enqueued
+    // and before the one synchronisation: what the caller wants done on s, and read back, in the same wait (a
+    // re-equilibration's refresh passes; a create passes nothing).  Every write, the initial ones of d, e and cstate
+    // included, is ordered on s, so work a live handle still has in flight on s is never overtaken
     template <typename RuizStep>
     int equilibrate(hipStream_t s, const chip_solver_settings &st, const std::vector<ConeSpec> &cones, int ncost,
                     size_t nbits, RuizStep ruiz_step, double *c_out) {
+        return equilibrate(s, st, cones, ncost, nbits, ruiz_step, c_out, [](const double *) { return 0; });
+    }
+    template <typename RuizStep, typename Tail>
+    int equilibrate(hipStream_t s, const chip_solver_settings &st, const std::vector<ConeSpec> &cones, int ncost,
+                    size_t nbits, RuizStep ruiz_step, double *c_out, Tail tail) {
         const std::vector<double> ones((size_t)std::max({n, m, 2 * ncost}), 1.0);
-        if (n) CHIP_HIP(hipMemcpy(d, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-        if (m) CHIP_HIP(hipMemcpy(e, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
+        if (n) CHIP_HIP(hipMemcpyAsync(d, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+        if (m) CHIP_HIP(hipMemcpyAsync(e, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
         std::fill(c_out, c_out + ncost, 1.0);
-        if (!st.equilibrate_enable) {
-            if (n) CHIP_HIP(hipMemcpy(dinv, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-            if (m) CHIP_HIP(hipMemcpy(einv, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice));
-            return CHIP_OK;
-        }
         DevPool work;
-        unsigned long long *bits = nullptr;
-        double *cstate = nullptr, *delta = nullptr;
+        double *cstate = nullptr;
         int rc;
-        if ((rc = work.alloc(&bits, nbits)) || (rc = work.alloc(&cstate, 2 * (size_t)ncost)) ||
-            (rc = work.alloc(&delta, (size_t)m)))
+        if ((rc = work.alloc(&cstate, 2 * (size_t)ncost))) return rc;
+        CHIP_HIP(hipMemcpyAsync(cstate, ones.data(), 2 * (size_t)ncost * 8, hipMemcpyHostToDevice, s));
+        if (!st.equilibrate_enable) {
+            if (n) CHIP_HIP(hipMemcpyAsync(dinv, ones.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+            if (m) CHIP_HIP(hipMemcpyAsync(einv, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
+            rc = tail(cstate);
+            CHIP_HIP(hipStreamSynchronize(s));
             return rc;
-        CHIP_HIP(hipMemcpy(cstate, ones.data(), 2 * (size_t)ncost * 8, hipMemcpyHostToDevice));
+        }
+        unsigned long long *bits = nullptr;
+        double *delta = nullptr;
+        if ((rc = work.alloc(&bits, nbits)) || (rc = work.alloc(&delta, (size_t)m))) return rc;
         for (int it = 0; it < st.equilibrate_max_iter; it++) {
             CHIP_HIP(hipMemsetAsync(bits, 0, nbits * sizeof(unsigned long long), s));
             ruiz_step(bits, cstate);
@@ -154,9 +165,19 @@ struct ProblemData {
         }
         dev::eq_invert(s, d, dinv, n, e, einv, m);
         CHIP_HIP(hipGetLastError());
-        CHIP_HIP(hipMemcpyAsync(c_out, cstate, (size_t)ncost * 8, hipMemcpyDeviceToHost, s));
+        rc = tail(cstate);
+        if (!rc) CHIP_HIP(hipMemcpyAsync(c_out, cstate, (size_t)ncost * 8, hipMemcpyDeviceToHost, s));
         CHIP_HIP(hipStreamSynchronize(s));
-        return CHIP_OK;
+        return rc;
+    }
+    // the load pass of a re-equilibration (reequilibrate.hip), enqueued on s: the caller's raw values from device
+    // memory into M.Px, M.Ax, q, b, with b capped as upload caps it; uq / ub (null: none): unscaled copies of q and b
+    void reload(hipStream_t s, const double *P_dev, const double *q_dev, const double *A_dev, const double *b_dev,
+                double *uq, double *ub) {
+        dev::re_load(s, M.Px, nullptr, P_dev, M.nnzP, false);
+        dev::re_load(s, M.Ax, nullptr, A_dev, M.nnzA, false);
+        dev::re_load(s, q, uq, q_dev, n, false);
+        dev::re_load(s, b, ub, b_dev, m, true);
     }
     // the scaled values as the handle holds them (null: not wanted), once the work on `stream` is done
     int get_scaled(hipStream_t stream, double *Px, double *Ax, double *qh, double *bh) const {

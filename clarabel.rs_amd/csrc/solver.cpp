@@ -56,6 +56,11 @@ struct chip_solver {
     int *pos = nullptr, *flag = nullptr;
     unsigned long long *npart = nullptr;
     double *nout = nullptr;
+    // a re-equilibration (chip_reequilibrate_problem) runs create's Ruiz loop again: the cones it rectifies, and the
+    // cost partials of a Ruiz step, allocated by the first one
+    std::vector<ConeSpec> cones;
+    double *eq_partials = nullptr;
+    long req_launches = 0, req_syncs = 0; // of the last re-equilibration
 
     ~chip_solver() {
         if (stream) (void)hipStreamSynchronize(stream);
@@ -87,6 +92,11 @@ struct chip_solver {
     static int update_args(chip_solver *h, int which, const void *idx, const double *vals, int64_t k);
     int stage_upload(const uint64_t *idx, const double *vals, size_t k) { return stage.upload(stream, idx, vals, k); }
     int update(int which, const int64_t *idx_dev, const double *vals_dev, int k);
+    int reequilibrate_gate(const char *fn);
+    int stage_upload4(const double *const src[4], const size_t len[4], const double *at[4]) {
+        return stage.upload4(stream, src, len, at, &req_launches, &req_syncs);
+    }
+    int reequilibrate(const double *P_dev, const double *q_dev, const double *A_dev, const double *b_dev);
     double t_solve0 = 0;
 };
 
@@ -164,7 +174,7 @@ int32_t chip_solver_create(chip_solver **out, int64_t n, int64_t m, const uint64
         }
     }
     if (!a.fits_int32()) return fail(CHIP_ERR_DIM, "chip_solver_create: sizes out of int32 range");
-    std::vector<ConeSpec> cones;
+    std::vector<ConeSpec> &cones = h->cones;
     int64_t mm = 0, p = 0, nHs = 0;
     if (build_cone_specs(a.ncones, a.cone_tags, a.cone_dims, a.cone_dims2, cones, mm, p, nHs))
         return fail(CHIP_ERR_ARG, "chip_solver_create: bad cone");
@@ -535,6 +545,71 @@ int chip_solver::update_args(chip_solver *h, int which, const void *idx, const d
 }
 
 CHIP_UPDATE_ENTRIES(chip_problem_update_, chip_solver)
+
+// ---------------------------------------------------------------------------------------------------------------
+// Re-equilibration: new full data on the fixed patterns, equilibrated from d = e = 1, c = 1 by
+// create's own ProblemData::equilibrate on the handle's stream, then every copy and derived value of the audit
+// refreshed by the data updates' passes.  The symbolic side (chip_kkt, chip_kktsystem) is left alone.  One host
+// synchronisation, equilibrate's own, in which c, the norms and max |P_ii| come back.
+// ---------------------------------------------------------------------------------------------------------------
+int chip_solver::reequilibrate_gate(const char *fn) {
+    if (tf) // the rule of the updates (data_updating.rs: PresolveIsActive / ChordalDecompositionIsActive)
+        return fail(CHIP_ERR_UPDATE_NOT_ALLOWED,
+                    std::string(fn) + ": presolve or chordal decomposition is active (nothing changed)");
+    req_launches = req_syncs = 0;
+    return CHIP_OK;
+}
+
+int chip_solver::reequilibrate(const double *P_dev, const double *q_dev, const double *A_dev, const double *b_dev) {
+    int rc;
+    if ((rc = update_work())) return rc;
+    if (!eq_partials && (rc = mem.alloc(&eq_partials, (size_t)dev::eq_cost_partials()))) return rc;
+    const double te = now_s();
+    hipStream_t s = stream;
+    const dev::EqMats &M = pd.M;
+    // the raw values, b capped, and the norms create takes from them (before the loop scales them in place)
+    pd.reload(s, P_dev, q_dev, A_dev, b_dev, nullptr, nullptr);
+    dev::re_absmax(s, pd.q, pd.n, npart, nout);
+    dev::re_absmax(s, pd.b, pd.m, npart, nout + 1);
+    CHIP_HIP(hipGetLastError());
+    req_launches += 8;
+    double hn[3] = {0, 0, 0};
+    auto ruiz_step = [&](unsigned long long *bits, double *cstate) {
+        dev::eq_ruiz_step(s, M, pd.q, pd.b, pd.d, pd.e, pd.n, pd.m, bits, eq_partials, cstate,
+                          st.equilibrate_min_scaling, st.equilibrate_max_scaling);
+        req_launches += 2; // (with the clear of bits)
+    };
+    rc = pd.equilibrate(s, st, cones, 1, dev::eq_bits_words(pd.n, pd.m), ruiz_step, &c, [&](const double *) -> int {
+        // the copies the loop reads (4.11's audit), from the equilibrated arrays in place
+        int rc1;
+        if ((rc1 = kkt_update_values_dev(kkt, UPD_P, M.Px, nullptr, M.nnzP)) ||
+            (rc1 = kkt_update_values_dev(kkt, UPD_A, M.Ax, nullptr, M.nnzA)) ||
+            (rc1 = kktsystem_update_data_dev(sys, M.Px, M.Ax, pd.q, pd.b)))
+            return rc1;
+        dev::pu_norms(s, 4, nullptr, nullptr, 0, nullptr, nullptr, 0, M.Prow, M.Pcol, M.Px, M.nnzP, npart, nout);
+        CHIP_HIP(hipGetLastError());
+        CHIP_HIP(hipMemcpyAsync(hn, nout, sizeof(hn), hipMemcpyDeviceToHost, s));
+        req_launches += 2 + 5 + 2 + 1;
+        return (int)CHIP_OK;
+    });
+    req_launches += 7; // d, e, cstate, the rectification, the inversion (or dinv, einv), c
+    req_syncs++;
+    if (rc) return rc;
+    normq = hn[0];
+    normb = hn[1];
+    kkt_set_static_diag_max(kkt, hn[2]);
+    equilibration_time = now_s() - te;
+    return CHIP_OK;
+}
+
+int32_t chip_reequilibrate_problem(chip_solver *h, const double *Pnzval, const double *q, const double *Anzval,
+                                   const double *b) {
+    return reequilibrate_entry("chip_reequilibrate_problem", h, Pnzval, q, Anzval, b, true);
+}
+int32_t chip_reequilibrate_problem_dev(chip_solver *h, const double *Pnzval_dev, const double *q_dev,
+                                       const double *Anzval_dev, const double *b_dev) {
+    return reequilibrate_entry("chip_reequilibrate_problem_dev", h, Pnzval_dev, q_dev, Anzval_dev, b_dev, false);
+}
 
 // DefaultSolver::update_settings (core/solver.rs:207) with validate_as_update (settings.rs:307): the equilibration
 // fields as in the reference, and every field chip_kkt keeps its own copy of (all of linsys, with the two line-search

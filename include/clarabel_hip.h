@@ -674,6 +674,22 @@ int32_t chip_problem_update_allowed(const chip_solver *h, int32_t *allowed);
 /* solver.data as the solver holds it (P, A, q, b after the transforms and the equilibration: n_internal /
  * m_internal long, with the internal nnz): host copies, any pointer may be NULL */
 int32_t chip_problem_get_scaled(chip_solver *h, double *Px, double *Ax, double *q, double *b);
+/* ---- re-equilibration: new FULL data on the handle's patterns (Pnzval[nnz(P)], q[n], Anzval[nnz(A)], b[m]; all four
+ * required, an empty one still not NULL), equilibrated from scratch on the device as chip_solver_create would
+ * (from d = e = 1, c = 1: the Ruiz loop, the cone rectification; b capped at 1e20 first, as create caps it and unlike
+ * chip_problem_update_b).  Afterwards the handle is in the state a fresh chip_solver_create on the same patterns,
+ * cones, settings and these values would be in -- the scaled data, d, e, c, the norms of q and b, max |P_ii|, every
+ * copy the solve reads -- while the symbolic analysis stays the one of the original create: no ordering, no
+ * elimination tree, no host pass over the patterns.  With equilibrate_enable == 0 the call is a capped full reload.
+ * Later chip_problem_update_* calls scale with the new d, e, c; the next solve restarts from default_start.
+ * CHIP_ERR_ARG for a NULL handle or array, without touching a device; CHIP_ERR_UPDATE_NOT_ALLOWED, nothing changed,
+ * while presolve removed a row or a cone was decomposed (the rule of the updates).  One host synchronisation.
+ * (chip_reequilibrate_*, not chip_problem_*: that family is the reference's data-updating interface.) */
+int32_t chip_reequilibrate_problem(chip_solver *h, const double *Pnzval, const double *q, const double *Anzval,
+                                   const double *b);
+/* the same with the four arrays in device memory; the caller must have finished writing them before the call */
+int32_t chip_reequilibrate_problem_dev(chip_solver *h, const double *Pnzval_dev, const double *q_dev,
+                                       const double *Anzval_dev, const double *b_dev);
 
 /* ===========================================================================
  * Batched L4 solver: nprob INDEPENDENT problems solved in one interior-point loop on one GPU, each with its own tau,
@@ -752,6 +768,18 @@ int32_t chip_bdata_update_settings(chip_batch *h, const chip_solver_settings *se
  * members' norms (normq[nprob], normb[nprob]): host copies, any pointer may be NULL */
 int32_t chip_bdata_get_scaled(chip_batch *h, double *Px, double *Ax, double *q, double *b, double *normq,
                               double *normb);
+/* ---- re-equilibration of a batch: chip_reequilibrate_problem on the STACK (the stacked Pnzval, q, Anzval, b in full;
+ * all four required).  Afterwards the handle is in the state a fresh chip_batch_create on the same partition,
+ * patterns, cones, settings and these values would be in: the scaled data, d, e and the members' c_k (host and
+ * device), the unscaled copies of q and the capped b with the members' norms, max |P_ii| of the stack, every copy the
+ * solve and the derivative passes read.  The partition and the symbolic analysis stay.  As after an update, chip_bgrad_*
+ * and chip_bjvp_* are refused until the next chip_batch_solve; later chip_bdata_update_* calls scale with the new
+ * d, e, c_k.  CHIP_ERR_ARG for a NULL handle or array, without touching a device.  The number of enqueues does not
+ * depend on nprob; one host synchronisation. */
+int32_t chip_reequilibrate_bdata(chip_batch *h, const double *Pnzval, const double *q, const double *Anzval,
+                                 const double *b);
+int32_t chip_reequilibrate_bdata_dev(chip_batch *h, const double *Pnzval_dev, const double *q_dev,
+                                     const double *Anzval_dev, const double *b_dev);
 
 /* ---- gradients of a batch's solutions: given dL/dx, dL/dz, dL/ds of every member's (unscaled) solution, dL/dq,
  * dL/db, dL/dP and dL/dA of every member -- what a QP / LP layer inside a model needs for its backward pass.  With

@@ -145,6 +145,16 @@ int32_t chip_debug_bplan_bunit_reset(void *h, double *x, double *sv, double *z, 
 int32_t chip_debug_bplan_bunscale(void *h, double *xo, const double *x, const double *d, double *zo, const double *z,
                                   const double *e, double *so, const double *sv, const double *einv, const double *sx,
                                   const double *sz);
+/* ---- the re-equilibration (csrc/reequilibrate.hip, chip_reequilibrate_problem / chip_reequilibrate_bdata) ----
+ * chip_debug_reload_pass: the load pass (re_load) alone on `len` values.  HOST arrays: src[len]; dst[len + 4] and raw
+ * (may be NULL) [len + 4] are uploaded whole, written at [o, o + len) and copied back whole, so the caller sees that
+ * nothing around the range was touched.  o = 2 (a 16-byte boundary) for every array, or 1 (8 bytes past one) for the
+ * arrays whose bit of `misalign` is set: 1 = dst, 2 = raw, 4 = src (src sits at its own o in a device buffer).  cap:
+ * values above 1e20 become 1e20.
+ * chip_debug_create_count: how often this process entered chip_kkt_create (which = 0) / chip_kktsystem_create (1). */
+int32_t chip_debug_reload_pass(double *dst, double *raw_or_null, const double *src, int64_t len, int32_t cap,
+                               int32_t misalign);
+int32_t chip_debug_create_count(int32_t which, double *out);
 /* ---- the PSD cone kernels (csrc/cones.hip: k_psd_update_scaling, k_psd_ops<0..6>) alone ----
  * chip_debug_psd_create: a bare view over a vector that holds only the svec ranges of `ncones` PSD triangle cones of
  * sides dims[] (0 .. 1024), in order: rows = sum n (n + 1) / 2.  The sizing is the function chip_kkt_create calls (state
