@@ -1050,6 +1050,18 @@ class HipSolver(_DataUpdates):
                "chip_debug_solver_internal_solution")
         return x, s, z
 
+    def scaled_state(self):
+        """test hook: what the last solve left in the handle, SCALED (chip_debug_solver_scaled_state): a dict with the
+        iterate x, s, z, tau, kappa, the inverse scalings dinv, einv and the info in its flat 21-double form (cost_primal,
+        cost_dual, res_primal, res_dual, res_primal_inf, res_dual_inf, gap_abs, gap_rel, ktratio, six prev_ scalars,
+        r_tau, q'x, b'z, s'z, x'Px, status)"""
+        t = self.transform_info()
+        n, m = t["n_internal"], t["m_internal"]
+        x, s, z, tk, dinv, einv, info = (np.zeros(k) for k in (n, m, m, 2, n, m, 21))
+        _check(lib().chip_debug_solver_scaled_state(self._h, _pf(x), _pf(s), _pf(z), _pf(tk), _pf(dinv), _pf(einv),
+                                                    _pf(info)), "chip_debug_solver_scaled_state")
+        return dict(x=x, s=s, z=z, tau=float(tk[0]), kappa=float(tk[1]), dinv=dinv, einv=einv, info=info)
+
     def scaled_data(self):
         """solver.data as the solver holds it, after the transforms and the equilibration: (P.nzval, A.nzval, q, b)
         of the internal problem (the original sizes unless a transform is active)"""
@@ -1992,6 +2004,89 @@ def debug_reload_pass(src, cap=False, raw=False, misalign=0, fill=-7.0):
                                         C.c_int64(len(src)), C.c_int32(int(cap)), C.c_int32(misalign)),
            "chip_debug_reload_pass")
     return dst, rw, (1 if misalign & 1 else 2), (1 if misalign & 2 else 2)
+
+
+def debug_eq_ruiz_step(n, m, P, A, q, b, d, e, c, min_scaling, max_scaling):
+    """test hook: ONE Ruiz step (csrc/equilibrate.hip: eq_ruiz_step) from the state (P, A, q, b, d, e, c); P, A are
+    (colptr, rowval, nzval) CSC triplets (P the upper triangle).  The caller's arrays are left alone.  Returns a dict:
+    Px, Ax, q, b, d, e, c and `factor`, the step's cost factor (1.0: cost scaling skipped)"""
+    Pp, Pi, Px = _u(P[0]), _u(P[1]), _f(P[2]).copy()
+    Ap, Ai, Ax = _u(A[0]), _u(A[1]), _f(A[2]).copy()
+    q, b, d, e = (_f(a).copy() for a in (q, b, d, e))
+    assert len(Pp) == n + 1 and len(Ap) == n + 1 and len(q) == n and len(d) == n and len(b) == m and len(e) == m
+    assert len(Pi) == len(Px) == Pp[-1] and len(Ai) == len(Ax) == Ap[-1]
+    cstate = np.array([c, 1.0])
+    _check(lib().chip_debug_eq_ruiz_step(C.c_int64(n), C.c_int64(m), _pu(Pp), _pu(Pi), _pf(Px), _pu(Ap), _pu(Ai),
+                                         _pf(Ax), _pf(q), _pf(b), _pf(d), _pf(e), _pf(cstate),
+                                         C.c_double(min_scaling), C.c_double(max_scaling)), "chip_debug_eq_ruiz_step")
+    return dict(Px=Px, Ax=Ax, q=q, b=b, d=d, e=e, c=float(cstate[0]), factor=float(cstate[1]))
+
+
+def debug_eq_rectify(n, m, A, b, e, segments):
+    """test hook: the rectification (eq_rectify) over the row ranges segments = [(beg, end), ...] -> (Ax, b, e)"""
+    Ap, Ai, Ax = _u(A[0]), _u(A[1]), _f(A[2]).copy()
+    b, e = _f(b).copy(), _f(e).copy()
+    assert len(Ap) == n + 1 and len(Ai) == len(Ax) == Ap[-1] and len(b) == m and len(e) == m
+    sb = np.ascontiguousarray([s[0] for s in segments], dtype=np.int32)
+    se = np.ascontiguousarray([s[1] for s in segments], dtype=np.int32)
+    _check(lib().chip_debug_eq_rectify(C.c_int64(n), C.c_int64(m), _pu(Ap), _pu(Ai), _pf(Ax), _pf(b), _pf(e),
+                                       C.c_int32(len(sb)), sb.ctypes.data_as(P_I32), se.ctypes.data_as(P_I32)),
+           "chip_debug_eq_rectify")
+    return Ax, b, e
+
+
+def debug_eq_invert(d, e):
+    """test hook: eq_invert -> (dinv, einv); the outputs hold NaN before the call"""
+    d, e = _f(d), _f(e)
+    dinv, einv = np.full(len(d), np.nan), np.full(len(e), np.nan)
+    _check(lib().chip_debug_eq_invert(_pf(d), _pf(dinv), C.c_int64(len(d)), _pf(e), _pf(einv), C.c_int64(len(e))),
+           "chip_debug_eq_invert")
+    return dinv, einv
+
+
+def debug_wnorm_batch(specs, nslots):
+    """test hook: wnorm_batch on specs = [(v, w, slot), ...] (up to 8; v and w of one length per spec, and the SAME
+    object where they are to alias) -> out[nslots], sums of (v w)^2; slots no spec names keep the NaN they held"""
+    keep = {}
+
+    def arr(a):
+        if id(a) not in keep:
+            keep[id(a)] = (a, _f(a))
+        return keep[id(a)][1]
+
+    count = len(specs)
+    vs, ws = [arr(s[0]) for s in specs], [arr(s[1]) for s in specs]
+    assert all(len(v) == len(w) for v, w in zip(vs, ws))
+    pv, pw = (P_F64 * max(count, 1))(*[_pf(v) for v in vs]), (P_F64 * max(count, 1))(*[_pf(w) for w in ws])
+    ns = np.ascontiguousarray([len(v) for v in vs], dtype=np.int32)
+    slots = np.ascontiguousarray([s[2] for s in specs], dtype=np.int32)
+    out = np.full(nslots, np.nan)
+    _check(lib().chip_debug_wnorm_batch(C.c_int32(count), pv, pw, ns.ctypes.data_as(P_I32),
+                                        slots.ctypes.data_as(P_I32), C.c_int32(nslots), _pf(out)),
+           "chip_debug_wnorm_batch")
+    return out
+
+
+def debug_unscale(x, d, sx, z, e, sz, s, einv, ss):
+    """test hook: unscale -> (xo, zo, so) = ((x d) sx, (z e) sz, (s einv) ss); the outputs hold NaN before the call"""
+    x, d, z, e, s, einv = (_f(a) for a in (x, d, z, e, s, einv))
+    n, m = len(x), len(z)
+    assert len(d) == n and len(e) == m and len(s) == m and len(einv) == m
+    xo, zo, so = np.full(n, np.nan), np.full(m, np.nan), np.full(m, np.nan)
+    _check(lib().chip_debug_unscale(_pf(xo), _pf(x), _pf(d), C.c_double(sx), C.c_int64(n), _pf(zo), _pf(z), _pf(e),
+                                    C.c_double(sz), _pf(so), _pf(s), _pf(einv), C.c_double(ss), C.c_int64(m)),
+           "chip_debug_unscale")
+    return xo, zo, so
+
+
+def debug_ipm_info_update(info21, sq, tau, kappa, c, normq, normb):
+    """test hook: DefaultInfo::update (csrc/ipm_info.hpp) on a flat info (its dots in [15:20]) from the eight squared
+    weighted norms -> the updated copy"""
+    info, sq = _f(info21).copy(), _f(sq)
+    assert len(info) == 21 and len(sq) == 8
+    _check(lib().chip_debug_ipm_info_update(_pf(info), _pf(sq), C.c_double(tau), C.c_double(kappa), C.c_double(c),
+                                            C.c_double(normq), C.c_double(normb)), "chip_debug_ipm_info_update")
+    return info
 
 
 def debug_kkt_ints(kkt, name):

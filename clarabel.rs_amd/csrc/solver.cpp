@@ -749,4 +749,29 @@ int32_t chip_debug_ipm_info_update(double *info, const double *sq, double tau, d
     for (int k = 0; k < 9; k++) info[k] = I.*IPM_FIELD[k];
     return CHIP_OK;
 }
+int32_t chip_debug_solver_scaled_state(void *solver, double *x, double *s, double *z, double *tau_kappa, double *dinv,
+                                       double *einv, double *info21) {
+    chip_solver *h = (chip_solver *)solver;
+    if (!h) return fail(CHIP_ERR_ARG, "chip_debug_solver_scaled_state: bad argument");
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    CHIP_HIP(hipStreamSynchronize(h->stream));
+    const ProblemData &pd = h->pd;
+    const size_t nb = (size_t)pd.n * 8, mb = (size_t)pd.m * 8;
+    const chip_vars &v = h->vars;
+    if (x && nb) CHIP_HIP(hipMemcpy(x, v.x, nb, hipMemcpyDeviceToHost));
+    if (s && mb) CHIP_HIP(hipMemcpy(s, v.s, mb, hipMemcpyDeviceToHost));
+    if (z && mb) CHIP_HIP(hipMemcpy(z, v.z, mb, hipMemcpyDeviceToHost));
+    if (dinv && nb) CHIP_HIP(hipMemcpy(dinv, pd.dinv, nb, hipMemcpyDeviceToHost));
+    if (einv && mb) CHIP_HIP(hipMemcpy(einv, pd.einv, mb, hipMemcpyDeviceToHost));
+    if (tau_kappa) {
+        tau_kappa[0] = v.tau;
+        tau_kappa[1] = v.kappa;
+    }
+    if (info21) {
+        for (int k = 0; k < 15; k++) info21[k] = h->info.*IPM_FIELD[k];
+        std::copy(h->info.out5, h->info.out5 + 5, info21 + 15);
+        info21[20] = (double)h->info.status;
+    }
+    return CHIP_OK;
+}
 #endif

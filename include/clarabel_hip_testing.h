@@ -155,6 +155,34 @@ int32_t chip_debug_bplan_bunscale(void *h, double *xo, const double *x, const do
 int32_t chip_debug_reload_pass(double *dst, double *raw_or_null, const double *src, int64_t len, int32_t cap,
                                int32_t misalign);
 int32_t chip_debug_create_count(int32_t which, double *out);
+/* ---- the passes of csrc/equilibrate.hip (the five launchers of csrc/equilibrate.hpp), each alone ----
+ * The runners take HOST arrays, copy them to device buffers (one buffer per distinct host pointer, so aliased operands
+ * stay aliased; arrays the pass writes are uploaded as well, so entries it leaves alone come back unchanged), call the
+ * launcher ONCE on a private stream, synchronise and copy the written arrays back.  Sizes must fit the int32 indexing
+ * of the passes (CHIP_ERR_DIM otherwise); every index is checked before anything is launched.
+ * chip_debug_eq_ruiz_step: ONE Ruiz step from the state (Px, Ax, q, b, d, e, cstate = {c, the last factor}): P (n x n,
+ * upper triangle) and A (m x n) are the caller's CSC triplets, turned into coordinate form by the function setup uses;
+ * the norm words are zeroed as the equilibration loop zeroes them.  Px, Ax, q, b, d, e and cstate[0..1] are updated in place.
+ * chip_debug_eq_rectify: the rectification over the row ranges [seg_beg[k], seg_end[k]) (0 <= beg < end <= m); Ax, b and
+ * e are updated in place.  chip_debug_eq_invert: dinv[n] = 1 / d, einv[m] = 1 / e.
+ * chip_debug_wnorm_batch: `count` <= 8 specs (v[j], w[j] of n[j] entries, into out[slot[j]], slot[j] < nslots); out is
+ * uploaded and copied back whole.  chip_debug_unscale: xo[n] = (x d) sx, zo[m] = (z e) sz, so[m] = (sv einv) ss.
+ * chip_debug_solver_scaled_state reads a chip_solver after a solve: the SCALED iterate x[n], s[m], z[m] and
+ * tau_kappa[2], its dinv[n], einv[m] (internal sizes), and its info in the 21-double form above (info21[20] = status);
+ * any may be NULL. */
+int32_t chip_debug_eq_ruiz_step(int64_t n, int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval, double *Px,
+                                const uint64_t *Acolptr, const uint64_t *Arowval, double *Ax, double *q, double *b,
+                                double *d, double *e, double *cstate, double min_scaling, double max_scaling);
+int32_t chip_debug_eq_rectify(int64_t n, int64_t m, const uint64_t *Acolptr, const uint64_t *Arowval, double *Ax,
+                              double *b, double *e, int32_t nseg, const int32_t *seg_beg, const int32_t *seg_end);
+int32_t chip_debug_eq_invert(const double *d, double *dinv, int64_t n, const double *e, double *einv, int64_t m);
+int32_t chip_debug_wnorm_batch(int32_t count, const double *const *v, const double *const *w, const int32_t *n,
+                               const int32_t *slot, int32_t nslots, double *out);
+int32_t chip_debug_unscale(double *xo, const double *x, const double *d, double sx, int64_t n, double *zo,
+                           const double *z, const double *e, double sz, double *so, const double *sv, const double *einv,
+                           double ss, int64_t m);
+int32_t chip_debug_solver_scaled_state(void *solver, double *x, double *s, double *z, double *tau_kappa, double *dinv,
+                                       double *einv, double *info21);
 /* ---- the PSD cone kernels (csrc/cones.hip: k_psd_update_scaling, k_psd_ops<0..6>) alone ----
  * chip_debug_psd_create: a bare view over a vector that holds only the svec ranges of `ncones` PSD triangle cones of
  * sides dims[] (0 .. 1024), in order: rows = sum n (n + 1) / 2.  The sizing is the function chip_kkt_create calls (state
