@@ -49,6 +49,7 @@ STATUS_NAMES = {0: "ok", -1: "IncompatibleDimension", -2: "EmptyColumn", -3: "No
                 -4: "ZeroPivot", -5: "InvalidPermutation", -6: "NotFactored", -7: "NoDevice", -8: "HipError",
                 -9: "BadArgument", -10: "Unsupported", -11: "UpdateNotAllowed"}
 DEVICE_HOST_ONLY = -2
+BJAC_MAX_DIR = 16  # CHIP_BJAC_MAX_DIR: the directions of one chip_bjac_* call
 
 # SupportedConeT tags
 ZeroConeT, NonnegativeConeT, SecondOrderConeT, ExponentialConeT, PowerConeT, GenPowerConeT, PSDTriangleConeT = range(7)
@@ -1320,7 +1321,147 @@ class HipBatchSolver(_DataUpdates):
                                 ("chip_bjvp_apply", "chip_bjvp_apply_dev", "chip_bjvp_get", "chip_bjvp_get_dev"),
                                 "qbb", BatchTangent)
 
+    # ---- blocks of tangents and the members' Jacobians (chip_bjac_*) ------------------------------------------------
+    def _block_input(self, name, g, key):
+        """one piece of a block of directions -> ("none", None), ("host", float64 array [K, len]) or ("dev",
+        contiguous GPU tensor [K, len])"""
+        name = "jvp_block %s" % name
+        length = self._len[key]
+        if g is None:
+            return ("none", None)
+        if _is_torch(g) and g.is_cuda:
+            import torch
+            if g.dtype != torch.float64:
+                raise TypeError("%s: GPU values must be float64, not %s" % (name, g.dtype))
+            if g.dim() != 2 or g.shape[1] != length:
+                raise ChipError(ERR_DIM, "%s: a [K, %d] matrix is needed" % (name, length))
+            return ("dev", g.detach().contiguous())
+        a = np.asarray(g.detach().numpy() if _is_torch(g) else g)
+        if a.dtype != f64:
+            raise TypeError("%s: host values must be float64, not %s" % (name, a.dtype))
+        if a.ndim != 2 or a.shape[1] != length:
+            raise ChipError(ERR_DIM, "%s: a [K, %d] matrix is needed" % (name, length))
+        return ("host", _f(a))
+
+    def _block_result(self, ndir, device=None):
+        """(dx[ndir, n], dz[ndir, m], ds[ndir, m]) of the last block: numpy arrays, or copies on the GPU `device`"""
+        L = lib()
+        lens = [self._len[key] for key in "qbb"]
+        if device is None:
+            res = [np.zeros((ndir, ln)) for ln in lens]
+            _check(L.chip_bjac_get(self._h, *[_pf(v) for v in res], None), "chip_bjac_get")
+            return res
+        out = [C.c_void_p() for _ in lens]
+        _check(L.chip_bjac_get_dev(self._h, *[C.byref(o) for o in out], None), "chip_bjac_get_dev")
+        return [_torch_copy(o.value, ndir * ln, "float64", device).view(ndir, ln) for o, ln in zip(out, lens)]
+
+    def _block_valid(self):
+        valid = np.zeros(len(self), dtype=np.int32)
+        _check(lib().chip_bjac_get(self._h, None, None, None, valid.ctypes.data_as(P_I32)), "chip_bjac_get")
+        return valid
+
+    def jvp_block(self, dq=None, db=None, dP=None, dA=None):
+        """K directions at once: jvp() with every piece a [K, len] matrix (row t = direction t; float64 numpy arrays,
+        or contiguous float64 torch tensors on the GPU: the result then holds GPU tensors and nothing crosses to the
+        host); None = zeros in every direction; at least one piece is given, all given pieces share K >= 1 and are all
+        host or all GPU.  Up to 16 directions are one call with one host synchronisation (chip_bjac_apply); more are
+        cut into calls of 16.  Returns a BatchTangentBlock.  Validity, zeros and refusals as for jvp()."""
+        names = (("dq", "q"), ("db", "b"), ("dP", "P"), ("dA", "A"))
+        forms = [self._block_input(nm, g, key) for (nm, key), g in zip(names, (dq, db, dP, dA))]
+        kinds = {f[0] for f in forms} - {"none"}
+        if not kinds:
+            raise ChipError(ERR_DIM, "jvp_block: at least one piece is needed (it gives the number of directions)")
+        if len(kinds) > 1:
+            raise TypeError("jvp_block: dq, db, dP and dA must all be host arrays or all GPU tensors")
+        counts = {int(f[1].shape[0]) for f in forms if f[0] != "none"}
+        if len(counts) != 1 or min(counts) < 1:
+            raise ChipError(ERR_DIM, "jvp_block: the pieces must share one number of directions K >= 1, not %s"
+                            % sorted(counts))
+        K = counts.pop()
+        on_dev = kinds == {"dev"}
+        device = None
+        if on_dev:
+            import torch
+            device = [f[1] for f in forms if f[0] == "dev"][0].device
+            torch.cuda.current_stream(device).synchronize()  # the values are written before the call reads them
+        L = lib()
+        parts = []
+        for t0 in range(0, K, BJAC_MAX_DIR):
+            nd = min(BJAC_MAX_DIR, K - t0)
+            if on_dev:
+                ptr = [None if f[0] == "none" else C.c_void_p(f[1].data_ptr() + 8 * t0 * f[1].shape[1]) for f in forms]
+                _check(L.chip_bjac_apply_dev(self._h, C.c_int32(nd), *ptr), "chip_bjac_apply_dev")
+            else:
+                rows = [None if f[0] == "none" else f[1][t0:t0 + nd] for f in forms]
+                _check(L.chip_bjac_apply(self._h, C.c_int32(nd), *[None if r is None else _pf(r) for r in rows]),
+                       "chip_bjac_apply")
+            parts.append(self._block_result(nd, device))
+        if on_dev:
+            import torch
+            cat = lambda vs: vs[0] if len(vs) == 1 else torch.cat(vs, dim=0)  # noqa: E731
+        else:
+            cat = lambda vs: vs[0] if len(vs) == 1 else np.concatenate(vs, axis=0)  # noqa: E731
+        return BatchTangentBlock(*[cat([p[i] for p in parts]) for i in range(3)], self._block_valid(), self._offsets)
+
+    def member_jacobians(self, wrt="q", torch=False):
+        """the Jacobians of every member's solution with respect to its own q (wrt="q") or b (wrt="b"): a list with
+        one entry per member, None where the member has no derivative (valid[k] == 0), else (dx_dw [n_k x w_k],
+        dz_dw [m_k x w_k], ds_dw [m_k x w_k]) with w_k the member's number of entries of q / b -- numpy arrays, or with
+        torch=True tensors on the GPU (nothing crosses to the host).  K is block-diagonal over the members, so one
+        direction that holds unit vector j of every member's own q yields column j of every Jacobian: the cost is
+        ceil(max_k w_k / 16) calls of chip_bjac_units -- max_k w_k refined solves, not sum_k w_k."""
+        if wrt not in ("q", "b"):
+            raise ValueError("member_jacobians: wrt is \"q\" or \"b\"")
+        piece = 0 if wrt == "q" else 1
+        widths = [int(v) for v in (self.n_part if piece == 0 else self.m_part)]
+        wmax = max(widths)
+        device = None
+        if torch:
+            import torch as th
+            device = th.device("cuda")
+            new = lambda r, c: th.zeros((r, c), dtype=th.float64, device=device)  # noqa: E731
+        else:
+            new = lambda r, c: np.zeros((r, c))  # noqa: E731
+        out = [tuple(new(int(r), w) for r in (self.n_part[k], self.m_part[k], self.m_part[k]))
+               for k, w in enumerate(widths)]
+        off = [self._offsets[key] for key in "qbb"]
+        valid = None
+        for first in range(0, max(wmax, 1), BJAC_MAX_DIR):  # (no entries at all: one call, for the valid flags)
+            nd = max(1, min(BJAC_MAX_DIR, wmax - first))
+            _check(lib().chip_bjac_units(self._h, C.c_int32(piece), C.c_int64(first), C.c_int32(nd)),
+                   "chip_bjac_units")
+            block = self._block_result(nd, device)
+            if valid is None:
+                valid = self._block_valid()
+            for k, w in enumerate(widths):
+                cols = min(nd, w - first)
+                if cols <= 0 or not valid[k]:
+                    continue
+                for mat, res, o in zip(out[k], block, off):
+                    mat[:, first:first + cols] = res[:cols, int(o[k]):int(o[k + 1])].T
+        return [mats if valid[k] else None for k, mats in enumerate(out)]
+
     # ---- test hooks (include/clarabel_hip_testing.h) ----
+    def debug_jac_rhs(self, ndir, x, z, valid, dq=None, db=None, dP=None, dA=None):
+        """the right-hand side pass of a block alone (no solve needed): pieces [ndir, len] -> the scaled
+        (rx[ndir, n], rz[ndir, m])"""
+        keep = [None if v is None else _f(v) for v in (x, z, dq, db, dP, dA)]
+        valid = np.ascontiguousarray(valid, dtype=np.int32)
+        rx, rz = np.zeros((ndir, self._len["q"])), np.zeros((ndir, self._len["b"]))
+        ptr = [None if v is None else _pf(v) for v in keep]
+        _check(lib().chip_debug_batch_jac_rhs(self._h, C.c_int32(ndir), ptr[0], ptr[1], valid.ctypes.data_as(P_I32),
+                                              *ptr[2:], _pf(rx), _pf(rz)), "chip_debug_batch_jac_rhs")
+        return rx, rz
+
+    def debug_jac_units(self, piece, first, ndir, valid):
+        """the unit right-hand sides of a block alone (no solve needed) -> the scaled (rx[ndir, n], rz[ndir, m])"""
+        valid = np.ascontiguousarray(valid, dtype=np.int32)
+        rx, rz = np.zeros((ndir, self._len["q"])), np.zeros((ndir, self._len["b"]))
+        _check(lib().chip_debug_batch_jac_units(self._h, C.c_int32(piece), C.c_int64(first), C.c_int32(ndir),
+                                                valid.ctypes.data_as(P_I32), _pf(rx), _pf(rz)),
+               "chip_debug_batch_jac_units")
+        return rx, rz
+
     def debug_jvp_rhs(self, x, z, valid, dq=None, db=None, dP=None, dA=None):
         """the right-hand side pass of jvp alone (no solve needed) -> the scaled (rx[n], rz[m])"""
         keep = [None if v is None else _f(v) for v in (x, z, dq, db, dP, dA)]
@@ -1370,6 +1511,21 @@ class BatchTangent(_BatchDerivative):
     """the result of HipBatchSolver.jvp: dx[n], dz[m], ds[m] of the stack as numpy arrays or torch GPU tensors, and
     valid[nprob] (numpy int32): 1 where the member has a derivative, else its entries are exact zeros"""
     FIELDS = (("dx", "q"), ("dz", "b"), ("ds", "b"))
+
+
+class BatchTangentBlock:
+    """the result of HipBatchSolver.jvp_block: dx[K, n], dz[K, m], ds[K, m] of the stack, row t = direction t, as
+    numpy arrays or torch GPU tensors, and valid[nprob] (numpy int32): 1 where the member has a derivative, else its
+    entries are exact zeros in every direction"""
+    FIELDS = BatchTangent.FIELDS
+
+    def __init__(self, dx, dz, ds, valid, offsets):
+        self.dx, self.dz, self.ds, self.valid, self._offsets = dx, dz, ds, valid, offsets
+
+    def per_member(self, k):
+        """member k's columns of the three matrices: (dx[:, n_k], dz[:, m_k], ds[:, m_k])"""
+        o = self._offsets
+        return tuple(getattr(self, name)[:, int(o[key][k]):int(o[key][k + 1])] for name, key in self.FIELDS)
 
 
 def _torch_copy(ptr, n, dtype, device=None):

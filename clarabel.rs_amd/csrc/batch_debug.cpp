@@ -1,6 +1,7 @@
 // batch_debug.cpp -- the test hooks of the batched solver (include/clarabel_hip_testing.h: chip_debug_batch_*,
 // chip_debug_bplan_*); empty in the build that ships
 #include "batch_handle.hpp"
+#include "batch_jacobian.hpp"
 #include "batch_tangent.hpp"
 #include "debug_stage.hpp"
 
@@ -27,6 +28,11 @@ int32_t chip_debug_batch_counter(void *batch, const char *name, double *out) {
     else if (nm == "jvp_launches") *out = (double)h->tan.launches;
     else if (nm == "jvp_host_syncs") *out = (double)h->tan.syncs;
     else if (nm == "jvp_refactors") *out = (double)h->tan.refactors;
+    else if (nm == "jac_launches") *out = (double)h->jac.launches;
+    else if (nm == "jac_host_syncs") *out = (double)h->jac.syncs;
+    else if (nm == "jac_refactors") *out = (double)h->jac.refactors;
+    else if (nm == "jac_repeats") *out = (double)h->jac_repeats;
+    else if (nm == "jac_calls") *out = (double)h->jac_calls;
     else return fail(CHIP_ERR_ARG, "chip_debug_batch_counter: unknown name");
     return CHIP_OK;
 }
@@ -91,6 +97,63 @@ int32_t chip_debug_batch_jvp_rhs(void *batch, const double *x, const double *z, 
     dev::bt_rhs(s, h->plan, Psym, Acol, Arow,
                 dev::BtRhs{dvalid, dx_, dz_, ddq, ddb, ddP, ddA, h->pd.d, h->pd.e, h->dc, drx, drz, nullptr, nullptr,
                            nullptr, nullptr});
+    rc = st.finish(s);
+    (void)hipStreamDestroy(s);
+    return rc;
+}
+
+int32_t chip_debug_batch_jac_rhs(void *batch, int32_t ndir, const double *x, const double *z, const int32_t *valid,
+                                 const double *dq, const double *db, const double *dPx, const double *dAx, double *rx,
+                                 double *rz) {
+    chip_batch *h = (chip_batch *)batch;
+    if (!h || ndir < 1 || ndir > CHIP_BJAC_MAX_DIR || !valid || (h->pd.n && (!x || !rx)) || (h->pd.m && (!z || !rz)))
+        return fail(CHIP_ERR_ARG, "chip_debug_batch_jac_rhs: bad argument");
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    int rc;
+    dev::SpPattern Psym, Arow, Acol;
+    if ((rc = kktsystem_pattern(h->sys, 0, &Psym)) || (rc = kktsystem_pattern(h->sys, 1, &Arow)) ||
+        (rc = kktsystem_pattern(h->sys, 2, &Acol)))
+        return rc;
+    DebugStage st;
+    const size_t n = (size_t)h->pd.n, m = (size_t)h->pd.m, nP = (size_t)h->pd.M.nnzP, nA = (size_t)h->pd.M.nnzA;
+    const size_t K = (size_t)ndir;
+    const double *dx_, *dz_, *ddq, *ddb, *ddP, *ddA;
+    const int32_t *dvalid;
+    double *drx, *drz;
+    if ((rc = st.in(x, n, &dx_)) || (rc = st.in(z, m, &dz_)) || (rc = st.in(valid, (size_t)h->nprob, &dvalid)) ||
+        (rc = st.in(dq, K * n, &ddq)) || (rc = st.in(db, K * m, &ddb)) || (rc = st.in(dPx, K * nP, &ddP)) ||
+        (rc = st.in(dAx, K * nA, &ddA)) || (rc = st.out(rx, K * n, &drx)) || (rc = st.out(rz, K * m, &drz)))
+        return rc;
+    hipStream_t s = nullptr;
+    CHIP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    dev::bj_rhs(s, h->plan, Psym, Acol, Arow,
+                dev::BjRhs{dev::BtRhs{dvalid, dx_, dz_, ddq, ddb, ddP, ddA, h->pd.d, h->pd.e, h->dc, drx, drz, nullptr,
+                                      nullptr, nullptr, nullptr},
+                           ndir, n, m, nP, nA, n, m});
+    rc = st.finish(s);
+    (void)hipStreamDestroy(s);
+    return rc;
+}
+
+int32_t chip_debug_batch_jac_units(void *batch, int32_t piece, int64_t first, int32_t ndir, const int32_t *valid,
+                                   double *rx, double *rz) {
+    chip_batch *h = (chip_batch *)batch;
+    if (!h || ndir < 1 || ndir > CHIP_BJAC_MAX_DIR || (piece != 0 && piece != 1) || first < 0 || !valid ||
+        (h->pd.n && !rx) || (h->pd.m && !rz))
+        return fail(CHIP_ERR_ARG, "chip_debug_batch_jac_units: bad argument");
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    int rc;
+    DebugStage st;
+    const size_t n = (size_t)h->pd.n, m = (size_t)h->pd.m, K = (size_t)ndir;
+    const int32_t *dvalid;
+    double *drx, *drz;
+    if ((rc = st.in(valid, (size_t)h->nprob, &dvalid)) || (rc = st.out(rx, K * n, &drx)) || (rc = st.out(rz, K * m, &drz)))
+        return rc;
+    hipStream_t s = nullptr;
+    CHIP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    dev::bj_units(s, h->plan,
+                  dev::BjUnits{dvalid, h->pd.d, h->pd.e, h->dc, drx, drz, n, m, piece, ndir, (long long)first, nullptr,
+                               nullptr, nullptr, nullptr});
     rc = st.finish(s);
     (void)hipStreamDestroy(s);
     return rc;

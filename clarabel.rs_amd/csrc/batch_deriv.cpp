@@ -1,7 +1,8 @@
-// batch_deriv.cpp -- the derivative passes of the batched solver (chip_bgrad_*, chip_bjvp_*) on the handle of
-// batch_handle.hpp
+// batch_deriv.cpp -- the derivative passes of the batched solver (chip_bgrad_*, chip_bjvp_*, chip_bjac_*) on the handle
+// of batch_handle.hpp
 #include "batch_adjoint.hpp"
 #include "batch_handle.hpp"
+#include "batch_jacobian.hpp"
 #include "batch_tangent.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -230,4 +231,154 @@ int32_t chip_bjvp_get(chip_batch *h, double *dx, double *dz, double *ds, int32_t
 
 int32_t chip_bjvp_get_dev(chip_batch *h, double **dx_dev, double **dz_dev, double **ds_dev, int32_t **valid_dev) {
     return deriv_get_dev(h, "chip_bjvp_get_dev", &chip_batch::tan, {dx_dev, dz_dev, ds_dev}, valid_dev);
+}
+
+// ---- blocks of tangents (chip_bjac_*): up to CHIP_BJAC_MAX_DIR applies with ONE synchronisation.
+// The mathematics of every direction is the apply's above.  What differs is the host sequence: one right-hand side
+// launch for all directions, every direction's refined solve ENQUEUED (the refinement decisions are taken on the
+// device), the products and one output launch behind them, and chip_kkt_collect as the one synchronisation, which
+// brings all verdicts.  A solve that is pending borrows its right-hand side, so every direction owns its right-hand
+// side, solution and product in jac_work: per direction [rx n' | rz m' | vx n' | vz m' | w m'] with n', m' the
+// lengths rounded up to even (16-byte aligned slices)
+namespace {
+struct JacWork {
+    size_t stride;
+    double *rx, *rz, *vx, *vz, *w; // of direction 0; direction t: + t * stride
+    explicit JacWork(const chip_batch *h) {
+        const size_t np = ((size_t)h->pd.n + 1) & ~(size_t)1, mp = ((size_t)h->pd.m + 1) & ~(size_t)1;
+        stride = 2 * np + 3 * mp;
+        rx = h->jac_work;
+        rz = rx + np;
+        vx = rz + mp;
+        vz = vx + np;
+        w = vz + mp;
+    }
+};
+
+int jac_begin(chip_batch *h, const char *fn, int32_t ndir) {
+    if (!h) return fail(CHIP_ERR_ARG, std::string(fn) + ": bad argument");
+    if (ndir < 1 || ndir > CHIP_BJAC_MAX_DIR)
+        return fail(CHIP_ERR_ARG, std::string(fn) + ": a block holds 1 to CHIP_BJAC_MAX_DIR directions");
+    return deriv_begin(h, fn, &chip_batch::jac, &chip_batch::jac_alloc);
+}
+} // namespace
+
+int chip_batch::jac_alloc() {
+    if (jac.valid) return CHIP_OK;
+    const size_t n = (size_t)pd.n, m = (size_t)pd.m, K = CHIP_BJAC_MAX_DIR;
+    int rc;
+    if ((rc = mem.alloc(&jac_work, K * JacWork(this).stride))) return rc;
+    return deriv_alloc(this, jac, {}, {K * n, K * m, K * m});
+}
+
+int chip_batch::jac_block(int ndir, int piece, long long first, const double *dq, const double *db, const double *dP,
+                          const double *dA) {
+    int rc;
+    jac.done = false; // (a block that fails part-way leaves no result behind)
+    jac_calls++;
+    const size_t lens[3] = {(size_t)pd.n, (size_t)pd.m, (size_t)pd.m};
+    for (int i = 0; i < 3; i++) jac.out_len[i] = (size_t)ndir * lens[i];
+    const JacWork k(this);
+    if ((rc = deriv_valid(this, jac))) return rc;
+    const bool refactor = !kkt_final;
+    double *ss = refactor ? ds : nullptr, *zs = refactor ? dz : nullptr;
+    if (piece < 0) {
+        dev::SpPattern Psym, Arow, Acol;
+        if ((rc = kktsystem_pattern(sys, 0, &Psym)) || (rc = kktsystem_pattern(sys, 1, &Arow)) ||
+            (rc = kktsystem_pattern(sys, 2, &Acol)))
+            return rc;
+        dev::bj_rhs(stream, plan, Psym, Acol, Arow,
+                    dev::BjRhs{dev::BtRhs{jac.valid, xo, zo, dq, db, dP, dA, pd.d, pd.e, dc, k.rx, k.rz, vs, vz, ss, zs},
+                               ndir, (size_t)pd.n, (size_t)pd.m, (size_t)pd.M.nnzP, (size_t)pd.M.nnzA, k.stride,
+                               k.stride});
+    } else {
+        dev::bj_units(stream, plan,
+                      dev::BjUnits{jac.valid, pd.d, pd.e, dc, k.rx, k.rz, k.stride, k.stride, piece, ndir, first, vs, vz,
+                                   ss, zs});
+    }
+    jac.launches++;
+    if (refactor && (rc = deriv_factor(this, jac))) return rc;
+    // every direction's solve, enqueued.  (A system without the fused solve launch takes its refinement decisions on
+    // the host: its enqueue is a synchronous solve)
+    double model[8] = {};
+    if ((rc = chip_kkt_work_model(kkt, model))) return rc;
+    for (int t = 0; t < ndir && !rc; t++) {
+        const size_t o = (size_t)t * k.stride;
+        if (!(rc = chip_kkt_setrhs_dev(kkt, k.rx + o, k.rz + o))) rc = chip_kkt_solve_dev_enqueue(kkt, k.vx + o, k.vz + o);
+        if (!rc) jac.launches++, jac.syncs += model[7] > 0.0 ? 0 : 1;
+    }
+    if (rc) {
+        (void)chip_kkt_collect(kkt, nullptr, nullptr, nullptr); // (no solve stays pending behind a failed call)
+        return rc;
+    }
+    // E rz - A^ vx^ of every direction, then all outputs in one launch
+    auto outputs = [&]() -> int {
+        for (int t = 0; t < ndir; t++) {
+            const size_t o = (size_t)t * k.stride;
+            if (int e = kktsystem_spmv(sys, 1, k.w + o, k.rz + o, -1.0, k.vx + o)) return e;
+        }
+        double *const *r = jac.out; // dx, dz, ds
+        dev::bj_out(stream, plan,
+                    dev::BjOut{dev::BtOut{jac.valid, k.vx, k.vz, k.w, pd.d, pd.e, pd.einv, dc, r[0], r[1], r[2]}, ndir,
+                               k.stride, k.stride});
+        jac.launches += ndir + 1;
+        return CHIP_OK;
+    };
+    rc = outputs();
+    int32_t nsolves = 0, verdict[16] = {};
+    const int rcc = chip_kkt_collect(kkt, nullptr, &nsolves, verdict); // the one synchronisation
+    jac.syncs++;
+    if (rc || (rc = rcc) < 0) return rc;
+    bool repeated = false;
+    for (int t = 0; t < ndir; t++) {
+        if (t >= nsolves || verdict[t] == 0)
+            return fail(CHIP_ERR_ZERO_PIVOT, std::string(jac.name) + ": a solve at the final iterate failed");
+        repeated = repeated || verdict[t] == 2;
+    }
+    if (repeated) { // the solve was repeated at the collect: what consumed its solution before that read garbage
+        jac_repeats++;
+        if ((rc = outputs())) return rc;
+        CHIP_HIP(hipStreamSynchronize(stream));
+        jac.syncs++;
+    }
+    CHIP_HIP(hipGetLastError());
+    jac.done = true;
+    return CHIP_OK;
+}
+
+int32_t chip_bjac_apply(chip_batch *h, int32_t ndir, const double *dq, const double *db, const double *dPx,
+                        const double *dAx) {
+    const double *in[4] = {dq, db, dPx, dAx};
+    int rc = jac_begin(h, "chip_bjac_apply", ndir);
+    if (rc) return rc;
+    DerivPass &p = h->jac;
+    const size_t lens[4] = {(size_t)h->pd.n, (size_t)h->pd.m, (size_t)h->pd.M.nnzP, (size_t)h->pd.M.nnzA};
+    p.nin = 4;
+    for (int i = 0; i < 4; i++) { // the staging of a full block, allocated by the first host form that gives the input
+        if (in[i] && !p.in[i] && (rc = h->mem.alloc(&p.in[i], (size_t)CHIP_BJAC_MAX_DIR * lens[i]))) return rc;
+        p.in_len[i] = (size_t)ndir * lens[i];
+    }
+    if ((rc = deriv_stage(h, p, in))) return rc;
+    return h->jac_block(ndir, -1, 0, in[0], in[1], in[2], in[3]);
+}
+
+int32_t chip_bjac_apply_dev(chip_batch *h, int32_t ndir, const double *dq_dev, const double *db_dev,
+                            const double *dPx_dev, const double *dAx_dev) {
+    const int rc = jac_begin(h, "chip_bjac_apply_dev", ndir);
+    return rc ? rc : h->jac_block(ndir, -1, 0, dq_dev, db_dev, dPx_dev, dAx_dev);
+}
+
+int32_t chip_bjac_units(chip_batch *h, int32_t piece, int64_t first, int32_t ndir) {
+    if (h && ((piece != 0 && piece != 1) || first < 0))
+        return fail(CHIP_ERR_ARG, "chip_bjac_units: piece is 0 (q) or 1 (b), first is not negative");
+    const int rc = jac_begin(h, "chip_bjac_units", ndir);
+    return rc ? rc : h->jac_block(ndir, piece, (long long)first, nullptr, nullptr, nullptr, nullptr);
+}
+
+int32_t chip_bjac_get(chip_batch *h, double *dx, double *dz, double *ds, int32_t *valid) {
+    return deriv_get(h, "chip_bjac_get", &chip_batch::jac, {dx, dz, ds}, valid);
+}
+
+int32_t chip_bjac_get_dev(chip_batch *h, double **dx_dev, double **dz_dev, double **ds_dev, int32_t **valid_dev) {
+    return deriv_get_dev(h, "chip_bjac_get_dev", &chip_batch::jac, {dx_dev, dz_dev, ds_dev}, valid_dev);
 }

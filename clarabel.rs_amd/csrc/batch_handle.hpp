@@ -1,7 +1,7 @@
 // batch_handle.hpp -- the handle of the batched solver (struct chip_batch) and the host partition it is built from,
 // for the translation units that work on it: batch.cpp (plan, create / destroy, the IPM loop, getters, data updates),
-// batch_deriv.cpp (chip_bgrad_*, chip_bjvp_*) and batch_debug.cpp (the test hooks).  Internal: nothing here is part of
-// the C ABI, and no other translation unit includes it.
+// batch_deriv.cpp (chip_bgrad_*, chip_bjvp_*, chip_bjac_*) and batch_debug.cpp (the test hooks).  Internal: nothing
+// here is part of the C ABI, and no other translation unit includes it.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -42,9 +42,9 @@ CHIP_INTERNAL int host_plan_build(HostPlan &hp, int64_t nprob, const int64_t *n_
                                   const int64_t *cone_dims2);
 CHIP_INTERNAL int host_plan_upload(DevPool &mem, const HostPlan &hp, dev::BatchPlan *pl);
 
-// one derivative pass of the handle (the gradients or the tangents): what the shared steps of the two passes work on.
-// Each pass owns its valid flags and its results, so neither disturbs what the other's get_dev handed out.  The
-// buffers are allocated by the pass's first call
+// one derivative pass of the handle (the gradients, the tangents or the blocks of tangents): what the shared steps of
+// the passes work on.  Each pass owns its valid flags and its results, so none disturbs what another's get_dev handed
+// out.  The buffers are allocated by the pass's first call
 struct CHIP_INTERNAL DerivPass {
     const char *name;             // the call that runs the pass, as the messages name it
     bool done = false;            // the results hold a pass since the last solve
@@ -123,6 +123,13 @@ struct chip_batch {
     bool solve_current = false, kkt_final = false;
     DerivPass grad{"chip_bgrad_backward"}; // gx, gz, gs -> dq, db, dP, dA
     DerivPass tan{"chip_bjvp_apply"};      // dq, db, dP, dA -> dx, dz, ds
+    // blocks of up to CHIP_BJAC_MAX_DIR tangents with one synchronisation (chip_bjac_*).  in / out hold
+    // the directions one after the other (in_len / out_len: those of the last block; the staging is allocated by the
+    // first host form); jac_work holds, per direction, its own right-hand side, solution and A product: a solve that
+    // is pending borrows its right-hand side until the collect
+    DerivPass jac{"chip_bjac_apply"};
+    double *jac_work = nullptr;
+    long jac_calls = 0, jac_repeats = 0; // blocks run / blocks whose outputs were issued again after the collect
 
     ~chip_batch() {
         if (stream) (void)hipStreamSynchronize(stream);
@@ -213,4 +220,7 @@ struct chip_batch {
     int backward(const double *gx_dev, const double *gz_dev, const double *gs_dev);
     int jvp_work();
     int jvp_apply(const double *dq_dev, const double *db_dev, const double *dP_dev, const double *dA_dev);
+    int jac_alloc();
+    int jac_block(int ndir, int piece, long long first, const double *dq_dev, const double *db_dev, const double *dP_dev,
+                  const double *dA_dev);
 };

@@ -13,8 +13,18 @@ that did not end Solved, or own a SecondOrder cone, get zero gradients (solver.l
 
 Forward mode works through the same Function: under torch.autograd.forward_ad.dual_level() (or torch.func.jvp) the
 tangents of (x, z, s) come from HipBatchSolver.jvp (chip_bjvp_*: one KKT solve at the final iterates per direction,
-DESIGN.md 4.16); solver.last_tangent.valid tells which members have one."""
+DESIGN.md 4.16); solver.last_tangent.valid tells which members have one.
+
+Full sensitivities: batch_jacobians(solver, "q" | "b") gives every member's Jacobian of (x, z, s) with respect to its
+own q or b as GPU tensors, in max_k w_k solves for the whole batch (chip_bjac_units)."""
 import torch
+
+
+def batch_jacobians(solver, wrt="q"):
+    """the Jacobians of the members' solutions of the solver's last solve with respect to their own q or b, on the
+    GPU: a list with one entry per member, None where the member has no derivative, else (dx_dw [n_k x w_k],
+    dz_dw [m_k x w_k], ds_dw [m_k x w_k]) -- HipBatchSolver.member_jacobians(wrt, torch=True)"""
+    return solver.member_jacobians(wrt, torch=True)
 
 
 class BatchQPFunction(torch.autograd.Function):

@@ -772,8 +772,8 @@ int32_t chip_bdata_get_scaled(chip_batch *h, double *Px, double *Ax, double *q, 
  * all four required).  Afterwards the handle is in the state a fresh chip_batch_create on the same partition,
  * patterns, cones, settings and these values would be in: the scaled data, d, e and the members' c_k (host and
  * device), the unscaled copies of q and the capped b with the members' norms, max |P_ii| of the stack, every copy the
- * solve and the derivative passes read.  The partition and the symbolic analysis stay.  As after an update, chip_bgrad_*
- * and chip_bjvp_* are refused until the next chip_batch_solve; later chip_bdata_update_* calls scale with the new
+ * solve and the derivative passes read.  The partition and the symbolic analysis stay.  As after an update, chip_bgrad_*,
+ * chip_bjvp_* and chip_bjac_* are refused until the next chip_batch_solve; later chip_bdata_update_* calls scale with the new
  * d, e, c_k.  CHIP_ERR_ARG for a NULL handle or array, without touching a device.  The number of enqueues does not
  * depend on nprob; one host synchronisation. */
 int32_t chip_reequilibrate_bdata(chip_batch *h, const double *Pnzval, const double *q, const double *Anzval,
@@ -833,6 +833,37 @@ int32_t chip_bjvp_apply_dev(chip_batch *h, const double *dq_dev, const double *d
                             const double *dAx_dev);
 int32_t chip_bjvp_get(chip_batch *h, double *dx, double *dz, double *ds, int32_t *valid);
 int32_t chip_bjvp_get_dev(chip_batch *h, double **dx_dev, double **dz_dev, double **ds_dev, int32_t **valid_dev);
+
+/* ---- BLOCKS of forward-mode derivatives, and the members' Jacobians: up to CHIP_BJAC_MAX_DIR directions in one call
+ * with ONE host synchronisation.  Every direction is the computation of chip_bjvp_apply above; a block
+ * uploads the valid flags once, forms all right-hand sides in one launch (reading the index patterns once per four
+ * directions), enqueues every direction's refined solve with the refinement decisions on the device, and reads all
+ * verdicts in one synchronisation.  K is block-diagonal over the members, so ONE direction that holds "unit vector j of
+ * its own q" for every member yields column j of EVERY member's Jacobian: the Jacobians of all members with respect to
+ * q cost max_k n_k solves, not sum_k n_k.
+ *   Layout: every non-NULL input holds ndir directions, direction-major: direction t of dq starts at t * n, of db at
+ *   t * m, of dPx at t * nnz(P), of dAx at t * nnz(A); NULL = zeros for all directions.  The results likewise:
+ *   dx[ndir][n], dz[ndir][m], ds[ndir][m]; valid[nprob] as for chip_bjvp_get.
+ *   chip_bjac_apply   host inputs; _dev: device pointers (the caller must have finished writing them before the call)
+ *   chip_bjac_units   no input is read: direction t is, for every member, the unit vector at LOCAL position first + t
+ *                     of that member's own q (piece 0) or b (piece 1); a member with fewer entries gets a zero
+ *                     direction.  Column first + t of member k's Jacobian is member k's slice of direction t.
+ *   chip_bjac_get     host copies (any may be NULL) of the last block; _dev: the handle's own device buffers, valid
+ *                     until the next block, solve, update or destroy.
+ * CHIP_ERR_ARG: a NULL handle; ndir < 1 or ndir > CHIP_BJAC_MAX_DIR; piece not 0 or 1; first < 0; no finished
+ * chip_batch_solve on the data the handle holds now; a get without a block since the last solve.
+ * CHIP_ERR_ZERO_PIVOT (and no result): the factorisation at the final iterates failed, or any solve of the block did.
+ * A block keeps its own results: it does not disturb the buffers of chip_bjvp_get[_dev] or chip_bgrad_get[_dev], and
+ * neither disturbs a block's.  It factors K at the final iterates only when no backward, apply or block of this solve
+ * has done so already, and leaves the factorisation for those that follow. */
+#define CHIP_BJAC_MAX_DIR 16 /* = the pending-solve limit of chip_kkt_collect */
+int32_t chip_bjac_apply(chip_batch *h, int32_t ndir, const double *dq, const double *db, const double *dPx,
+                        const double *dAx);
+int32_t chip_bjac_apply_dev(chip_batch *h, int32_t ndir, const double *dq_dev, const double *db_dev,
+                            const double *dPx_dev, const double *dAx_dev);
+int32_t chip_bjac_units(chip_batch *h, int32_t piece, int64_t first, int32_t ndir);
+int32_t chip_bjac_get(chip_batch *h, double *dx, double *dz, double *ds, int32_t *valid);
+int32_t chip_bjac_get_dev(chip_batch *h, double **dx_dev, double **dz_dev, double **ds_dev, int32_t **valid_dev);
 
 /* ===========================================================================
  * Sharded path: one process per GPU, whole connected components of the elimination

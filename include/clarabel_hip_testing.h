@@ -109,7 +109,18 @@ int32_t chip_debug_ipm_info_update(double *info, const double *sq, double tau, d
  * chip_debug_batch_jvp_rhs: the right-hand side pass of chip_bjvp_apply (csrc/batch_tangent.hip: bt_rhs) alone on a
  * created handle, on a private stream; no solve is needed.  HOST arrays: x[n], z[m] (the unscaled solution the pass
  * reads), valid[nprob], the direction dq[n], db[m], dPx[nnz(P)], dAx[nnz(A)] (any of the four may be NULL = zeros);
- * returns the SCALED right-hand side rx[n] = c_k d (-(dq + dP_sym x + dA' z)), rz[m] = e (db - dA x). */
+ * returns the SCALED right-hand side rx[n] = c_k d (-(dq + dP_sym x + dA' z)), rz[m] = e (db - dA x).
+ * Of the blocks (chip_bjac_*): the counters "jac_launches" / "jac_host_syncs" (of the last block call), "jac_refactors"
+ * (scaling updates + refactors that blocks have paid), "jac_repeats" (blocks whose outputs were issued again because
+ * chip_kkt_collect repeated a solve) and "jac_calls" (block calls that passed the argument checks).
+ * chip_debug_batch_jac_rhs: the block form of chip_debug_batch_jvp_rhs (csrc/batch_jacobian.hip: bj_rhs): the inputs
+ * hold ndir directions (direction-major, any of the four may be NULL), the results are rx[ndir][n], rz[ndir][m].
+ * chip_debug_batch_jac_units: the unit right-hand sides (bj_units) of piece / first / ndir alone, the same results. */
+int32_t chip_debug_batch_jac_rhs(void *batch, int32_t ndir, const double *x, const double *z, const int32_t *valid,
+                                 const double *dq, const double *db, const double *dPx, const double *dAx, double *rx,
+                                 double *rz);
+int32_t chip_debug_batch_jac_units(void *batch, int32_t piece, int64_t first, int32_t ndir, const int32_t *valid,
+                                   double *rx, double *rz);
 int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration);
 int32_t chip_debug_batch_counter(void *batch, const char *name, double *out);
 int32_t chip_debug_batch_jvp_rhs(void *batch, const double *x, const double *z, const int32_t *valid, const double *dq,
