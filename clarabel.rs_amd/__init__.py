@@ -50,6 +50,7 @@ STATUS_NAMES = {0: "ok", -1: "IncompatibleDimension", -2: "EmptyColumn", -3: "No
                 -9: "BadArgument", -10: "Unsupported", -11: "UpdateNotAllowed"}
 DEVICE_HOST_ONLY = -2
 BJAC_MAX_DIR = 16  # CHIP_BJAC_MAX_DIR: the directions of one chip_bjac_* call
+BVJP_MAX_DIR = 16  # CHIP_BVJP_MAX_DIR: the cotangents of one chip_bvjp_* call
 
 # SupportedConeT tags
 ZeroConeT, NonnegativeConeT, SecondOrderConeT, ExponentialConeT, PowerConeT, GenPowerConeT, PSDTriangleConeT = range(7)
@@ -1322,10 +1323,10 @@ class HipBatchSolver(_DataUpdates):
                                 "qbb", BatchTangent)
 
     # ---- blocks of tangents and the members' Jacobians (chip_bjac_*) ------------------------------------------------
-    def _block_input(self, name, g, key):
-        """one piece of a block of directions -> ("none", None), ("host", float64 array [K, len]) or ("dev",
-        contiguous GPU tensor [K, len])"""
-        name = "jvp_block %s" % name
+    def _block_input(self, name, g, key, fn="jvp_block"):
+        """one piece of a block of directions (or, for backward_block, of cotangents) -> ("none", None), ("host",
+        float64 array [K, len]) or ("dev", contiguous GPU tensor [K, len])"""
+        name = "%s %s" % (fn, name)
         length = self._len[key]
         if g is None:
             return ("none", None)
@@ -1441,7 +1442,163 @@ class HipBatchSolver(_DataUpdates):
                     mat[:, first:first + cols] = res[:cols, int(o[k]):int(o[k + 1])].T
         return [mats if valid[k] else None for k, mats in enumerate(out)]
 
+    # ---- blocks of cotangents and the rows of the members' Jacobians (chip_bvjp_*) ----------------------------------
+    @staticmethod
+    def _want_bits(want, fn):
+        if not isinstance(want, str) or not want or any(ch not in "qbPA" for ch in want):
+            raise ValueError("%s: the wanted pieces are a non-empty subset of \"qbPA\"" % fn)
+        return sum(1 << "qbPA".index(ch) for ch in set(want))
+
+    def _vjp_result(self, ndir, bits, device=None):
+        """[dq[ndir, n], db[ndir, m], dP[ndir, nnz(P)], dA[ndir, nnz(A)]] of the last block, None for a piece that is
+        not in `bits`: numpy arrays, or copies on the GPU `device`"""
+        L = lib()
+        lens = [self._len[key] for key in "qbPA"]
+        has = [bool((bits >> i) & 1) for i in range(4)]
+        if device is None:
+            res = [np.zeros((ndir, ln)) if h else None for ln, h in zip(lens, has)]
+            _check(L.chip_bvjp_get(self._h, *[None if v is None else _pf(v) for v in res], None), "chip_bvjp_get")
+            return res
+        out = [C.c_void_p() for _ in lens]
+        _check(L.chip_bvjp_get_dev(self._h, *[C.byref(o) for o in out], None), "chip_bvjp_get_dev")
+        return [_torch_copy(o.value, ndir * ln, "float64", device).view(ndir, ln) if h else None
+                for o, ln, h in zip(out, lens, has)]
+
+    def _vjp_valid(self):
+        valid = np.zeros(len(self), dtype=np.int32)
+        _check(lib().chip_bvjp_get(self._h, None, None, None, None, valid.ctypes.data_as(P_I32)), "chip_bvjp_get")
+        return valid
+
+    def backward_block(self, gx=None, gz=None, gs=None, want="qbPA"):
+        """K cotangents at once: backward() with every piece a [K, len] matrix (row t = cotangent t; float64 numpy
+        arrays, or contiguous float64 torch tensors on the GPU: the result then holds GPU tensors and nothing crosses
+        to the host); None = zeros in every cotangent; at least one piece is given, all given pieces share K >= 1 and
+        are all host or all GPU.  want: the pieces of the result to compute, a non-empty subset of "qbPA"; the others
+        are None in the result and cost neither time nor memory.  Up to 16 cotangents are one call with one host
+        synchronisation (chip_bvjp_apply); more are cut into calls of 16.  K is factored at the final iterates only by
+        the first derivative call after a solve.  Returns a BatchGradientBlock.  Validity, zeros and refusals as for
+        backward()."""
+        bits = self._want_bits(want, "backward_block")
+        names = (("gx", "q"), ("gz", "b"), ("gs", "b"))
+        forms = [self._block_input(nm, g, key, "backward_block") for (nm, key), g in zip(names, (gx, gz, gs))]
+        kinds = {f[0] for f in forms} - {"none"}
+        if not kinds:
+            raise ChipError(ERR_DIM, "backward_block: at least one piece is needed (it gives the number of cotangents)")
+        if len(kinds) > 1:
+            raise TypeError("backward_block: gx, gz and gs must all be host arrays or all GPU tensors")
+        counts = {int(f[1].shape[0]) for f in forms if f[0] != "none"}
+        if len(counts) != 1 or min(counts) < 1:
+            raise ChipError(ERR_DIM, "backward_block: the pieces must share one number of cotangents K >= 1, not %s"
+                            % sorted(counts))
+        K = counts.pop()
+        on_dev = kinds == {"dev"}
+        device = None
+        if on_dev:
+            import torch
+            device = [f[1] for f in forms if f[0] == "dev"][0].device
+            torch.cuda.current_stream(device).synchronize()  # the values are written before the call reads them
+        L = lib()
+        parts = []
+        for t0 in range(0, K, BVJP_MAX_DIR):
+            nd = min(BVJP_MAX_DIR, K - t0)
+            if on_dev:
+                ptr = [None if f[0] == "none" else C.c_void_p(f[1].data_ptr() + 8 * t0 * f[1].shape[1]) for f in forms]
+                _check(L.chip_bvjp_apply_dev(self._h, C.c_int32(nd), C.c_int32(bits), *ptr), "chip_bvjp_apply_dev")
+            else:
+                rows = [None if f[0] == "none" else f[1][t0:t0 + nd] for f in forms]
+                _check(L.chip_bvjp_apply(self._h, C.c_int32(nd), C.c_int32(bits),
+                                         *[None if r is None else _pf(r) for r in rows]), "chip_bvjp_apply")
+            parts.append(self._vjp_result(nd, bits, device))
+        if on_dev:
+            import torch
+            cat = lambda vs: vs[0] if len(vs) == 1 else torch.cat(vs, dim=0)  # noqa: E731
+        else:
+            cat = lambda vs: vs[0] if len(vs) == 1 else np.concatenate(vs, axis=0)  # noqa: E731
+        res = [None if parts[0][i] is None else cat([p[i] for p in parts]) for i in range(4)]
+        return BatchGradientBlock(*res, self._vjp_valid(), self._offsets)
+
+    def member_jacobian_rows(self, of="x", wrt="qb", torch=False):
+        """the Jacobians of every member's x (of="x"), z or s with respect to its own q, b and the stored entries of
+        its P and A (wrt: a non-empty subset of "qbPA"), built row by row: a list with one entry per member, None
+        where the member has no derivative (valid[k] == 0), else a dict that maps each key of wrt to a matrix
+        [len(of)_k x w_k], w_k the member's number of entries of q / b, or of stored entries of P / A in the order of
+        its own nzval -- numpy arrays, or with torch=True tensors on the GPU (nothing crosses to the host).  A stored
+        (i, j), i < j, of P stands for both triangles.  K is block-diagonal over the members, so one cotangent that
+        holds unit vector j of every member's own x yields row j of every Jacobian, with respect to all of wrt at
+        once: the cost is ceil(max_k len(of)_k / 16) calls of chip_bvjp_units -- max_k len(of)_k refined solves."""
+        if of not in ("x", "z", "s"):
+            raise ValueError("member_jacobian_rows: of is \"x\", \"z\" or \"s\"")
+        bits = self._want_bits(wrt, "member_jacobian_rows")
+        keys = [key for key in "qbPA" if key in wrt]
+        piece = "xzs".index(of)
+        heights = [int(v) for v in (self.n_part if piece == 0 else self.m_part)]
+        hmax = max(heights)
+        device = None
+        if torch:
+            import torch as th
+            device = th.device("cuda")
+            new = lambda r, c: th.zeros((r, c), dtype=th.float64, device=device)  # noqa: E731
+        else:
+            new = lambda r, c: np.zeros((r, c))  # noqa: E731
+        off = {key: self._offsets[key] for key in keys}
+        out = [{key: new(hk, int(off[key][k + 1]) - int(off[key][k])) for key in keys} for k, hk in enumerate(heights)]
+        valid = None
+        for first in range(0, max(hmax, 1), BVJP_MAX_DIR):  # (no entries at all: one call, for the valid flags)
+            nd = max(1, min(BVJP_MAX_DIR, hmax - first))
+            _check(lib().chip_bvjp_units(self._h, C.c_int32(piece), C.c_int64(first), C.c_int32(nd), C.c_int32(bits)),
+                   "chip_bvjp_units")
+            block = dict(zip("qbPA", self._vjp_result(nd, bits, device)))
+            if valid is None:
+                valid = self._vjp_valid()
+            for k, hk in enumerate(heights):
+                rows = min(nd, hk - first)
+                if rows <= 0 or not valid[k]:
+                    continue
+                for key in keys:
+                    o = off[key]
+                    out[k][key][first:first + rows, :] = block[key][:rows, int(o[k]):int(o[k + 1])]
+        return [mats if valid[k] else None for k, mats in enumerate(out)]
+
     # ---- test hooks (include/clarabel_hip_testing.h) ----
+    def debug_vjp_rhs(self, form, ndir, s, z, valid, gx=None, gz=None, gs=None):
+        """the right-hand side pass of a block of cotangents alone (no solve needed): form 1 the block launcher once,
+        form 0 the single launcher once per cotangent; pieces [ndir, len] -> the scaled (rx[ndir, n] = d gx,
+        ws[ndir, m] = gs / e, rz[ndir, m] = e gz / c)"""
+        keep = [None if v is None else _f(v) for v in (s, z, gx, gz, gs)]
+        valid = np.ascontiguousarray(valid, dtype=np.int32)
+        n, m = self._len["q"], self._len["b"]
+        rx, ws, rz = np.zeros((ndir, n)), np.zeros((ndir, m)), np.zeros((ndir, m))
+        ptr = [None if v is None else _pf(v) for v in keep]
+        _check(lib().chip_debug_batch_vjp_rhs(self._h, C.c_int32(form), C.c_int32(ndir), ptr[0], ptr[1],
+                                              valid.ctypes.data_as(P_I32), *ptr[2:], _pf(rx), _pf(ws), _pf(rz)),
+               "chip_debug_batch_vjp_rhs")
+        return rx, ws, rz
+
+    def debug_vjp_units(self, piece, first, ndir, valid):
+        """the unit right-hand sides of a block of cotangents alone (no solve needed) -> the scaled (rx[ndir, n],
+        ws[ndir, m], rz[ndir, m])"""
+        valid = np.ascontiguousarray(valid, dtype=np.int32)
+        n, m = self._len["q"], self._len["b"]
+        rx, ws, rz = np.zeros((ndir, n)), np.zeros((ndir, m)), np.zeros((ndir, m))
+        _check(lib().chip_debug_batch_vjp_units(self._h, C.c_int32(piece), C.c_int64(first), C.c_int32(ndir),
+                                                valid.ctypes.data_as(P_I32), _pf(rx), _pf(ws), _pf(rz)),
+               "chip_debug_batch_vjp_units")
+        return rx, ws, rz
+
+    def debug_vjp_out(self, form, ndir, want, x, z, valid, vx, vz, gs=None, fill=0.0):
+        """the output passes of a block of cotangents alone (no solve needed) on given solve results vx[ndir, n],
+        vz[ndir, m]: form 1 the block launchers once, form 0 the single launchers once per cotangent -> (dq, db, dP,
+        dA), each [ndir, len] and pre-filled with `fill`: a piece that is not in `want` comes back as it went in"""
+        bits = self._want_bits(want, "debug_vjp_out")
+        keep = [None if v is None else _f(v) for v in (x, z, vx, vz, gs)]
+        valid = np.ascontiguousarray(valid, dtype=np.int32)
+        res = [np.full((ndir, self._len[key]), float(fill)) for key in "qbPA"]
+        ptr = [None if v is None else _pf(v) for v in keep]
+        _check(lib().chip_debug_batch_vjp_out(self._h, C.c_int32(form), C.c_int32(ndir), C.c_int32(bits), ptr[0],
+                                              ptr[1], valid.ctypes.data_as(P_I32), *ptr[2:], *[_pf(v) for v in res]),
+               "chip_debug_batch_vjp_out")
+        return tuple(res)
+
     def debug_jac_rhs(self, ndir, x, z, valid, dq=None, db=None, dP=None, dA=None):
         """the right-hand side pass of a block alone (no solve needed): pieces [ndir, len] -> the scaled
         (rx[ndir, n], rz[ndir, m])"""
@@ -1526,6 +1683,23 @@ class BatchTangentBlock:
         """member k's columns of the three matrices: (dx[:, n_k], dz[:, m_k], ds[:, m_k])"""
         o = self._offsets
         return tuple(getattr(self, name)[:, int(o[key][k]):int(o[key][k + 1])] for name, key in self.FIELDS)
+
+
+class BatchGradientBlock:
+    """the result of HipBatchSolver.backward_block: dq[K, n], db[K, m], dP[K, nnz(P)], dA[K, nnz(A)] of the stack, row
+    t = cotangent t, as numpy arrays or torch GPU tensors (None for a piece that was not wanted), and valid[nprob]
+    (numpy int32): 1 where the member has a gradient, else its entries are exact zeros in every cotangent"""
+    FIELDS = BatchGradient.FIELDS
+
+    def __init__(self, dq, db, dP, dA, valid, offsets):
+        self.dq, self.db, self.dP, self.dA, self.valid, self._offsets = dq, db, dP, dA, valid, offsets
+
+    def per_member(self, k):
+        """member k's columns of the four matrices: (dq[:, n_k], db[:, m_k], dP[:, nnz(P_k)], dA[:, nnz(A_k)]); None
+        for a piece that was not wanted"""
+        o = self._offsets
+        return tuple(None if getattr(self, name) is None
+                     else getattr(self, name)[:, int(o[key][k]):int(o[key][k + 1])] for name, key in self.FIELDS)
 
 
 def _torch_copy(ptr, n, dtype, device=None):

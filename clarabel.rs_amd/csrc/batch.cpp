@@ -591,7 +591,7 @@ int32_t chip_batch_solve(chip_batch *h) {
     h->held_done.assign((size_t)np, 0);
     h->t_solve0 = now_s();
     h->solve_time = h->setup_time;
-    h->solve_current = h->kkt_final = h->grad.done = h->tan.done = h->jac.done = false;
+    h->solve_current = h->kkt_final = h->grad.done = h->tan.done = h->jac.done = h->vjp.done = false;
     int rc;
     if ((rc = h->default_start())) return rc;
     for (int k = 0; k < np; k++) h->hm(M_ACTIVE, k) = 1;
@@ -944,7 +944,7 @@ int chip_batch::reequilibrate(const double *P_dev, const double *q_dev, const do
     if (!req_out && ((rc = mem.alloc(&eq_colsum, np)) || (rc = mem.alloc(&req_out, 2 * np + 3)))) return rc;
     req_host.assign(2 * np + 3, 0.0);
     // as after an update that changed something: no gradient and no reuse of K's factorisation until the next solve
-    solve_current = kkt_final = grad.done = tan.done = jac.done = false;
+    solve_current = kkt_final = grad.done = tan.done = jac.done = vjp.done = false;
     const double te = now_s();
     hipStream_t s = stream;
     const dev::EqMats &M = pd.M;

@@ -1,5 +1,7 @@
 // batch_debug.cpp -- the test hooks of the batched solver (include/clarabel_hip_testing.h: chip_debug_batch_*,
 // chip_debug_bplan_*); empty in the build that ships
+#include "batch_adjoint.hpp"
+#include "batch_cotangent.hpp"
 #include "batch_handle.hpp"
 #include "batch_jacobian.hpp"
 #include "batch_tangent.hpp"
@@ -33,6 +35,11 @@ int32_t chip_debug_batch_counter(void *batch, const char *name, double *out) {
     else if (nm == "jac_refactors") *out = (double)h->jac.refactors;
     else if (nm == "jac_repeats") *out = (double)h->jac_repeats;
     else if (nm == "jac_calls") *out = (double)h->jac_calls;
+    else if (nm == "vjp_launches") *out = (double)h->vjp.launches;
+    else if (nm == "vjp_host_syncs") *out = (double)h->vjp.syncs;
+    else if (nm == "vjp_refactors") *out = (double)h->vjp.refactors;
+    else if (nm == "vjp_repeats") *out = (double)h->vjp_repeats;
+    else if (nm == "vjp_calls") *out = (double)h->vjp_calls;
     else return fail(CHIP_ERR_ARG, "chip_debug_batch_counter: unknown name");
     return CHIP_OK;
 }
@@ -156,6 +163,115 @@ int32_t chip_debug_batch_jac_units(void *batch, int32_t piece, int64_t first, in
                                nullptr, nullptr, nullptr});
     rc = st.finish(s);
     (void)hipStreamDestroy(s);
+    return rc;
+}
+
+// ---- the passes of a block of cotangents alone (batch_cotangent.hip), or the single launchers once per cotangent
+int32_t chip_debug_batch_vjp_rhs(void *batch, int32_t form, int32_t ndir, const double *s, const double *z,
+                                 const int32_t *valid, const double *gx, const double *gz, const double *gs, double *rx,
+                                 double *ws, double *rz) {
+    chip_batch *h = (chip_batch *)batch;
+    if (!h || (form != 0 && form != 1) || ndir < 1 || ndir > CHIP_BVJP_MAX_DIR || !valid || (h->pd.n && !rx) ||
+        (h->pd.m && (!s || !z || !ws || !rz)))
+        return fail(CHIP_ERR_ARG, "chip_debug_batch_vjp_rhs: bad argument");
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    int rc;
+    DebugStage st;
+    const size_t n = (size_t)h->pd.n, m = (size_t)h->pd.m, K = (size_t)ndir;
+    const double *ds_, *dz_, *dgx, *dgz, *dgs;
+    const int32_t *dvalid;
+    double *drx, *dws, *drz, *dss, *dzs;
+    if ((rc = st.in(s, m, &ds_)) || (rc = st.in(z, m, &dz_)) || (rc = st.in(valid, (size_t)h->nprob, &dvalid)) ||
+        (rc = st.in(gx, K * n, &dgx)) || (rc = st.in(gz, K * m, &dgz)) || (rc = st.in(gs, K * m, &dgs)) ||
+        (rc = st.out(rx, K * n, &drx)) || (rc = st.out(ws, K * m, &dws)) || (rc = st.out(rz, K * m, &drz)) ||
+        (rc = st.mem.alloc(&dss, m)) || (rc = st.mem.alloc(&dzs, m)))
+        return rc;
+    hipStream_t q = nullptr;
+    CHIP_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
+    if (form == 1) {
+        dev::bc_rhs(q, h->plan,
+                    dev::BcRhs{dvalid, dgx, dgz, dgs, h->pd.d, h->pd.e, h->dc, ds_, dz_, drx, dws, drz, n, m, m, ndir, dss, dzs});
+    } else {
+        for (size_t t = 0; t < K; t++)
+            dev::ba_rhs(q, h->plan,
+                        dev::BaRhs{dvalid, dgx ? dgx + t * n : nullptr, dgz ? dgz + t * m : nullptr,
+                                   dgs ? dgs + t * m : nullptr, h->pd.d, h->pd.e, h->dc, ds_, dz_, drx + t * n, dws + t * m,
+                                   drz + t * m, dss, dzs});
+    }
+    rc = st.finish(q);
+    (void)hipStreamDestroy(q);
+    return rc;
+}
+
+int32_t chip_debug_batch_vjp_units(void *batch, int32_t piece, int64_t first, int32_t ndir, const int32_t *valid,
+                                   double *rx, double *ws, double *rz) {
+    chip_batch *h = (chip_batch *)batch;
+    if (!h || ndir < 1 || ndir > CHIP_BVJP_MAX_DIR || piece < 0 || piece > 2 || first < 0 || !valid || (h->pd.n && !rx) ||
+        (h->pd.m && (!ws || !rz)))
+        return fail(CHIP_ERR_ARG, "chip_debug_batch_vjp_units: bad argument");
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    int rc;
+    DebugStage st;
+    const size_t n = (size_t)h->pd.n, m = (size_t)h->pd.m, K = (size_t)ndir;
+    const int32_t *dvalid;
+    double *drx, *dws, *drz;
+    if ((rc = st.in(valid, (size_t)h->nprob, &dvalid)) || (rc = st.out(rx, K * n, &drx)) ||
+        (rc = st.out(ws, K * m, &dws)) || (rc = st.out(rz, K * m, &drz)))
+        return rc;
+    hipStream_t q = nullptr;
+    CHIP_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
+    dev::bc_units(q, h->plan,
+                  dev::BcUnits{dvalid, h->pd.d, h->pd.e, h->dc, nullptr, nullptr, drx, dws, drz, n, m, m, piece, ndir,
+                               (long long)first, nullptr, nullptr});
+    rc = st.finish(q);
+    (void)hipStreamDestroy(q);
+    return rc;
+}
+
+int32_t chip_debug_batch_vjp_out(void *batch, int32_t form, int32_t ndir, int32_t want, const double *x, const double *z,
+                                 const int32_t *valid, const double *vx, const double *vz, const double *gs, double *dq,
+                                 double *db, double *dP, double *dA) {
+    chip_batch *h = (chip_batch *)batch;
+    const size_t n = h ? (size_t)h->pd.n : 0, m = h ? (size_t)h->pd.m : 0;
+    const size_t nP = h ? (size_t)h->pd.M.nnzP : 0, nA = h ? (size_t)h->pd.M.nnzA : 0;
+    if (!h || (form != 0 && form != 1) || ndir < 1 || ndir > CHIP_BVJP_MAX_DIR || want < 1 || want > dev::BC_WANT_ALL ||
+        !valid || (n && (!x || !vx)) || (m && (!z || !vz)) || ((want & 1) && n && !dq) || ((want & 2) && m && !db) ||
+        ((want & 4) && nP && !dP) || ((want & 8) && nA && !dA))
+        return fail(CHIP_ERR_ARG, "chip_debug_batch_vjp_out: bad argument");
+    CHIP_HIP(hipSetDevice(h->pd.device));
+    int rc;
+    DebugStage st;
+    const size_t K = (size_t)ndir, lens[4] = {n, m, nP, nA};
+    const double *dx_, *dz_, *dvx, *dvz, *dgs;
+    const int32_t *dvalid;
+    double *host[4] = {dq, db, dP, dA}, *o[4], *dux, *duz;
+    if ((rc = st.in(x, n, &dx_)) || (rc = st.in(z, m, &dz_)) || (rc = st.in(valid, (size_t)h->nprob, &dvalid)) ||
+        (rc = st.in(vx, K * n, &dvx)) || (rc = st.in(vz, K * m, &dvz)) || (rc = st.in(gs, K * m, &dgs)) ||
+        (rc = st.mem.alloc(&dux, n)) || (rc = st.mem.alloc(&duz, m)))
+        return rc;
+    for (int i = 0; i < 4; i++) { // an unwanted piece: the block form gets no buffer, the single launchers a private one
+        if ((want >> i) & 1) rc = st.out(host[i], K * lens[i], &o[i]);
+        else if (form == 0) rc = st.mem.alloc(&o[i], K * lens[i]);
+        else o[i] = nullptr;
+        if (rc) return rc;
+    }
+    hipStream_t q = nullptr;
+    CHIP_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
+    if (form == 1) {
+        const dev::BcGrad g{dvalid, dvx, dvz, dgs, h->pd.d, h->pd.e, h->dc, dx_, dz_, n, m, ndir, want, 0, 0, o[0], o[1],
+                            o[2], o[3]};
+        dev::bc_grad_vectors(q, h->plan, g);
+        dev::bc_grad_matrices(q, h->plan, h->pd.M, g);
+    } else {
+        for (size_t t = 0; t < K; t++) {
+            const dev::BaGrad g{dvalid, dvx + t * n, dvz + t * m, dgs ? dgs + t * m : nullptr, h->pd.d, h->pd.e, h->dc,
+                                dx_, dz_, dux, duz, o[0] + t * n, o[1] + t * m, o[2] + t * nP, o[3] + t * nA};
+            dev::ba_grad_vectors(q, h->plan, g);
+            dev::ba_grad_matrices(q, h->plan, h->pd.M, g);
+        }
+    }
+    rc = st.finish(q);
+    (void)hipStreamDestroy(q);
     return rc;
 }
 

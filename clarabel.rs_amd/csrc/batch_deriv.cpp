@@ -1,6 +1,7 @@
-// batch_deriv.cpp -- the derivative passes of the batched solver (chip_bgrad_*, chip_bjvp_*, chip_bjac_*) on the handle
-// of batch_handle.hpp
+// batch_deriv.cpp -- the derivative passes of the batched solver (chip_bgrad_*, chip_bjvp_*, chip_bjac_*, chip_bvjp_*)
+// on the handle of batch_handle.hpp
 #include "batch_adjoint.hpp"
+#include "batch_cotangent.hpp"
 #include "batch_handle.hpp"
 #include "batch_jacobian.hpp"
 #include "batch_tangent.hpp"
@@ -255,6 +256,50 @@ struct JacWork {
     }
 };
 
+// the two ends every block of pending solves shares (the tangents here, the cotangents below).
+// block_solves: the refined solve of every direction t, ENQUEUED: [vx; vz] + t * stride = K^-1 ([rx; rz] + t * stride).
+// (A system without the fused solve launch takes its refinement decisions on the host: its enqueue is a synchronous
+// solve.)  A failure collects before it returns: no solve stays pending behind a failed call
+int block_solves(chip_batch *h, DerivPass &p, int ndir, size_t stride, const double *rx, const double *rz, double *vx,
+                 double *vz) {
+    double model[8] = {};
+    int rc;
+    if ((rc = chip_kkt_work_model(h->kkt, model))) return rc;
+    for (int t = 0; t < ndir && !rc; t++) {
+        const size_t o = (size_t)t * stride;
+        if (!(rc = chip_kkt_setrhs_dev(h->kkt, rx + o, rz + o))) rc = chip_kkt_solve_dev_enqueue(h->kkt, vx + o, vz + o);
+        if (!rc) p.launches++, p.syncs += model[7] > 0.0 ? 0 : 1;
+    }
+    if (rc) (void)chip_kkt_collect(h->kkt, nullptr, nullptr, nullptr);
+    return rc;
+}
+
+// block_finish: `outputs` enqueues what consumes the solutions; chip_kkt_collect behind it is the one synchronisation
+// and brings all verdicts.  A solve that was repeated at the collect (verdict 2) means that what consumed its solution
+// before that read garbage: the outputs are issued once more and the stream synchronised a second time
+template <class Outputs> int block_finish(chip_batch *h, DerivPass &p, int ndir, long &repeats, Outputs outputs) {
+    int rc = outputs();
+    int32_t nsolves = 0, verdict[16] = {};
+    const int rcc = chip_kkt_collect(h->kkt, nullptr, &nsolves, verdict);
+    p.syncs++;
+    if (rc || (rc = rcc) < 0) return rc;
+    bool repeated = false;
+    for (int t = 0; t < ndir; t++) {
+        if (t >= nsolves || verdict[t] == 0)
+            return fail(CHIP_ERR_ZERO_PIVOT, std::string(p.name) + ": a solve at the final iterate failed");
+        repeated = repeated || verdict[t] == 2;
+    }
+    if (repeated) {
+        repeats++;
+        if ((rc = outputs())) return rc;
+        CHIP_HIP(hipStreamSynchronize(h->stream));
+        p.syncs++;
+    }
+    CHIP_HIP(hipGetLastError());
+    p.done = true;
+    return CHIP_OK;
+}
+
 int jac_begin(chip_batch *h, const char *fn, int32_t ndir) {
     if (!h) return fail(CHIP_ERR_ARG, std::string(fn) + ": bad argument");
     if (ndir < 1 || ndir > CHIP_BJAC_MAX_DIR)
@@ -298,21 +343,9 @@ int chip_batch::jac_block(int ndir, int piece, long long first, const double *dq
     }
     jac.launches++;
     if (refactor && (rc = deriv_factor(this, jac))) return rc;
-    // every direction's solve, enqueued.  (A system without the fused solve launch takes its refinement decisions on
-    // the host: its enqueue is a synchronous solve)
-    double model[8] = {};
-    if ((rc = chip_kkt_work_model(kkt, model))) return rc;
-    for (int t = 0; t < ndir && !rc; t++) {
-        const size_t o = (size_t)t * k.stride;
-        if (!(rc = chip_kkt_setrhs_dev(kkt, k.rx + o, k.rz + o))) rc = chip_kkt_solve_dev_enqueue(kkt, k.vx + o, k.vz + o);
-        if (!rc) jac.launches++, jac.syncs += model[7] > 0.0 ? 0 : 1;
-    }
-    if (rc) {
-        (void)chip_kkt_collect(kkt, nullptr, nullptr, nullptr); // (no solve stays pending behind a failed call)
-        return rc;
-    }
+    if ((rc = block_solves(this, jac, ndir, k.stride, k.rx, k.rz, k.vx, k.vz))) return rc;
     // E rz - A^ vx^ of every direction, then all outputs in one launch
-    auto outputs = [&]() -> int {
+    return block_finish(this, jac, ndir, jac_repeats, [&]() -> int {
         for (int t = 0; t < ndir; t++) {
             const size_t o = (size_t)t * k.stride;
             if (int e = kktsystem_spmv(sys, 1, k.w + o, k.rz + o, -1.0, k.vx + o)) return e;
@@ -323,27 +356,7 @@ int chip_batch::jac_block(int ndir, int piece, long long first, const double *dq
                                k.stride, k.stride});
         jac.launches += ndir + 1;
         return CHIP_OK;
-    };
-    rc = outputs();
-    int32_t nsolves = 0, verdict[16] = {};
-    const int rcc = chip_kkt_collect(kkt, nullptr, &nsolves, verdict); // the one synchronisation
-    jac.syncs++;
-    if (rc || (rc = rcc) < 0) return rc;
-    bool repeated = false;
-    for (int t = 0; t < ndir; t++) {
-        if (t >= nsolves || verdict[t] == 0)
-            return fail(CHIP_ERR_ZERO_PIVOT, std::string(jac.name) + ": a solve at the final iterate failed");
-        repeated = repeated || verdict[t] == 2;
-    }
-    if (repeated) { // the solve was repeated at the collect: what consumed its solution before that read garbage
-        jac_repeats++;
-        if ((rc = outputs())) return rc;
-        CHIP_HIP(hipStreamSynchronize(stream));
-        jac.syncs++;
-    }
-    CHIP_HIP(hipGetLastError());
-    jac.done = true;
-    return CHIP_OK;
+    });
 }
 
 int32_t chip_bjac_apply(chip_batch *h, int32_t ndir, const double *dq, const double *db, const double *dPx,
@@ -381,4 +394,140 @@ int32_t chip_bjac_get(chip_batch *h, double *dx, double *dz, double *ds, int32_t
 
 int32_t chip_bjac_get_dev(chip_batch *h, double **dx_dev, double **dz_dev, double **ds_dev, int32_t **valid_dev) {
     return deriv_get_dev(h, "chip_bjac_get_dev", &chip_batch::jac, {dx_dev, dz_dev, ds_dev}, valid_dev);
+}
+
+// ---- blocks of cotangents (chip_bvjp_*): up to CHIP_BVJP_MAX_DIR backwards with ONE synchronisation,
+// and only the pieces of the result the caller wants.  The mathematics of every cotangent is the backward's above.
+// What differs is the host sequence, which is jac_block's: one right-hand side launch for all cotangents, the A'
+// products only when a gs is given, the refactor only when K is not factored at the final iterates yet (a backward
+// always pays it), every cotangent's refined solve enqueued, the output launches behind them, and chip_kkt_collect as
+// the one synchronisation.  Every cotangent owns its slices of vjp_work: [t n' | ws m' | rx n' | rz m' | vx n' | vz m']
+// with n', m' the lengths rounded up to even (16-byte aligned slices); t = D gx and ws = gs / e are the operands of
+// the A' product and stay unused without a gs, where the right-hand side pass writes D gx into rx itself
+namespace {
+struct VjpWork {
+    size_t stride;
+    double *t, *ws, *rx, *rz, *vx, *vz; // of cotangent 0; cotangent u: + u * stride
+    explicit VjpWork(const chip_batch *h) {
+        const size_t np = ((size_t)h->pd.n + 1) & ~(size_t)1, mp = ((size_t)h->pd.m + 1) & ~(size_t)1;
+        stride = 3 * np + 3 * mp;
+        t = h->vjp_work;
+        ws = t + np;
+        rx = ws + mp;
+        rz = rx + np;
+        vx = rz + mp;
+        vz = vx + np;
+    }
+};
+
+int vjp_begin(chip_batch *h, const char *fn, int32_t ndir, int32_t want) {
+    if (!h) return fail(CHIP_ERR_ARG, std::string(fn) + ": bad argument");
+    if (ndir < 1 || ndir > CHIP_BVJP_MAX_DIR)
+        return fail(CHIP_ERR_ARG, std::string(fn) + ": a block holds 1 to CHIP_BVJP_MAX_DIR cotangents");
+    if (want < 1 || want > dev::BC_WANT_ALL)
+        return fail(CHIP_ERR_ARG, std::string(fn) + ": want holds bits 0 (dq), 1 (db), 2 (dP), 3 (dA), at least one");
+    // the kernels index [x space; z space] and [P; A] together in int32 (chip_batch_create refuses a larger stack)
+    const int64_t lim = 1ll << 31;
+    if ((int64_t)h->pd.n + (int64_t)h->pd.m >= lim || (int64_t)h->pd.M.nnzP + (int64_t)h->pd.M.nnzA >= lim)
+        return fail(CHIP_ERR_DIM, std::string(fn) + ": sizes out of int32 range");
+    return deriv_begin(h, fn, &chip_batch::vjp, &chip_batch::vjp_alloc);
+}
+} // namespace
+
+int chip_batch::vjp_alloc() {
+    if (vjp.valid) return CHIP_OK;
+    int rc;
+    if ((rc = mem.alloc(&vjp_work, (size_t)CHIP_BVJP_MAX_DIR * VjpWork(this).stride))) return rc;
+    rc = deriv_alloc(this, vjp, {}, {});
+    vjp.nout = 4; // (allocated piece by piece, by the first block that wants the piece)
+    return rc;
+}
+
+int chip_batch::vjp_block(int ndir, int want, int piece, long long first, const double *gx, const double *gz,
+                          const double *gs) {
+    int rc;
+    vjp.done = false; // (a block that fails part-way leaves no result behind)
+    vjp_calls++;
+    const size_t lens[4] = {(size_t)pd.n, (size_t)pd.m, (size_t)pd.M.nnzP, (size_t)pd.M.nnzA};
+    for (int i = 0; i < 4; i++) {
+        const bool wanted = (want >> i) & 1;
+        if (wanted && !vjp.out[i] && (rc = mem.alloc(&vjp.out[i], (size_t)CHIP_BVJP_MAX_DIR * lens[i]))) return rc;
+        vjp.out_len[i] = wanted ? (size_t)ndir * lens[i] : 0;
+    }
+    vjp_want = want;
+    const VjpWork k(this);
+    if ((rc = deriv_valid(this, vjp))) return rc;
+    const bool refactor = !kkt_final, with_gs = piece == 2 || (piece < 0 && gs);
+    double *ss = refactor ? ds : nullptr, *zs = refactor ? dz : nullptr;
+    // with a gs the pass writes the operands of the A' product, without one the right-hand side itself
+    double *dgx = with_gs ? k.t : k.rx, *ws = with_gs ? k.ws : nullptr;
+    if (piece < 0)
+        dev::bc_rhs(stream, plan,
+                    dev::BcRhs{vjp.valid, gx, gz, gs, pd.d, pd.e, dc, vs, vz, dgx, ws, k.rz, k.stride, k.stride, k.stride,
+                               ndir, ss, zs});
+    else
+        dev::bc_units(stream, plan,
+                      dev::BcUnits{vjp.valid, pd.d, pd.e, dc, vs, vz, dgx, ws, k.rz, k.stride, k.stride, k.stride, piece,
+                                   ndir, first, ss, zs});
+    vjp.launches++;
+    for (int t = 0; t < ndir && with_gs; t++) { // D gx - A^' (gs / e), as the backward forms it
+        const size_t o = (size_t)t * k.stride;
+        if ((rc = kktsystem_spmv(sys, 2, k.rx + o, k.t + o, -1.0, k.ws + o))) return rc;
+        vjp.launches++;
+    }
+    if (refactor && (rc = deriv_factor(this, vjp))) return rc;
+    if ((rc = block_solves(this, vjp, ndir, k.stride, k.rx, k.rz, k.vx, k.vz))) return rc;
+    // the wanted gradients of all cotangents: one launch for dq / db, one for dP / dA
+    double *const *r = vjp.out; // dq, db, dP, dA
+    const dev::BcGrad g{vjp.valid, k.vx, k.vz, piece < 0 ? gs : nullptr, pd.d, pd.e, dc, xo, zo, k.stride, k.stride, ndir,
+                        want, piece == 2 ? 1 : 0, first, r[0], r[1], r[2], r[3]};
+    return block_finish(this, vjp, ndir, vjp_repeats, [&]() -> int {
+        if (want & (dev::BC_WANT_Q | dev::BC_WANT_B)) dev::bc_grad_vectors(stream, plan, g), vjp.launches++;
+        if (want & (dev::BC_WANT_P | dev::BC_WANT_A)) dev::bc_grad_matrices(stream, plan, pd.M, g), vjp.launches++;
+        return CHIP_OK;
+    });
+}
+
+int32_t chip_bvjp_apply(chip_batch *h, int32_t ndir, int32_t want, const double *gx, const double *gz,
+                        const double *gs) {
+    const double *in[3] = {gx, gz, gs};
+    int rc = vjp_begin(h, "chip_bvjp_apply", ndir, want);
+    if (rc) return rc;
+    DerivPass &p = h->vjp;
+    const size_t lens[3] = {(size_t)h->pd.n, (size_t)h->pd.m, (size_t)h->pd.m};
+    p.nin = 3;
+    for (int i = 0; i < 3; i++) { // the staging of a full block, allocated by the first host form that gives the input
+        if (in[i] && !p.in[i] && (rc = h->mem.alloc(&p.in[i], (size_t)CHIP_BVJP_MAX_DIR * lens[i]))) return rc;
+        p.in_len[i] = (size_t)ndir * lens[i];
+    }
+    if ((rc = deriv_stage(h, p, in))) return rc;
+    return h->vjp_block(ndir, want, -1, 0, in[0], in[1], in[2]);
+}
+
+int32_t chip_bvjp_apply_dev(chip_batch *h, int32_t ndir, int32_t want, const double *gx_dev, const double *gz_dev,
+                            const double *gs_dev) {
+    const int rc = vjp_begin(h, "chip_bvjp_apply_dev", ndir, want);
+    return rc ? rc : h->vjp_block(ndir, want, -1, 0, gx_dev, gz_dev, gs_dev);
+}
+
+int32_t chip_bvjp_units(chip_batch *h, int32_t piece, int64_t first, int32_t ndir, int32_t want) {
+    if (h && (piece < 0 || piece > 2 || first < 0))
+        return fail(CHIP_ERR_ARG, "chip_bvjp_units: piece is 0 (x), 1 (z) or 2 (s), first is not negative");
+    const int rc = vjp_begin(h, "chip_bvjp_units", ndir, want);
+    return rc ? rc : h->vjp_block(ndir, want, piece, (long long)first, nullptr, nullptr, nullptr);
+}
+
+// (out_len of a piece the last block did not want is 0: nothing is written through its pointer)
+int32_t chip_bvjp_get(chip_batch *h, double *dq, double *db, double *dPx, double *dAx, int32_t *valid) {
+    return deriv_get(h, "chip_bvjp_get", &chip_batch::vjp, {dq, db, dPx, dAx}, valid);
+}
+
+int32_t chip_bvjp_get_dev(chip_batch *h, double **dq_dev, double **db_dev, double **dPx_dev, double **dAx_dev,
+                          int32_t **valid_dev) {
+    if (int rc = deriv_result(h, "chip_bvjp_get_dev", &chip_batch::vjp)) return rc;
+    double **dst[4] = {dq_dev, db_dev, dPx_dev, dAx_dev};
+    for (int i = 0; i < 4; i++)
+        if (dst[i]) *dst[i] = ((h->vjp_want >> i) & 1) ? h->vjp.out[i] : nullptr;
+    if (valid_dev) *valid_dev = h->vjp.valid;
+    return CHIP_OK;
 }

@@ -1,7 +1,7 @@
 // batch_handle.hpp -- the handle of the batched solver (struct chip_batch) and the host partition it is built from,
 // for the translation units that work on it: batch.cpp (plan, create / destroy, the IPM loop, getters, data updates),
-// batch_deriv.cpp (chip_bgrad_*, chip_bjvp_*, chip_bjac_*) and batch_debug.cpp (the test hooks).  Internal: nothing
-// here is part of the C ABI, and no other translation unit includes it.
+// batch_deriv.cpp (chip_bgrad_*, chip_bjvp_*, chip_bjac_*, chip_bvjp_*) and batch_debug.cpp (the test hooks).
+// Internal: nothing here is part of the C ABI, and no other translation unit includes it.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -42,9 +42,9 @@ CHIP_INTERNAL int host_plan_build(HostPlan &hp, int64_t nprob, const int64_t *n_
                                   const int64_t *cone_dims2);
 CHIP_INTERNAL int host_plan_upload(DevPool &mem, const HostPlan &hp, dev::BatchPlan *pl);
 
-// one derivative pass of the handle (the gradients, the tangents or the blocks of tangents): what the shared steps of
-// the passes work on.  Each pass owns its valid flags and its results, so none disturbs what another's get_dev handed
-// out.  The buffers are allocated by the pass's first call
+// one derivative pass of the handle (the gradients, the tangents, the blocks of tangents or of cotangents): what the
+// shared steps of the passes work on.  Each pass owns its valid flags and its results, so none disturbs what another's
+// get_dev handed out.  The buffers are allocated by the pass's first call
 struct CHIP_INTERNAL DerivPass {
     const char *name;             // the call that runs the pass, as the messages name it
     bool done = false;            // the results hold a pass since the last solve
@@ -130,6 +130,14 @@ struct chip_batch {
     DerivPass jac{"chip_bjac_apply"};
     double *jac_work = nullptr;
     long jac_calls = 0, jac_repeats = 0; // blocks run / blocks whose outputs were issued again after the collect
+    // blocks of up to CHIP_BVJP_MAX_DIR cotangents with one synchronisation (chip_bvjp_*).  out holds
+    // the cotangents one after the other; a piece's buffer is allocated by the first block that wants it (vjp_want:
+    // the pieces the last block computed); vjp_work holds, per cotangent, D gx and gs / e (the operands of the A'
+    // product), its own right-hand side and its solution
+    DerivPass vjp{"chip_bvjp_apply"};
+    double *vjp_work = nullptr;
+    int vjp_want = 0;
+    long vjp_calls = 0, vjp_repeats = 0;
 
     ~chip_batch() {
         if (stream) (void)hipStreamSynchronize(stream);
@@ -223,4 +231,7 @@ struct chip_batch {
     int jac_alloc();
     int jac_block(int ndir, int piece, long long first, const double *dq_dev, const double *db_dev, const double *dP_dev,
                   const double *dA_dev);
+    int vjp_alloc();
+    int vjp_block(int ndir, int want, int piece, long long first, const double *gx_dev, const double *gz_dev,
+                  const double *gs_dev);
 };

@@ -16,7 +16,10 @@ tangents of (x, z, s) come from HipBatchSolver.jvp (chip_bjvp_*: one KKT solve a
 DESIGN.md 4.16); solver.last_tangent.valid tells which members have one.
 
 Full sensitivities: batch_jacobians(solver, "q" | "b") gives every member's Jacobian of (x, z, s) with respect to its
-own q or b as GPU tensors, in max_k w_k solves for the whole batch (chip_bjac_units)."""
+own q or b as GPU tensors, in max_k w_k solves for the whole batch (chip_bjac_units).
+batch_jacobian_rows(solver, "x" | "z" | "s", wrt) builds the same Jacobians row by row, which also reaches the stored
+entries of P and A (wrt any subset of "qbPA"), and batch_vjp_block(solver, GX, GZ, GS, want) runs K backwards at once
+with one host synchronisation per 16 (chip_bvjp_*).  BatchQPFunction itself is unchanged."""
 import torch
 
 
@@ -25,6 +28,20 @@ def batch_jacobians(solver, wrt="q"):
     GPU: a list with one entry per member, None where the member has no derivative, else (dx_dw [n_k x w_k],
     dz_dw [m_k x w_k], ds_dw [m_k x w_k]) -- HipBatchSolver.member_jacobians(wrt, torch=True)"""
     return solver.member_jacobians(wrt, torch=True)
+
+
+def batch_vjp_block(solver, GX=None, GZ=None, GS=None, want="qbPA"):
+    """K cotangents of the solver's last solve at once: GX [K, n], GZ [K, m], GS [K, m] (float64 GPU tensors; None =
+    zeros) -> a BatchGradientBlock of GPU tensors holding the pieces named in `want`, with one host synchronisation
+    per 16 cotangents -- HipBatchSolver.backward_block (chip_bvjp_*)"""
+    return solver.backward_block(gx=GX, gz=GZ, gs=GS, want=want)
+
+
+def batch_jacobian_rows(solver, of="x", wrt="qb"):
+    """the Jacobians of the members' x, z or s of the solver's last solve with respect to their own q, b and the
+    stored entries of their P and A, on the GPU: a list with one entry per member, None where the member has no
+    derivative, else {key: [len(of)_k x w_k]} -- HipBatchSolver.member_jacobian_rows(of, wrt, torch=True)"""
+    return solver.member_jacobian_rows(of, wrt, torch=True)
 
 
 class BatchQPFunction(torch.autograd.Function):

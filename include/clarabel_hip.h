@@ -773,7 +773,7 @@ int32_t chip_bdata_get_scaled(chip_batch *h, double *Px, double *Ax, double *q, 
  * patterns, cones, settings and these values would be in: the scaled data, d, e and the members' c_k (host and
  * device), the unscaled copies of q and the capped b with the members' norms, max |P_ii| of the stack, every copy the
  * solve and the derivative passes read.  The partition and the symbolic analysis stay.  As after an update, chip_bgrad_*,
- * chip_bjvp_* and chip_bjac_* are refused until the next chip_batch_solve; later chip_bdata_update_* calls scale with the new
+ * chip_bjvp_*, chip_bjac_* and chip_bvjp_* are refused until the next chip_batch_solve; later chip_bdata_update_* calls scale with the new
  * d, e, c_k.  CHIP_ERR_ARG for a NULL handle or array, without touching a device.  The number of enqueues does not
  * depend on nprob; one host synchronisation. */
 int32_t chip_reequilibrate_bdata(chip_batch *h, const double *Pnzval, const double *q, const double *Anzval,
@@ -864,6 +864,49 @@ int32_t chip_bjac_apply_dev(chip_batch *h, int32_t ndir, const double *dq_dev, c
 int32_t chip_bjac_units(chip_batch *h, int32_t piece, int64_t first, int32_t ndir);
 int32_t chip_bjac_get(chip_batch *h, double *dx, double *dz, double *ds, int32_t *valid);
 int32_t chip_bjac_get_dev(chip_batch *h, double **dx_dev, double **dz_dev, double **ds_dev, int32_t **valid_dev);
+
+/* ---- BLOCKS of gradients, and the ROWS of the members' Jacobians: up to CHIP_BVJP_MAX_DIR cotangents (gx, gz, gs) in
+ * one call with ONE host synchronisation, and only the pieces of the result the caller wants.  Every
+ * cotangent is the computation of chip_bgrad_backward above.  What a call costs: one upload of the valid flags, one
+ * right-hand side launch for all cotangents, one A' product per cotangent only when gs is given (or piece 2), one
+ * enqueued refined KKT solve per cotangent, one output launch for dq / db and one for dP / dA (each only when wanted),
+ * and the one synchronisation that reads all verdicts.  WHEN IT REFACTORS: only when no backward, apply or block of
+ * this solve has factored K at the final iterates yet -- the scaling update, the refactor and a second synchronisation
+ * are then paid once and the factorisation is left for the calls that follow (chip_bgrad_backward pays them on every
+ * call).  K is block-diagonal over the members, so ONE cotangent that holds "unit vector j of its own x" for every
+ * member yields row j of EVERY member's Jacobian with respect to q, b, P and A at once: the rows of dx/d(q, b, P, A) of
+ * all members cost max_k n_k solves.
+ *   want: bit 0 dq, bit 1 db, bit 2 dP, bit 3 dA.  Only the wanted pieces are computed, allocated (at
+ *   CHIP_BVJP_MAX_DIR times the piece's length, by the first call that wants the piece) and returned; without bits 2
+ *   and 3 no matrix launch is made at all.
+ *   Layout: every non-NULL input holds ndir cotangents, cotangent-major: gx[ndir][n], gz[ndir][m], gs[ndir][m]; NULL =
+ *   zeros in every cotangent.  The results likewise: dq[ndir][n], db[ndir][m], dPx[ndir][nnz(P)], dAx[ndir][nnz(A)] in
+ *   the order of the stack's nzval; valid[nprob] as for chip_bgrad_get.
+ *   chip_bvjp_apply   host inputs; _dev: device pointers (the caller must have finished writing them before the call)
+ *   chip_bvjp_units   no input is read: cotangent t is, for every member, the unit vector at LOCAL position first + t
+ *                     of that member's own x (piece 0), z (piece 1) or s (piece 2); a member with fewer entries gets a
+ *                     zero cotangent.  Row first + t of member k's Jacobian is member k's slice of cotangent t.
+ *   chip_bvjp_get     host copies (any may be NULL) of the last block; nothing is written through the pointer of a
+ *                     piece the last block did not want.  _dev: the handle's own device buffers, valid until the next
+ *                     block, solve, update or destroy; NULL for a piece the last block did not want.
+ * valid[k] = 1 iff member k ended CHIP_SOLVER_SOLVED and owns only Zero / Nonnegative cones.  Every other member has
+ * exact +0.0 in all results, and nothing of it is read as a number, neither its iterate nor its part of the inputs.
+ * CHIP_ERR_ARG, before any device is touched: a NULL handle; ndir < 1 or ndir > CHIP_BVJP_MAX_DIR; want 0 or with bits
+ * beyond 3; piece not 0, 1 or 2; first < 0.  CHIP_ERR_ARG also without a finished chip_batch_solve on the data the
+ * handle holds now, and for a get without a block since the last solve.  CHIP_ERR_DIM: a stack whose entries cannot be
+ * indexed in 32 bits.  CHIP_ERR_ZERO_PIVOT (and no result): the factorisation at the final iterates failed, or any
+ * solve of the block did.  A block keeps its own results: it does not disturb the buffers of chip_bgrad_get[_dev],
+ * chip_bjvp_get[_dev] or chip_bjac_get[_dev], and none of those calls disturbs a block's.  A following chip_batch_solve
+ * behaves as if the block had not run. */
+#define CHIP_BVJP_MAX_DIR 16 /* = the pending-solve limit of chip_kkt_collect, as CHIP_BJAC_MAX_DIR */
+int32_t chip_bvjp_apply(chip_batch *h, int32_t ndir, int32_t want, const double *gx, const double *gz,
+                        const double *gs);
+int32_t chip_bvjp_apply_dev(chip_batch *h, int32_t ndir, int32_t want, const double *gx_dev, const double *gz_dev,
+                            const double *gs_dev);
+int32_t chip_bvjp_units(chip_batch *h, int32_t piece, int64_t first, int32_t ndir, int32_t want);
+int32_t chip_bvjp_get(chip_batch *h, double *dq, double *db, double *dPx, double *dAx, int32_t *valid);
+int32_t chip_bvjp_get_dev(chip_batch *h, double **dq_dev, double **db_dev, double **dPx_dev, double **dAx_dev,
+                          int32_t **valid_dev);
 
 /* ===========================================================================
  * Sharded path: one process per GPU, whole connected components of the elimination

@@ -121,6 +121,27 @@ int32_t chip_debug_batch_jac_rhs(void *batch, int32_t ndir, const double *x, con
                                  double *rz);
 int32_t chip_debug_batch_jac_units(void *batch, int32_t piece, int64_t first, int32_t ndir, const int32_t *valid,
                                    double *rx, double *rz);
+/* Of the blocks of cotangents (chip_bvjp_*): the counters "vjp_launches" / "vjp_host_syncs" (of the last block call),
+ * "vjp_refactors" (scaling updates + refactors that blocks have paid), "vjp_repeats" (blocks whose outputs were issued
+ * again because chip_kkt_collect repeated a solve) and "vjp_calls" (block calls that passed the argument checks).
+ * The three passes of a block alone on a created handle, on a private stream; no solve is needed; HOST arrays; the
+ * valid flags are given.  form = 1 runs the block launcher (csrc/batch_cotangent.hip) ONCE; form = 0 runs the single
+ * launchers of chip_bgrad_backward (csrc/batch_adjoint.hip) once per cotangent on that cotangent's slices.
+ * chip_debug_batch_vjp_rhs: s[m], z[m] (the internal iterate the scaling point is read from), gx[ndir][n], gz[ndir][m],
+ * gs[ndir][m] (any of the three may be NULL = zeros) -> rx[ndir][n] = d gx, ws[ndir][m] = gs / e,
+ * rz[ndir][m] = e gz / c_k (the A' product is not part of the pass).
+ * chip_debug_batch_vjp_units: the unit right-hand sides (bc_units) of piece / first / ndir alone, the same results.
+ * chip_debug_batch_vjp_out: x[n], z[m] (the unscaled solution), the solves' results vx[ndir][n], vz[ndir][m] and
+ * gs[ndir][m] (may be NULL) -> dq[ndir][n], db[ndir][m], dP[ndir][nnz(P)], dA[ndir][nnz(A)]; only the pieces in `want`
+ * (bit 0 dq .. bit 3 dA) are written, in either form, and only their pointers are needed. */
+int32_t chip_debug_batch_vjp_rhs(void *batch, int32_t form, int32_t ndir, const double *s, const double *z,
+                                 const int32_t *valid, const double *gx, const double *gz, const double *gs, double *rx,
+                                 double *ws, double *rz);
+int32_t chip_debug_batch_vjp_units(void *batch, int32_t piece, int64_t first, int32_t ndir, const int32_t *valid,
+                                   double *rx, double *ws, double *rz);
+int32_t chip_debug_batch_vjp_out(void *batch, int32_t form, int32_t ndir, int32_t want, const double *x, const double *z,
+                                 const int32_t *valid, const double *vx, const double *vz, const double *gs, double *dq,
+                                 double *db, double *dP, double *dA);
 int32_t chip_debug_batch_inject_nan(void *batch, int64_t member, int32_t iteration);
 int32_t chip_debug_batch_counter(void *batch, const char *name, double *out);
 int32_t chip_debug_batch_jvp_rhs(void *batch, const double *x, const double *z, const int32_t *valid, const double *dq,
