@@ -1114,7 +1114,8 @@ def batch_stack(problems):
 class HipBatchSolver(_DataUpdates):
     """many independent problems in ONE batched interior-point solve on the device (chip_batch_*): every member keeps
     its own tau, kappa, mu, sigma, step length, termination and status.  problems: a list of (P, q, A, b, cones) as
-    HipSolver takes them, with Zero / Nonnegative / SecondOrder cones; one settings for every member.
+    HipSolver takes them, with Zero / Nonnegative / SecondOrder cones (and PSDTriangle cones with cones="symmetric");
+    one settings for every member.
 
     Data updates (chip_bdata_*; update(), update_P / _A / _q / _b): new values on the stack's fixed patterns, then
     solve() again.  Each piece is a stacked value vector (or a CscMatrix with the stack's pattern), an (index, values)
@@ -1125,8 +1126,15 @@ class HipBatchSolver(_DataUpdates):
 
     _UPDATE_PREFIX = "chip_bdata_update_"
     _REEQUILIBRATE = "chip_reequilibrate_bdata"
+    _CREATE = {"basic": "chip_batch_create", "symmetric": "chip_bsym_create"}
 
-    def __init__(self, problems, settings=None):
+    def __init__(self, problems, settings=None, cones="basic"):
+        """cones: "basic" (Zero / Nonnegative / SecondOrder members, chip_batch_create) or "symmetric" (PSDTriangle
+        members as well, chip_bsym_create: the same solver and the same methods; a member that owns a PSD cone has no
+        derivative, valid[k] = 0)"""
+        if cones not in self._CREATE:
+            raise ValueError('cones must be "basic" or "symmetric", not %r' % (cones,))
+        create = self._CREATE[cones]
         problems = list(problems)
         st = batch_stack(problems)
         self.stack = st
@@ -1147,13 +1155,13 @@ class HipBatchSolver(_DataUpdates):
         self._h = C.c_void_p()
         Pp, Pi, Px = st["P"]
         Ap, Ai, Ax = st["A"]
-        _check(lib().chip_batch_create(C.byref(self._h), C.c_int64(len(problems)),
-                                       self.n_part.ctypes.data_as(P_I64), self.m_part.ctypes.data_as(P_I64),
-                                       C.c_int64(st["n"]), C.c_int64(st["m"]), _pu(Pp), _pu(Pi), _pf(Px), _pf(st["q"]),
-                                       _pu(Ap), _pu(Ai), _pf(Ax), _pf(st["b"]), C.c_int64(len(tags)),
-                                       tags.ctypes.data_as(P_I32), dims.ctypes.data_as(P_I64),
-                                       dims2.ctypes.data_as(P_I64), _pf(alphas), None, C.byref(self.settings)),
-               "chip_batch_create")
+        _check(getattr(lib(), create)(C.byref(self._h), C.c_int64(len(problems)),
+                                      self.n_part.ctypes.data_as(P_I64), self.m_part.ctypes.data_as(P_I64),
+                                      C.c_int64(st["n"]), C.c_int64(st["m"]), _pu(Pp), _pu(Pi), _pf(Px), _pf(st["q"]),
+                                      _pu(Ap), _pu(Ai), _pf(Ax), _pf(st["b"]), C.c_int64(len(tags)),
+                                      tags.ctypes.data_as(P_I32), dims.ctypes.data_as(P_I64),
+                                      dims2.ctypes.data_as(P_I64), _pf(alphas), None, C.byref(self.settings)),
+               create)
 
     def __len__(self):
         return len(self.n_part)
@@ -1301,8 +1309,8 @@ class HipBatchSolver(_DataUpdates):
         the GPU (float64; the result then holds torch tensors on the GPU and nothing crosses to the host), or a list
         with one entry per member (None = zeros for that member; the entries are HOST vectors, as in update()'s list
         form -- gradients that live on the GPU go in as stacked tensors).  Returns a BatchGradient.  Members that did not end
-        Solved, or own a SecondOrder cone, have valid[k] = 0 and exact zeros.  ChipError(ERR_ARG) before a solve and
-        after an update that was not followed by a solve."""
+        Solved, or own a SecondOrder or PSDTriangle cone, have valid[k] = 0 and exact zeros.  ChipError(ERR_ARG) before
+        a solve and after an update that was not followed by a solve."""
         return self._derivative("backward", (("gx", "q"), ("gz", "b"), ("gs", "b")), (gx, gz, gs),
                                 ("chip_bgrad_backward", "chip_bgrad_backward_dev", "chip_bgrad_get",
                                  "chip_bgrad_get_dev"), "qbPA", BatchGradient)
@@ -1812,15 +1820,19 @@ class BatchPlanDebug:
     ITEM_NN, ITEM_SOC = range(2)
     CHUNK, SEG_MAX = 4096, 16
 
-    def __init__(self, n_part, m_part, cones):
+    PSD_NAMES = ("degree", "psd_sizes", "psd_mem", "psd_start", "psd_dim", "psd_view", "psd_first", "psd_diag")
+    ROW_PSD = 4
+
+    def __init__(self, n_part, m_part, cones, symmetric=False):
+        """symmetric: the plan of chip_bsym_create (chip_debug_bsymplan_create), which takes PSDTriangle cones too"""
         n_part = np.ascontiguousarray(n_part, dtype=np.int64)
         m_part = np.ascontiguousarray(m_part, dtype=np.int64)
         tags, dims, _, _ = _cone_arrays(cones)
         self._h = C.c_void_p()
-        _check(lib().chip_debug_bplan_create(C.byref(self._h), C.c_int64(len(n_part)), n_part.ctypes.data_as(P_I64),
-                                             m_part.ctypes.data_as(P_I64), C.c_int64(len(tags)),
-                                             tags.ctypes.data_as(P_I32), dims.ctypes.data_as(P_I64)),
-               "chip_debug_bplan_create")
+        create = "chip_debug_bsymplan_create" if symmetric else "chip_debug_bplan_create"
+        _check(getattr(lib(), create)(C.byref(self._h), C.c_int64(len(n_part)), n_part.ctypes.data_as(P_I64),
+                                      m_part.ctypes.data_as(P_I64), C.c_int64(len(tags)),
+                                      tags.ctypes.data_as(P_I32), dims.ctypes.data_as(P_I64)), create)
         self.nprob, self.n, self.m, self.ncx, self.ncz, self.nitems = [int(v) for v in self.get("sizes")]
 
     def __del__(self):

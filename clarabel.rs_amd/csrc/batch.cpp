@@ -10,6 +10,9 @@
 // The L2 cone operations without a scalar (affine ds, ds from dz, Hs products, scaling update, unit initialisation)
 // run on the whole stack as they are; combined_ds_shift runs with sigma mu = 0 and the member's sigma mu is then
 // subtracted at the unit vector's entries, which is the same arithmetic for Nonnegative and SecondOrder cones.
+// Members with PSDTriangle cones come in through chip_bsym_create, the same body with another mask of accepted cones:
+// the L2 handle's per-cone eigenvalue results are folded per member on the device and the unit-vector operations run
+// on the cones' diagonal entries (batch_psd.hpp).  A handle without PSD cones runs none of that.
 // This file: the partition, create / destroy, the loop, the getters and the data updates.  The handle itself is in
 // batch_handle.hpp, the derivative passes in batch_deriv.cpp, the test hooks in batch_debug.cpp.
 #include <algorithm>
@@ -33,11 +36,14 @@ enum { R_QX, R_XPX, R_NX, R_NRXI, R_NPX, R_NRX, R_BADX, R_BZ, R_SZ, R_NZ, R_NS, 
 enum { D_QX1, D_BZ1, D_XIPX1, D_DPD, D_BAD, D_COUNT };
 } // namespace
 
-int batch_cones_supported(int64_t ncones, const int32_t *cone_tags) {
+const BatchEntry BATCH_ENTRY_BASIC{"chip_batch_create", BATCH_CONES_BASIC, "only Zero, Nonnegative and SecondOrder cones"};
+const BatchEntry BATCH_ENTRY_SYMMETRIC{"chip_bsym_create", BATCH_CONES_SYMMETRIC,
+                                       "only Zero, Nonnegative, SecondOrder and PSDTriangle cones"};
+
+int batch_cones_supported(const BatchEntry &entry, int64_t ncones, const int32_t *cone_tags) {
     for (int64_t i = 0; i < ncones; i++)
-        if (cone_tags[i] != CHIP_CONE_ZERO && cone_tags[i] != CHIP_CONE_NONNEGATIVE &&
-            cone_tags[i] != CHIP_CONE_SECONDORDER)
-            return fail(CHIP_ERR_UNSUPPORTED, "chip_batch_create: only Zero, Nonnegative and SecondOrder cones");
+        if (cone_tags[i] < 0 || cone_tags[i] >= 32 || !((entry.accepted >> cone_tags[i]) & 1u))
+            return fail(CHIP_ERR_UNSUPPORTED, std::string(entry.fn) + ": " + entry.only);
     return CHIP_OK;
 }
 
@@ -46,6 +52,7 @@ int batch_cones_supported(int64_t ncones, const int32_t *cone_tags) {
 int host_plan_build(HostPlan &hp, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n, int64_t m,
                     int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims, const int64_t *cone_dims2) {
     const int np = (int)nprob;
+    const std::string fn(hp.fn);
     hp.nprob = np;
     hp.n = (int)n;
     hp.m = (int)m;
@@ -53,13 +60,13 @@ int host_plan_build(HostPlan &hp, int64_t nprob, const int64_t *n_part, const in
     xoff.assign((size_t)np + 1, 0);
     zoff.assign((size_t)np + 1, 0);
     for (int k = 0; k < np; k++) {
-        if (n_part[k] < 0 || m_part[k] < 0) return fail(CHIP_ERR_ARG, "chip_batch_create: negative part");
+        if (n_part[k] < 0 || m_part[k] < 0) return fail(CHIP_ERR_ARG, fn + ": negative part");
         const int64_t xn = (int64_t)xoff[k] + n_part[k], zn = (int64_t)zoff[k] + m_part[k];
-        if (xn > n || zn > m) return fail(CHIP_ERR_ARG, "chip_batch_create: the parts exceed n or m");
+        if (xn > n || zn > m) return fail(CHIP_ERR_ARG, fn + ": the parts exceed n or m");
         xoff[k + 1] = (int)xn;
         zoff[k + 1] = (int)zn;
     }
-    if (xoff[np] != n || zoff[np] != m) return fail(CHIP_ERR_ARG, "chip_batch_create: the parts do not add up to n, m");
+    if (xoff[np] != n || zoff[np] != m) return fail(CHIP_ERR_ARG, fn + ": the parts do not add up to n, m");
     xmem.assign((size_t)n, 0);
     zmem.assign((size_t)m, 0);
     for (int k = 0; k < np; k++) {
@@ -69,16 +76,19 @@ int host_plan_build(HostPlan &hp, int64_t nprob, const int64_t *n_part, const in
     hp.parts_ok = true;
     int64_t mm = 0, pdim = 0, nHs = 0;
     if (build_cone_specs(ncones, cone_tags, cone_dims, cone_dims2, hp.cones, mm, pdim, nHs))
-        return fail(CHIP_ERR_ARG, "chip_batch_create: bad cone");
-    if (mm != m) return fail(CHIP_ERR_DIM, "chip_batch_create: cone dimensions do not add up to m");
+        return fail(CHIP_ERR_ARG, fn + ": bad cone");
+    if (mm != m) return fail(CHIP_ERR_DIM, fn + ": cone dimensions do not add up to m");
     hp.rtype.assign((size_t)m, dev::ROW_ZERO);
     hp.degree.assign((size_t)np, 0);
     hp.has_soc.assign((size_t)np, 0);
+    hp.has_psd.assign((size_t)np, 0);
+    hp.psd_total = 0;
     std::vector<int> &it_beg = hp.it_beg, &it_end = hp.it_end, &it_type = hp.it_type, it_mem;
     for (const ConeSpec &cs : hp.cones) {
+        const int view = cs.tag == CHIP_CONE_PSDTRIANGLE ? hp.psd_total++ : -1; // (a cone of side 0 counts there too)
         if (cs.numel == 0) continue;
         const int r0 = (int)cs.start, r1 = (int)(cs.start + cs.numel), k = zmem[r0];
-        if (zmem[r1 - 1] != k) return fail(CHIP_ERR_ARG, "chip_batch_create: a cone crosses a member's rows");
+        if (zmem[r1 - 1] != k) return fail(CHIP_ERR_ARG, fn + ": a cone crosses a member's rows");
         if (cs.tag == CHIP_CONE_NONNEGATIVE) {
             for (int i = r0; i < r1; i++) hp.rtype[i] = dev::ROW_NN;
             hp.degree[k] += cs.numel;
@@ -97,12 +107,25 @@ int host_plan_build(HostPlan &hp, int64_t nprob, const int64_t *n_part, const in
             it_end.push_back(r1);
             it_type.push_back(dev::ITEM_SOC);
             it_mem.push_back(k);
+        } else if (cs.tag == CHIP_CONE_PSDTRIANGLE) { // no item: its reductions are the L2 handle's (batch_psd.hpp)
+            const int side = (int)cs.dim;
+            hp.has_psd[k] = 1;
+            for (int i = r0; i < r1; i++) hp.rtype[i] = dev::ROW_PSD;
+            hp.degree[k] += side; // psdtrianglecone.rs:77-79
+            hp.psd_mem.push_back(k);
+            hp.psd_start.push_back(r0);
+            hp.psd_dim.push_back(side);
+            hp.psd_view.push_back(view);
+            for (int j = 0; j < side; j++) hp.psd_diag.push_back(r0 + j * (j + 1) / 2 + j);
         }
     }
     // cones are in row order, so the items are sorted by member
     hp.it_first.assign((size_t)np + 1, 0);
     for (int k : it_mem) hp.it_first[k + 1]++;
     for (int k = 0; k < np; k++) hp.it_first[k + 1] += hp.it_first[k];
+    hp.psd_first.assign((size_t)np + 1, 0);
+    for (int k : hp.psd_mem) hp.psd_first[k + 1]++;
+    for (int k = 0; k < np; k++) hp.psd_first[k + 1] += hp.psd_first[k];
     std::vector<int> &ch_beg = hp.ch_beg, &ch_end = hp.ch_end;
     hp.cx_first.assign((size_t)np + 1, 0);
     hp.cz_first.assign((size_t)np + 1, 0);
@@ -142,35 +165,46 @@ int host_plan_upload(DevPool &mem, const HostPlan &hp, dev::BatchPlan *pl) {
     return CHIP_OK;
 }
 
-int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n,
-                          int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval, const double *Pnzval,
-                          const double *q, const uint64_t *Acolptr, const uint64_t *Arowval, const double *Anzval,
-                          const double *b, int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims,
-                          const int64_t *cone_dims2, const double *cone_alphas_or_null,
-                          const double *genpow_alphas_or_null, const chip_solver_settings *settings) {
-    (void)cone_alphas_or_null;
-    (void)genpow_alphas_or_null;
-    if (!out) return fail(CHIP_ERR_ARG, "chip_batch_create: bad argument");
+// the device copy of the plan's PSD cones, owned by `mem`; zmem is the uploaded plan's
+int host_plan_upload_psd(DevPool &mem, const HostPlan &hp, const dev::BatchPlan &pl, dev::BatchPsdPlan *pp) {
+    int rc;
+    int *d_first, *d_view, *d_diag;
+    if ((rc = mem.upload(&d_first, hp.psd_first)) || (rc = mem.upload(&d_view, hp.psd_view)) ||
+        (rc = mem.upload(&d_diag, hp.psd_diag)))
+        return rc;
+    *pp = dev::BatchPsdPlan{hp.nprob, (int)hp.psd_view.size(), (int)hp.psd_diag.size(), d_first, d_view, d_diag, pl.zmem};
+    return CHIP_OK;
+}
+
+// chip_batch_create and chip_bsym_create: one body, the entry decides which cones pass
+static int32_t batch_create(const BatchEntry &entry, chip_batch **out, int64_t nprob, const int64_t *n_part,
+                            const int64_t *m_part, int64_t n, int64_t m, const uint64_t *Pcolptr,
+                            const uint64_t *Prowval, const double *Pnzval, const double *q, const uint64_t *Acolptr,
+                            const uint64_t *Arowval, const double *Anzval, const double *b, int64_t ncones,
+                            const int32_t *cone_tags, const int64_t *cone_dims, const int64_t *cone_dims2,
+                            const chip_solver_settings *settings) {
+    const std::string fn(entry.fn);
+    if (!out) return fail(CHIP_ERR_ARG, fn + ": bad argument");
     *out = nullptr;
     if (nprob < 1 || !n_part || !m_part || n < 0 || m < 0 || !Pcolptr || !Acolptr || ncones < 0 ||
         (ncones && (!cone_tags || !cone_dims)))
-        return fail(CHIP_ERR_ARG, "chip_batch_create: bad argument");
+        return fail(CHIP_ERR_ARG, fn + ": bad argument");
     if ((Pcolptr[n] && (!Prowval || !Pnzval)) || (Acolptr[n] && (!Arowval || !Anzval)) || (n && !q) || (m && !b))
-        return fail(CHIP_ERR_ARG, "chip_batch_create: missing data");
+        return fail(CHIP_ERR_ARG, fn + ": missing data");
     const double t0 = now_s();
     std::unique_ptr<chip_batch> h(new chip_batch());
     chip_solver_settings &st = h->st;
     create_settings(settings, st);
     if (st.presolve_enable || st.chordal_decomposition_enable)
-        return fail(CHIP_ERR_UNSUPPORTED, "chip_batch_create: presolve and chordal decomposition are not supported");
-    if (int rc = batch_cones_supported(ncones, cone_tags)) return rc;
+        return fail(CHIP_ERR_UNSUPPORTED, fn + ": presolve and chordal decomposition are not supported");
+    if (int rc = batch_cones_supported(entry, ncones, cone_tags)) return rc;
     const ProblemArgs a{n,      m,         Pcolptr,   Prowval,  Pnzval, q, Acolptr, Arowval, Anzval, b,
                         ncones, cone_tags, cone_dims, cone_dims2};
-    if (nprob >= (1ll << 31) || !a.fits_int32())
-        return fail(CHIP_ERR_DIM, "chip_batch_create: sizes out of int32 range");
+    if (nprob >= (1ll << 31) || !a.fits_int32()) return fail(CHIP_ERR_DIM, fn + ": sizes out of int32 range");
     // ---- the partition and the checks that every entry and cone stays inside its member
     const int np = (int)nprob;
     HostPlan hp;
+    hp.fn = entry.fn;
     const int plan_rc = host_plan_build(hp, nprob, n_part, m_part, n, m, ncones, cone_tags, cone_dims, cone_dims2);
     if (plan_rc && !hp.parts_ok) return plan_rc;
     const std::vector<int> &xoff = hp.xoff, &zoff = hp.zoff, &zmem = hp.zmem, &xmem = hp.xmem;
@@ -179,10 +213,10 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     int rc = coordinate_form(a, co, [&](char mat, int64_t j, int64_t r) {
         const int k = xmem[j];
         if (mat == 'P') {
-            if (r < xoff[k]) return fail(CHIP_ERR_ARG, "chip_batch_create: an entry of P crosses two members' blocks");
+            if (r < xoff[k]) return fail(CHIP_ERR_ARG, fn + ": an entry of P crosses two members' blocks");
             lp_init[k] = 0;
         } else if (zmem[r] != k) {
-            return fail(CHIP_ERR_ARG, "chip_batch_create: an entry of A crosses two members' blocks");
+            return fail(CHIP_ERR_ARG, fn + ": an entry of A crosses two members' blocks");
         }
         return (int)CHIP_OK;
     });
@@ -190,7 +224,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     if (plan_rc) return plan_rc; // a refused cone: reported after the entries of P and A, its text still the last error
     // ---- the device
     if (st.linsys.device == CHIP_DEVICE_HOST_ONLY || chip_device_count() < 1)
-        return fail(CHIP_ERR_NO_DEVICE, "chip_batch_create: no HIP device (the product has no CPU fallback)");
+        return fail(CHIP_ERR_NO_DEVICE, fn + ": no HIP device (the product has no CPU fallback)");
     ProblemData &pd = h->pd;
     if (st.linsys.device >= 0) CHIP_HIP(hipSetDevice(st.linsys.device));
     CHIP_HIP(hipGetDevice(&pd.device));
@@ -199,6 +233,7 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     h->zoff = zoff;
     h->degree = hp.degree;
     h->has_soc = hp.has_soc;
+    h->has_psd = hp.has_psd;
     h->cones = hp.cones;
     h->lp_init = lp_init;
     h->anyP = a.nnzP() > 0;
@@ -206,6 +241,11 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     DevPool &mem = h->mem;
     dev::BatchPlan &pl = h->plan;
     if ((rc = host_plan_upload(mem, hp, &pl))) return rc;
+    if (!hp.psd_view.empty()) { // (a handle without a PSD cone of side > 0 carries nothing of them)
+        h->psd_total = hp.psd_total;
+        if ((rc = host_plan_upload_psd(mem, hp, pl, &h->psd)) || (rc = mem.alloc(&h->psd_res, 4 * (size_t)hp.psd_total)))
+            return rc;
+    }
     // ---- the data, with the unscaled q and (capped) b kept beside it; per member the norms of the two
     std::vector<double> bcap;
     if ((rc = pd.upload(mem, a, co, bcap)) || (rc = mem.upload(&h->uq, q, (size_t)n)) ||
@@ -236,6 +276,8 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     // ---- one KKT system of the equilibrated stack (block-diagonal K)
     if ((rc = pd.create_kkt(a, nullptr, st.linsys, &h->kkt, &h->sys, &h->stream, [](chip_kkt *) { return 0; })))
         return rc;
+    if (h->psd.ncones && kkt_psd_cones(h->kkt) != h->psd_total) // (view[] indexes the L2 handle's per-cone results)
+        return fail(CHIP_ERR_ARG, fn + ": the PSD cones of the plan are not those of the KKT handle");
     const size_t N = (size_t)n, Mm = (size_t)m;
     if ((rc = mem.alloc(&h->vx, N)) || (rc = mem.alloc(&h->vs, Mm)) || (rc = mem.alloc(&h->vz, Mm)) ||
         (rc = mem.alloc(&h->px, N)) || (rc = mem.alloc(&h->ps, Mm)) || (rc = mem.alloc(&h->pz, Mm)) ||
@@ -268,6 +310,30 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
     h->setup_time = now_s() - t0;
     *out = h.release();
     return CHIP_OK;
+}
+
+int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n,
+                          int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval, const double *Pnzval,
+                          const double *q, const uint64_t *Acolptr, const uint64_t *Arowval, const double *Anzval,
+                          const double *b, int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims,
+                          const int64_t *cone_dims2, const double *cone_alphas_or_null,
+                          const double *genpow_alphas_or_null, const chip_solver_settings *settings) {
+    (void)cone_alphas_or_null;
+    (void)genpow_alphas_or_null;
+    return batch_create(BATCH_ENTRY_BASIC, out, nprob, n_part, m_part, n, m, Pcolptr, Prowval, Pnzval, q, Acolptr, Arowval,
+                        Anzval, b, ncones, cone_tags, cone_dims, cone_dims2, settings);
+}
+
+int32_t chip_bsym_create(chip_batch **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n,
+                         int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval, const double *Pnzval,
+                         const double *q, const uint64_t *Acolptr, const uint64_t *Arowval, const double *Anzval,
+                         const double *b, int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims,
+                         const int64_t *cone_dims2, const double *cone_alphas_or_null,
+                         const double *genpow_alphas_or_null, const chip_solver_settings *settings) {
+    (void)cone_alphas_or_null;
+    (void)genpow_alphas_or_null;
+    return batch_create(BATCH_ENTRY_SYMMETRIC, out, nprob, n_part, m_part, n, m, Pcolptr, Prowval, Pnzval, q, Acolptr,
+                        Arowval, Anzval, b, ncones, cone_tags, cone_dims, cone_dims2, settings);
 }
 
 void chip_batch_destroy(chip_batch *h) {
@@ -307,6 +373,10 @@ int chip_batch::default_start() {
         double *v = pass == 0 ? vs : vz;
         dev::cone_minima(s, plan, dev::CONE_MARGINS, nullptr, nullptr, v, nullptr, nullptr, dred, dred + nprob,
                          cone_scr);
+        if (psd.ncones) { // the PSD cones' margins (psdtrianglecone.rs:104-121) join the member's on the device
+            if ((rc = kkt_psd_margins_dev(kkt, v, pres(0), pres(1)))) return rc;
+            dev::bp_fold(s, psd, dev::BP_MARGINS, pres(0), pres(1), dred, dred + nprob);
+        }
         if ((rc = read_red(2 * (size_t)nprob))) return rc;
         for (int k = 0; k < nprob; k++) {
             const double mn = red(0, k), pos = red(1, k);
@@ -324,6 +394,10 @@ int chip_batch::default_start() {
         if ((rc = push_scalars())) return rc;
         dev::bunit_shift(s, plan, v, sc(S_SHIFT1), pass == 0, nullptr);
         dev::bunit_shift(s, plan, v, sc(S_SHIFT2), pass == 0, nullptr);
+        if (psd.ncones) {
+            dev::bp_diag_shift(s, psd, v, sc(S_SHIFT1), nullptr);
+            dev::bp_diag_shift(s, psd, v, sc(S_SHIFT2), nullptr);
+        }
     }
     for (int k = 0; k < nprob; k++) tau[k] = kappa[k] = 1.0;
     // the previous iterate starts as the initial one (a member that fails before its first step reports it)
@@ -370,6 +444,13 @@ int chip_batch::residual_pass() {
     dev::cone_minima(stream, plan, dev::CONE_INTERIOR, nullptr, nullptr, vz, vs, nullptr, dred + (size_t)R_COUNT * nprob,
                      nullptr, cone_scr);
     launches += 4;
+    if (psd.ncones) { // the smallest eigenvalues of the PSD cones' s and z, folded behind the other cones' minima
+        int rc2;
+        if ((rc2 = kkt_psd_margins_dev(kkt, vs, pres(0), pres(1))) || (rc2 = kkt_psd_margins_dev(kkt, vz, pres(2), pres(3))))
+            return rc2;
+        dev::bp_fold(stream, psd, dev::BP_INTERIOR, pres(0), pres(2), dred + (size_t)R_COUNT * nprob, nullptr);
+        launches += 3;
+    }
     return read_red((size_t)(R_COUNT + 1) * nprob);
 }
 
@@ -479,6 +560,11 @@ int chip_batch::step_length(const std::vector<double> &lkappa, bool combined) {
     if ((rc = push_scalars())) return rc;
     dev::cone_minima(stream, plan, dev::CONE_STEP, lz, ls, vz, vs, sc(S_AMAX), dred, nullptr, cone_scr);
     launches += 2;
+    if (psd.ncones) { // psdtrianglecone.rs:235-279 per cone with alpha_max = 1: the member's S_AMAX <= 1 is in its slot
+        if ((rc = kkt_psd_step_length_dev(kkt, lz, ls, 1.0, pres(0)))) return rc;
+        dev::bp_fold(stream, psd, dev::BP_STEP, pres(0), nullptr, dred, nullptr);
+        launches += 2;
+    }
     if ((rc = read_red((size_t)nprob))) return rc;
     for (int k = 0; k < nprob; k++) {
         double a = red(0, k);
@@ -547,6 +633,10 @@ int chip_batch::hold_and_reset() {
     if ((rc = push_masks())) return rc;
     dev::bunit_reset(stream, plan, vx, vs, vz, mk(M_SEL));
     launches++;
+    if (psd.ncones) { // (bunit_reset has written 0 on every PSD row of these members)
+        dev::bp_diag_unit(stream, psd, vs, vz, mk(M_SEL));
+        launches++;
+    }
     CHIP_HIP(hipGetLastError());
     return CHIP_OK;
 }
@@ -627,6 +717,12 @@ int32_t chip_batch_solve(chip_batch *h) {
                     h->tau[k] = h->ptau[k];
                     h->kappa[k] = h->pkappa[k];
                 }
+                // a member with PSD cones leaves the stack at its final iterate: the last step can take s or z to
+                // the cones' boundary within rounding (mu of 1e-16), where the Cholesky factors of the next scaling
+                // update -- which the single solver never takes at its final iterate -- break down and no member
+                // would account for it.  Its iterate is held aside as it is (restored first, if it is to be) and
+                // its s and z become the unit vector; post_process puts it back unchanged
+                if (h->has_psd[k]) h->held[k] = 1;
                 continue;
             }
             // the pre-update check: s and z finite and strictly interior, x finite
@@ -704,6 +800,10 @@ int32_t chip_batch_solve(chip_batch *h) {
         if (iter == 1) h->lin(h->lz, h->lz, nullptr, h->sc(S_ALPHA), nullptr, 1.0, 0.0, 1, nullptr, 0);
         if ((rc = chip_kkt_combined_ds_shift_dev(h->kkt, h->dz, h->lz, h->ls, 0.0))) return rc; // dz is work
         dev::bunit_shift(h->stream, h->plan, h->dz, h->sc(S_NEGSM), 0, nullptr);                 // - sigma_mu e
+        if (h->psd.ncones) { // (0.5 (Z + Z') - 0 and then - sigma_mu on the diagonal: the single kernel's bits)
+            dev::bp_diag_shift(h->stream, h->psd, h->dz, h->sc(S_NEGSM), nullptr);
+            h->launches++;
+        }
         dev::waxpby(h->stream, h->ds, 1.0, h->ds, 1.0, h->dz, h->pd.m);
         h->lin(h->dz, h->rz, nullptr, h->sc(S_OMS), nullptr, 1.0, 0.0, 1, nullptr, 0);
         if ((rc = chip_kkt_ds_from_dz_offset_dev(h->kkt, h->conicw, h->ds, h->vz))) return rc;

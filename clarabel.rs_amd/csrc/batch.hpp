@@ -26,9 +26,13 @@ struct BatchPlan {
     // cone items for the minima / margins: a slice of at most BATCH_CHUNK Nonnegative rows, or one second-order cone
     const int *it_beg, *it_end, *it_type, *it_first; // it_first: [nprob + 1]
     int nitems;
-    const int *rtype; // per row: ROW_ZERO / ROW_NN / ROW_SOC_HEAD / ROW_SOC_TAIL
+    const int *rtype; // per row: ROW_ZERO / ROW_NN / ROW_SOC_HEAD / ROW_SOC_TAIL / ROW_PSD
 };
-enum { ROW_ZERO = 0, ROW_NN = 1, ROW_SOC_HEAD = 2, ROW_SOC_TAIL = 3 };
+// ROW_PSD (only in a plan of chip_bsym_create): a row of a PSDTriangle cone.  The kernels of this unit and of the
+// derivative units take it for a row that carries no unit-vector entry and is not a Zero row either: no item covers it,
+// bunit_shift leaves it alone (its primal form zeroes Zero rows only), bunit_reset and the scaling points write 0.
+// batch_psd.hpp holds the cones' own description and adds the 1 of their diagonals
+enum { ROW_ZERO = 0, ROW_NN = 1, ROW_SOC_HEAD = 2, ROW_SOC_TAIL = 3, ROW_PSD = 4 };
 enum { ITEM_NN = 0, ITEM_SOC = 1 };
 
 // segmented sums: out[slot * nprob + k] = the member-k part of the spec

@@ -275,28 +275,40 @@ int32_t chip_debug_batch_vjp_out(void *batch, int32_t form, int32_t ndir, int32_
     return rc;
 }
 
-int32_t chip_debug_bplan_create(void **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t ncones,
-                                const int32_t *cone_tags, const int64_t *cone_dims) {
-    if (!out) return fail(CHIP_ERR_ARG, "chip_debug_bplan_create: bad argument");
+static int32_t debug_plan_create(const std::string &fn, const BatchEntry &entry, void **out, int64_t nprob,
+                                 const int64_t *n_part, const int64_t *m_part, int64_t ncones, const int32_t *cone_tags,
+                                 const int64_t *cone_dims) {
+    if (!out) return fail(CHIP_ERR_ARG, fn + ": bad argument");
     *out = nullptr;
     if (nprob < 1 || !n_part || !m_part || ncones < 0 || (ncones && (!cone_tags || !cone_dims)))
-        return fail(CHIP_ERR_ARG, "chip_debug_bplan_create: bad argument");
-    if (int rc = batch_cones_supported(ncones, cone_tags)) return rc;
-    if (nprob >= (1ll << 31)) return fail(CHIP_ERR_DIM, "chip_debug_bplan_create: sizes out of int32 range");
+        return fail(CHIP_ERR_ARG, fn + ": bad argument");
+    if (int rc = batch_cones_supported(entry, ncones, cone_tags)) return rc;
+    if (nprob >= (1ll << 31)) return fail(CHIP_ERR_DIM, fn + ": sizes out of int32 range");
     int64_t n = 0, m = 0;
     for (int64_t k = 0; k < nprob; k++) {
-        if (n_part[k] < 0 || m_part[k] < 0) return fail(CHIP_ERR_ARG, "chip_debug_bplan_create: negative part");
+        if (n_part[k] < 0 || m_part[k] < 0) return fail(CHIP_ERR_ARG, fn + ": negative part");
         n += n_part[k];
         m += m_part[k];
         if (n >= (1ll << 31) || m >= (1ll << 31) || n + 2 * m >= (1ll << 31))
-            return fail(CHIP_ERR_DIM, "chip_debug_bplan_create: sizes out of int32 range");
+            return fail(CHIP_ERR_DIM, fn + ": sizes out of int32 range");
     }
     std::unique_ptr<DebugPlan> h(new DebugPlan());
+    h->hp.fn = entry.fn;
     std::vector<int64_t> dims2((size_t)ncones, 0);
     if (int rc = host_plan_build(h->hp, nprob, n_part, m_part, n, m, ncones, cone_tags, cone_dims, dims2.data()))
         return rc;
     *out = h.release();
     return CHIP_OK;
+}
+int32_t chip_debug_bplan_create(void **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t ncones,
+                                const int32_t *cone_tags, const int64_t *cone_dims) {
+    return debug_plan_create("chip_debug_bplan_create", BATCH_ENTRY_BASIC, out, nprob, n_part, m_part, ncones, cone_tags,
+                             cone_dims);
+}
+int32_t chip_debug_bsymplan_create(void **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part,
+                                   int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims) {
+    return debug_plan_create("chip_debug_bsymplan_create", BATCH_ENTRY_SYMMETRIC, out, nprob, n_part, m_part, ncones,
+                             cone_tags, cone_dims);
 }
 void chip_debug_bplan_destroy(void *h) { delete (DebugPlan *)h; }
 
@@ -306,7 +318,17 @@ int32_t chip_debug_bplan_get(const void *handle, const char *name, int64_t *len,
     const HostPlan &hp = h->hp;
     const std::string nm(name);
     const std::vector<int> sizes{hp.nprob, hp.n, hp.m, hp.ncx, hp.ncz, (int)hp.it_beg.size()};
+    const std::vector<int> degree(hp.degree.begin(), hp.degree.end()); // (at most m each)
+    const std::vector<int> psd_sizes{(int)hp.psd_view.size(), (int)hp.psd_diag.size(), hp.psd_total};
     const std::vector<int> *v = nm == "sizes"      ? &sizes
+                                : nm == "degree"    ? &degree
+                                : nm == "psd_sizes" ? &psd_sizes
+                                : nm == "psd_mem"   ? &hp.psd_mem
+                                : nm == "psd_start" ? &hp.psd_start
+                                : nm == "psd_dim"   ? &hp.psd_dim
+                                : nm == "psd_view"  ? &hp.psd_view
+                                : nm == "psd_first" ? &hp.psd_first
+                                : nm == "psd_diag"  ? &hp.psd_diag
                                 : nm == "xoff"     ? &hp.xoff
                                 : nm == "zoff"     ? &hp.zoff
                                 : nm == "xmem"     ? &hp.xmem

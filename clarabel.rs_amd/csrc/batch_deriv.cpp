@@ -62,7 +62,8 @@ int deriv_stage(chip_batch *h, DerivPass &p, const double **in) {
 }
 
 int deriv_valid(chip_batch *h, DerivPass &p) {
-    for (int k = 0; k < h->nprob; k++) p.hvalid[k] = h->info[k].status == CHIP_SOLVER_SOLVED && !h->has_soc[k];
+    for (int k = 0; k < h->nprob; k++)
+        p.hvalid[k] = h->info[k].status == CHIP_SOLVER_SOLVED && !h->has_soc[k] && !h->has_psd[k];
     CHIP_HIP(hipMemcpyAsync(p.valid, p.hvalid.data(), (size_t)h->nprob * sizeof(int), hipMemcpyHostToDevice, h->stream));
     p.launches++;
     return CHIP_OK;
@@ -72,6 +73,10 @@ int deriv_valid(chip_batch *h, DerivPass &p) {
 int deriv_factor(chip_batch *h, DerivPass &p) {
     int rc;
     h->kkt_final = false; // (a refactor that fails leaves nothing to reuse)
+    if (h->psd.ncones) { // a member with a PSD cone is never valid: the pass wrote 0 on its PSD rows, the unit vector's
+        dev::bp_diag_unit(h->stream, h->psd, h->ds, h->dz, nullptr); // diagonal is 1
+        p.launches++;
+    }
     if ((rc = chip_kkt_update_scaling_dev(h->kkt, h->ds, h->dz, 1.0, 0)) < 0) return rc;
     rc = chip_kkt_update(h->kkt, nullptr);
     p.syncs++;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "batch.hpp"
+#include "batch_psd.hpp"
 #include "engine.hpp"
 #include "host_util.hpp"
 #include "ipm_info.hpp"
@@ -33,14 +34,35 @@ struct CHIP_INTERNAL HostPlan {
     std::vector<char> has_soc;
     std::vector<ConeSpec> cones;
     bool parts_ok = false;
+    const char *fn = "chip_batch_create"; // the entry point the messages name
+    // the PSDTriangle cones of side > 0 (dev::BatchPsdPlan, batch_psd.hpp, is the device copy), in row order and so
+    // sorted by member: owner, first row, side, index among all PSD cones of the stack (the L2 handle's PsdView
+    // order, which counts the cones of side 0 too), the member's first cone, and the rows of the diagonal entries
+    std::vector<int> psd_mem, psd_start, psd_dim, psd_view, psd_first, psd_diag;
+    std::vector<char> has_psd;
+    int psd_total = 0; // all PSD cones of the stack, side 0 included
 };
 
-// the partition itself and its device copy (batch.cpp); batch_cones_supported: only the cones the batch takes
-CHIP_INTERNAL int batch_cones_supported(int64_t ncones, const int32_t *cone_tags);
+// the two entry points of create and the cones each takes (bit t: cone tag t)
+struct CHIP_INTERNAL BatchEntry {
+    const char *fn;    // as the messages name it
+    unsigned accepted; // mask of the cone tags
+    const char *only;  // the refusal of any other cone
+};
+constexpr unsigned BATCH_CONES_BASIC =
+    (1u << CHIP_CONE_ZERO) | (1u << CHIP_CONE_NONNEGATIVE) | (1u << CHIP_CONE_SECONDORDER);
+constexpr unsigned BATCH_CONES_SYMMETRIC = BATCH_CONES_BASIC | (1u << CHIP_CONE_PSDTRIANGLE);
+extern CHIP_INTERNAL const BatchEntry BATCH_ENTRY_BASIC, BATCH_ENTRY_SYMMETRIC;
+
+// the partition itself and its device copies (batch.cpp); batch_cones_supported: only the cones the entry takes.
+// host_plan_build describes every cone it is given (the caller has refused the others) and names hp.fn in its messages
+CHIP_INTERNAL int batch_cones_supported(const BatchEntry &entry, int64_t ncones, const int32_t *cone_tags);
 CHIP_INTERNAL int host_plan_build(HostPlan &hp, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n,
                                   int64_t m, int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims,
                                   const int64_t *cone_dims2);
 CHIP_INTERNAL int host_plan_upload(DevPool &mem, const HostPlan &hp, dev::BatchPlan *pl);
+CHIP_INTERNAL int host_plan_upload_psd(DevPool &mem, const HostPlan &hp, const dev::BatchPlan &pl,
+                                       dev::BatchPsdPlan *pp);
 
 // one derivative pass of the handle (the gradients, the tangents, the blocks of tangents or of cotangents): what the
 // shared steps of the passes work on.  Each pass owns its valid flags and its results, so none disturbs what another's
@@ -50,7 +72,7 @@ struct CHIP_INTERNAL DerivPass {
     bool done = false;            // the results hold a pass since the last solve
     long syncs = 0, launches = 0; // of the last call
     long refactors = 0;           // of the handle's life
-    std::vector<int32_t> hvalid;  // the member has a derivative: it ended Solved and owns no SecondOrder cone
+    std::vector<int32_t> hvalid;  // the member has a derivative: it ended Solved and owns no SecondOrder or PSD cone
     int *valid = nullptr;         // ... on the device
     int nin = 0, nout = 0;
     size_t in_len[4] = {}, out_len[4] = {};
@@ -64,6 +86,12 @@ struct chip_batch {
     DevPool mem;
     std::vector<int> xoff, zoff;
     dev::BatchPlan plan{};
+    // the PSDTriangle cones of a handle of chip_bsym_create (ncones == 0: none, and no pass of batch_psd.hpp runs);
+    // psd_res: four arrays of one double per PSD cone of the stack for the per-cone results the L2 handle leaves
+    dev::BatchPsdPlan psd{};
+    double *psd_res = nullptr;
+    int psd_total = 0;
+    double *pres(int j) { return psd_res + (size_t)j * psd_total; }
     ProblemData pd; // the whole stack
     double *negq = nullptr;
     // for the data updates (chip_bdata_*): the unscaled q and b (the members' norms are taken from them, as create
@@ -120,6 +148,7 @@ struct chip_batch {
     // the handle holds now; kkt_final: K is factored at the final iterates of that solve (by a backward or an apply),
     // so an apply needs no scaling update and no refactor
     std::vector<char> has_soc; // the member owns a SecondOrder cone: no derivative
+    std::vector<char> has_psd; // ... a PSDTriangle cone: no derivative either; held aside when it terminates
     bool solve_current = false, kkt_final = false;
     DerivPass grad{"chip_bgrad_backward"}; // gx, gz, gs -> dq, db, dP, dA
     DerivPass tan{"chip_bjvp_apply"};      // dq, db, dP, dA -> dx, dz, ds

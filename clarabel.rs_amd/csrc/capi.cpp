@@ -9,6 +9,7 @@
 #include <cstring>
 #include <memory>
 
+#include "batch_psd.hpp"
 #include "engine.hpp"
 #include "host_util.hpp"
 #include "problem_update.hpp"
@@ -462,6 +463,24 @@ int kkt_update_values_dev(::chip_kkt *h, int block, const double *src_dev, const
     return CHIP_OK;
 }
 void kkt_set_static_diag_max(::chip_kkt *h, double v) { h->static_diag_max = v; }
+// the batched solver's PSD members (batch_psd.hpp): the per-cone reductions of the handle's PsdView, enqueued on its
+// stream into the caller's device arrays and left there -- the batch folds them per member without a host round trip
+int kkt_psd_cones(const ::chip_kkt *h) { return h->psd.ncones; }
+int kkt_psd_margins_dev(::chip_kkt *h, const double *z_dev, double *pmin_dev, double *psum_dev) {
+    Engine &E = h->E;
+    if (E.host_only) return fail(CHIP_ERR_NO_DEVICE, "host-only handle: no numeric work without a GPU");
+    (void)dev::psd_margins(E.stream, h->psd, z_dev, pmin_dev, psum_dev);
+    CHIP_HIP(hipGetLastError());
+    return CHIP_OK;
+}
+int kkt_psd_step_length_dev(::chip_kkt *h, const double *dz_dev, const double *ds_dev, double alpha_max,
+                            double *alpha_dev) {
+    Engine &E = h->E;
+    if (E.host_only) return fail(CHIP_ERR_NO_DEVICE, "host-only handle: no numeric work without a GPU");
+    (void)dev::psd_step_length(E.stream, h->psd, dz_dev, ds_dev, alpha_max, alpha_dev);
+    CHIP_HIP(hipGetLastError());
+    return CHIP_OK;
+}
 } // namespace chip
 }
 

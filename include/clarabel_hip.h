@@ -718,6 +718,19 @@ int32_t chip_batch_create(chip_batch **out, int64_t nprob, const int64_t *n_part
                           const double *b, int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims,
                           const int64_t *cone_dims2, const double *cone_alphas_or_null,
                           const double *genpow_alphas_or_null, const chip_solver_settings *settings);
+/* chip_batch_create for members of all four symmetric cones: Zero, Nonnegative, SecondOrder and PSDTriangle (cone_dims:
+ * the side n; the cone's rows are its svec of n (n + 1) / 2 entries, as for chip_solver_create).  The same arguments,
+ * the same handle -- every call that takes a chip_batch takes it -- and the same refusals, with CHIP_ERR_UNSUPPORTED
+ * for Exponential, Power and GenPower cones.  A handle made from members without a PSD cone behaves bit for bit like
+ * chip_batch_create's.  A PSD handle adds a fixed number of launches per iteration and no host synchronisation; a
+ * member that owns a PSD cone has no derivative (valid[k] = 0 in chip_bgrad_* / chip_bjvp_* / chip_bjac_* /
+ * chip_bvjp_*), the other members of its batch keep theirs.  DESIGN.md 4.20. */
+int32_t chip_bsym_create(chip_batch **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t n,
+                         int64_t m, const uint64_t *Pcolptr, const uint64_t *Prowval, const double *Pnzval,
+                         const double *q, const uint64_t *Acolptr, const uint64_t *Arowval, const double *Anzval,
+                         const double *b, int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims,
+                         const int64_t *cone_dims2, const double *cone_alphas_or_null,
+                         const double *genpow_alphas_or_null, const chip_solver_settings *settings);
 void chip_batch_destroy(chip_batch *h);
 /* runs the batched loop; CHIP_OK (the outcomes are the members' statuses) or a negative chip_status */
 int32_t chip_batch_solve(chip_batch *h);

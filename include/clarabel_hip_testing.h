@@ -161,6 +161,14 @@ int32_t chip_debug_batch_jvp_rhs(void *batch, const double *x, const double *z, 
  * seg_reduce: `count` <= 16 specs (kind / space / slot / a / b per spec) into out[nslots * nprob]. */
 int32_t chip_debug_bplan_create(void **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part, int64_t ncones,
                                 const int32_t *cone_tags, const int64_t *cone_dims);
+/* the plan chip_bsym_create builds: PSDTriangle cones (cone_dims: the side) are accepted as well.  The handle is a
+ * chip_debug_bplan handle (destroy, get and the runners take it).  Its rows of PSD cones have rtype 4 (ROW_PSD) and no
+ * item; chip_debug_bplan_get knows, for either create, "degree" (per member), "psd_sizes" = {PSD cones of side > 0,
+ * their diagonal entries, all PSD cones} and per PSD cone of side > 0, in row order, "psd_mem" (owner), "psd_start"
+ * (first row), "psd_dim" (side), "psd_view" (index among all PSD cones, side 0 included), with "psd_first" (nprob + 1:
+ * the member's first cone) and "psd_diag" (the rows of the diagonal svec entries, cone after cone). */
+int32_t chip_debug_bsymplan_create(void **out, int64_t nprob, const int64_t *n_part, const int64_t *m_part,
+                                   int64_t ncones, const int32_t *cone_tags, const int64_t *cone_dims);
 void chip_debug_bplan_destroy(void *h);
 int32_t chip_debug_bplan_get(const void *h, const char *name, int64_t *len, int32_t *out);
 int32_t chip_debug_bplan_seg_reduce(void *h, int32_t count, const int32_t *kind, const int32_t *space,
