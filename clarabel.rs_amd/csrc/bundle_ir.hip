@@ -1142,12 +1142,15 @@ __device__ __forceinline__ int opaque_tid() {
 // bundle_symv_split (e of the non-leaf rows at xs[nleaf .. nloc), x of the non-leaf nodes in the space around it).
 // keep_e: a further round can follow -- the leaves' residual is put into xs[0 .. nleaf) at the end, so xs holds the whole
 // residual; otherwise only the norms leave.
-template <int TW, int NPT, int NLP>
+// FIXED (k_bundle_irs_fixed): one top row and the flat range from the record, as compile-time constants.
+template <int TW, int NPT, int NLP, bool FIXED>
 __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, const int *runs, const double (&c)[NPT],
-                                         bool keep_e, double *xs, double *red, double *tacc3, int k, int s0,
+                                         bool keep_e, double *xs, double *red, double *tacc3, int k_, int s0,
                                          int nloc, int nleaf, const double *xt, double *out_norm, double *out_share,
-                                         int du, bool have_fl, int fl_b, int fl_e, bool next_fwd,
+                                         int du, bool have_fl_, int fl_b, int fl_e, bool next_fwd,
                                          const int *lev_e, int nl, int dl, FlatBatch &nextb) {
+    const int k = FIXED ? 1 : k_;
+    const bool have_fl = FIXED || have_fl_;
     // have_fl: the flat range [fl_b, fl_e) comes from the bundle's record.  next_fwd: the first batch of the NEXT round's forward sweep is requested in front of the closing
     // reductions (nextb, flat_request_first).
     double cl[NLP]; // the candidate at the thread's leaf nodes, then (keep_e) their residual
@@ -1316,9 +1319,14 @@ __device__ __forceinline__ void irs_flag_timeout(const IrView &ir) {
     ir.res[2] = 1;
     if (ir.res_host) ir.res_host[2] = 1;
 }
-template <int TW, int NLP>
-__global__ __launch_bounds__(TW) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
+// The body of k_bundle_irs and k_bundle_irs_fixed.  FIXED: what every arrow system with one top row, a record per
+// bundle, the default flags and refinement enabled has as constants -- k == 1, record prologue, loads ahead, refinement
+// on, the last candidate written ahead of its verdict, x0 in registers, no permuted copy, no test drop -- is folded at
+// compile time (each as FIXED || <the run-time expression>: ONE copy of the code); the tolerances, maxiter, the epoch,
+// the host mirror and the stamps stay run-time values.  The switches are what spills in the general instance (16 VGPRs,
+// 68 B of scratch per lane through the round loop); the fixed one has no scratch at all.
+template <int TW, int NLP, bool FIXED>
+__device__ __forceinline__ void irs_body(LdlView v, BundleView bv, FoldView fold, IrView ir) {
     constexpr int NPT = IRS_NPT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double *xs = (double *)smem;
@@ -1332,17 +1340,21 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
     __shared__ int hdr[12]; // the head of the bundle's record (IrsDesc: s0 .. nruns)
     const int nb = bv.nb, G = gridDim.x, b = blockIdx.x;
     int tid = threadIdx.x; // (made opaque again at the top of every round, see there)
-    const int k = fold.k;
+    const int k = FIXED ? 1 : fold.k;
     const bool folded = k > 0; // a barrier in the middle of every round
     const int NF = k ? fold.NF : ir.N;
-    if (ir.test_drop && b == G - 1 && G > 1) return; // (tests: a launch that is not co-resident)
+    // (FIXED || ir.ir_enable is written out at each use: as one local up here it stays live across every phase of the
+    // round loop and costs the general instance 9 more spilled scalar registers, 243 against 234)
+    const bool spec_out = FIXED || ir.spec_out;
+    double *const bp = FIXED ? nullptr : ir.bp;
+    if (!FIXED && ir.test_drop && b == G - 1 && G > 1) return; // (tests: a launch that is not co-resident)
     // The bundle's scalars, level table and runs.  With a record per bundle (IRS_F_DESC; kernels.hpp: IrsDesc) they arrive
     // in ONE trip, a dword per lane of two waves; without, through the chain bundle_ptr / blvl_ptr / run_ptr -> blvl, runs
     // -> Lp[..]: three to four dependent trips before the first byte of the right-hand side is asked for.
-    const bool use_desc = (ir.sf_flags & IRS_F_DESC) != 0;
+    const bool use_desc = FIXED || (ir.sf_flags & IRS_F_DESC) != 0;
     // loads that do not depend on the vector are requested a phase ahead (the sweeps' first batches, 1 / d, the residual's
     // leaf rows); IRS_F_CHAINED: where the phase itself stands, as before
-    const bool ahead = (ir.sf_flags & IRS_F_CHAINED) == 0;
+    const bool ahead = FIXED || (ir.sf_flags & IRS_F_CHAINED) == 0;
     static_assert(IRS_DESC_RUNS == IR_MAXRUNS && IRS_DESC_LEVELS + 1 <= FLAT_MAXLEV + 1 && TW >= IRS_DESC_INTS, "IrsDesc");
     if (use_desc && tid < IRS_DESC_INTS) {
         constexpr int LEV0 = offsetof(IrsDesc, lev_e) / sizeof(int), RUN0 = offsetof(IrsDesc, runs) / sizeof(int);
@@ -1401,7 +1413,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
     auto load_top_constants = [&]() {
         if (tid < 8) {
             st.btop[tid] = tid < k ? ir_rhs(ir, ir.perm[NF + tid]) : 0.0;
-            if (ir.bp && tid < k && b == 0) ir.bp[NF + tid] = st.btop[tid];
+            if (bp && tid < k && b == 0) bp[NF + tid] = st.btop[tid];
             st.curt[tid] = 0.0;
             st.dinvt[tid] = tid < k ? v.Dinv[NF + tid] : 0.0;
         } else if (tid >= 64 && tid < 64 + k * k) {
@@ -1474,7 +1486,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
                 if (resid) {
                     if (first) mb = nanmax(mb, ir_load(&pnb[q]));
                     m = nanmax(m, ir_load(&pn[(size_t)rpar * nb + q]));
-                    if (ir.ir_enable && k >= 1) r0 += ir_load(&shs[(size_t)rpar * nb * k + (size_t)q * k]);
+                    if ((FIXED || ir.ir_enable) && k >= 1) r0 += ir_load(&shs[(size_t)rpar * nb * k + (size_t)q * k]);
                 }
             }
             f0 = wave_sum(f0);
@@ -1511,7 +1523,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
                 double pf = 0.0, pr = 0.0;
                 for (int q = tid; q < nb; q += TW) {
                     if (fwd) pf += ir_load(&shf[(size_t)q * k + i]);
-                    if (resid && ir.ir_enable) pr += ir_load(&shs[(size_t)rpar * nb * k + (size_t)q * k + i]);
+                    if (resid && (FIXED || ir.ir_enable)) pr += ir_load(&shs[(size_t)rpar * nb * k + (size_t)q * k + i]);
                 }
                 pf = block_sum(pf, red);
                 pr = block_sum(pr, red);
@@ -1538,7 +1550,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
             for (int i = 0; i < k; ++i) {
                 double sacc = st.pubv[k + 2 + i];
                 for (int cc = 0; cc < k; ++cc) sacc += st.ktt[i * 8 + cc] * st.candt[cc];
-                st.rtop[i] = ir.ir_enable ? st.btop[i] - sacc : st.candt[i];
+                st.rtop[i] = (FIXED || ir.ir_enable) ? st.btop[i] - sacc : st.candt[i];
                 m = nanmax(m, fabs(st.rtop[i]));
             }
             // (ir_verdict's body, ir_refine.hpp, written out: through the shared function -- by reference, by value, as a
@@ -1552,7 +1564,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
                 if (!(newnorm - newnorm == 0.0)) { // non-finite (:284-286; without refinement: x.is_finite(), :180)
                     st.ok = 0;
                     done = true;
-                } else if (!ir.ir_enable || ir.maxiter <= 0 || newnorm <= tol) {
+                } else if (!(FIXED || ir.ir_enable) || ir.maxiter <= 0 || newnorm <= tol) {
                     done = true;
                 }
             } else {
@@ -1600,7 +1612,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
             const int i = tid + u * TW;
             if (i < nloc) {
                 xs[i] = c[u];
-                if (ir.bp) ir.bp[s0 + i] = c[u]; // (only when the host asks for the permuted copy)
+                if (bp) bp[s0 + i] = c[u]; // (only when the host asks for the permuted copy)
                 norm_take(c[u], mx, nan);
             }
         }
@@ -1673,7 +1685,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
         }
         stamp();
         // the candidate: x (round 0) or x + dx (directldlkktsolver.rs:300 axpby(1, x, 1)), into the registers
-        const bool more_possible = ir.ir_enable && round < ir.maxiter;
+        const bool more_possible = (FIXED || ir.ir_enable) && round < ir.maxiter;
         double c[NPT];
         {
             const int tid = opaque_tid();
@@ -1700,11 +1712,11 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
                     c[u] = i < nloc ? 1.0 * xk[u] + 1.0 * xs[i] : 0.0;
                 }
             }
-            if (more_possible && round == 0 && (ir.sf_flags & 1)) {
+            if (more_possible && round == 0 && (FIXED || (ir.sf_flags & IRS_F_X0_REGS))) {
 #pragma unroll
                 for (int u = 0; u < NPT; ++u) xk[u] = c[u];
                 xk_valid = true;
-            } else if (more_possible || !ir.spec_out) {
+            } else if (more_possible || !spec_out) {
                 // (a later round may build on it / the result vectors overlap the right-hand side: through xa / xb)
 #pragma unroll
                 for (int u = 0; u < NPT; ++u) {
@@ -1725,7 +1737,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
                 spec_done = true;
             }
         }
-        if (!ir.ir_enable) { // no refinement: only x.is_finite() is asked for (:180)
+        if (!(FIXED || ir.ir_enable)) { // no refinement: only x.is_finite() is asked for (:180)
             double mx = 0.0;
             bool nan = false;
 #pragma unroll
@@ -1735,7 +1747,7 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
             if (tid == 0) ir_store(&pn[(size_t)par * nb + b], mx);
         } else {
             stamp();
-            irs_symv<TW, NPT, NLP>(v, ir, st.runs, c, more_possible, xs, red, tacc3, k, s0, nloc, nleaf, st.candt,
+            irs_symv<TW, NPT, NLP, FIXED>(v, ir, st.runs, c, more_possible, xs, red, tacc3, k, s0, nloc, nleaf, st.candt,
                                    &pn[(size_t)par * nb + b], &shs[(size_t)par * nb * k + (size_t)b * k],
                                    __builtin_amdgcn_readfirstlane(pat[1]), use_desc, fl_b, fl_e,
                                    ahead && folded && more_possible, lev_e, nl, __builtin_amdgcn_readfirstlane(pat[0]), fwdb);
@@ -1793,6 +1805,17 @@ void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
     }
     stamp();
     ir_grid_exit(ir.ctl, __builtin_amdgcn_readfirstlane(st.gen) + 1, G);
+}
+template <int TW, int NLP>
+__global__ __launch_bounds__(TW) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_bundle_irs(LdlView v, BundleView bv, FoldView fold, IrView ir) {
+    irs_body<TW, NLP, false>(v, bv, fold, ir);
+}
+// the same for a launch whose switches are the usual constants (bundle_ir() below decides per launch)
+template <int TW, int NLP>
+__global__ __launch_bounds__(TW) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_bundle_irs_fixed(LdlView v, BundleView bv, FoldView fold, IrView ir) {
+    irs_body<TW, NLP, true>(v, bv, fold, ir);
 }
 
 } // namespace
@@ -1859,22 +1882,40 @@ int bundle_ir_capacity(const BundleView &bv, int *tw) {
 }
 // k_bundle_irs can take this handle's solves: co-resident grid of nb workgroups of 256 threads (the per-bundle conditions
 // -- flat sweeps, nodes per thread, runs of the permutation -- are the caller's to check, see irs_bundle_ok)
-bool bundle_irs_capacity_ok(const BundleView &bv) {
-    if (!bv.nb || !bv.symv_split) return false;
+static bool irs_kernel_capacity_ok(const void *fn, const BundleView &bv) {
     const size_t lds = bundle_ir_lds(bv);
-    if (raise_dynamic_lds((const void *)k_bundle_irs<256, 4>, lds) != hipSuccess) return false;
+    if (raise_dynamic_lds(fn, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
     int per_cu = 0, dev = 0;
     hipDeviceProp_t prop;
     hipFuncAttributes fa;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_bundle_irs<256, 4>, 256, lds) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds) != hipSuccess ||
         hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-        hipFuncGetAttributes(&fa, (const void *)k_bundle_irs<256, 4>) != hipSuccess) {
+        hipFuncGetAttributes(&fa, fn) != hipSuccess) {
         (void)hipGetLastError();
         return false;
     }
     const size_t per_wg = ((fa.sharedSizeBytes + lds + 1023) / 1024) * 1024;
     per_cu = std::min(per_cu, std::min((int)(prop.maxSharedMemoryPerMultiProcessor / per_wg), 4));
     return per_cu * prop.multiProcessorCount >= bv.nb;
+}
+bool bundle_irs_capacity_ok(const BundleView &bv) {
+    if (!bv.nb || !bv.symv_split) return false;
+    return irs_kernel_capacity_ok((const void *)k_bundle_irs<256, 4>, bv);
+}
+// the same for k_bundle_irs_fixed (a handle whose grid it cannot hold co-resident keeps the general kernel)
+bool bundle_irs_fixed_capacity_ok(const BundleView &bv) {
+    if (!bv.nb || !bv.symv_split) return false;
+    return irs_kernel_capacity_ok((const void *)k_bundle_irs_fixed<256, 4>, bv);
+}
+// whether THIS launch's switches are the constants k_bundle_irs_fixed is compiled for (the handle's part -- fixed_ok:
+// bundle_irs_fixed_capacity_ok -- is the caller's)
+bool bundle_irs_takes_fixed(const FoldView &fold, const IrView &ir) {
+    constexpr int want = IRS_F_DESC | IRS_F_X0_REGS | IRS_F_SPEC_OUT;
+    constexpr int mask = want | IRS_F_CHAINED | IRS_F_GENERAL;
+    return ir.sf && fold.k == 1 && (ir.sf_flags & mask) == want && ir.ir_enable && ir.spec_out && !ir.bp && !ir.test_drop;
 }
 bool irs_bundle_ok(int nloc, int nleaf, int nlevels, int nruns) {
     return nloc >= FLAT_MIN_NODES && nloc <= IRS_NPT * 256 && nleaf <= 4 * 256 && nlevels <= FLAT_MAXLEV && nruns > 0 &&
@@ -1885,8 +1926,9 @@ int bundle_ir(hipStream_t s, const LdlView &v, const BundleView &bv, const FoldV
     // grid <= bundle_ir_capacity(): every workgroup is resident on an otherwise idle device, and a grid
     // barrier that cannot complete times out instead of hanging
     const size_t lds = bundle_ir_lds(bv);
-    if (ir.sf) { // (the caller has checked bundle_irs_capacity_ok / irs_bundle_ok)
-        k_bundle_irs<256, 4><<<bv.nb, 256, lds, s>>>(v, bv, fold, ir);
+    if (ir.sf) { // (the caller has checked bundle_irs_capacity_ok / irs_bundle_ok, and for sf == 2 bundle_irs_takes_fixed)
+        if (ir.sf == 2) k_bundle_irs_fixed<256, 4><<<bv.nb, 256, lds, s>>>(v, bv, fold, ir);
+        else k_bundle_irs<256, 4><<<bv.nb, 256, lds, s>>>(v, bv, fold, ir);
         return (int)hipGetLastError();
     }
     if (gf.ng > 0) {

@@ -239,6 +239,8 @@ struct chip_kkt {
     // follows without a new setrhs() reads the noted vectors (rhs_x / rhs_z) again -- they stay borrowed until the next
     // setrhs (include/clarabel_hip.h)
     bool ir_sf = false, bp_stale = false;
+    bool irs_fixed_ok = false;       // k_bundle_irs_fixed is co-resident for this handle's grid (the launch decides, see enqueue)
+    long long irs_fixed_launches = 0; // test hook: fused solve launches that took k_bundle_irs_fixed
     // k_bundle_irs: one dev::IrsDesc per bundle (irs_descriptors below), built once here because nothing in it changes
     // after creation; empty / nullptr: some bundle does not fit the record, the kernel keeps its chained prologue.
     // The host copy is there on host-only handles too (tests read it back: chip_debug_kkt_ints).
@@ -1000,6 +1002,7 @@ int32_t chip_kkt_create(chip_kkt **out, int64_t n, int64_t m, const uint64_t *Pc
                 sf = dev::irs_bundle_ok(nloc, nleaf, nlev, rp[(size_t)b + 1] - rp[(size_t)b]);
             }
             h->ir_sf = sf && dev::bundle_irs_capacity_ok(E.bundles);
+            h->irs_fixed_ok = h->ir_sf && E.fold.k == 1 && dev::bundle_irs_fixed_capacity_ok(E.bundles);
             // (update and solves each end in a launch that can leave its verdict in the host's mirror of the mailbox)
             E.mb_mirror_on = h->ir_sf && E.fold.k == 1 && E.fast_prep_ok;
             if (h->ir_sf && !switches().no_shared_pattern && (rc = E.upload_patterns(pat))) return rc;
@@ -1721,6 +1724,12 @@ static int fused_enqueue(chip_kkt *h, double *lhsx_dev, double *lhsz_dev, int *s
             ir.sf_flags |= dev::IRS_F_DESC;
         }
         if (E.mirror_writes()) ir.res_host = E.mb_mirror->ring + 4 * *slot; // (workgroup 0 writes the verdict there as well)
+        // this launch's switches are the constants k_bundle_irs_fixed has folded: per launch, set_settings can switch
+        // refinement between two solves
+        if (h->irs_fixed_ok && dev::bundle_irs_takes_fixed(E.fold, ir)) {
+            ir.sf = 2;
+            h->irs_fixed_launches += 1;
+        }
         rc = dev::bundle_ir(E.stream, lv, E.bundles, E.fold, ir, E.ir_grid, E.ir_tw, E.gfold);
     } else {
         rc = dev::bundle_ir(E.stream, E.view(), E.bundles, E.fold, ir, E.ir_grid, E.ir_tw, E.gfold);
@@ -2425,6 +2434,7 @@ int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out
         const int flags = switches().irs_flags < 0 ? 3 : switches().irs_flags;
         *out = (h->ir_sf && h->irs_desc && !(flags & dev::IRS_F_CHAINED) && h->irs_desc_shared == shared) ? E.bundles.nb : 0;
     }
+    else if (k == "irs_fixed_launches") *out = (double)h->irs_fixed_launches; // fused solve launches that took k_bundle_irs_fixed
     else if (k == "mailbox_mirror_on") *out = E.mirror_writes() ? 1 : 0;   // update and solves end in launches that write the host mirror
     else if (k == "mailbox_copies") *out = (double)E.mailbox_copies;       // collects that copied the mailbox
     else if (k == "mailbox_mirror_reads") *out = (double)E.mailbox_mirror_reads; // ... that read the host mirror the kernels wrote

@@ -213,6 +213,7 @@ inline bool irs_desc_fits(int nlevels, int nruns) { return nlevels >= 1 && nleve
 constexpr int IRS_F_X0_REGS = 1;   // round 0's iterate stays in registers
 constexpr int IRS_F_SPEC_OUT = 2;  // the last candidate may be written before its verdict
 constexpr int IRS_F_CHAINED = 4;   // no phase-ahead loads, chained prologue (the form before the descriptors; tests compare both)
+constexpr int IRS_F_GENERAL = 8;   // k_bundle_irs also where k_bundle_irs_fixed applies (tests and A/B runs compare both on one build)
 constexpr int IRS_F_DESC = 256;    // (set by the host, not by CHIP_IRS_FLAGS) the pat_off slot holds the descriptor table
 struct IrView {
     const double *rx, *rz; // right-hand side in the caller's order: entry o < n from rx, n <= o < n + m from rz,
@@ -247,7 +248,8 @@ struct IrView {
     int epoch;             // k_bundle_irs: distinguishes this launch's messages from an earlier launch's (the host counts)
     int sf_flags;          // k_bundle_irs, experiment bits (CHIP_IRS_FLAGS): IRS_F_* above
     int spec_out;          // k_bundle_irs: lhsx / lhsz do not overlap rx / rz -- the last candidate may be written before its verdict
-    int sf;                // k_bundle_irs (one bundle per workgroup, the candidate in registers; bp may be nullptr: not written)
+    int sf;                // k_bundle_irs (one bundle per workgroup, the candidate in registers; bp may be nullptr: not written);
+                           // 2: this launch takes k_bundle_irs_fixed (bundle_irs_takes_fixed holds and the handle can)
     int *res_host;         // k_bundle_irs: the same 4 ints in page-locked host memory, written beside res (plain stores), or nullptr
 };
 int ir_rel_ints();
@@ -261,6 +263,11 @@ int bundle_ir(hipStream_t s, const LdlView &v, const BundleView &bv, const FoldV
               int tw, const GFoldView &gf);
 // k_bundle_irs: whether a co-resident grid of one 256-thread workgroup per bundle exists / whether a bundle qualifies
 bool bundle_irs_capacity_ok(const BundleView &bv);
+// k_bundle_irs_fixed, the instance with the usual switches folded (k == 1, record prologue, loads ahead, refinement on,
+// spec_out, x0 in registers, no bp, no test drop): whether its grid is co-resident for these bundles (per handle) /
+// whether a launch with this view has exactly those switches (per launch)
+bool bundle_irs_fixed_capacity_ok(const BundleView &bv);
+bool bundle_irs_takes_fixed(const FoldView &fold, const IrView &ir);
 bool irs_bundle_ok(int nloc, int nleaf, int nlevels, int nruns);
 // grouped fold, after bundle_factor: every bundle's contribution to the Schur complement of its group's top
 // (k_gfold_schur -> gf.fac), then the k x k LDL' of every group's top (k_gfold_top_factor)

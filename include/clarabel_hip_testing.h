@@ -27,6 +27,8 @@ int32_t chip_debug_set_switch(const char *name, const char *value_or_null);
  * the full arrays and how many differed), "pattern_shared_bundles" (bundles whose fused solve launch reads a shared copy:
  * 0 on a host-only handle or with CHIP_NO_SHARED_PATTERN), "irs_desc_bundles" (bundles whose fused solve launch reads its
  * per-bundle record under the current switches: 0 with CHIP_IRS_FLAGS bit 4, the chained prologue),
+ * "irs_fixed_launches" (fused solve launches of this handle that took k_bundle_irs_fixed, the instance with the usual
+ * switches folded: it stays 0 with CHIP_IRS_FLAGS bit 8, without refinement, with more than one top row),
  * "mailbox_mirror_on" (1: the handle's update and
  * solves end in launches that store their verdict words into the host mirror of the mailbox; 0 with
  * CHIP_NO_HOST_MAILBOX), "mailbox_copies" / "mailbox_mirror_reads" (collects that copied the mailbox / that only waited
