@@ -42,7 +42,7 @@ void bp_diag_unit(hipStream_t s, const BatchPsdPlan &p, double *sv, double *z, c
 
 } // namespace dev
 
-// L2 (capi.cpp): dev::psd_margins / dev::psd_step_length on the handle's PsdView and stream, one result per PSD cone
+// L2 (kkt_cones.cpp): dev::psd_margins / dev::psd_step_length on the handle's PsdView and stream, one result per PSD cone
 // of the stack (kkt_psd_cones of them) into device arrays of the caller.  Enqueued only: no copy, no synchronisation.
 // The step length is that of the scaling the handle holds (chip_kkt_update_scaling_dev)
 int kkt_psd_cones(const ::chip_kkt *h);

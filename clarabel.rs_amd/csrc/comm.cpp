@@ -44,7 +44,7 @@ int fail_nccl(ncclResult_t r, const char *what) {
 } // namespace
 
 namespace chip {
-hipStream_t kkt_stream(::chip_kkt *h);      // capi.cpp
+hipStream_t kkt_stream(::chip_kkt *h);      // capi.cpp (kkt_handle.hpp is private to the L1 / L2 units)
 void kkt_set_world(::chip_kkt *h, int world);
 int kkt_note_exchange(::chip_kkt *h, hipStream_t comm_stream);
 } // namespace chip
@@ -146,7 +146,7 @@ int32_t chip_kkt_allgather_step(chip_kkt *h, chip_comm *c, const double *send_de
         CHIP_NCCL(ncclGroupEnd());
     }
     CHIP_HIP(hipEventRecord(c->ev_done, c->stream));
-    // the handle's next PERSISTENT solve launch waits for the exchange on the device (capi.cpp: chip_kkt::exch_event); the
+    // the handle's next PERSISTENT solve launch waits for the exchange on the device (kkt_step.cpp: kkt_note_exchange); the
     // cone update and the factorisation enqueued before it run beside the collective's kernels
     return chip::kkt_note_exchange(h, c->stream);
 }

@@ -254,7 +254,7 @@ struct Engine {
     }
     int upload_factor_runs(const Symbolic &S);
     // pattern classes of the bundles (host.hpp: PatternShare).  The figures are kept on every handle of a system that
-    // k_bundle_irs can take (capi.cpp: chip_kkt_create; all 0 elsewhere), host-only ones included; the shared index
+    // k_bundle_irs can take (kkt_create.cpp: fused_plan; all 0 elsewhere), host-only ones included; the shared index
     // arrays and the offset table are on the device only where k_bundle_irs takes the solves (pat_off == nullptr: that
     // kernel reads the full arrays with offset 0, like every other kernel)
     int pat_classes = 0, pat_bundles = 0, pat_verified = 0, pat_mismatches = 0;

@@ -1,5 +1,5 @@
 // problem_update.hpp -- launchers of problem_update.hip (the L4 solver's data updates, default/data_updating.rs) and
-// the internal device-value entry points of L2 (capi.cpp) and L3 (kktsystem.cpp) they feed.  Internal to the library.
+// the internal device-value entry points of L2 (kkt_step.cpp) and L3 (kktsystem.cpp) they feed.  Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,7 +29,7 @@ void pu_write_full(hipStream_t s, const PuTarget &t, const double *vals);
 void pu_write_partial(hipStream_t s, const PuTarget &t, const int64_t *idx, const double *vals, int k, int *pos);
 // Kx[map[i]] = src[i] for i = t (idx == nullptr) or i = idx[t], t < k (a repeated i writes the same value twice)
 void pu_scatter(hipStream_t s, double *Kx, const int *map, const double *src, const int64_t *idx, int k);
-// the stored norms (problemdata.rs:168-189) and max |P_ii| (capi.cpp: static_diag_max), as maxima of |x| over the bit
+// the stored norms (problemdata.rs:168-189) and max |P_ii| (kkt_handle.hpp: diag_P_max), as maxima of |x| over the bit
 // patterns (a NaN wins).  mask bit 0: out[0] = max |q dinv|; bit 1: out[1] = max |b einv|; bit 2: out[2] = max over
 // the diagonal entries of P (Prow == Pcol).  partials: pu_norm_partials() words
 int pu_norm_partials();

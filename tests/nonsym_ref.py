@@ -557,7 +557,7 @@ def gpw_unit(alpha, d2):
 
 # ---- step_length -------------------------------------------------------------------------------------------------
 def first_candidate(alpha_max, sym_step=np.inf):
-    """compositecone.rs:329-330, in double as capi.cpp forms it"""
+    """compositecone.rs:329-330, in double as kkt_cones.cpp (KktCones::step_length) forms it"""
     return min(min(float(alpha_max), float(sym_step)), 1.0 - np.sqrt(EPS))
 
 

@@ -1,5 +1,5 @@
 """CPU-side test of the per-bundle records of the fused solve kernel k_bundle_irs (csrc/kernels.hpp: IrsDesc; built once per
-handle by capi.cpp: irs_descriptors): every record must say exactly what the kernel's chained prologue finds by walking
+handle by kkt_create.cpp: irs_descriptors): every record must say exactly what the kernel's chained prologue finds by walking
 bundle_ptr, blvl_ptr -> blvl -> Lp, Up, run_ptr -> runs and the pattern offsets.  Host-only handles: the records and the
 arrays of the chain are host analysis (include/clarabel_hip_testing.h: chip_debug_kkt_ints)."""
 import numpy as np

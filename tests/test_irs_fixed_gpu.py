@@ -1,5 +1,5 @@
 """-m gpu: k_bundle_irs_fixed, the instance of the fused solve kernel with the usual switches folded at compile time
-(csrc/bundle_ir.hip: irs_body, FIXED; the choice is made per launch, capi.cpp: fused_enqueue), against the CPU oracle on
+(csrc/bundle_ir.hip: irs_body, FIXED; the choice is made per launch, kkt_step.cpp: fused_choose), against the CPU oracle on
 the same inputs and the same permutation, and against the general kernel on the same build (CHIP_IRS_FLAGS bit 8).  The
 shapes are those of tests/test_irs_ahead_gpu.py: the smallest bundle the kernel takes, levels around the batch of 1024
 entries, a bundle that fills all 12 slots of a thread, grids of 5 and 19 workgroups (fewer than the barrier's sub-groups,

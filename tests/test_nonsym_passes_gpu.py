@@ -88,7 +88,7 @@ Wrong kernels against these tests (the first three were built in a scratch copy 
     other cone gets entries of its neighbours: test_exp_pow_scaling fails from 42 cones on;
   * NOT CAUGHT: `c > v.ncones` as the guard of k_ns3_update_scaling.  The one extra thread, c == ncones, exists in the
     handles of 1, 42, 43, 255 and 257 cones (256 has no idle thread).  It reads start[ncones], tag[ncones] and alpha[ncones]
-    past their arrays and writes 18 doubles past `state`, which is an allocation of its own (capi.cpp `E.alloc(&pst, ncones *
+    past their arrays and writes 18 doubles past `state`, which is an allocation of its own (kkt_cones.cpp `zeroed(E, ns3.state, ncones *
     18)`): nothing that a test here reads lies behind it, and the cones' own outputs stay right.  It is an out-of-bounds
     access, not a wrong value, and no test of this file fails for it.
 """
@@ -546,7 +546,7 @@ def test_every_cone_in_one_handle(hipdev, set_name, strategy):
 
 @pytest.mark.parametrize("alpha", R.BARRIER_ALPHAS)
 def test_genpow_barrier_scratch_leaves_the_symmetric_state(hipdev, alpha):
-    """capi.cpp passes the handle's w buffer -- the nonnegative and second-order scaling state -- to gpw_barrier as
+    """kkt_cones.cpp (KktCones::barrier) passes the handle's w buffer -- the nonnegative and second-order scaling state -- to gpw_barrier as
     scratch for the primal gradients (`g = work + off`: the GenPow cone's own rows).  On the mixed handle: the barrier of
     the whole handle with ONE GenPow cone moved from its pair to its barrier pair changes by exactly what the cone alone
     gives (within the rounding of the sum); the SOC and nonnegative observations (W e, W^-1 e, K entries) are bitwise
@@ -591,7 +591,7 @@ MIXED_STEP_CASES = (("every cone stays feasible", "stays feasible", None, None),
 @pytest.mark.parametrize("label,ns3_case,gpw_size,gpw_case", MIXED_STEP_CASES, ids=[c[0] for c in MIXED_STEP_CASES])
 def test_step_length_in_one_handle(hipdev, label, ns3_case, gpw_size, gpw_case):
     """step_length of the mixed handle: the symmetric cones at rest (their step is alpha_max), the exp / pow partials in
-    d_partial[0 .. 1] and the GenPow cones' behind them (capi.cpp `h->d_partial + used`); one cone, or none, limits the step.
+    d_partial[0 .. 1] and the GenPow cones' behind them (kkt_cones.cpp `d_partial + used`); one cone, or none, limits the step.
     Bit for bit the smallest of the cones' exactly decided candidates"""
     lay = layout(hipdev, "mixed")
     set_name = R.STEP_SETS[0]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-phase statistics of the time stamps EVERY workgroup of a k_bundle_ir launch leaves with CHIP_IR_DEBUG=2
-(csrc/capi.cpp: fused_enqueue writes the last launch's stamps to CHIP_IR_DEBUG_FILE, default /tmp/chip_ir_stamps.bin).
+(csrc/kkt_step.cpp: IrStamps, after fused_enqueue, writes the last launch's stamps to CHIP_IR_DEBUG_FILE, default /tmp/chip_ir_stamps.bin).
 usage:  CHIP_IR_DEBUG=2 python bench.py --no-extras --steps 1 --warmup 1 ... ; python tools/ir_skew.py [file]"""
 import collections
 import sys
