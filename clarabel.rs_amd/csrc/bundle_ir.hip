@@ -301,15 +301,45 @@ __device__ __forceinline__ void flat_request_first(const LdlView &v, const int *
         flat_batch_clear(fb);
     }
 }
+// Replica slots of a bundle's dense targets (kernels.hpp: IRS_REP_R; irs_body only).  An entry's 16-bit target is
+// node | r << 12; r > 0 adds into slot rep0 + (node - first) * (R - 1) + r - 1 = base + node * (R - 1) + r.  All scalars.
+struct RepView {
+    int nd;    // replicated nodes (0: every r is ignored)
+    int first; // the first of them: nodes first .. first + nd - 1
+    int fold;  // forward level in front of which the slots are folded into the nodes
+    int rep0;  // first slot, behind everything else the launch keeps in xs
+    __device__ __forceinline__ int rmask() const { return nd ? ~IRS_NODE_MASK : 0; }
+    __device__ __forceinline__ int base() const { return rep0 - first * (IRS_REP_R - 1) - 1; }
+    __device__ __forceinline__ static int slot(int raw, int rmask_, int base_) {
+        const int node = raw & IRS_NODE_MASK, r = (raw & rmask_) >> IRS_NODE_BITS;
+        return r ? base_ + node * (IRS_REP_R - 1) + r : node;
+    }
+    __device__ __forceinline__ void zero(double *xs, int tid) const {
+        if ((unsigned)(tid - 8) < (unsigned)(nd * (IRS_REP_R - 1))) xs[rep0 + tid - 8] = 0.0;
+    }
+    // the caller has passed an lds_barrier behind the last add and issues one behind this
+    __device__ __forceinline__ void fold_slots(double *xs, int tid) const {
+        if (tid < nd) {
+            double s = 0.0;
+#pragma unroll
+            for (int q = 0; q < IRS_REP_R - 1; ++q) s += xs[rep0 + tid * (IRS_REP_R - 1) + q];
+            xs[first + tid] += s;
+        }
+    }
+};
 // HAVE_FIRST = false (k_bundle_ir): the sweep requests its first batch itself, behind its opening barrier.
-template <bool FWDMODE, int TW, bool HAVE_FIRST = true>
+// REP (irs_body only): the row indices carry replica ids, see RepView; every other caller's instance is what it was.
+template <bool FWDMODE, int TW, bool HAVE_FIRST = true, bool REP = false>
 __device__ __forceinline__ void bundle_sweep_flat_ahead(const LdlView &v, double *xs, const double *xt, double *tacc, int k,
-                                                        const int *lev_e, int dl, int nloc, int nl, const FlatBatch &first) {
+                                                        const int *lev_e, int dl, int nloc, int nl, const FlatBatch &first,
+                                                        const RepView &rv = RepView{}) {
     static_assert(TW != 512, "two batches in flight: not within the 80 registers of the 512-thread form");
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid)); // (no hoisting of this phase's address arithmetic out of the caller's round loop)
     const int lane = tid & 63;
     if (FWDMODE && tid < 8) tacc[tid] = 0.0;
+    if (REP && FWDMODE) rv.zero(xs, tid);
+    const int rmask = REP ? rv.rmask() : 0, rbase = REP ? rv.base() : 0;
     double tpart = 0.0;
     // a stream of batches of TW * FLAT_U entries, level after level; the next batch's loads are issued before the
     // current one is consumed -- across a level boundary too (the entries do not depend on x), so a level costs its
@@ -362,11 +392,11 @@ __device__ __forceinline__ void bundle_sweep_flat_ahead(const LdlView &v, double
         if (nstep < nl) request(nbase, nee, ni, nj, nv);
 #pragma unroll
         for (int u = 0; u < FLAT_U; ++u) {
-            const int i = ci[u];
-            if (i < 0) continue;
+            if (ci[u] < 0) continue;
+            const int i = REP ? ci[u] & IRS_NODE_MASK : ci[u];
             if (FWDMODE) {
                 const double val = cv[u] * xs[cj[u]];
-                if (i < nloc) atomicAdd(&xs[i], -val);
+                if (i < nloc) atomicAdd(&xs[REP ? RepView::slot(ci[u], rmask, rbase) : i], -val);
                 else if (k == 1) tpart += val;
                 else atomicAdd(&tacc[i - nloc], val);
             } else {
@@ -374,6 +404,10 @@ __device__ __forceinline__ void bundle_sweep_flat_ahead(const LdlView &v, double
             }
         }
         if (nstep != step) lds_barrier(); // the level is complete
+        if (REP && FWDMODE && rv.nd && step < rv.fold && nstep >= rv.fold) { // (wave-uniform) the first replicated node's level is next
+            rv.fold_slots(xs, tid);
+            lds_barrier();
+        }
         step = nstep;
         base = nbase;
         ee = nee;
@@ -1148,7 +1182,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
                                          bool keep_e, double *xs, double *red, double *tacc3, int k_, int s0,
                                          int nloc, int nleaf, const double *xt, double *out_norm, double *out_share,
                                          int du, bool have_fl_, int fl_b, int fl_e, bool next_fwd,
-                                         const int *lev_e, int nl, int dl, FlatBatch &nextb) {
+                                         const int *lev_e, int nl, int dl, FlatBatch &nextb, const RepView &rv) {
     const int k = FIXED ? 1 : k_;
     const bool have_fl = FIXED || have_fl_;
     // have_fl: the flat range [fl_b, fl_e) comes from the bundle's record.  next_fwd: the first batch of the NEXT round's forward sweep is requested in front of the closing
@@ -1192,6 +1226,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
     }
     double tpart = 0.0;
     if (k > 1 && tid < 8) tacc3[tid] = 0.0;
+    rv.zero(xs, tid); // (the replica slots of the flat range's column targets)
     double mleaf = 0.0;
     bool nan = false;
     lds_barrier();
@@ -1263,6 +1298,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
                 pv[u] = ok ? Ux[t] : 0.0;
             }
         };
+        const int rmask = rv.rmask(), rbase = rv.base();
         if (fb < fe) request(fb, fi, fj, fv);
         for (int base = fb; base < fe; base += TW * FLAT_U) {
             if (base + TW * FLAT_U < fe) request(base + TW * FLAT_U, ni, nj, nv);
@@ -1272,7 +1308,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
             }
 #pragma unroll
             for (int u = 0; u < FLAT_U; ++u) {
-                const int i = fi[u], j = fj[u];
+                const int i = fi[u], j = fj[u] & IRS_NODE_MASK; // (the column carries a replica id: RepView)
                 if (i < 0) continue;
                 const double xi = xs[xpos(i - nleaf)];
                 if (j >= nloc) {
@@ -1283,7 +1319,7 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
                     atomicAdd(&xs[i], -(fv[u] * xi));
                 } else {
                     atomicAdd(&xs[i], -(fv[u] * xs[xpos(j - nleaf)]));
-                    atomicAdd(&xs[j], -(fv[u] * xi));
+                    atomicAdd(&xs[RepView::slot(fj[u], rmask, rbase)], -(fv[u] * xi));
                 }
             }
 #pragma unroll
@@ -1296,6 +1332,10 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
     }
     if (next_fwd) flat_request_first<true, TW>(v, lev_e, nl, dl, tid, nextb);
     lds_barrier();
+    if (rv.nd) { // (wave-uniform)
+        rv.fold_slots(xs, tid);
+        lds_barrier();
+    }
     double m = mleaf;
 #pragma unroll
     for (int u = 0; u < NPT; ++u) {
@@ -1314,6 +1354,12 @@ __device__ __forceinline__ void irs_symv(const LdlView &v, const IrView &ir, con
     symv_close<true>(m, nan, tpart, k, tid, tacc3, red, out_norm, out_share);
 }
 
+// The bundle's replica slots as scalars, picked up from LDS at the call site of each phase that uses them (repw[0] is 0
+// without a record and in a launch without IRS_F_REP); the slots lie behind the launch's dynamic LDS slice.
+__device__ __forceinline__ RepView irs_rep_view(const int *repw, const BundleView &bv) {
+    return RepView{__builtin_amdgcn_readfirstlane(repw[0]) & 0xff, __builtin_amdgcn_readfirstlane(repw[1]),
+                   __builtin_amdgcn_readfirstlane(repw[2]), (max(bv.max_nodes, bv.ir_lds_doubles) + 1) & ~1};
+}
 // a grid barrier of k_bundle_irs ran out of its budget: said in the ring slot and in its host mirror
 __device__ __forceinline__ void irs_flag_timeout(const IrView &ir) {
     ir.res[2] = 1;
@@ -1338,6 +1384,7 @@ __device__ __forceinline__ void irs_body(LdlView v, BundleView bv, FoldView fold
     // picked up as scalars at every phase's call site (loaded from the table per phase they cost scratch and registers)
     __shared__ int pat[2];
     __shared__ int hdr[12]; // the head of the bundle's record (IrsDesc: s0 .. nruns)
+    __shared__ int repw[IRS_REP_INTS]; // the bundle's replica slots (irs_rep_view)
     const int nb = bv.nb, G = gridDim.x, b = blockIdx.x;
     int tid = threadIdx.x; // (made opaque again at the top of every round, see there)
     const int k = FIXED ? 1 : fold.k;
@@ -1365,6 +1412,10 @@ __device__ __forceinline__ void irs_body(LdlView v, BundleView bv, FoldView fold
         else st.runs[tid - RUN0] = w;
         if (tid == 4 || tid == 5) pat[tid - 4] = w;
     }
+    // (the words behind the records, kernels.hpp: IRS_REP_INTS, by a wave that does not read the record)
+    static_assert(TW >= IRS_DESC_INTS + IRS_REP_INTS, "IrsDesc");
+    if (tid >= IRS_DESC_INTS && tid < IRS_DESC_INTS + IRS_REP_INTS)
+        repw[tid - IRS_DESC_INTS] = (use_desc && (ir.sf_flags & IRS_F_REP)) ? ((const int *)(ir.desc + nb))[IRS_REP_INTS * b + tid - IRS_DESC_INTS] : 0;
     int s0 = 0, nloc = 0, nleaf = 0, nl = 0;
     if (!use_desc) {
         s0 = bv.bundle_ptr[b], nloc = bv.bundle_ptr[b + 1] - s0;
@@ -1639,7 +1690,7 @@ __device__ __forceinline__ void irs_body(LdlView v, BundleView bv, FoldView fold
             const int dl = __builtin_amdgcn_readfirstlane(pat[0]);
             if (!fwd_have) flat_request_first<true, TW>(v, lev_e, nl, dl, opaque_tid(), fwdb);
             fwd_have = false;
-            bundle_sweep_flat_ahead<true, TW>(v, xs, nullptr, st.tacc, k, lev_e, dl, nloc, nl, fwdb);
+            bundle_sweep_flat_ahead<true, TW, true, true>(v, xs, nullptr, st.tacc, k, lev_e, dl, nloc, nl, fwdb, irs_rep_view(repw, bv));
             flat_batch_clear(fwdb);
         }
         stamp();
@@ -1678,7 +1729,7 @@ __device__ __forceinline__ void irs_body(LdlView v, BundleView bv, FoldView fold
                 const int i = t_ + u * TW;
                 if (i < nloc) xs[i] *= dinv[u];
             }
-            bundle_sweep_flat_ahead<false, TW>(v, xs, st.dxt, nullptr, k, lev_e, dl, nloc, nl, bwdb);
+            bundle_sweep_flat_ahead<false, TW, true, true>(v, xs, st.dxt, nullptr, k, lev_e, dl, nloc, nl, bwdb);
             flat_batch_clear(bwdb); // (consumed: constants again, see flat_batch_clear)
 #pragma unroll
             for (int u = 0; u < NPT; ++u) dinv[u] = 0.0;
@@ -1750,7 +1801,8 @@ __device__ __forceinline__ void irs_body(LdlView v, BundleView bv, FoldView fold
             irs_symv<TW, NPT, NLP, FIXED>(v, ir, st.runs, c, more_possible, xs, red, tacc3, k, s0, nloc, nleaf, st.candt,
                                    &pn[(size_t)par * nb + b], &shs[(size_t)par * nb * k + (size_t)b * k],
                                    __builtin_amdgcn_readfirstlane(pat[1]), use_desc, fl_b, fl_e,
-                                   ahead && folded && more_possible, lev_e, nl, __builtin_amdgcn_readfirstlane(pat[0]), fwdb);
+                                   ahead && folded && more_possible, lev_e, nl, __builtin_amdgcn_readfirstlane(pat[0]), fwdb,
+                                   irs_rep_view(repw, bv));
             fwd_have = ahead && folded && more_possible; // (the next round's forward sweep follows at once)
         }
         pending = true;
@@ -1882,8 +1934,11 @@ int bundle_ir_capacity(const BundleView &bv, int *tw) {
 }
 // k_bundle_irs can take this handle's solves: co-resident grid of nb workgroups of 256 threads (the per-bundle conditions
 // -- flat sweeps, nodes per thread, runs of the permutation -- are the caller's to check, see irs_bundle_ok)
-static bool irs_kernel_capacity_ok(const void *fn, const BundleView &bv) {
-    const size_t lds = bundle_ir_lds(bv);
+static size_t bundle_irs_lds(const BundleView &bv, bool rep) { // (rep: the replica slots behind the slice, irs_rep_view)
+    return bundle_ir_lds(bv) + (rep ? (size_t)IRS_REP_DOUBLES * sizeof(double) : 0);
+}
+static bool irs_kernel_capacity_ok(const void *fn, const BundleView &bv, bool rep) {
+    const size_t lds = bundle_irs_lds(bv, rep);
     if (raise_dynamic_lds(fn, lds) != hipSuccess) {
         (void)hipGetLastError();
         return false;
@@ -1901,14 +1956,14 @@ static bool irs_kernel_capacity_ok(const void *fn, const BundleView &bv) {
     per_cu = std::min(per_cu, std::min((int)(prop.maxSharedMemoryPerMultiProcessor / per_wg), 4));
     return per_cu * prop.multiProcessorCount >= bv.nb;
 }
-bool bundle_irs_capacity_ok(const BundleView &bv) {
+bool bundle_irs_capacity_ok(const BundleView &bv, bool rep) {
     if (!bv.nb || !bv.symv_split) return false;
-    return irs_kernel_capacity_ok((const void *)k_bundle_irs<256, 4>, bv);
+    return irs_kernel_capacity_ok((const void *)k_bundle_irs<256, 4>, bv, rep);
 }
 // the same for k_bundle_irs_fixed (a handle whose grid it cannot hold co-resident keeps the general kernel)
-bool bundle_irs_fixed_capacity_ok(const BundleView &bv) {
+bool bundle_irs_fixed_capacity_ok(const BundleView &bv, bool rep) {
     if (!bv.nb || !bv.symv_split) return false;
-    return irs_kernel_capacity_ok((const void *)k_bundle_irs_fixed<256, 4>, bv);
+    return irs_kernel_capacity_ok((const void *)k_bundle_irs_fixed<256, 4>, bv, rep);
 }
 // whether THIS launch's switches are the constants k_bundle_irs_fixed is compiled for (the handle's part -- fixed_ok:
 // bundle_irs_fixed_capacity_ok -- is the caller's)
@@ -1918,6 +1973,7 @@ bool bundle_irs_takes_fixed(const FoldView &fold, const IrView &ir) {
     return ir.sf && fold.k == 1 && (ir.sf_flags & mask) == want && ir.ir_enable && ir.spec_out && !ir.bp && !ir.test_drop;
 }
 bool irs_bundle_ok(int nloc, int nleaf, int nlevels, int nruns) {
+    static_assert(IRS_NPT * 256 + 8 <= IRS_NODE_MASK + 1, "a row index of these bundles (node or top row) has 12 bits: the rest carries the replica id");
     return nloc >= FLAT_MIN_NODES && nloc <= IRS_NPT * 256 && nleaf <= 4 * 256 && nlevels <= FLAT_MAXLEV && nruns > 0 &&
            nruns <= IR_MAXRUNS;
 }
@@ -1927,8 +1983,9 @@ int bundle_ir(hipStream_t s, const LdlView &v, const BundleView &bv, const FoldV
     // barrier that cannot complete times out instead of hanging
     const size_t lds = bundle_ir_lds(bv);
     if (ir.sf) { // (the caller has checked bundle_irs_capacity_ok / irs_bundle_ok, and for sf == 2 bundle_irs_takes_fixed)
-        if (ir.sf == 2) k_bundle_irs_fixed<256, 4><<<bv.nb, 256, lds, s>>>(v, bv, fold, ir);
-        else k_bundle_irs<256, 4><<<bv.nb, 256, lds, s>>>(v, bv, fold, ir);
+        const size_t lds_s = bundle_irs_lds(bv, (ir.sf_flags & IRS_F_REP) != 0);
+        if (ir.sf == 2) k_bundle_irs_fixed<256, 4><<<bv.nb, 256, lds_s, s>>>(v, bv, fold, ir);
+        else k_bundle_irs<256, 4><<<bv.nb, 256, lds_s, s>>>(v, bv, fold, ir);
         return (int)hipGetLastError();
     }
     if (gf.ng > 0) {

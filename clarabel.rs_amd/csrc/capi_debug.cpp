@@ -170,6 +170,13 @@ int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out
         const int flags = switches().irs_flags < 0 ? 3 : switches().irs_flags;
         *out = (h->ir_sf && h->irs_desc && !(flags & dev::IRS_F_CHAINED) && h->irs_desc_shared == shared) ? E.bundles.nb : 0;
     }
+    // bundles whose fused solve launch adds into replica slots under the current switches / their replicated nodes
+    else if (k == "irs_replica_bundles" || k == "irs_replica_nodes") {
+        const int flags = switches().irs_flags < 0 ? 3 : switches().irs_flags;
+        const bool on = h->irs_rep_bundles && !(flags & (dev::IRS_F_CHAINED | dev::IRS_F_NOREP)) && !switches().no_shared_pattern &&
+                        (h->E.host_only || (h->ir_sf && h->irs_desc));
+        *out = !on ? 0 : k == "irs_replica_bundles" ? h->irs_rep_bundles : h->irs_rep_nodes;
+    }
     else if (k == "irs_fixed_launches") *out = (double)h->irs_fixed_launches; // fused solve launches that took k_bundle_irs_fixed
     else if (k == "mailbox_mirror_on") *out = E.mirror_writes() ? 1 : 0;   // update and solves end in launches that write the host mirror
     else if (k == "mailbox_copies") *out = (double)E.mailbox_copies;       // collects that copied the mailbox
@@ -191,6 +198,13 @@ int32_t chip_debug_kkt_ints(const void *handle, const char *name, int64_t *len, 
     else if (k == "run_ptr") v = &h->t_run_ptr;
     else if (k == "runs") v = &h->t_runs;
     else if (k == "pat_off") v = &h->t_pat_off;
+    else if (k == "irs_rep") v = &h->h_irs_rep;
+    else if (k == "replica_plan") v = &h->t_rep_plan;
+    else if (k == "pat_Li16") v = &h->t_pat_Li16;
+    else if (k == "pat_Ucol16") v = &h->t_pat_Ucol16;
+    else if (k == "pat_Urow16") v = &h->t_pat_Urow16;
+    else if (k == "Li16") v = &h->t_Li16;
+    else if (k == "Ucol16") v = &h->t_Ucol16;
     else if (k == "factor_bundle_desc") v = &h->t_fr_bdesc;
     else if (k == "factor_class_usr") v = &h->t_fc_usr;
     else if (k == "factor_class_col") v = &h->t_fc_col;

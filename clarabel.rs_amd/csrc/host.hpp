@@ -287,9 +287,22 @@ struct PatternShare {
     i32 verified = 0, mismatches = 0; // bundles whose slices were compared through their offsets / that differed
     std::vector<uint16_t> Li16, Lj16, Ucol16, Urow16;
     std::vector<i32> off;             // 2 per bundle
+    // Replica ids (kernels.hpp: IRS_REP_R).  Per class: nodes first .. nloc - 1 (nd <= 4 of them, none a leaf) are
+    // "replicated" when one of the last four nodes is the target of at least 64 entries of one level of the forward
+    // stream or of the residual's flat range; first is the smallest such node.  An entry that adds into a replicated
+    // node carries r = (its ordinal among the entries with this target, in stream order) mod R in the top 4 bits of the
+    // shared Li16 (levels in front of `fold`, the level of node `first`, only: the slots are folded there) / of the
+    // shared Ucol16 (flat range, off the diagonal); everything else keeps r = 0.  Nothing else reads these copies.
+    struct Rep {
+        i32 nd = 0, first = 0, fold = 0;
+    };
+    std::vector<Rep> rep;             // per class (empty: no replica ids anywhere)
+    std::vector<i32> cls;             // bundle -> class
+    i32 rep_bundles = 0, rep_nodes = 0; // bundles with replicated nodes / replicated nodes over all bundles
+    void strip_replicas();            // back to r = 0 everywhere (a handle whose launch cannot have the slots)
     size_t index_bytes() const { return (Li16.size() + Lj16.size() + Ucol16.size() + Urow16.size()) * sizeof(uint16_t); }
 };
-void bundle_pattern_classes(const Symbolic &S, PatternShare &P);
+void bundle_pattern_classes(const Symbolic &S, PatternShare &P, bool replicas = true);
 
 // ---------------------------------------------------------------------------
 // KKT assembly (kkt_assembly.cpp)  -- kkt_assembly.rs:20-183, datamaps.rs

@@ -198,6 +198,21 @@ void bundle_symv(hipStream_t s, const BundleView &bv, const int *Up, const int *
 // handle is created (capi.cpp: irs_descriptors) -- none of it changes afterwards.  The kernel reads it in one trip.
 constexpr int IRS_DESC_LEVELS = 19; // levels of a bundle the record holds (more: the handle keeps the chained prologue)
 constexpr int IRS_DESC_RUNS = 32;   // runs of the permutation slice (bundle_ir.hip: IR_MAXRUNS)
+// Replica slots (k_bundle_irs / k_bundle_irs_fixed with a shared index pattern only).  A wave instruction of ds_add_f64
+// takes ~1.7 cycles more per lane that hits an address another lane hits (78 cycles when 2 x 21 lanes share
+// two doubles, 17 when each of the two is spread over 8), and the last nodes of a bundle -- the expansion columns of a
+// second-order cone -- are the target of a third of a level's entries.  The host gives such a node R - 1 further slots
+// behind the slice and writes a replica id r into the top 4 bits of the entries of the SHARED Li16 (forward target) and
+// Ucol16 (residual column target, flat range) that add into it: r = 0 is the node's own slot, r > 0 slot
+// rep0 + (node - rep_first) * (R - 1) + r - 1.  The kernel folds the slots into the node before anything reads it.
+// Where they are travels beside the bundle's record: IRS_REP_INTS words per bundle BEHIND the nb records of the table
+// (IrView::desc + nb), {ND | R << 8 (0: none), first replicated node (nodes first .. nloc - 1 are), the forward level in
+// front of which the slots are folded, 0}; read only in a launch with IRS_F_REP.
+constexpr int IRS_REP_INTS = 4;
+constexpr int IRS_REP_R = 8;      // slots per replicated node, its own included (the smallest within 10 % of the best measured)
+constexpr int IRS_REP_MAXND = 4;  // replicated nodes per bundle: among its last 4
+constexpr int IRS_REP_DOUBLES = IRS_REP_MAXND * (IRS_REP_R - 1);
+constexpr int IRS_NODE_BITS = 12, IRS_NODE_MASK = (1 << IRS_NODE_BITS) - 1; // (irs_bundle_ok: at most 12 x 256 nodes + 8 top rows)
 struct alignas(16) IrsDesc {
     int s0, nloc, nleaf, nl;            // first node, nodes, leaf nodes, levels
     int dl, du;                         // entry offsets into the index arrays of L / U (host.hpp: PatternShare; 0: own copy)
@@ -214,6 +229,8 @@ constexpr int IRS_F_X0_REGS = 1;   // round 0's iterate stays in registers
 constexpr int IRS_F_SPEC_OUT = 2;  // the last candidate may be written before its verdict
 constexpr int IRS_F_CHAINED = 4;   // no phase-ahead loads, chained prologue (the form before the descriptors; tests compare both)
 constexpr int IRS_F_GENERAL = 8;   // k_bundle_irs also where k_bundle_irs_fixed applies (tests and A/B runs compare both on one build)
+constexpr int IRS_F_NOREP = 16;    // no replica slots: the handle is built without replica ids, a launch of a handle that has them ignores them
+constexpr int IRS_F_REP = 512;     // (set by the host) the shared index copies carry replica ids, the records say where, the launch has IRS_REP_DOUBLES more LDS
 constexpr int IRS_F_DESC = 256;    // (set by the host, not by CHIP_IRS_FLAGS) the pat_off slot holds the descriptor table
 struct IrView {
     const double *rx, *rz; // right-hand side in the caller's order: entry o < n from rx, n <= o < n + m from rz,
@@ -262,11 +279,12 @@ int bundle_ir_capacity(const BundleView &bv, int *tw);
 int bundle_ir(hipStream_t s, const LdlView &v, const BundleView &bv, const FoldView &fold, const IrView &ir, int grid,
               int tw, const GFoldView &gf);
 // k_bundle_irs: whether a co-resident grid of one 256-thread workgroup per bundle exists / whether a bundle qualifies
-bool bundle_irs_capacity_ok(const BundleView &bv);
+// (rep: with the IRS_REP_DOUBLES of replica slots behind the slice)
+bool bundle_irs_capacity_ok(const BundleView &bv, bool rep = false);
 // k_bundle_irs_fixed, the instance with the usual switches folded (k == 1, record prologue, loads ahead, refinement on,
 // spec_out, x0 in registers, no bp, no test drop): whether its grid is co-resident for these bundles (per handle) /
 // whether a launch with this view has exactly those switches (per launch)
-bool bundle_irs_fixed_capacity_ok(const BundleView &bv);
+bool bundle_irs_fixed_capacity_ok(const BundleView &bv, bool rep = false);
 bool bundle_irs_takes_fixed(const FoldView &fold, const IrView &ir);
 bool irs_bundle_ok(int nloc, int nleaf, int nlevels, int nruns);
 // grouped fold, after bundle_factor: every bundle's contribution to the Schur complement of its group's top

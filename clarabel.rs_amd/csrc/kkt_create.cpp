@@ -52,6 +52,7 @@ void bundle_perm_runs(const Symbolic &S, i64 n, i64 m, std::vector<int> &rp, std
 // the index arrays, offsets 0).  Empty when some bundle does not fit the record.
 std::vector<int> irs_descriptors(const Symbolic &S, const std::vector<int> &rp, const std::vector<int> &runs,
                                  const std::vector<i32> *pat_off) {
+    static_assert(dev::IRS_REP_R == 8 && dev::IRS_REP_MAXND == 4 && dev::IRS_NODE_BITS == 12, "symbolic.cpp: REP_R, REP_MAXND, NODE_BITS");
     const int nb = S.bundle_ptr.empty() ? 0 : (int)S.bundle_ptr.size() - 1;
     std::vector<int> out;
     if (nb <= 0 || (int)rp.size() != nb + 1) return out;
@@ -73,6 +74,19 @@ std::vector<int> irs_descriptors(const Symbolic &S, const std::vector<int> &rp, 
         for (int l = 0; l <= d.nl; l++) d.lev_e[l] = S.Lp[(size_t)lv[l]];
         std::copy_n(&runs[3 * (size_t)rp[(size_t)b]], 3 * (size_t)d.nruns, d.runs);
         std::memcpy(&out[(size_t)b * dev::IRS_DESC_INTS], &d, sizeof d);
+    }
+    return out;
+}
+// the classes' replica slots (host.hpp: PatternShare::Rep) per bundle, the words that travel behind the records
+// (kernels.hpp: IRS_REP_INTS); all zero when no class has any
+std::vector<int> irs_replica_words(const PatternShare &pat, int nb) {
+    std::vector<int> out((size_t)nb * dev::IRS_REP_INTS, 0);
+    if (pat.rep.empty()) return out;
+    for (int b = 0; b < nb; b++) {
+        const PatternShare::Rep &r = pat.rep[(size_t)pat.cls[(size_t)b]];
+        if (!r.nd) continue;
+        int *w = &out[(size_t)b * dev::IRS_REP_INTS];
+        w[0] = r.nd | dev::IRS_REP_R << 8, w[1] = r.first, w[2] = r.fold;
     }
     return out;
 }
@@ -137,7 +151,9 @@ void fused_plan(chip_kkt *h, const Symbolic &S, FusedPlan &fp, PhaseClock &clk) 
     const bool nonempty = !S.bundle_ptr.empty() && S.bundle_ptr.size() > 1;
     fp.pat_cand = !S.Li16.empty() && S.gf_ng == 0 && S.nfold >= 1 && nonempty && irs_bundles_ok(S, [](i32) { return 1; });
     if (fp.pat_cand) {
-        bundle_pattern_classes(S, fp.pat);
+        // (replica ids only where the records can say where they are: a shared pattern, no CHIP_IRS_FLAGS bit 16)
+        const bool no_rep = switches().no_shared_pattern || (switches().irs_flags >= 0 && (switches().irs_flags & dev::IRS_F_NOREP));
+        bundle_pattern_classes(S, fp.pat, !no_rep);
         h->E.note_patterns(fp.pat);
         clk("pattern classes");
     }
@@ -148,6 +164,9 @@ void fused_plan(chip_kkt *h, const Symbolic &S, FusedPlan &fp, PhaseClock &clk) 
     bool fit = true;
     for (size_t b = 0; b + 1 < fp.run_ptr.size() && fit; b++) fit = fp.run_ptr[b + 1] - fp.run_ptr[b] <= dev::IRS_DESC_RUNS;
     if (fit) h->h_irs_desc = irs_descriptors(S, fp.run_ptr, fp.runs, fp.pat_shared ? &fp.pat.off : nullptr);
+    if (h->h_irs_desc.empty() || !fp.pat_shared) fp.pat.strip_replicas(); // (a bundle of more than 19 levels: the chained prologue)
+    if (!h->h_irs_desc.empty()) h->h_irs_rep = irs_replica_words(fp.pat, (int)(h->h_irs_desc.size() / dev::IRS_DESC_INTS));
+    h->irs_rep_bundles = fp.pat.rep_bundles, h->irs_rep_nodes = fp.pat.rep_nodes;
     clk("bundle descriptors");
 }
 
@@ -157,7 +176,20 @@ void finish_host_only(chip_kkt *h, Symbolic &S, const chip_settings &st, const F
     if (fp.pat_cand) {
         h->t_bundle_ptr = S.bundle_ptr, h->t_blvl_ptr = S.blvl_ptr, h->t_blvl = S.blvl;
         h->t_Lp = S.Lp, h->t_Up = S.Up, h->t_run_ptr = fp.run_ptr, h->t_runs = fp.runs;
-        if (fp.pat_shared) h->t_pat_off = fp.pat.off;
+        if (fp.pat_shared) {
+            h->t_pat_off = fp.pat.off;
+            h->t_pat_Li16.assign(fp.pat.Li16.begin(), fp.pat.Li16.end()), h->t_pat_Ucol16.assign(fp.pat.Ucol16.begin(), fp.pat.Ucol16.end());
+            h->t_pat_Urow16.assign(fp.pat.Urow16.begin(), fp.pat.Urow16.end());
+            if (S.Li16.size() + S.Ucol16.size() <= ((size_t)1 << 21)) // (the bundles' own slices, for small problems)
+                h->t_Li16.assign(S.Li16.begin(), S.Li16.end()), h->t_Ucol16.assign(S.Ucol16.begin(), S.Ucol16.end());
+        }
+    }
+    // what the replica rule (host.hpp: PatternShare::Rep) says about this system's bundles whether or not k_bundle_irs can
+    // take them (bundles under its 512 nodes: the rule's threshold of 64 entries lies there), for the tests of the rule
+    if (!S.Li16.empty() && S.gf_ng == 0 && S.nfold >= 1 && S.bundle_ptr.size() > 1) {
+        PatternShare plan;
+        bundle_pattern_classes(S, plan, true);
+        if (!plan.off.empty()) h->t_rep_plan = irs_replica_words(plan, (int)S.bundle_ptr.size() - 1);
     }
 #else
     (void)fp;
@@ -245,13 +277,22 @@ int fused_bind(chip_kkt *h, const Symbolic &S, FusedPlan &fp) {
                     irs_bundles_ok(S, [&rp](i32 b) { return rp[(size_t)b + 1] - rp[(size_t)b]; });
     h->ir_sf = sf && dev::bundle_irs_capacity_ok(E.bundles);
     h->irs_fixed_ok = h->ir_sf && E.fold.k == 1 && dev::bundle_irs_fixed_capacity_ok(E.bundles);
+    // replica slots: only when every kernel that can take the launch is still co-resident with the larger LDS request
+    if (fp.pat.rep_bundles && !(h->ir_sf && dev::bundle_irs_capacity_ok(E.bundles, true) &&
+                                (!h->irs_fixed_ok || dev::bundle_irs_fixed_capacity_ok(E.bundles, true)))) {
+        fp.pat.strip_replicas();
+        std::fill(h->h_irs_rep.begin(), h->h_irs_rep.end(), 0);
+        h->irs_rep_bundles = h->irs_rep_nodes = 0;
+    }
     // (update and solves each end in a launch that can leave its verdict in the host's mirror of the mailbox)
     E.mb_mirror_on = h->ir_sf && E.fold.k == 1 && E.fast_prep_ok;
     if (h->ir_sf && !switches().no_shared_pattern && (rc = E.upload_patterns(fp.pat))) return rc;
     // (the records carry the offsets of the shared arrays: only beside them, or with offsets 0 without them)
-    if (h->ir_sf && !h->h_irs_desc.empty() && (E.pat_off != nullptr) == fp.pat_shared &&
-        (rc = E.upload(&h->irs_desc, h->h_irs_desc, h->h_irs_desc.size())))
-        return rc;
+    if (h->ir_sf && !h->h_irs_desc.empty() && (E.pat_off != nullptr) == fp.pat_shared) {
+        std::vector<int> table = h->h_irs_desc; // (the records, then the replica words of every bundle)
+        table.insert(table.end(), h->h_irs_rep.begin(), h->h_irs_rep.end());
+        if ((rc = E.upload(&h->irs_desc, table, table.size()))) return rc;
+    }
     h->irs_desc_shared = fp.pat_shared;
     return CHIP_OK;
 }

@@ -136,11 +136,16 @@ struct chip_kkt {
     // changes after creation; empty / nullptr: some bundle does not fit the record, the kernel keeps its chained prologue.
     // The host copy is there on host-only handles too (tests read it back: chip_debug_kkt_ints).
     std::vector<int> h_irs_desc;
+    // the bundles' replica slots (kernels.hpp: IRS_REP_INTS per bundle, behind the records on the device; all zero: none)
+    // and what the test hooks count: bundles with replicated nodes, replicated nodes over all bundles
+    std::vector<int> h_irs_rep;
+    int irs_rep_bundles = 0, irs_rep_nodes = 0;
     int *irs_desc = nullptr;
     bool irs_desc_shared = false; // the records on the device carry offsets into the SHARED index arrays
 #ifdef CHIP_TESTING
     // host-only handles: the arrays the chained prologue walks, kept so that a test can walk them itself
     std::vector<int> t_bundle_ptr, t_blvl_ptr, t_blvl, t_Lp, t_Up, t_run_ptr, t_runs, t_pat_off;
+    std::vector<int> t_pat_Li16, t_pat_Ucol16, t_pat_Urow16, t_Li16, t_Ucol16, t_rep_plan; // the shared index copies as the kernel reads them, the bundles' own
     // ... and the update records of the flat bundle factorisation, plain and run-coded (chip_debug_factor_updates)
     std::vector<uint16_t> t_fu_rec, t_fr_rec;
     std::vector<int> t_fu_ptr, t_fr_desc, t_fr_ptr, t_fr_rptr, t_fu_lvl_ptr, t_fr_bdesc, t_fc_usr, t_fc_col, t_fc_sgn, t_fc_desc, t_fc_rec;

@@ -212,7 +212,7 @@ dev::IrView ir_view_fill(chip_kkt *h, double *lhsx_dev, double *lhsz_dev, int sl
     // (the residual of the last round still reads the right-hand side when that round's candidate is written)
     auto overlap = [](const double *a, size_t na, const double *b_, size_t nb_) { return a && b_ && a < b_ + nb_ && b_ < a + na; };
     const size_t n = (size_t)h->K.n, m = (size_t)h->K.m;
-    ir.sf_flags = (switches().irs_flags < 0 ? 3 : switches().irs_flags) & ~dev::IRS_F_DESC;
+    ir.sf_flags = (switches().irs_flags < 0 ? 3 : switches().irs_flags) & ~(dev::IRS_F_DESC | dev::IRS_F_REP);
     ir.spec_out = (ir.sf_flags & 2) && !(overlap(lhsx_dev, n, ir.rx, n) || overlap(lhsx_dev, n, ir.rz, m) ||
                                          overlap(lhsz_dev, m, ir.rx, n) || overlap(lhsz_dev, m, ir.rz, m));
     return ir;
@@ -241,6 +241,8 @@ FusedKernel fused_choose(const chip_kkt *h, dev::IrView &ir, dev::LdlView &lv, i
     if (h->irs_desc && !(ir.sf_flags & (dev::IRS_F_CHAINED)) && h->irs_desc_shared == (ir.pat_off != nullptr)) {
         ir.desc = (const dev::IrsDesc *)h->irs_desc;
         ir.sf_flags |= dev::IRS_F_DESC;
+        // (the shared copies of this handle carry replica ids and the words behind the records say where)
+        if (h->irs_rep_bundles && ir.pat_off && !(ir.sf_flags & dev::IRS_F_NOREP)) ir.sf_flags |= dev::IRS_F_REP;
     }
     if (E.mirror_writes()) ir.res_host = E.mb_mirror->ring + 4 * slot; // (workgroup 0 writes the verdict there as well)
     // this launch's switches are the constants k_bundle_irs_fixed has folded: per launch, set_settings can switch

@@ -1926,7 +1926,67 @@ int analyse(i64 n, const i64 *Ap, const i64 *Ai, const int8_t *dsigns, const std
 }
 
 // ---- pattern classes of the bundles (host.hpp: PatternShare) ----------------------------------------
-void bundle_pattern_classes(const Symbolic &S, PatternShare &P) {
+namespace {
+constexpr i32 REP_R = 8, REP_MAXND = 4, REP_MIN = 64, NODE_BITS = 12, NODE_MASK = (1 << NODE_BITS) - 1; // (kernels.hpp: IRS_REP_R ..; kkt_create.cpp asserts that they agree)
+// replica ids of one class, written into its slices of the shared Li16 / Ucol16 (at l0 / u0); lv: the member's level
+// table (nl + 1 node boundaries, absolute), Lp / Up: the member's own entry pointers
+PatternShare::Rep encode_replicas(const Symbolic &S, i32 s0, i32 nloc, const i32 *lv, i32 nl, uint16_t *Li, uint16_t *Uc,
+                                  const uint16_t *Ur) {
+    PatternShare::Rep out;
+    const i32 nleaf = lv[1] - s0;
+    if (nloc + 8 > NODE_MASK + 1 || nl < 2) return out;
+    const i32 c0 = std::max(nloc - REP_MAXND, nleaf);
+    const i64 lb = S.Lp[s0], ub = S.Up[s0], fb = S.Up[s0 + nleaf], fe = S.Up[s0 + nloc];
+    i32 first = nloc;
+    for (i32 l = 0; l < nl; l++) { // a level of the forward stream with >= 64 entries into one of the last nodes
+        i32 cnt[REP_MAXND] = {0, 0, 0, 0};
+        for (i64 t = S.Lp[lv[l]]; t < S.Lp[lv[l + 1]]; t++) {
+            const i32 i = Li[t - lb];
+            if (i >= c0 && i < nloc) cnt[i - c0]++;
+        }
+        for (i32 q = 0; q < nloc - c0; q++)
+            if (cnt[q] >= REP_MIN) first = std::min(first, c0 + q);
+    }
+    {
+        i32 cnt[REP_MAXND] = {0, 0, 0, 0};
+        for (i64 t = fb; t < fe; t++) {
+            const i32 j = Uc[t - ub];
+            if (j >= c0 && j < nloc && j != (i32)Ur[t - ub]) cnt[j - c0]++;
+        }
+        for (i32 q = 0; q < nloc - c0; q++)
+            if (cnt[q] >= REP_MIN) first = std::min(first, c0 + q);
+    }
+    if (first >= nloc) return out;
+    out.nd = nloc - first;
+    out.first = first;
+    for (i32 l = 0; l < nl; l++)
+        if (lv[l] - s0 <= first && first < lv[l + 1] - s0) out.fold = l;
+    i32 ord[REP_MAXND] = {0, 0, 0, 0};
+    for (i64 t = S.Lp[lv[0]]; t < S.Lp[lv[out.fold]]; t++) {
+        const i32 i = Li[t - lb];
+        if (i >= first && i < nloc) Li[t - lb] = (uint16_t)(i | (ord[i - first]++ % REP_R) << NODE_BITS);
+    }
+    i32 oru[REP_MAXND] = {0, 0, 0, 0};
+    for (i64 t = fb; t < fe; t++) {
+        const i32 j = Uc[t - ub];
+        if (j >= first && j < nloc && j != (i32)Ur[t - ub]) Uc[t - ub] = (uint16_t)(j | (oru[j - first]++ % REP_R) << NODE_BITS);
+    }
+    return out;
+}
+bool equal_masked(const uint16_t *a, const uint16_t *b, i64 n) { // a: a shared copy that may carry replica ids
+    for (i64 t = 0; t < n; t++)
+        if ((a[t] & NODE_MASK) != b[t]) return false;
+    return true;
+}
+} // namespace
+void PatternShare::strip_replicas() {
+    if (rep.empty()) return;
+    for (uint16_t &e : Li16) e &= NODE_MASK;
+    for (uint16_t &e : Ucol16) e &= NODE_MASK;
+    rep.clear();
+    rep_bundles = rep_nodes = 0;
+}
+void bundle_pattern_classes(const Symbolic &S, PatternShare &P, bool replicas) {
     P = PatternShare();
     if (S.Li16.empty() || S.bundle_ptr.size() < 2) return;
     const i32 nb = (i32)S.bundle_ptr.size() - 1;
@@ -2010,6 +2070,18 @@ void bundle_pattern_classes(const Symbolic &S, PatternShare &P) {
         std::copy_n(&S.Urow16[(size_t)a.u0], a.un, &P.Urow16[(size_t)nu]);
         nl += a.ln, nu += a.un;
     }
+    P.cls = cls;
+    if (replicas) {
+        P.rep.resize(rep.size());
+        bool any = false;
+        for (size_t c = 0; c < rep.size(); c++) {
+            const Slices a = slices(rep[c]);
+            P.rep[c] = encode_replicas(S, a.s0, a.nloc, a.lv, a.nlv - 1, &P.Li16[(size_t)cl0[c]], &P.Ucol16[(size_t)cu0[c]],
+                                       &P.Urow16[(size_t)cu0[c]]);
+            any = any || P.rep[c].nd > 0;
+        }
+        if (!any) P.rep.clear();
+    }
     P.off.resize(2 * (size_t)nb);
     for (i32 b = 0; b < nb; b++) {
         const Slices a = slices(b);
@@ -2022,15 +2094,17 @@ void bundle_pattern_classes(const Symbolic &S, PatternShare &P) {
         const i64 l = a.l0 + P.off[2 * (size_t)b], u = a.u0 + P.off[2 * (size_t)b + 1];
         const size_t lb = (size_t)a.ln * sizeof(uint16_t), ub = (size_t)a.un * sizeof(uint16_t);
         const bool ok = l >= 0 && l + a.ln < (i64)P.Li16.size() && u >= 0 && u + a.un < (i64)P.Ucol16.size() &&
-                        std::memcmp(&P.Li16[(size_t)l], &S.Li16[(size_t)a.l0], lb) == 0 &&
+                        equal_masked(&P.Li16[(size_t)l], &S.Li16[(size_t)a.l0], a.ln) &&
                         std::memcmp(&P.Lj16[(size_t)l], &S.Lj16[(size_t)a.l0], lb) == 0 &&
-                        std::memcmp(&P.Ucol16[(size_t)u], &S.Ucol16[(size_t)a.u0], ub) == 0 &&
+                        equal_masked(&P.Ucol16[(size_t)u], &S.Ucol16[(size_t)a.u0], a.un) &&
                         std::memcmp(&P.Urow16[(size_t)u], &S.Urow16[(size_t)a.u0], ub) == 0;
         P.verified++;
         if (!ok) P.mismatches++;
+        if (!P.rep.empty() && P.rep[(size_t)cls[(size_t)b]].nd) P.rep_bundles++, P.rep_nodes += P.rep[(size_t)cls[(size_t)b]].nd;
     }
     if (P.mismatches) { // (never seen; the kernel must not get an offset that was not verified)
         P.Li16.clear(), P.Lj16.clear(), P.Ucol16.clear(), P.Urow16.clear(), P.off.clear();
+        P.rep.clear(), P.rep_bundles = P.rep_nodes = 0;
     }
 }
 

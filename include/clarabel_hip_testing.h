@@ -29,6 +29,9 @@ int32_t chip_debug_set_switch(const char *name, const char *value_or_null);
  * per-bundle record under the current switches: 0 with CHIP_IRS_FLAGS bit 4, the chained prologue),
  * "irs_fixed_launches" (fused solve launches of this handle that took k_bundle_irs_fixed, the instance with the usual
  * switches folded: it stays 0 with CHIP_IRS_FLAGS bit 8, without refinement, with more than one top row),
+ * "irs_replica_bundles" / "irs_replica_nodes" (bundles whose fused solve launch adds into replica slots of their dense
+ * targets under the current switches, and those targets over all bundles; host analysis, on host-only handles too: 0
+ * with CHIP_IRS_FLAGS bit 16 or bit 4, with CHIP_NO_SHARED_PATTERN, without records),
  * "mailbox_mirror_on" (1: the handle's update and
  * solves end in launches that store their verdict words into the host mirror of the mailbox; 0 with
  * CHIP_NO_HOST_MAILBOX), "mailbox_copies" / "mailbox_mirror_reads" (collects that copied the mailbox / that only waited
@@ -45,6 +48,11 @@ int32_t chip_debug_counter(const void *kkt_handle, const char *name, double *out
  * identical bundles: "factor_class_usr", "factor_class_col" (bit patterns of unsigned words), "factor_class_sgn",
  * "factor_class_desc" (8 ints per run), "factor_class_rec" (4 per record); chip_debug_counter: "factor_classes",
  * "factor_class_verified" (bundles compared with what their record reaches), "factor_class_mismatches".
+ * Replica slots (csrc/kernels.hpp: IRS_REP_R): "irs_rep", 4 ints per bundle {ND | R << 8, first replicated node, fold
+ * level, 0} as they travel behind the records; on host-only handles "pat_Li16" / "pat_Ucol16" / "pat_Urow16", the shared
+ * index copies as the kernel reads them (replica id in the top 4 bits), "Li16" / "Ucol16", the bundles' own (small
+ * problems only), and "replica_plan": the words of "irs_rep" by the rule alone, also for systems whose bundles the
+ * kernel does not take.
  * Returns CHIP_ERR_ARG for an unknown name. */
 int32_t chip_debug_kkt_ints(const void *kkt_handle, const char *name, int64_t *len, int32_t *out);
 /* the update records of the flat bundle factorisation (csrc/host.hpp: Symbolic::fu_rec / fr_desc) of one bundle of a
